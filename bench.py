@@ -18,9 +18,17 @@ builds the dictionary tables and broadcasts them once over RCCL.
 their code.  Inside a rank, WORLD_SIZE must equal --gpus and (backend nccl) every rank must own a device, or the rank
 exits non-zero: a line with `n_gpus: N` is never printed by fewer than N devices.
 
-Prints ONE JSON line on rank 0.  At N = 1 the line also carries, measured in the same process over a few
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the line; nothing else.
+`--full` adds, after the timed steps: the `roofline` (the dominant kernel's time by HIP events, over a profiled pass of
+its own of --steps steps) and a range check of the atom ids; at N = 1 also, measured in the same process over a few
 steps each: the FP64 kernel on the same voxels (`fp64_kernel`), BASELINE configs 4, 1 and 5 (`c4`, `c1`, `c5`), the two-fascicle + CSF class (`k2_csf`), the
 PCIe-inclusive rate of the host entry point (`host_api`) and the CPU baseline on all host cores.
+
+`--dump-outputs DIR` writes what the last timed step computed, as the caller of mfx_fit_batch_dev receives it: the
+[V, 7] float64 parameter rows (M0, nu1, nu2, id1, id2, MSE, R2) as DIR/params.npy (DIR/params_rank<r>.npy with N > 1).
+Beyond OUTPUT_BUDGET_BYTES in all, a fixed seeded sample of rows is written, with their row numbers in
+DIR/params_rows.npy (float64).  The inputs depend only on the arguments (seeded), so two builds can be compared
+output for output.
 """
 import argparse
 import json
@@ -56,6 +64,7 @@ FLOP_PER_VOXEL_C5 = 3 * 2.0 * C5_N * C5_N * 300 + 40.0 * float(C5_N) ** 3
 PMC_PROFILE = os.path.join("profiles", "r03_pmc_traffic_k2s.json")
 PMC_C4 = os.path.join("profiles", "r03_pmc_k2x.json")
 PMC_C5 = os.path.join("profiles", "r03_pmc_k3_screen.json")
+OUTPUT_BUDGET_BYTES = 64 * 1024 * 1024     # --dump-outputs: all ranks together
 
 
 def _pmc_field(rel, key):
@@ -76,9 +85,32 @@ def parse():
     ap.add_argument("--atoms", type=int, default=782)
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak")
     ap.add_argument("--cpu-sample", type=int, default=0, help="voxels timed on the host cores (0: ~40 per core)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the fp64_kernel / c4 / c1 / host_api measurements")
-    return ap.parse_args()
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the fp64_kernel / c4 / c1 / host_api measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: roofline (profiled pass), atom-id check, the other configurations and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return a
+
+
+def dump_outputs(d_out, outdir, rank, world):
+    """The last timed step's parameter rows -> outdir/params[_rank<r>].npy (float64); a seeded sample of rows beyond this
+    rank's share of OUTPUT_BUDGET_BYTES, with the row numbers beside it."""
+    os.makedirs(outdir, exist_ok=True)
+    suffix = "" if world == 1 else "_rank%d" % rank
+    out = d_out.cpu().numpy().astype(np.float64, copy=False)
+    max_rows = max(1, OUTPUT_BUDGET_BYTES // world // (out.shape[1] * 8 + 8))
+    if out.shape[0] > max_rows:
+        rows = np.sort(np.random.default_rng(4242 + rank).choice(out.shape[0], max_rows, replace=False))
+        out = out[rows]
+        np.save(os.path.join(outdir, "params%s_rows.npy" % suffix), rows.astype(np.float64))
+    np.save(os.path.join(outdir, "params%s.npy" % suffix), np.ascontiguousarray(out))
 
 
 def build_model(atoms):
@@ -282,25 +314,21 @@ def main(a=None):
 
     for _ in range(a.warmup):
         step()
-    # ---- timed region: barrier + sync on both sides; HIP events on the launch stream for the kernel
-    lib.mfx_set_profiling(1)
+    # ---- timed region: barrier + sync on both sides, the steps queued back to back
     torch.cuda.synchronize(dev)
     if use_dist:
         dist.barrier()
     t0 = time.perf_counter()
-    kern_ms = []
     for _ in range(a.steps):
         step()
-        # the event pair is recorded on the launch stream inside the library; reading it waits
-        # for that launch only (the next launch is queued right after)
-        kern_ms.append(lib.mfx_last_kernel_ms())
     torch.cuda.synchronize(dev)
     if use_dist:
         dist.barrier()
     t1 = time.perf_counter()
-    lib.mfx_set_profiling(0)
     L.check(lib.mfx_plan_status(plan.handle(), stream.cuda_stream))
     elapsed = t1 - t0
+    if a.dump_outputs:
+        dump_outputs(d_out, a.dump_outputs, rank, world)
     ranks_seen, vox_per_rank, dev_per_rank = 1, [V], [torch.cuda.get_device_name(dev)]
     if use_dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
@@ -316,16 +344,21 @@ def main(a=None):
         dev_per_rank = [i[1] for i in info]
     ms_per_step = elapsed / a.steps * 1e3
     value = global_V * a.steps / elapsed
-    handed_back = int(lib.mfx_debug_last_fallback_count())
 
-    # sanity: selected atoms are plausible indices
-    ids = d_out[:, 3:5]
-    assert bool(((ids >= 0) & (ids < N)).all()), "atom ids out of range"
+    if a.full:
+        # sanity: selected atoms are plausible indices
+        ids = d_out[:, 3:5]
+        assert bool(((ids >= 0) & (ids < N)).all()), "atom ids out of range"
 
     res = None
     if rank == 0:
         screen = os.environ.get("MFX_K2_SCREEN", "1") != "0"
-        kavg = float(np.mean(kern_ms)) if kern_ms and min(kern_ms) > 0 else None
+        kavg, handed_back = None, None
+        if a.full:
+            # the dominant kernel's time: HIP events on the launch stream, over a pass of its own after the timed steps
+            _, kavg = timed(step, a.steps, 0, dev, lib)
+            L.check(lib.mfx_plan_status(plan.handle(), stream.cuda_stream))
+            handed_back = int(lib.mfx_debug_last_fallback_count())
         roof = None
         if kavg:
             ach = FLOP_PER_VOXEL * V / (kavg * 1e-3) / 1e12
@@ -387,17 +420,17 @@ def main(a=None):
                         "flop_per_voxel": FLOP_PER_VOXEL, "hbm_bytes_per_voxel_algorithmic": BYTES_PER_VOXEL,
                         "achieved_hbm_GBps_algorithmic": round(BYTES_PER_VOXEL * V / (kavg * 1e-3) / 1e9, 3)}
         extras = {}
-        if world == 1 and not a.no_extras:
+        if a.full and world == 1 and not a.no_extras:
             extras = extra_measurements(plan, ms, sch, d_Y, d_peaks, peaks_h, d_out, V, N, M, dev, lib, screen)
         cpu = None
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             cpu = cpu_baseline(sch, ms, d_Y, peaks_h, d_out, V, a.cpu_sample)
         res = {"metric": "voxels/sec, 2-fascicle exhaustive NNLS, 782-atom x 200-measurement dictionary",
                "value": round(value, 1), "unit": "voxels/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
                "ms_per_step": round(ms_per_step, 3), "ms_per_voxel": round(ms_per_step / max(global_V // world, 1), 6),
                "higher_is_better": True, "scaling": a.scaling if world > 1 else "weak", "vs_baseline": None,
                "dtype": "f64" if not screen else "f64 (pairs ranked on split-f16 MFMA, short list re-evaluated in f64)",
-               "data": "synthetic",
+               "data": "synthetic", "full": a.full,
                "config": {"workload": "C2: %d voxels%s, 2 fascicles, %d atoms x %d measurements"
                                       % (a.voxels, "/GPU" if a.scaling == "weak" else " in total", N, M),
                           "voxels_per_gpu": global_V // world, "global_voxels": global_V, "atoms": N, "measurements": M,
