@@ -9,4 +9,5 @@ rensonnetg/microstructure_fingerprinting (``MFModel.fit`` / ``mf_utils``).
 __version__ = "0.1.0"
 
 from . import mf_utils  # noqa: E402,F401
+from . import mcf  # noqa: E402,F401
 from .mf import MFModel, MFModelFit, cleanup_2fascicles  # noqa: E402,F401

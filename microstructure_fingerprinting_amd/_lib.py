@@ -24,6 +24,9 @@ EXPORTS = [
     "mfx_solve_exhaustive", "mfx_monte_carlo_average", "mfx_monte_carlo_average_dev", "mfx_cleanup_2fascicles", "mfx_cleanup_2fascicles_dev", "mfx_last_kernel_ms", "mfx_set_profiling", "mfx_debug_set_stamps", "mfx_debug_last_fallback_count", "mfx_debug_last_guard_count", "mfx_debug_last_counter", "mfx_debug_set_k2_screen", "mfx_debug_set_k2_wide", "mfx_debug_set_k2x_screen", "mfx_debug_set_k2_maxc", "mfx_debug_set_k2x_maxc", "mfx_debug_set_k2s_cap", "mfx_debug_set_k2s_images", "mfx_debug_set_k3_cap", "mfx_debug_set_force_generic", "mfx_debug_set_k3_screen",
 ]
 
+# every symbol include/mfx_mcf.h declares (MCF signal synthesis; versioned on its own)
+MCF_EXPORTS = ["mfx_mcf_abi_version", "mfx_mcf_pgse", "mfx_mcf_dde"]
+
 
 class MfxError(RuntimeError):
     pass
@@ -100,6 +103,10 @@ def lib():
     L.mfx_debug_set_k3_screen.restype = None
     L.mfx_debug_set_k2s_images.argtypes = [C.c_int]
     L.mfx_debug_set_k2s_images.restype = None
+    L.mfx_mcf_abi_version.restype = C.c_int
+    for fn in ("mfx_mcf_pgse", "mfx_mcf_dde"):
+        getattr(L, fn).argtypes = [dp, dp, C.c_int, dp, C.c_int64, dp, dp, C.c_int64, dp, C.c_double, dp]
+        getattr(L, fn).restype = C.c_int
     _lib = L
     return L
 

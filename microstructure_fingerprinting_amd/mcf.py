@@ -1,0 +1,339 @@
+"""Multiple-correlation-function (MCF) signal synthesis (reference ``mcf.py``).
+
+Signal attenuation inside an impermeable cylinder for every row of a PGSE or DDE protocol,
+from the matrix formalism of Grebenkov (2008) on the first ``M`` Neumann Laplace eigenmodes.
+Validation and messages follow the reference line by line; the matrix exponentials run on the
+GPU (``csrc/mcf.hip``, C ABI ``include/mfx_mcf.h``).  The eigenvalue / coupling tables are
+computed here instead of being loaded from ``MCF_data/*.mat``.
+
+    import microstructure_fingerprinting_amd as mf
+    E = mf.mcf.MCF_PGSE('cylinder', 2e-6, 1.7e-9, scheme=sch)            # [n_seq]
+    D = mf.mcf.MCF_PGSE_atoms('cylinder', radii, diffs, scheme=sch)       # [n_seq, n_atoms]
+"""
+
+import numpy as np
+
+from . import _lib
+from . import mf_utils as mfu
+
+__all__ = ["mcf_tables", "import_DDE_scheme", "MCF_PGSE", "MCF_PGSE_atoms", "MCF_DDE"]
+
+_M_MAX = 60
+_TABLES = {}
+
+
+def _domain_type(domain):
+    if domain in ['c', 'cylinder']:
+        return 'cylinder'
+    if domain in ['s', 'sphere']:
+        return 'sphere'
+    if domain in ['p', 'planes']:
+        return 'interval'
+    raise ValueError('Unknown domain %s.' % (domain,))
+
+
+def _gauss_legendre_01(n):
+    x, w = np.polynomial.legendre.leggauss(n)
+    return 0.5 * (x + 1.0), 0.5 * w
+
+
+def _cylinder_tables(M):
+    """Neumann modes J_n(alpha r) cos(n phi) of the unit disk, ordered by alpha^2 (J_n'(alpha) = 0,
+    (n, k) = (0, 0) first with alpha = 0), normalised to a mean square of 1 over the disk;
+    B_ij = <u_i | x | u_j> (mean over the disk), non-zero for |n - n'| = 1 only."""
+    from scipy import special as sp
+    modes = [(0.0, 0)]
+    n = 0
+    while True:   # every zero below the M-th smallest: scan orders until the first zero of J_n' exceeds it
+        z = sp.jnp_zeros(n, M)
+        if len(modes) >= M and z[0] > sorted(a for a, _ in modes)[M - 1]:
+            break
+        modes += [(float(a), n) for a in z]
+        n += 1
+    modes.sort(key=lambda t: (t[0], t[1]))
+    modes = modes[:M]
+    alpha = np.array([a for a, _ in modes])
+    order = np.array([k for _, k in modes])
+    # radial integrals by Gauss-Legendre on [0, 1] (the integrands are entire: 200 nodes are exact to rounding)
+    r, w = _gauss_legendre_01(200)
+    R = np.array([sp.jv(k, a * r) for a, k in modes])
+    ang = np.where(order == 0, 2.0 * np.pi, np.pi)   # int_0^2pi cos^2(n phi)
+    R = R / np.sqrt(ang * (R * R * r * w).sum(axis=1) / np.pi)[:, None]
+    B = np.zeros((M, M))
+    for i in range(M):
+        for j in range(M):
+            ni, nj = order[i], order[j]
+            if abs(ni - nj) != 1:
+                continue
+            # int_0^2pi cos(ni phi) cos(phi) cos(nj phi) dphi = pi/2 (1 + [ni + nj == 1])
+            angij = 0.5 * np.pi * (2.0 if ni + nj == 1 else 1.0)
+            B[i, j] = abs(angij * np.sum(R[i] * R[j] * r * r * w) / np.pi)
+    return alpha ** 2, B
+
+
+def _sphere_eigenvalues(M):
+    """alpha^2 with j_l'(alpha) = 0 (alpha = 0 for l = 0 included), one mode per (l, k), ascending."""
+    from scipy import special as sp
+    from scipy.optimize import brentq
+    vals = [0.0]
+    xmax = np.pi * (M + 2)
+    x = np.linspace(1e-3, xmax, 200 * (M + 2))
+    for l in range(0, M + 2):
+        f = sp.spherical_jn(l, x, derivative=True)
+        idx = np.nonzero(np.sign(f[:-1]) * np.sign(f[1:]) < 0)[0]
+        for i in idx:
+            vals.append(brentq(lambda t: sp.spherical_jn(l, t, derivative=True), x[i], x[i + 1], xtol=1e-15, rtol=1e-15))
+    vals = np.sort(np.array(vals))[:M]
+    return vals ** 2
+
+
+def mcf_tables(domain, M=60):
+    """(Lamvec[M], B[M, M]) of a domain: Laplace eigenvalues (ascending, first 0) and the gradient
+    coupling matrix, in place of the reference's ``MCF_data/MCF_{L,B}{cl,sl,pl}.mat``.  Only the
+    cylinder's B is computed (sphere and planes have no signal code in the reference); for those B is
+    None.  Cached per (domain, M); the arrays returned are read-only."""
+    return _tables(_domain_type(domain), M)
+
+
+def _tables(dom, M):
+    M = int(M)
+    if M < 1 or M > _M_MAX:
+        raise ValueError('M must be between 1 and %d (got %d).' % (_M_MAX, M))
+    key = (dom, M)
+    if key not in _TABLES:
+        if dom == 'cylinder':
+            lam, B = _cylinder_tables(M)
+        elif dom == 'sphere':
+            lam, B = _sphere_eigenvalues(M), None
+        else:
+            lam, B = (np.pi * np.arange(M)) ** 2, None
+        lam.setflags(write=False)
+        if B is not None:
+            B.setflags(write=False)
+        _TABLES[key] = (lam, B)
+    return _TABLES[key]
+
+
+def _tables_for(dom, M, tables):
+    if tables is not None:
+        Lamvec = np.asarray(tables[0], dtype=np.float64).ravel()[0:M]
+        B = None if tables[1] is None else np.asarray(tables[1], dtype=np.float64)[0:M, 0:M]
+        return Lamvec, B
+    return _tables(dom, M)
+
+
+def _q_over_p_check(Lamvec, M, Tall, L, diff, gamma, Gall):
+    # Eq. [36] of Grebenkov 2008, as the reference checks it (mcf.py:140-170, 352-381)
+    p = diff * Tall / L ** 2
+    q = gamma * Tall * L * Gall
+    q_over_p = (gamma * L) * (L ** 2 / diff) * Gall
+    idx_bad = np.where(q_over_p >= Lamvec[-1])[0]
+    n_bad = idx_bad.size
+    if n_bad > 0:
+        badlist = " ".join("%d" % (idx,) for idx in idx_bad)
+        bad1 = idx_bad[0]
+        msg = ('Number of eigenvalues and eigenfunctions M=%d too small'
+               ' to ensure accuracy of final DW-MRI signal for the'
+               ' physical parameters provided in the following %d '
+               'sequence(s):\n%s\n'
+               'In seq. %d for instance, detected lambda_M=%g <'
+               ' q/p=%g, with p=D*T/L^2=%g and q=gam*T*L*G=%g.'
+               'This code is only reliable for a smaller L, a smaller G '
+               'or a higher diff. Otherwise you may want to try to '
+               'approximate the DW-MRI signal with a formula based '
+               'on the Gaussian phase distribution (GPD) for instance.' %
+               (M, n_bad, badlist, bad1, Lamvec[-1],
+                q_over_p[bad1], p[bad1], q[bad1]))
+        raise ValueError(msg)
+
+
+def _normalized_envdir(envdir):
+    dir_norm = np.sqrt(np.sum(envdir ** 2))
+    if dir_norm == 0:
+        raise ValueError('Direction (orientation) of environment cannot'
+                         ' be a zero vector.')
+    return envdir / dir_norm
+
+
+def _launch(fn, Lamvec, B, seq, L, diff, envdir, gamma):
+    lib = _lib.lib()
+    M = Lamvec.size
+    lam = _lib.f64c(Lamvec)
+    Bc = _lib.f64c(B)
+    seq = _lib.f64c(seq)
+    L = _lib.f64c(L)
+    diff = _lib.f64c(diff)
+    env = _lib.f64c(np.asarray(envdir, dtype=np.float64).ravel()[:3])
+    n_seq, n_atoms = seq.shape[0], L.size
+    E = np.empty((n_seq, n_atoms), dtype=np.float64)
+    _lib.check(getattr(lib, fn)(_lib.dptr(lam), _lib.dptr(Bc), M, _lib.dptr(seq), n_seq, _lib.dptr(L),
+                                _lib.dptr(diff), n_atoms, _lib.dptr(env), float(gamma), _lib.dptr(E)))
+    return E
+
+
+def import_DDE_scheme(schemefile):
+    """Import a DDE scheme file or matrix with 14 entries per row (reference mcf.py:24-80)."""
+    if isinstance(schemefile, str):
+        sch_mat = np.loadtxt(schemefile, skiprows=1)
+    elif isinstance(schemefile, np.ndarray):
+        sch_mat = schemefile
+    else:
+        raise TypeError("Unable to import a DDE scheme matrix from input")
+    if sch_mat.ndim == 1:
+        sch_mat = sch_mat[np.newaxis, :]
+    if sch_mat.shape[1] != 14:
+        raise RuntimeError("Detected %s instead of expected 14 colums in"
+                           " PGSE scheme matrix." % sch_mat.shape[1])
+    grad_norm1 = np.sqrt(np.sum(sch_mat[:, :3]**2, axis=1))
+    num_bad_norms1 = np.sum(np.abs(1-grad_norm1[grad_norm1 > 0]) > 1e-4)
+    if num_bad_norms1 > 0:
+        raise ValueError("Detected %d non-zero gradients in the first "
+                         "encoding module which did not have"
+                         " unit norm. Please normalize." % num_bad_norms1)
+    grad_norm2 = np.sqrt(np.sum(sch_mat[:, 7:10]**2, axis=1))
+    num_bad_norms2 = np.sum(np.abs(1-grad_norm2[grad_norm2 > 0]) > 1e-4)
+    if num_bad_norms2 > 0:
+        raise ValueError("Detected %d non-zero gradients in the second "
+                         "encoding module which did not have"
+                         " unit norm. Please normalize." % num_bad_norms2)
+    Del1 = sch_mat[:, 4]
+    del1 = sch_mat[:, 5]
+    Del2 = sch_mat[:, 11]
+    del2 = sch_mat[:, 12]
+    tau_mix = sch_mat[:, 6]
+    TE = sch_mat[:, 13]
+    T = Del1 + del1 + tau_mix + Del2 + del2
+    n_bad_del1 = np.sum(Del1 < del1)
+    if n_bad_del1 > 0:
+        raise ValueError("Detected %d sequences in first encoding module"
+                         " where gradient separation Delta was less than"
+                         " gradient duration delta." % n_bad_del1)
+    n_bad_del2 = np.sum(Del2 < del2)
+    if n_bad_del2 > 0:
+        raise ValueError("Detected %d sequences in second encoding module"
+                         " where gradient separation Delta was less than"
+                         " gradient duration delta." % n_bad_del2)
+    n_bad_T = np.sum(T > TE)
+    if n_bad_T > 0:
+        raise ValueError("Detected %d sequences in which the total "
+                         "diffusion time (Delta1+delta1+tau_mix+Delta2"
+                         "+delta2) exceeded the echo time TE." % n_bad_T)
+    return sch_mat
+
+
+def MCF_DDE(domain, L, diff, scheme,
+            envdir=np.array([0, 0, 1]),
+            gamma=mfu.get_gyromagnetic_ratio('hydrogen'),
+            M=60, *, tables=None):
+    """Intracellular DDE signal attenuation (reference mcf.py:83-235).  ``tables=(Lamvec, B)``
+    replaces the generated eigenvalue / coupling tables (both truncated to M)."""
+    sch_mat = import_DDE_scheme(scheme)
+    Gall1 = sch_mat[:, 3]
+    Gall2 = sch_mat[:, 10]
+    Tall = sch_mat[:, 4] + sch_mat[:, 5] + sch_mat[:, 6] + sch_mat[:, 11] + sch_mat[:, 12]
+    envdir = _normalized_envdir(envdir)
+    M = np.min([M, _M_MAX])
+    dom = _domain_type(domain)
+    Lamvec, B = _tables_for(dom, M, tables)
+    _q_over_p_check(Lamvec, M, Tall, L, diff, gamma, np.maximum(Gall1, Gall2))
+    active = ~((Gall1 == 0) & (Gall2 == 0))
+    if dom != 'cylinder':
+        if np.any(active):
+            raise NotImplementedError()
+        return np.ones(sch_mat.shape[0])
+    E = _launch("mfx_mcf_dde", Lamvec, B, sch_mat, np.atleast_1d(np.float64(L)),
+                np.atleast_1d(np.float64(diff)), envdir, gamma)
+    return E[:, 0]
+
+
+def _pgse_rows(scheme, G, Delta, delta):
+    """(sch_mat [n_seq x 7], scheme_mode) as the reference's argument handling builds it (mcf.py:282-325)."""
+    if scheme is not None:
+        return mfu.import_PGSE_scheme(scheme)
+    all_missing = ((G is None) and (Delta is None) and (delta is None))
+    if all_missing:
+        raise ValueError('Either provide a scheme matrix or specify'
+                         ' G, Delta and delta.')
+    missing = ((G is None) or (Delta is None) or (delta is None))
+    if missing:
+        raise ValueError('Without a scheme matrix provided (non-scheme'
+                         ' mode), G, Delta and delta are all required.')
+    Gall = np.atleast_1d(G)
+    Delall = np.atleast_1d(Delta)
+    delall = np.atleast_1d(delta)
+    samesize = (Gall.size == Delall.size) and (Delall.size == delall.size)
+    if not samesize:
+        raise ValueError('G, Delta and delta should contain the same'
+                         ' number of elements. Detected %d, %d and '
+                         '%d, respectively.' %
+                         (Gall.size, Delall.size, delall.size))
+    n_seq = Gall.size
+    # non-scheme mode: environment along z, gradient along x
+    sch = np.zeros((n_seq, 7))
+    sch[:, 0] = 1.0
+    sch[:, 3] = Gall.ravel()
+    sch[:, 4] = Delall.ravel()
+    sch[:, 5] = delall.ravel()
+    sch[:, 6] = sch[:, 4] + sch[:, 5]
+    return sch
+
+
+def _pgse(domain, L, diff, sch_mat, envdir, gamma, M, tables):
+    Gall = sch_mat[:, 3]
+    Delall = sch_mat[:, 4]
+    delall = sch_mat[:, 5]
+    Tall = Delall + delall
+    n_bad_del = np.sum(Delall < delall)
+    if n_bad_del > 0:
+        raise ValueError('Detected %d sequence(s) with big Delta smaller'
+                         ' than small delta. In a PGSE sequence, Delta>=delta'
+                         ' should always be enforced.' % (n_bad_del,))
+    envdir = _normalized_envdir(envdir)
+    M = np.min([M, _M_MAX])
+    dom = _domain_type(domain)
+    Lamvec, B = _tables_for(dom, M, tables)
+    for a in range(L.size):
+        _q_over_p_check(Lamvec, M, Tall, L[a], diff[a], gamma, Gall)
+    # the reference's loop: G == 0 gives 1; otherwise the direction must be a unit vector, then the domain decides
+    for i in np.nonzero(Gall != 0)[0]:
+        gdirnorm = np.sqrt(np.sum(sch_mat[i, :3]**2))
+        if np.abs(1-gdirnorm) > 1e-4:
+            raise ValueError('Sequence %d: gradient direction not normalized'
+                             ' (found %g)' % (i, gdirnorm))
+        if dom != 'cylinder':
+            raise NotImplementedError()
+    if dom != 'cylinder':
+        return np.ones((sch_mat.shape[0], L.size))
+    return _launch("mfx_mcf_pgse", Lamvec, B, sch_mat, L, diff, envdir, gamma)
+
+
+def MCF_PGSE_atoms(domain, L, diff, *, scheme, envdir=np.array([0, 0, 1]),
+                   gamma=mfu.get_gyromagnetic_ratio('hydrogen'), M=60, tables=None):
+    """MCF_PGSE for many (radius, diffusivity) atoms at once: ``L`` and ``diff`` are 1-D arrays of
+    equal length; returns ``[n_seq, n_atoms]``, laid out like ``dic['dictionary']``.  Each atom is
+    validated as MCF_PGSE validates its single one.  ``tables=(Lamvec, B)`` overrides the generated
+    tables."""
+    L = np.atleast_1d(np.asarray(L, dtype=np.float64))
+    diff = np.atleast_1d(np.asarray(diff, dtype=np.float64))
+    if L.ndim != 1 or diff.ndim != 1 or L.size != diff.size:
+        raise ValueError('L and diff should be 1-D arrays of the same length. Detected shapes %s and %s.'
+                         % (L.shape, diff.shape))
+    sch_mat = _pgse_rows(scheme, None, None, None)
+    return _pgse(domain, L, diff, sch_mat, envdir, gamma, M, tables)
+
+
+def MCF_PGSE(domain, L, diff, *,  # all subsequent args must be named
+             scheme=None, envdir=np.array([0, 0, 1]),
+             G=None, Delta=None, delta=None,
+             L2=None,
+             gamma=mfu.get_gyromagnetic_ratio('hydrogen'), M=60, tables=None):
+    """Intracellular PGSE signal attenuation using the MCF approach (reference mcf.py:238-426).
+
+    Either ``scheme`` ([gx gy gz G Delta delta TE] rows) or all of ``G``, ``Delta``, ``delta``
+    (non-scheme mode: gradient along x, environment along z).  ``L`` is the radius of the
+    cylinder; ``L2`` (finite cylinders) is accepted and unused, as in the reference.
+    ``tables=(Lamvec, B)`` overrides the generated tables.  One atom of :func:`MCF_PGSE_atoms`.
+    """
+    sch_mat = _pgse_rows(scheme, G, Delta, delta)
+    return _pgse(domain, np.atleast_1d(np.float64(L)), np.atleast_1d(np.float64(diff)), sch_mat, envdir,
+                 gamma, M, tables)[:, 0]
