@@ -27,6 +27,10 @@ EXPORTS = [
 # every symbol include/mfx_mcf.h declares (MCF signal synthesis; versioned on its own)
 MCF_EXPORTS = ["mfx_mcf_abi_version", "mfx_mcf_pgse", "mfx_mcf_dde"]
 
+# every symbol include/mfx_rot2d.h declares (2-D protocol rotation; versioned on its own)
+ROT2D_EXPORTS = ["mfx_rot2d_abi_version", "mfx_rot2d_create", "mfx_rot2d_destroy", "mfx_rot2d_rotate",
+                 "mfx_rot2d_rotate_dev", "mfx_rot2d_rotate_cols", "mfx_rot2d_rotate_cols_dev"]
+
 
 class MfxError(RuntimeError):
     pass
@@ -107,6 +111,15 @@ def lib():
     for fn in ("mfx_mcf_pgse", "mfx_mcf_dde"):
         getattr(L, fn).argtypes = [dp, dp, C.c_int, dp, C.c_int64, dp, dp, C.c_int64, dp, C.c_double, dp]
         getattr(L, fn).restype = C.c_int
+    L.mfx_rot2d_abi_version.restype = C.c_int
+    L.mfx_rot2d_create.argtypes = [dp, C.c_int, ip, ip, C.c_int, ip, dp, ip, ip, ip, dp, C.c_int, ip, dp, dp, C.c_int,
+                                   C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(vp)]
+    L.mfx_rot2d_destroy.argtypes = [vp]
+    L.mfx_rot2d_destroy.restype = None
+    L.mfx_rot2d_rotate.argtypes = [vp, dp, C.c_int64, dp, ip]
+    L.mfx_rot2d_rotate_dev.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
+    L.mfx_rot2d_rotate_cols.argtypes = [vp, dp, ip, C.c_int64, dp, ip]
+    L.mfx_rot2d_rotate_cols_dev.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp]
     _lib = L
     return L
 

@@ -232,6 +232,30 @@ def rotate_columns_dev(plan, d_dirs, d_cols, normalise=False):
     return out
 
 
+def rotate2d_dev(tables, d_dirs, d_cols=None):
+    """Device-resident 2-D protocol rotation (mfx_rot2d_rotate_dev / mfx_rot2d_rotate_cols_dev) for a
+    mf_utils.RotateAtom2DTables: torch CUDA tensors dirs [B,3] f64 (and cols [B] int: one atom per direction)
+    -> (out [B,M,N] f64, or [B,M] with cols; status [B,4] int32), enqueued on torch's current stream without a
+    host synchronisation.  A failing direction's output is NaN; ``tables.raise_for_status(status.cpu())``
+    raises the reference's exception for the first one."""
+    import torch
+    assert d_dirs.is_cuda and d_dirs.dtype == torch.float64 and d_dirs.is_contiguous()
+    B = d_dirs.shape[0]
+    h = tables.handle()
+    st = torch.cuda.current_stream(d_dirs.device).cuda_stream
+    status = torch.empty((B, 4), dtype=torch.int32, device=d_dirs.device)
+    if d_cols is None:
+        out = torch.empty((B, tables.M, tables.N), dtype=torch.float64, device=d_dirs.device)
+        L.check(L.lib().mfx_rot2d_rotate_dev(h, d_dirs.data_ptr(), B, out.data_ptr(), status.data_ptr(), st))
+    else:
+        cols = d_cols.to(torch.int32).contiguous()
+        assert cols.shape == (B,)
+        out = torch.empty((B, tables.M), dtype=torch.float64, device=d_dirs.device)
+        L.check(L.lib().mfx_rot2d_rotate_cols_dev(h, d_dirs.data_ptr(), cols.data_ptr(), B, out.data_ptr(),
+                                                  status.data_ptr(), st))
+    return out, status
+
+
 def cleanup_select(f1, f2, p1, p2, cos_min, ratio, w_keep, w_small, device=0):
     """Voxel loop of cleanup_2fascicles (mfx_cleanup_2fascicles; ref mf.py:170-335): weights f1, f2 [n] and directions p1, p2
     [n x 3] of the ROI voxels -> (peaks [n x 6], count [n])."""

@@ -12,6 +12,10 @@ init_PGSE_multishell_interp (ref:1959)         per-shell knot tables built once 
                                                uploaded lazily to HBM (mfx_tables_create)
 interp_PGSE_from_multishell (ref:1693)         checks on host, evaluation on device (mfx_rotate)
 rotate_atom (ref:1205)                         per-shell knot tables on host, evaluation on device
+rotate_atom_2Dprotocol (ref:1440)              reference side on host (NumPy), per-direction plan and
+                                               evaluation on device (mfx_rot2d_*)
+rotate_scheme_mat, vrrotvec2mat, rotate_vector host (O(M) NumPy)
+get_perp_vector, project_PGSE_scheme_xy_plane  host
 import_PGSE_scheme (ref:2128)                  host (input normalisation, once per fit)
 get_PGSE_scheme_from_bval_bvec_dense (2197)    host
 monte_carlo_average (ref:2762)                 device (mfx_monte_carlo_average)
@@ -33,7 +37,9 @@ from . import engine
 
 __all__ = ["get_gyromagnetic_ratio", "solve_exhaustive_posweights", "init_PGSE_multishell_interp",
            "interp_PGSE_from_multishell", "rotate_atom", "RotateAtomTables", "import_PGSE_scheme",
-           "get_PGSE_scheme_from_bval_bvec_dense", "loadmat", "MultiShellInterpolator"]
+           "get_PGSE_scheme_from_bval_bvec_dense", "loadmat", "MultiShellInterpolator",
+           "rotate_atom_2Dprotocol", "RotateAtom2DTables", "rotate_scheme_mat", "vrrotvec2mat", "rotate_vector",
+           "get_perp_vector", "project_PGSE_scheme_xy_plane"]
 
 
 def get_gyromagnetic_ratio(element='H'):
@@ -319,6 +325,307 @@ def rotate_atom(sig, sch_mat, ordir, newdir, DIFF, S0, warnings=True):
         raise ValueError('Nan detected after rotation of substrate(s) for %d substrate(s): [%s]'
                          % (bad.shape[0], " ".join("%d" % b for b in bad)))
     return np.reshape(out, T.sig_shape)
+
+
+# ---------------------------------------------------------------------------------------------
+# rotations and 2-D (AxCaliber-like) protocols
+# ---------------------------------------------------------------------------------------------
+def get_perp_vector(v):
+    """Unit vector(s) with a zero dot product with ``v`` along the first axis (ref:769-811).
+
+    Where ``v`` has zero entries the result has ones there; otherwise its first entries are 1 and the
+    last one cancels the dot product.  Normalised along the first axis."""
+    u = np.zeros(v.shape)
+    zero = np.abs(v) < (10 * 2.2204e-16)
+    full = np.sum(zero, axis=0) == 0
+    u[zero] = 1
+    u[:-1, full] = 1
+    u[-1, full] = -np.sum(v[:-1, full], axis=0) / v[-1, full]
+    return u / np.sqrt(np.sum(u ** 2, axis=0))
+
+
+def rotate_vector(v, rot_axis, theta):
+    """Rotation of the 3-vector ``v`` by ``theta`` radians about the unit axis ``rot_axis`` (ref:814-839)."""
+    nsq = np.sum(rot_axis ** 2)
+    if ~np.isclose(1, nsq):
+        raise ValueError("rotation axis should have unit norm, detected %g" % np.sqrt(nsq))
+    c = np.cos(theta)
+    return c * v + np.sin(theta) * np.cross(rot_axis, v) + (1 - c) * (np.dot(rot_axis, v) * rot_axis)
+
+
+def vrrotvec2mat(rotax, theta):
+    """3x3 rotation matrix of angle ``theta`` about the unit axis ``rotax`` (ref:842-862)."""
+    if rotax.size != 3:
+        raise ValueError("rotation axis should be a 3-element NumPy array")
+    if ~np.isclose(np.sum(rotax ** 2), 1):
+        raise ValueError("rotation axis should have unit norm")
+    s, c = np.sin(theta), np.cos(theta)
+    t = 1 - c
+    x, y, z = rotax[0], rotax[1], rotax[2]
+    return np.array([[t * x * x + c, t * x * y - s * z, t * x * z + s * y],
+                     [t * x * y + s * z, t * y * y + c, t * y * z - s * x],
+                     [t * x * z - s * y, t * y * z + s * x, t * z * z + c]])
+
+
+def rotate_scheme_mat(sch_mat, cyldir1, cyldir2):
+    """Scheme matrix seen by a fascicle along ``cyldir1`` when the fascicle is along ``cyldir2`` (ref:1153-1202).
+
+    Gradients are rotated by ``vrrotvec2mat(cyldir1 x cyldir2, -arccos(cyldir1 . cyldir2))``, entries with
+    magnitude <= eps are set to 0 and non-zero rows renormalised.  When the two directions are parallel the
+    input object itself is returned, as the reference does."""
+    if cyldir1.size != 3 or cyldir2.size != 3:
+        raise ValueError("cyldir1 and cyldir2 should be 3-elements NumPy arrays.")
+    if ~np.isclose(np.sum(cyldir1 ** 2), 1) or ~np.isclose(np.sum(cyldir2 ** 2), 1):
+        raise ValueError("cyldir1 and cyldir2 should have unit norm.")
+    ax = np.cross(cyldir1, cyldir2)
+    axsq = np.sum(ax ** 2)
+    if not axsq > 0:
+        return sch_mat
+    R = vrrotvec2mat(ax / np.sqrt(axsq), -np.arccos(np.dot(cyldir1, cyldir2)))
+    g = sch_mat[:, :3] @ R.T
+    g[np.abs(g) <= np.finfo(float).eps] = 0
+    gn = np.sqrt(np.sum(g ** 2, axis=1, keepdims=True))
+    nz = np.squeeze(gn > 0)
+    g[nz, :] = g[nz, :] / gn[nz, :]
+    if sch_mat.shape[1] > 3:
+        return np.hstack((g, sch_mat[:, 3:]))
+    return g
+
+
+def project_PGSE_scheme_xy_plane(sch_mat):
+    """Scheme with the gradients' z component removed (ref:2088-2125).
+
+    ``sch_mat``: array, or path of a text file with a one-line header.  The result has gz = 0, unit
+    [gx, gy] and G' with (gz G)^2 + G'^2 = G^2; zero gradients stay zero, the other columns are kept."""
+    if isinstance(sch_mat, str):
+        sch_mat = np.loadtxt(sch_mat, skiprows=1)
+    if sch_mat.ndim == 1:
+        sch_mat = sch_mat[np.newaxis, :]
+    gxy = np.sqrt(sch_mat[:, 0] ** 2 + sch_mat[:, 1] ** 2)
+    out = np.zeros(sch_mat.shape)
+    out[:, 3] = sch_mat[:, 3] * gxy
+    gxy[gxy == 0] = 1
+    out[:, :2] = sch_mat[:, :2] / gxy[:, np.newaxis]
+    out[sch_mat[:, 3] == 0, :4] = 0
+    out[:, 4:] = sch_mat[:, 4:]
+    Gz = np.abs(sch_mat[:, 2]) * sch_mat[:, 3]
+    G_chk_sq = out[:, 3] ** 2 + Gz ** 2
+    assert np.all(np.abs(np.sqrt(G_chk_sq) - sch_mat[:, 3]) <= 1e-4 * sch_mat[:, 3]), \
+        "Inconsistency with gradient intensities during projection in xy plane"
+    return out
+
+
+# status codes of include/mfx_rot2d.h
+ROT2D_OK, ROT2D_NEWDIR_NORM, ROT2D_CHK_NEW, ROT2D_CHK_PAR_NEW, ROT2D_REF_UNIQUE, ROT2D_REF_PAIRS, ROT2D_NEW_UNIQUE, \
+    ROT2D_NEW_PAIRS, ROT2D_VANISHED, ROT2D_INTERP_B0, ROT2D_NO_REF_LINE = range(11)
+
+
+def _perp_components(sm_eff, G):
+    """g_perp (normalised first two columns, a view of ``sm_eff``, normalised in place like the reference),
+    |g_perp| before normalisation, G_perp and G_par (ref:1509-1516, 1532-1539)."""
+    g_perp = sm_eff[:, 0:2]
+    n = np.sqrt(np.sum(g_perp ** 2, axis=1))
+    nz = n > 0
+    g_perp[nz, :] = sm_eff[nz, 0:2] / n[nz][:, np.newaxis]
+    return g_perp, n, G * n, np.abs(sm_eff[:, 2]) * G
+
+
+class RotateAtom2DTables:
+    """Direction-independent part of :func:`rotate_atom_2Dprotocol` (ref:1440-1690), built once on the host
+    with the reference's NumPy arithmetic and kept in HBM: the reference fascicle's S_par / S_perp, per
+    (Delta, delta) pair its unique perpendicular directions and opposite pairs, the b0 values that rows
+    without a perpendicular component take, and one sorted knot table per reference line.
+
+    ``rotate(newdirs)`` -> [B, M, N] and ``rotate_cols(newdirs, cols)`` -> [B, M] evaluate B directions
+    in one device call; ``engine.rotate2d_dev`` is the device-resident variant.  ``sch_mat`` is not
+    modified (the reference normalises its first two columns in place when ``refdir`` is along z; the
+    new fascicle's side sees those normalised columns here too)."""
+
+    def __init__(self, sig, sch_mat, refdir, DIFF, device=0):
+        sig = np.asarray(sig, dtype=np.float64)
+        self.sig_shape = sig.shape
+        if sig.ndim == 1:
+            sig = sig[:, np.newaxis]
+        sch = np.array(sch_mat, dtype=np.float64)          # private copy (see the class docstring)
+        if np.any(sch[:, 2] != 0):
+            raise ValueError("Use the original schemefile with zeros for gz.\n"
+                             "Specify the reference and new orientations separately.")
+        if self.sig_shape[0] != sch.shape[0]:
+            raise ValueError("Signal and scheme matrix must have the same number of elements (sequences) along "
+                             "their first dimension. Detected %d and %d." % (self.sig_shape[0], sch.shape[0]))
+        gam = get_gyromagnetic_ratio('H')
+        G, Delta, delta = sch[:, 3], sch[:, 4], sch[:, 5]
+        is_b0 = G == 0
+        sm_ref = rotate_scheme_mat(sch, np.array([0, 0, 1]), np.asarray(refdir))
+        g_perp_ref, _, G_perp_ref, G_par_ref = _perp_components(sm_ref, G)
+        chk_ref = np.isclose(G ** 2, G_perp_ref ** 2 + G_par_ref ** 2)
+        assert np.all(chk_ref), "Inconsistency in parallel and perpendicular gradient components for reference fasicle."
+        b_par_ref = (gam * delta * G_par_ref) ** 2 * (Delta - delta / 3)
+        S_par_ref = np.exp(-b_par_ref * DIFF)
+        S_perp_ref = sig / S_par_ref[:, np.newaxis]
+        chk_par_ref = np.isclose(S_par_ref[is_b0], 1)
+        assert np.all(chk_par_ref), "Reference fascicle: parallel signal should  be one in b0 sequences."
+        self.sm_eff_ref, self.S_par_ref, self.S_perp_ref = sm_ref, S_par_ref, S_perp_ref
+
+        M, N = sig.shape
+        _, i_un = np.unique(sch[:, 4:6], return_inverse=True, axis=0)
+        i_un = np.asarray(i_un).reshape(-1)
+        P = int(i_un.max()) + 1
+        # constant rows: every b0 row's signal, then the mean b0 signal of pairs with several b0 rows
+        cst = [sig[m] for m in np.where(is_b0)[0]]
+        row_const = np.full(M, -1, dtype=np.int32)
+        row_const[is_b0] = np.arange(len(cst), dtype=np.int32)
+        pair_off, pair_rows = [0], []
+        ref_info = np.zeros((P, 3), dtype=np.int32)
+        ref_dirs = np.zeros((P, 5, 2))
+        ref_tab = np.full((P, 5), -1, dtype=np.int32)
+        van_const = np.full(P, -1, dtype=np.int32)
+        tab_off, kx, ky = [0], [], []
+        for p in range(P):
+            ind = np.where(i_un == p)[0]
+            pair_rows.append(ind)
+            pair_off.append(pair_off[-1] + ind.size)
+            b0 = np.where(is_b0 & (i_un == p))[0]
+            if b0.size == 1:
+                van_const[p] = row_const[b0[0]]
+            elif b0.size > 1:
+                van_const[p] = len(cst)
+                cst.append(np.mean(sig[b0, :], axis=0))
+            # reference side (ref:1571-1601); a failure is recorded, the device reports it in the reference's order
+            un, inv = np.unique(g_perp_ref[ind, :], return_inverse=True, axis=0)
+            inv = np.asarray(inv).reshape(-1)
+            if un.shape[0] not in (3, 5):
+                ref_info[p] = (ROT2D_REF_UNIQUE, un.shape[0], 0)
+                continue
+            ig, ig_op = np.where(np.isclose(un @ un.T, -1))
+            if ig.size not in (2, 4):
+                ref_info[p] = (ROT2D_REF_PAIRS, ig.size, 0)
+                continue
+            ref_info[p] = (ROT2D_OK, 0, un.shape[0])
+            ref_dirs[p, :un.shape[0]] = un
+            for u in range(un.shape[0]):
+                k = np.where(ig == u)[0]
+                if k.size != 1:
+                    ref_tab[p, u] = -1 - k.size          # the reference's comparison would not broadcast
+                    continue
+                rows = ind[(inv == ig[k[0]]) | (inv == ig_op[k[0]])]
+                x = G_perp_ref[rows] * np.sign(g_perp_ref[rows, :] @ un[u])
+                order = np.argsort(x, kind="mergesort")     # interp1d(assume_sorted=False)
+                ref_tab[p, u] = len(tab_off) - 1
+                kx.append(x[order])
+                ky.append(S_perp_ref[rows, :][order])
+                tab_off.append(tab_off[-1] + rows.size)
+        self.M, self.N, self.P, self.device = M, N, P, device
+        self._arrays = dict(
+            sch=np.ascontiguousarray(sch[:, :6]), pair_off=np.array(pair_off, dtype=np.int32),
+            pair_rows=np.ascontiguousarray(np.concatenate(pair_rows), dtype=np.int32), ref_info=ref_info,
+            ref_dirs=ref_dirs, ref_tab=ref_tab, row_const=row_const, van_const=van_const,
+            cst=np.ascontiguousarray(np.array(cst).reshape(-1, N)) if cst else np.zeros((1, N)),
+            tab_off=np.array(tab_off, dtype=np.int32),
+            kx=np.ascontiguousarray(np.concatenate(kx)) if kx else np.zeros(1),
+            ky=np.ascontiguousarray(np.concatenate(ky, axis=0)) if ky else np.zeros((1, N)))
+        self.num_const = len(cst)
+        self.num_tables = len(tab_off) - 1
+        self.gamma, self.DIFF = gam, float(DIFF)
+        self._h = None
+
+    def handle(self):
+        if self._h is None:
+            a = self._arrays
+            h = C.c_void_p()
+            L.check(L.lib().mfx_rot2d_create(
+                L.dptr(a["sch"]), self.M, L.iptr(a["pair_off"]), L.iptr(a["pair_rows"]), self.P, L.iptr(a["ref_info"]),
+                L.dptr(a["ref_dirs"]), L.iptr(a["ref_tab"]), L.iptr(a["row_const"]), L.iptr(a["van_const"]),
+                L.dptr(a["cst"]), self.num_const, L.iptr(a["tab_off"]), L.dptr(a["kx"]), L.dptr(a["ky"]),
+                self.num_tables, self.N, self.gamma, self.DIFF, self.device, C.byref(h)))
+            self._h = h
+        return self._h
+
+    def close(self):
+        if self._h is not None:
+            L.lib().mfx_rot2d_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def error_for(self, rec):
+        """The exception the reference raises for a status record {code, pair, value, value2}."""
+        code, p, v, v2 = (int(r) for r in rec)
+        P = self.P
+        if code == ROT2D_NEWDIR_NORM:
+            return ValueError("cyldir1 and cyldir2 should have unit norm.")
+        if code == ROT2D_CHK_NEW:
+            return AssertionError("Inconsistency in parallel and perpendicular gradient components for new fascicle.")
+        if code == ROT2D_CHK_PAR_NEW:
+            return AssertionError("New fascicle: parallel signal should  be equal to 1 in b0 sequences.")
+        if code in (ROT2D_REF_UNIQUE, ROT2D_NEW_UNIQUE):
+            return AssertionError("Problem at delta pair %d/%d: found %d unique gradient directions in plane "
+                                  "perpendicular to %s fascicle (including b0 zero dirs)."
+                                  % (p + 1, P, v, "reference" if code == ROT2D_REF_UNIQUE else "new"))
+        if code == ROT2D_REF_PAIRS:
+            return AssertionError("Problem at delta pair %d/%d: found %d instead of 4 (2x2, redundant) pairs of "
+                                  "opposite directions in plane perpendicular to reference fascicle." % (p + 1, P, v))
+        if code == ROT2D_NEW_PAIRS:
+            return AssertionError("Problem at delta pair %d/%d: found %d instead of 2 pairs of opposite directions, "
+                                  "in plane  perpendicular to new fascicle." % (p + 1, P, v))
+        if code == ROT2D_VANISHED:
+            return AssertionError("Shell %d/%d: some new line directions are completely parallel to new fascicle, "
+                                  "implying free diffusion. However, no b0 measurements in the reference signal are "
+                                  "available for this shell. We therefore can't properly scale the new signal."
+                                  % (p + 1, P))
+        if code == ROT2D_INTERP_B0:
+            return AssertionError("Problem at delta pair %d/%d, new line direction %d/%d: trying to interpolate b0 "
+                                  "sequences." % (p + 1, P, v, v2))
+        if code == ROT2D_NO_REF_LINE:
+            return ValueError("operands could not be broadcast together with shapes (%d,) (%d,) " % (v, v2))
+        return L.MfxError("mfx_rot2d: unknown status %d" % code)
+
+    def raise_for_status(self, status):
+        """Raise the reference's exception for the lowest-index failing direction of a [B, 4] status array."""
+        status = np.asarray(status).reshape(-1, 4)
+        bad = np.nonzero(status[:, 0])[0]
+        if bad.size:
+            raise self.error_for(status[bad[0]])
+
+    def rotate(self, newdirs):
+        """Signals for fascicles along each of ``newdirs`` [B, 3] (not normalised) -> [B, M, N]."""
+        d = L.f64c(np.asarray(newdirs, dtype=np.float64).reshape(-1, 3))
+        out = np.zeros((d.shape[0], self.M, self.N))
+        status = np.zeros((d.shape[0], 4), dtype=np.int32)
+        if d.shape[0]:
+            L.check(L.lib().mfx_rot2d_rotate(self.handle(), L.dptr(d), d.shape[0], L.dptr(out), L.iptr(status)))
+        self.raise_for_status(status)
+        return out
+
+    def rotate_cols(self, newdirs, cols):
+        """Atom ``cols[b]`` for a fascicle along ``newdirs[b]`` -> [B, M]."""
+        d = L.f64c(np.asarray(newdirs, dtype=np.float64).reshape(-1, 3))
+        c = np.ascontiguousarray(np.asarray(cols).reshape(-1), dtype=np.int32)
+        if c.shape[0] != d.shape[0]:
+            raise ValueError("rotate_cols: one atom index per direction")
+        out = np.zeros((d.shape[0], self.M))
+        status = np.zeros((d.shape[0], 4), dtype=np.int32)
+        if d.shape[0]:
+            L.check(L.lib().mfx_rot2d_rotate_cols(self.handle(), L.dptr(d), L.iptr(c), d.shape[0], L.dptr(out),
+                                                  L.iptr(status)))
+        self.raise_for_status(status)
+        return out
+
+
+def rotate_atom_2Dprotocol(sig, sch_mat, refdir, newdir, DIFF):
+    """Signals of a 2-D (AxCaliber-like) protocol rotated from a fascicle along ``refdir`` to one along
+    ``newdir`` (ref:1440-1690).  ``sig`` [M] or [M, N]; returns the same shape.  ``newdir`` is not normalised."""
+    T = RotateAtom2DTables(sig, sch_mat, refdir, DIFF)
+    newdir = np.asarray(newdir, dtype=np.float64)
+    if newdir.size != 3:
+        raise ValueError("cyldir1 and cyldir2 should be 3-elements NumPy arrays.")
+    if ~np.isclose(np.sum(newdir ** 2), 1):         # also checked on the device, for batches
+        raise ValueError("cyldir1 and cyldir2 should have unit norm.")
+    return np.reshape(T.rotate(newdir.reshape(1, 3))[0], T.sig_shape)
 
 
 # ---------------------------------------------------------------------------------------------
