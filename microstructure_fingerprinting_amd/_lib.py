@@ -31,6 +31,9 @@ MCF_EXPORTS = ["mfx_mcf_abi_version", "mfx_mcf_pgse", "mfx_mcf_dde"]
 ROT2D_EXPORTS = ["mfx_rot2d_abi_version", "mfx_rot2d_create", "mfx_rot2d_destroy", "mfx_rot2d_rotate",
                  "mfx_rot2d_rotate_dev", "mfx_rot2d_rotate_cols", "mfx_rot2d_rotate_cols_dev"]
 
+# every symbol include/mfx_predict.h declares (forward model and magnitude noise; versioned on its own)
+PREDICT_EXPORTS = ["mfx_predict_abi_version", "mfx_predict_dev", "mfx_predict", "mfx_sos_noise_dev", "mfx_sos_noise"]
+
 
 class MfxError(RuntimeError):
     pass
@@ -120,6 +123,13 @@ def lib():
     L.mfx_rot2d_rotate_dev.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
     L.mfx_rot2d_rotate_cols.argtypes = [vp, dp, ip, C.c_int64, dp, ip]
     L.mfx_rot2d_rotate_cols_dev.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp]
+    L.mfx_predict_abi_version.restype = C.c_int
+    L.mfx_predict_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int64, vp, vp, C.c_int, C.c_int,
+                                  C.c_uint64, C.c_uint64, vp, vp, vp, vp]
+    L.mfx_predict.argtypes = [vp, dp, dp, C.c_int, C.c_int, C.c_int, dp, dp, C.c_int, C.c_int64, dp, dp, C.c_int, C.c_int,
+                              C.c_uint64, C.c_uint64, dp, dp]
+    L.mfx_sos_noise_dev.argtypes = [vp, C.c_int64, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint64, vp, C.c_int, vp]
+    L.mfx_sos_noise.argtypes = [dp, C.c_int64, dp, C.c_int, C.c_int, C.c_uint64, C.c_uint64, dp, C.c_int]
     _lib = L
     return L
 

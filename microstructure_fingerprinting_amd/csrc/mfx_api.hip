@@ -267,6 +267,10 @@ struct mfx_plan {
   }
 };
 
+void mfx_plan_view(const mfx_plan* p, TablesDev* T, PlanDev* P, int* device) {
+  *T = p->t->d; *P = p->d; *device = p->t->device;
+}
+
 static int require_device(int device) {
   int n = mfx_device_count();
   if (n <= 0) return fail(MFX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)");

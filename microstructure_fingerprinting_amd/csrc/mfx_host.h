@@ -129,6 +129,9 @@ int mfx_fb_accumulate(const int* d_counters, int n, hipStream_t st, int offset =
 int mfx_fb_accumulate_audit(const int* d_audit, hipStream_t st);   // [0] beyond DC/4 (+), [1] largest error (max), [2] audited pairs (+) -> counters 8..10
 int mfx_fb_end(hipStream_t st);
 
+// the device-side views of a plan and of its tables, and the device they live on (for translation units other than mfx_api.hip)
+void mfx_plan_view(const mfx_plan* p, TablesDev* T, PlanDev* P, int* device);
+
 // ---- kernel launchers, one translation unit each
 // FP64 two-fascicle kernel (tu_k2.hip).  With a.list_count set, a.vox_list is a device-side list whose length only the
 // device knows: the launch covers nvox blocks and those beyond *a.list_count exit at once.

@@ -232,6 +232,187 @@ def rotate_columns_dev(plan, d_dirs, d_cols, normalise=False):
     return out
 
 
+SIGMA_SCALAR, SIGMA_VOXEL, SIGMA_ELEMENT = 0, 1, 2   # include/mfx_predict.h
+_U64 = (1 << 64) - 1
+
+
+def _predict_shapes(plan, p_shape, pk_shape, maxfasc, csf_on, ear_on, y_shape, M_csf, ear_shape, E):
+    """Argument checks shared by predict and predict_dev (before any device call); returns V."""
+    maxfasc = int(maxfasc)
+    if maxfasc < 0 or maxfasc > 3:
+        raise ValueError("maxfasc must be 0..3")
+    npar = num_params(maxfasc, csf_on, ear_on)
+    if len(p_shape) != 2 or p_shape[1] != npar:
+        raise ValueError("params should have %d columns (maxfasc = %d, csf_on = %s, ear_on = %s), got shape %s"
+                         % (npar, maxfasc, bool(csf_on), bool(ear_on), tuple(p_shape)))
+    V = p_shape[0]
+    if maxfasc > 0 and (pk_shape is None or tuple(pk_shape) != (V, 3 * maxfasc)):
+        raise ValueError("peaks should have shape (%d, %d)" % (V, 3 * maxfasc))
+    if csf_on and M_csf != plan.M:
+        raise ValueError("sig_csf has %s entries, protocol has %d" % (M_csf, plan.M))
+    if ear_on and (ear_shape is None or tuple(ear_shape) != (plan.M, E) or E < 1):
+        raise ValueError("sig_ear should have shape (%d, E) with E >= 1" % plan.M)
+    if y_shape is not None and tuple(y_shape) != (V, plan.M):
+        raise ValueError("data has shape %s, protocol has %d measurements for %d voxels" % (tuple(y_shape), plan.M, V))
+    return V
+
+
+def _sigma_mode(shape, numel, V, M, what="sigma_g"):
+    if numel == 1:
+        return SIGMA_SCALAR
+    if tuple(shape) == (V, M):
+        return SIGMA_ELEMENT
+    if tuple(shape) in ((V,), (V, 1)):
+        return SIGMA_VOXEL
+    raise ValueError("%s should be a scalar, one value per voxel (%d) or one per element (%d, %d), got shape %s"
+                     % (what, V, V, M, tuple(shape)))
+
+
+def predict_bad_rows(params, maxfasc, csf_on, ear_on, N, E):
+    """bool [V]: the rows of params [V x num_params] that predict refuses - a weight M0 * nu that is negative or not
+    finite, or, beside a positive weight, an atom index that is not an integer in [0, N) (fascicles) or [0, E) (EAR).
+    The same rule as the library's (csrc/predict.hip), for callers that want to set such rows aside first."""
+    P = np.asarray(params, dtype=np.float64)
+    F = int(maxfasc)
+    cols = [(1 + k, 1 + F + k, N) for k in range(F)]
+    if csf_on:
+        cols.append((1 + 2 * F, None, 0))
+    if ear_on:
+        cols.append((1 + 2 * F + int(bool(csf_on)), 2 + 2 * F + int(bool(csf_on)), E))
+    bad = np.zeros(P.shape[0], dtype=bool)
+    with np.errstate(invalid='ignore', over='ignore'):
+        for iw, iid, lim in cols:
+            w = P[:, 0] * P[:, iw]
+            bad |= ~(w >= 0) | np.isinf(w)
+            if iid is not None:
+                i = P[:, iid]
+                bad |= (w > 0) & ~((i >= 0) & (i < lim) & (i == np.floor(i)))
+    return bad
+
+
+def predict_dev(plan, d_params, d_peaks, maxfasc, csf_on=False, ear_on=False, d_sig_csf=None, d_sig_ear=None, E=0,
+                d_Y=None, sigma_g=None, ncoils=0, seed=0, offset=0, out=None, check=True):
+    """Forward model on the device (mfx_predict_dev): parameter rows [V x num_params] in the layout fit_batch_dev
+    returns and peaks [V x 3 maxfasc] (torch CUDA float64 tensors) -> the signal [V x M] they stand for.  With
+    ``ncoils`` > 0 the magnitude noise of ``sos_noise_dev`` is applied in the same pass, ``sigma_g`` a number or a
+    tensor with one value, one per voxel or one per element; element (v, m) draws with index ``offset + v M + m``.
+    With ``d_Y`` [V x M] the per-voxel residual sum of squares and R2 come back too: ``(out, stats [V x 2])``.
+    Enqueues on torch's current stream; ``check=True`` then waits and raises the ValueError of a bad atom index or
+    weight (that voxel's row is NaN) or of a direction that is not a unit vector."""
+    import torch
+    assert d_params.is_cuda and d_params.dtype == torch.float64 and d_params.is_contiguous()
+    dev = d_params.device
+    for t in (d_peaks if maxfasc > 0 else None, d_sig_csf if csf_on else None, d_sig_ear if ear_on else None, d_Y):
+        assert t is None or (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous())
+    V = _predict_shapes(plan, d_params.shape, d_peaks.shape if maxfasc > 0 else None, maxfasc, csf_on, ear_on,
+                        d_Y.shape if d_Y is not None else None, d_sig_csf.numel() if csf_on else None,
+                        d_sig_ear.shape if ear_on else None, E)
+    M = plan.M
+    mode, d_sigma = SIGMA_SCALAR, None
+    if ncoils:
+        if sigma_g is None:
+            raise ValueError("noise (ncoils > 0) needs sigma_g")
+        d_sigma = (sigma_g.to(device=dev, dtype=torch.float64).contiguous() if torch.is_tensor(sigma_g)
+                   else torch.full((1,), float(sigma_g), dtype=torch.float64, device=dev))
+        mode = _sigma_mode(d_sigma.shape, d_sigma.numel(), V, M)
+    if out is None:
+        out = torch.empty((V, M), dtype=torch.float64, device=dev)
+    assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (V, M)
+    stats = torch.empty((V, 2), dtype=torch.float64, device=dev) if d_Y is not None else None
+    status = torch.zeros(2, dtype=torch.int32, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    L.check(L.lib().mfx_predict_dev(plan.handle(), d_params.data_ptr(), d_peaks.data_ptr() if maxfasc > 0 else None,
+                                    int(maxfasc), int(bool(csf_on)), int(bool(ear_on)),
+                                    d_sig_csf.data_ptr() if csf_on else None, d_sig_ear.data_ptr() if ear_on else None,
+                                    int(E), V, d_Y.data_ptr() if d_Y is not None else None,
+                                    d_sigma.data_ptr() if d_sigma is not None else None, mode, int(ncoils),
+                                    int(seed) & _U64, int(offset) & _U64, out.data_ptr(),
+                                    stats.data_ptr() if stats is not None else None, status.data_ptr(), st))
+    if check:
+        flag, vox = status.tolist()
+        dir_err = None
+        try:     # read (and clear) the plan's word in any case, so that nothing of this batch is reported by the next call
+            L.check(L.lib().mfx_plan_status(plan.handle(), st))
+        except ValueError as e:
+            dir_err = e
+        if flag:
+            raise ValueError("predict: voxel %d of the batch has %s" % (vox, " and ".join(
+                w for b, w in ((1, "an atom index that is not an integer inside its dictionary"),
+                               (2, "a weight M0 * nu that is negative or not finite")) if flag & b)))
+        if dir_err is not None:
+            raise dir_err
+    return out if stats is None else (out, stats)
+
+
+def predict(plan, params, peaks, maxfasc, csf_on=False, ear_on=False, sig_csf=None, sig_ear=None, E=0, Y=None,
+            sigma_g=None, ncoils=0, seed=0, offset=0):
+    """predict_dev on NumPy buffers (mfx_predict): returns out [V x M], or (out, stats [V x 2]) when Y is given.
+    Bad atom indices and weights raise ValueError before anything is launched."""
+    params = L.f64c(params)
+    pk = L.f64c(peaks) if maxfasc > 0 else None
+    sc = L.f64c(sig_csf).reshape(-1) if csf_on else None
+    se = L.f64c(sig_ear) if ear_on else None
+    Yc = L.f64c(Y) if Y is not None else None
+    V = _predict_shapes(plan, params.shape, pk.shape if pk is not None else None, maxfasc, csf_on, ear_on,
+                        Yc.shape if Yc is not None else None, sc.shape[0] if sc is not None else None,
+                        se.shape if se is not None else None, E)
+    M = plan.M
+    mode, sg = SIGMA_SCALAR, None
+    if ncoils:
+        if sigma_g is None:
+            raise ValueError("noise (ncoils > 0) needs sigma_g")
+        sg = np.atleast_1d(L.f64c(sigma_g))
+        mode = _sigma_mode(sg.shape, sg.size, V, M)
+    out = np.zeros((V, M))
+    stats = np.zeros((V, 2)) if Yc is not None else None
+    L.check(L.lib().mfx_predict(plan.handle(), L.dptr(params), L.dptr(pk) if pk is not None else None, int(maxfasc),
+                                int(bool(csf_on)), int(bool(ear_on)), L.dptr(sc) if sc is not None else None,
+                                L.dptr(se) if se is not None else None, int(E), V,
+                                L.dptr(Yc) if Yc is not None else None, L.dptr(sg) if sg is not None else None, mode,
+                                int(ncoils), int(seed) & _U64, int(offset) & _U64, L.dptr(out),
+                                L.dptr(stats) if stats is not None else None))
+    return out if stats is None else (out, stats)
+
+
+def sos_noise_dev(d_S0, sigma_g, ncoils=1, seed=0, offset=0, out=None):
+    """Sum-of-squares magnitude noise on the device (mfx_sos_noise_dev): sqrt(sum over ``ncoils`` coils of
+    (S0 + sigma a)^2 + (sigma b)^2), a, b standard normals.  ``d_S0``: torch CUDA float64 tensor of any shape;
+    ``sigma_g``: a number, or a tensor with one value or the shape of ``d_S0``.  Element i (C order) draws from the
+    counter ``offset + i`` of the Philox stream keyed by ``seed``: splitting an array into calls with matching
+    offsets gives the same values.  Enqueues on torch's current stream; ``out`` may be ``d_S0`` itself."""
+    import torch
+    assert d_S0.is_cuda and d_S0.dtype == torch.float64 and d_S0.is_contiguous()
+    dev = d_S0.device
+    d_sigma = (sigma_g.to(device=dev, dtype=torch.float64).contiguous() if torch.is_tensor(sigma_g)
+               else torch.full((1,), float(sigma_g), dtype=torch.float64, device=dev))
+    if d_sigma.numel() != 1 and d_sigma.shape != d_S0.shape:
+        raise ValueError("sigma_g should be a scalar or have the shape %s of S0, got %s"
+                         % (tuple(d_S0.shape), tuple(d_sigma.shape)))
+    if int(ncoils) < 1:
+        raise ValueError("ncoils should be at least 1")
+    if out is None:
+        out = torch.empty_like(d_S0)
+    assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.shape == d_S0.shape
+    st = torch.cuda.current_stream(dev).cuda_stream
+    L.check(L.lib().mfx_sos_noise_dev(d_S0.data_ptr(), d_S0.numel(), d_sigma.data_ptr(),
+                                      SIGMA_SCALAR if d_sigma.numel() == 1 else SIGMA_ELEMENT, int(ncoils),
+                                      int(seed) & _U64, int(offset) & _U64, out.data_ptr(),
+                                      dev.index if dev.index is not None else torch.cuda.current_device(), st))
+    return out
+
+
+def sos_noise(S0, sigma_g, ncoils=1, seed=0, offset=0, device=0):
+    """sos_noise_dev on NumPy buffers (mfx_sos_noise): S0 float64 of any shape, sigma_g with one value or S0's shape."""
+    S0 = L.f64c(S0)
+    sg = np.atleast_1d(L.f64c(sigma_g))
+    if sg.size != 1 and sg.shape != S0.shape:
+        raise ValueError("sigma_g should be a scalar or have the shape %s of S0, got %s" % (S0.shape, sg.shape))
+    out = np.zeros(S0.shape)
+    L.check(L.lib().mfx_sos_noise(L.dptr(S0), S0.size, L.dptr(sg), SIGMA_SCALAR if sg.size == 1 else SIGMA_ELEMENT,
+                                  int(ncoils), int(seed) & _U64, int(offset) & _U64, L.dptr(out), int(device)))
+    return out
+
+
 def rotate2d_dev(tables, d_dirs, d_cols=None):
     """Device-resident 2-D protocol rotation (mfx_rot2d_rotate_dev / mfx_rot2d_rotate_cols_dev) for a
     mf_utils.RotateAtom2DTables: torch CUDA tensors dirs [B,3] f64 (and cols [B] int: one atom per direction)

@@ -252,20 +252,8 @@ class MFModel():
                                  "zero vector, although numfasc specifies the presence of that population."
                                  % (n0, k + 1, maxfasc))
         # ---- protocol (ref:821-846)
-        if pgse_scheme is not None:
-            if isinstance(pgse_scheme, str):
-                pgse_scheme = np.loadtxt(pgse_scheme, skiprows=1)
-            if pgse_scheme.shape[1] != 7:
-                raise ValueError("pgse_scheme should have 7 columns,  detected %d instead." % (pgse_scheme.shape[1],))
-        else:
-            if bvals is None or bvecs is None:
-                raise TypeError("If no schemefile is provided, then both bvals and bvecs must be specified.")
-            pgse_scheme = mfu.get_PGSE_scheme_from_bval_bvec_dense(self.dic['sch_mat'], bvals, bvecs, 1e-3)
-        pgse_scheme = np.ascontiguousarray(pgse_scheme, dtype=np.float64)
+        pgse_scheme = self._protocol(pgse_scheme, bvals, bvecs)
         num_seq = pgse_scheme.shape[0]
-        gam = mfu.get_gyromagnetic_ratio('H')
-        G, Delta, delta, TE = pgse_scheme[:, 3], pgse_scheme[:, 4], pgse_scheme[:, 5], pgse_scheme[:, 6]
-        b = (gam * G * delta) ** 2 * (Delta - delta / 3)
         # ---- optional compartments (ref:852-894)
         csf_mask, aff = self._roi_flags(csf_mask, roi, img_shape, ROI_size, "csf_mask")
         if nii_affine is None:
@@ -280,15 +268,7 @@ class MFModel():
             print("WARNING: detected %d voxel(s) in mask with zero  axon population, no cerebrospinal fluid (CSF) "
                   "and no extra-axonal restricted (EAR) compartment specified. No estimation will be performed "
                   "there." % (n_empty,))
-        sig_csf = sig_ear = None
-        num_ear = int(self.dic['num_ear'])
-        if csf_on:   # ref:918-920
-            sig_csf = np.exp(-TE / self.dic['T2_csf']) * np.exp(-b * self.dic['DIFF_csf'])
-        if ear_on:   # ref:921-925
-            DIFF_ear = np.atleast_1d(self.dic['DIFF_ear'])
-            sig_ear = np.zeros((num_seq, num_ear))
-            for i in range(num_ear):
-                sig_ear[:, i] = np.exp(-TE / self.dic['T2_ear']) * np.exp(-b * DIFF_ear[i])
+        sig_csf, sig_ear, num_ear = self._extra_signals(pgse_scheme, csf_on, ear_on)
         if data_arr.shape[-1] != num_seq:
             raise ValueError("Data has %d measurements per voxel but the protocol has %d." % (data_arr.shape[-1],
                                                                                                 num_seq))
@@ -296,10 +276,7 @@ class MFModel():
         # (mf_utils.py:1786-1789 and 1804-1807), checked once per fit here: the protocol's timing must be the
         # dictionary's, its gradient directions zero or unit vectors
         if maxfasc > 0:
-            if not np.all(np.isclose(self.ms_interpolator['scheme_DeldelTE'], pgse_scheme[:, 4:7])):
-                raise ValueError("Delta, delta and TE values should all be identical to those in the multi-shell "
-                                 "sampling.")
-            mfu._check_gnorms(pgse_scheme)
+            self._check_protocol(pgse_scheme)
         # ---- the voxel loop, batched on the device (replaces ref:976-1032)
         # ROI order == np.where(mask > 0).  A float64 C-contiguous volume is handed over as it is with the ROI's row
         # numbers: the library gathers the rows while it stages the upload (the reference's data[mask > 0], ref:644)
@@ -327,12 +304,99 @@ class MFModel():
             print("Estimation performed in %g second(s)." % (time.time() - st))
         fitinfo = {'maxfasc': maxfasc, 'csf_on': csf_on, 'ear_on': ear_on, 'affine': nii_affine, 'mask': mask_arr,
                    'fasc_propnames': [x.strip() for x in self.dic['fasc_propnames']], 'peaks_roi': peaks_roi,
-                   'roi_index': roi_index}
+                   'roi_index': roi_index, 'model': self, 'pgse_scheme': pgse_scheme}
         for n in fitinfo['fasc_propnames']:
             fitinfo['_dict_' + n] = self.dic[n]
         if ear_on:
             fitinfo['DIFF_ear'] = np.atleast_1d(self.dic['DIFF_ear'])
         return MFModelFit(fitinfo, params_in_mask, verbose=VRB)
+
+    def _extra_signals(self, pgse_scheme, csf_on, ear_on):
+        """(sig_csf [M] | None, sig_ear [M x num_ear] | None, num_ear) of a protocol (ref:918-925)."""
+        gam = mfu.get_gyromagnetic_ratio('H')
+        G, Delta, delta, TE = pgse_scheme[:, 3], pgse_scheme[:, 4], pgse_scheme[:, 5], pgse_scheme[:, 6]
+        b = (gam * G * delta) ** 2 * (Delta - delta / 3)
+        sig_csf = sig_ear = None
+        num_ear = int(self.dic['num_ear'])
+        if csf_on:   # ref:918-920
+            sig_csf = np.exp(-TE / self.dic['T2_csf']) * np.exp(-b * self.dic['DIFF_csf'])
+        if ear_on:   # ref:921-925
+            DIFF_ear = np.atleast_1d(self.dic['DIFF_ear'])
+            sig_ear = np.zeros((pgse_scheme.shape[0], num_ear))
+            for i in range(num_ear):
+                sig_ear[:, i] = np.exp(-TE / self.dic['T2_ear']) * np.exp(-b * DIFF_ear[i])
+        return sig_csf, sig_ear, num_ear
+
+    def _check_protocol(self, pgse_scheme):
+        """What the reference checks in every voxel with a fascicle (mf_utils.py:1786-1789, 1804-1807)."""
+        if not np.all(np.isclose(self.ms_interpolator['scheme_DeldelTE'], pgse_scheme[:, 4:7])):
+            raise ValueError("Delta, delta and TE values should all be identical to those in the multi-shell "
+                             "sampling.")
+        mfu._check_gnorms(pgse_scheme)
+
+    def _protocol(self, pgse_scheme, bvals, bvecs):
+        """The protocol arguments of fit (ref:821-846) as a float64 [M x 7] scheme matrix."""
+        if pgse_scheme is not None:
+            if isinstance(pgse_scheme, str):
+                pgse_scheme = np.loadtxt(pgse_scheme, skiprows=1)
+            if pgse_scheme.shape[1] != 7:
+                raise ValueError("pgse_scheme should have 7 columns,  detected %d instead." % (pgse_scheme.shape[1],))
+        else:
+            if bvals is None or bvecs is None:
+                raise TypeError("If no schemefile is provided, then both bvals and bvecs must be specified.")
+            pgse_scheme = mfu.get_PGSE_scheme_from_bval_bvec_dense(self.dic['sch_mat'], bvals, bvecs, 1e-3)
+        return np.ascontiguousarray(pgse_scheme, dtype=np.float64)
+
+    def predict(self, params_in_mask, peaks, *, pgse_scheme=None, bvals=None, bvecs=None, data=None, sigma_g=None, N=0,
+                seed=0, offset=0):
+        """The DW-MRI signal that parameter rows stand for: the reference's ``y_rec`` (ref:413-419), which its fit
+        computes in every voxel and drops.
+
+        ``params_in_mask`` [V x num_params] has the layout of ``MFModelFit.params_in_mask`` (M0, nu_f, ID_f, nu_csf,
+        nu_ear, ID_ear, MSE, R2; the last two are ignored) and ``peaks`` [V x 3 maxfasc] the fascicle directions;
+        the number of columns says which optional compartments are there.  The protocol is given as in ``fit``.
+        Returns the signals [V x M]; with ``data`` [V x M] also ``stats`` [V x 2], the residual sum of squares and
+        R2 per voxel.  ``N`` >= 1 (with ``sigma_g``; one without the other is an error) adds the magnitude noise of ``mf_utils.gen_SoS_MRI`` with ``sigma_g`` (a scalar, one
+        value per voxel or one per element) in the same pass.  NumPy arrays in, NumPy arrays out; torch CUDA
+        float64 tensors in, tensors out on torch's current stream, nothing copied to the host."""
+        if sigma_g is not None and not N:
+            raise ValueError("sigma_g is given but the number of coils N is 0: pass N >= 1 for noise (simulate does)")
+        sch = self._protocol(pgse_scheme, bvals, bvecs)
+        on_dev = type(params_in_mask).__module__.split('.')[0] == 'torch'
+        if params_in_mask.ndim != 2:
+            raise ValueError("params_in_mask should be a 2-D array [voxels x parameters]")
+        maxfasc = 0 if peaks is None else int(peaks.shape[-1]) // 3
+        extra = params_in_mask.shape[1] - 3 - 2 * maxfasc
+        if peaks is not None and (peaks.ndim != 2 or peaks.shape[1] != 3 * maxfasc) or extra not in (0, 1, 2, 3):
+            raise ValueError("peaks should have 3 columns per fascicle and params_in_mask 1 + 2 maxfasc + csf + 2 ear + 2 "
+                             "columns; got shapes %s and %s" % (None if peaks is None else tuple(peaks.shape),
+                                                                tuple(params_in_mask.shape)))
+        csf_on, ear_on = bool(extra & 1), bool(extra & 2)
+        if maxfasc > 0:
+            self._check_protocol(sch)
+        sig_csf, sig_ear, num_ear = self._extra_signals(sch, csf_on, ear_on)
+        plan = self.ms_interpolator.plan_for(sch)
+        if on_dev:
+            import torch
+            dev = params_in_mask.device
+            d_csf = torch.as_tensor(sig_csf, device=dev) if csf_on else None
+            d_ear = torch.as_tensor(np.ascontiguousarray(sig_ear), device=dev) if ear_on else None
+            return engine.predict_dev(plan, params_in_mask, peaks, maxfasc, csf_on, ear_on, d_csf, d_ear, num_ear,
+                                      d_Y=data, sigma_g=sigma_g, ncoils=N, seed=seed, offset=offset)
+        return engine.predict(plan, params_in_mask, peaks, maxfasc, csf_on, ear_on, sig_csf, sig_ear, num_ear, Y=data,
+                              sigma_g=sigma_g, ncoils=N, seed=seed, offset=offset)
+
+    def simulate(self, params_in_mask, peaks, *, SNR=None, sigma_g=None, N=1, seed=None, offset=0, pgse_scheme=None,
+                 bvals=None, bvecs=None):
+        """``predict`` with the sum-of-squares magnitude noise of ``N`` coils (Rician for N = 1): give either
+        ``sigma_g`` or ``SNR``, which sets ``sigma_g = M0 / SNR`` in every voxel.  ``seed=None`` draws a seed from
+        NumPy's global generator; an int makes the call reproducible by itself."""
+        if (SNR is None) == (sigma_g is None):
+            raise ValueError("simulate needs exactly one of SNR and sigma_g")
+        if SNR is not None:
+            sigma_g = params_in_mask[:, 0] / SNR
+        return self.predict(params_in_mask, peaks, pgse_scheme=pgse_scheme, bvals=bvals, bvecs=bvecs, sigma_g=sigma_g,
+                            N=N, seed=mfu._sos_seed(seed), offset=offset)
 
     @staticmethod
     def _roi_flags(m, roi, img_shape, ROI_size, name):
@@ -396,6 +460,10 @@ class MFModelFit():
             flat = np.flatnonzero(np.asarray(mask) > 0)
         assert ROI_size == flat.shape[0], 'Inconsistent mask and model parameter array'
         self.params_in_mask = model_params
+        # what predict() needs (not maps: param_names and write_nifti do not see them)
+        self._model, self._pgse_scheme = fitinfo.get('model'), fitinfo.get('pgse_scheme')
+        self._nf, self._csf_on, self._ear_on = nf, bool(csf_on), bool(ear_on)
+        self._peaks_roi, self._roi_flat, self._grid = fitinfo.get('peaks_roi'), flat, tuple(mask.shape)
         whole = ROI_size == int(np.prod(mask.shape))
 
         def to_map(vals, extra=()):
@@ -437,6 +505,60 @@ class MFModelFit():
         self.param_names = names
         if verbose >= 2:
             print("Microstructure Fingerprinting fit object constructed; maps: %s" % ", ".join(names))
+
+    PREDICT_CHUNK = 1 << 16   # ROI voxels per device call of predict() / residuals()
+
+    def _predict_chunks(self):
+        """The predicted signals of the ROI, PREDICT_CHUNK voxels at a time: (ROI slice, [n x M] float64)."""
+        if self._model is None or self._pgse_scheme is None:
+            raise RuntimeError("this fit object was not made by MFModel.fit: it knows neither its model nor its protocol")
+        m = self._model
+        for i0 in range(0, self._roi_flat.shape[0], self.PREDICT_CHUNK):
+            sl = slice(i0, i0 + self.PREDICT_CHUNK)
+            P = self.params_in_mask[sl]
+            # a voxel whose parameters cannot be predicted (non-finite or negative weights, an index outside the
+            # dictionary: a fit of unusable data) gets a NaN row; it does not stop the volume
+            bad = engine.predict_bad_rows(P, self._nf, self._csf_on, self._ear_on, int(m.dic['num_atom']), int(m.dic['num_ear']))
+            if bad.any():
+                P = np.where(bad[:, None], 0.0, P)
+            pred = m.predict(P, self._peaks_roi[sl], pgse_scheme=self._pgse_scheme)
+            if bad.any():
+                pred[bad] = np.nan
+            yield sl, pred
+
+    def _volume_out(self, out, dtype):
+        shape = self._grid + (self._pgse_scheme.shape[0],)
+        if out is None:
+            return np.zeros(shape, dtype=dtype)
+        if not isinstance(out, np.ndarray) or out.shape != shape or not out.flags.c_contiguous:
+            raise ValueError("out should be a C-contiguous array of shape (%s)" % " ".join("%d" % x for x in shape))
+        out[...] = 0
+        return out
+
+    def predict(self, dtype=np.float64, out=None):
+        """The signal the fitted parameters stand for, shape ``mask.shape + (M,)``, zeros outside the ROI (the
+        reference computes it in every voxel, ref:413-419, and drops it).  ``dtype`` (or ``out``'s type) may be
+        np.float32: the volume is rounded from the float64 prediction one chunk of voxels at a time, so that a
+        whole-brain prediction never exists in float64.  A voxel whose parameters cannot be predicted (a weight that is
+        negative or not finite, an atom index outside its dictionary) is NaN."""
+        vol = self._volume_out(out, dtype)
+        rows = vol.reshape(-1, vol.shape[-1])
+        for sl, pred in self._predict_chunks():
+            rows[self._roi_flat[sl]] = pred
+        return vol
+
+    def residuals(self, data, dtype=np.float64, out=None):
+        """``data - predict()`` inside the ROI, zeros outside; ``data`` as given to ``fit`` (array or NIfTI file)."""
+        data_arr, _ = _load_volume(data)
+        vol = self._volume_out(out, dtype)
+        if data_arr.shape != vol.shape:
+            raise ValueError("data should have shape (%s), got (%s)" % (" ".join("%d" % x for x in vol.shape),
+                                                                        " ".join("%d" % x for x in data_arr.shape)))
+        rows = vol.reshape(-1, vol.shape[-1])
+        for sl, pred in self._predict_chunks():
+            idx = self._roi_flat[sl]
+            rows[idx] = np.asarray(data_arr[np.unravel_index(idx, self._grid)], dtype=np.float64) - pred
+        return vol
 
     def write_nifti(self, output_basename, affine=None):
         """One NIfTI file per parameter map, ``<stem>_<param><ext>``; returns the file names (reference mf.py:1177-1229).

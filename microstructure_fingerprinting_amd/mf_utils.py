@@ -18,6 +18,7 @@ rotate_scheme_mat, vrrotvec2mat, rotate_vector host (O(M) NumPy)
 get_perp_vector, project_PGSE_scheme_xy_plane  host
 import_PGSE_scheme (ref:2128)                  host (input normalisation, once per fit)
 get_PGSE_scheme_from_bval_bvec_dense (2197)    host
+gen_SoS_MRI (ref:2303)                         checks on host, Philox draws and magnitude on device (mfx_sos_noise)
 monte_carlo_average (ref:2762)                 device (mfx_monte_carlo_average)
 get_PGSE_from_phases (ref:2813)                file parsing / (Delta, delta) mapping on host, phase planes
                                                uploaded once, cosine reduction on device
@@ -39,7 +40,7 @@ __all__ = ["get_gyromagnetic_ratio", "solve_exhaustive_posweights", "init_PGSE_m
            "interp_PGSE_from_multishell", "rotate_atom", "RotateAtomTables", "import_PGSE_scheme",
            "get_PGSE_scheme_from_bval_bvec_dense", "loadmat", "MultiShellInterpolator",
            "rotate_atom_2Dprotocol", "RotateAtom2DTables", "rotate_scheme_mat", "vrrotvec2mat", "rotate_vector",
-           "get_perp_vector", "project_PGSE_scheme_xy_plane"]
+           "get_perp_vector", "project_PGSE_scheme_xy_plane", "gen_SoS_MRI"]
 
 
 def get_gyromagnetic_ratio(element='H'):
@@ -981,3 +982,73 @@ def loadmat(filename):
 
     data = scipy.io.loadmat(filename, struct_as_record=False, squeeze_me=True)
     return {k: conv(v) for k, v in data.items()}
+
+
+def gen_SoS_MRI(S0, sigma_g, N=1, *, seed=None, device=0):
+    """Simulates Sum-of-Squares MRI signal for phased-array systems (ref:2303-2354).
+
+    Produces S_out = sqrt{ sum_{i=1}^N |S_i|^2 }, where S_i = S_0 + eps1 + (1i)*eps2, with eps1, eps2 two
+    independent zero-mean Gaussian variables of standard deviation sigma_g, identical in all N coils and in both
+    channels.  S_out follows a non-central Chi distribution (Rician for N = 1).
+
+    Args:
+      S0: N-D NumPy array with the true, real-valued MRI contrast (a complex S0 raises TypeError: the reference's
+        arithmetic squares a complex in-phase term without taking its modulus and does not give the magnitude its
+        docstring promises).  A torch CUDA tensor stays on its device: a new float64 tensor comes back, on torch's
+        current stream, without a copy through the host (S0 itself is not changed; one that is not float64 and
+        contiguous is converted first).
+      sigma_g: scalar, or array with the shape of S0 (one standard deviation per entry).  Where an entry is 0
+        beside others that are not, the result there is sqrt(N) |S0|, as the reference's arithmetic gives.  A sigma_g
+        given as a tensor is not inspected on the host (that would wait for the device), so an all-zero tensor gives
+        sqrt(N) |S0| too, where the all-zero early return below gives sqrt(N) S0, sign included.
+      N: the effective number of coils.  Default is 1 (Rician noise).
+      seed: None draws a 64-bit seed from NumPy's global generator (np.random.seed makes a script repeatable, as
+        with the reference); an int makes the call reproducible by itself.  The draws are a Philox4x32-10 stream
+        of this library and do not reproduce NumPy's: the distribution is the contract.
+      device: GPU that draws for NumPy input.
+
+    Returns:
+      An array (or tensor) with the shape of S0; np.sqrt(N)*S0 when every sigma_g is 0.
+
+    Raises:
+      ValueError: if sigma_g is not a scalar but its shape does not match that of S0.
+    """
+    if type(S0).__module__.split('.')[0] == 'torch':
+        import torch
+        if S0.is_complex():
+            raise TypeError("gen_SoS_MRI: S0 should be real-valued, got %s" % (S0.dtype,))
+        if not torch.is_tensor(sigma_g) and np.ndim(sigma_g) == 0 and sigma_g == 0:
+            return np.sqrt(N) * S0
+        sg = sigma_g if torch.is_tensor(sigma_g) or np.ndim(sigma_g) == 0 else torch.as_tensor(np.asarray(sigma_g))
+        if torch.is_tensor(sg) and sg.numel() > 1 and sg.shape != S0.shape:
+            raise ValueError('sigma_g should either be a scalar or have the shape (%s) of S0 for 1-to-1 '
+                             'correspondance. Detected (%s) instead.'
+                             % (", ".join("%d" % x for x in S0.shape), ", ".join("%d" % x for x in sg.shape)))
+        if not S0.is_cuda:
+            raise TypeError("gen_SoS_MRI: a tensor S0 should live on the GPU (pass NumPy arrays otherwise)")
+        if torch.is_tensor(sg) and sg.numel() > 1:
+            sg = sg.reshape(S0.shape)
+        return engine.sos_noise_dev(S0.to(torch.float64).contiguous(), sg, int(N), _sos_seed(seed))
+    if np.iscomplexobj(S0) or np.iscomplexobj(sigma_g):
+        raise TypeError("gen_SoS_MRI: S0 and sigma_g should be real-valued, got %s" % (np.asarray(S0).dtype,))
+    if np.all(sigma_g == 0):
+        return np.sqrt(N) * S0  # perfect noiseless scenario (ref:2332-2333)
+    S0 = np.asarray(S0)
+    if np.ndim(sigma_g) > 0 and sigma_g.size > 1 and S0.shape != sigma_g.shape:   # ref:2335-2343
+        raise ValueError('sigma_g should either be a scalar or have '
+                         'the shape (%s) of S0 for 1-to-1 '
+                         'correspondance. Detected (%s) instead.'
+                         % (", ".join("%d" % x for x in S0.shape),
+                            ", ".join("%d" % x for x in sigma_g.shape)))
+    if int(N) != N or N < 1:
+        raise ValueError("N should be a positive integer, got %r" % (N,))
+    sg = np.asarray(sigma_g, dtype=np.float64)
+    out = engine.sos_noise(S0, sg.reshape(-1)[:1] if sg.size == 1 else sg, int(N), _sos_seed(seed), 0, device)
+    # a sigma_g of shape (1, 1) beside an S0 of shape (N,) still gives shape (N,) (ref:2350-2353)
+    return np.reshape(out, S0.shape)
+
+
+def _sos_seed(seed):
+    if seed is None:
+        return int(np.random.randint(0, 2 ** 64, dtype=np.uint64))
+    return int(seed) & ((1 << 64) - 1)
