@@ -34,6 +34,10 @@ ROT2D_EXPORTS = ["mfx_rot2d_abi_version", "mfx_rot2d_create", "mfx_rot2d_destroy
 # every symbol include/mfx_predict.h declares (forward model and magnitude noise; versioned on its own)
 PREDICT_EXPORTS = ["mfx_predict_abi_version", "mfx_predict_dev", "mfx_predict", "mfx_sos_noise_dev", "mfx_sos_noise"]
 
+# every symbol include/mfx_profile.h declares (objective profiles; versioned on its own)
+PROFILE_EXPORTS = ["mfx_profile_abi_version", "mfx_profile_cut", "mfx_profile_max_atoms", "mfx_profile_dev", "mfx_profile",
+                   "mfx_pair_objectives_dev", "mfx_pair_objectives"]
+
 
 class MfxError(RuntimeError):
     pass
@@ -130,6 +134,13 @@ def lib():
                               C.c_uint64, C.c_uint64, dp, dp]
     L.mfx_sos_noise_dev.argtypes = [vp, C.c_int64, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint64, vp, C.c_int, vp]
     L.mfx_sos_noise.argtypes = [dp, C.c_int64, dp, C.c_int, C.c_int, C.c_uint64, C.c_uint64, dp, C.c_int]
+    L.mfx_profile_abi_version.restype = C.c_int
+    L.mfx_profile_cut.restype = C.c_double
+    L.mfx_profile_max_atoms.argtypes = [vp, C.c_int, C.c_int]
+    L.mfx_profile_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int64, vp, vp, vp]
+    L.mfx_profile.argtypes = [vp, dp, dp, C.c_int, C.c_int, dp, C.c_int64, dp, ip]
+    L.mfx_pair_objectives_dev.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int64, vp, vp]
+    L.mfx_pair_objectives.argtypes = [vp, dp, dp, C.c_int, dp, C.c_int64, dp]
     _lib = L
     return L
 

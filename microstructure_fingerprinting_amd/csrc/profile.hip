@@ -1,0 +1,629 @@
+// profile.hip -- objective profiles (include/mfx_profile.h): per atom of each fascicle the best objective any partner
+// reaches with it, or the objective of every atom pair of a voxel.
+//
+// mfx_profile_k2_kernel   one workgroup per voxel, the structure of fit_k2.hip's phases 0-2: knot descriptors and y in
+//                         LDS, column statistics of both rotated dictionaries (one thread per atom), then the cross-Gram
+//                         D_0^T D_1 on v_mfma_f64_16x16x4_f64 with the wave's 16 atoms of D_0 in registers and D_1
+//                         generated chunk by chunk into LDS.  Unlike the fit's scan, EVERY pair is scored here - the
+//                         single-active cases included, and with CSF the projected three-unknown form - and what is kept
+//                         is a minimum per row and per column, not one candidate list:
+//                           rows     a wave owns its 16 atoms for a whole sweep over the chunks, so their minima live in
+//                                    registers (C/D layout: col = lane & 15, row = (lane >> 4) + 4 reg) and are folded
+//                                    over the 16 lanes of a row once per sweep;
+//                           columns  folded in the lane over its 4 rows, over the 4 lane groups by shuffles, then over
+//                                    the waves through a small LDS slab behind the barrier that ends the chunk anyway,
+//                                    into per-atom arrays in LDS.  No global atomics, no N x N store.
+//                         FP64 MFMA and VALU instructions do not overlap on a SIMD (fit_k2.hip), so the scan's
+//                         instruction count is its cost: without CSF a pair's score ||y||^2 - F is kept as a fraction
+//                         p / q, fractions are compared by cross-multiplication, and the division happens once per
+//                         reported atom.  The CSF form needs the pair's weights (the sign of w_x decides which value
+//                         holds) and divides per pair; it is the slow variant.
+//                         LAND = true: the same Gram and scoring, every pair's value stored [N x N], no minima kept.
+//                         All variants take the plain chunk loop of fit_k2.hip (the next chunk is generated before the
+//                         MFMAs of the current one where two LDS buffers fit); its pipelined k-loop is not ported.
+// mfx_profile_k1_kernel   one workgroup per voxel, one thread per atom: ||y||^2 - max(Y, 0)^2 / A (and the CSF form).
+//
+// Arithmetic: Gram entries and statistics in plain FP64 (separate products and sums, MFMA for the cross terms);
+// the closed forms use fma() like the fit's ranking math.  Error of a pair's value: each of the six Gram quantities
+// carries at most M eps |a||b|, carried through (z1^2 - 2 c z1 z2 + z2^2) / (1 - c^2); tests hold the kernel to
+// 16 M eps ||y||^2 / (1 - c^2).
+#include "mfx_host.h"
+#include "../../include/mfx_profile.h"
+
+#include <algorithm>
+
+#define MFX_PROFILE_CUT 1e-8   // pairs with 1 - c^2 <= this are scored as their better single atom (the fit's MFX_DET_REL)
+
+namespace {
+
+constexpr size_t PROF_LDS_MAX = 160 * 1024;
+constexpr int PROF_K1_WG = 256;
+
+struct ProfArgs {
+  TablesDev T;
+  PlanDev P;
+  const double* Y;      // [V x M]
+  const double* peaks;  // [V x 3 K]
+  const double* xc;     // [M] the CSF column (CSF variants)
+  double* obj;          // profile: [V x K x N]; landscape: [V x N x N]
+  int* partner;         // [V x K x N] or null
+};
+
+// score s = ||y||^2 - F of one atom pair as the fraction p / q (q > 0 whenever p > 0).  p1 = max(Y1, 0)^2 and
+// p2 likewise are the single atoms' numerators (denominators A11, A22).
+__device__ __forceinline__ void prof_pair_frac(double A11, double A22, double A12, double Y1, double Y2, double p1, double p2,
+                                               double& p, double& q) {
+  const double d1 = fma(-A12, Y2, A22 * Y1);   // w1 Det, mf_utils.py:425
+  const double d2 = fma(-A12, Y1, A11 * Y2);   // w2 Det
+  const double pd = A11 * A22;
+  const double Det = fma(-A12, A12, pd);
+  const double num = fma(Y2, d2, Y1 * d1);     // Y1 w1 + Y2 w2, times Det
+  const bool both = (d1 > 0.0) & (d2 > 0.0) & (Det > MFX_PROFILE_CUT * pd);
+  const bool first = p1 * A22 >= p2 * A11;     // the better single atom (ties: the row's)
+  p = both ? num : (first ? p1 : p2);
+  q = both ? Det : (first ? A11 : A22);
+}
+
+// the same with the weights (CSF form): i11 = 1 / A11 (0 for a null atom), returns the score
+__device__ __forceinline__ double prof_pair_w(double A11, double A22, double A12, double Y1, double Y2, double i11, double i22,
+                                              double& w1, double& w2) {
+  const double d1 = fma(-A12, Y2, A22 * Y1);
+  const double d2 = fma(-A12, Y1, A11 * Y2);
+  const double pd = A11 * A22;
+  const double Det = fma(-A12, A12, pd);
+  const bool both = (d1 > 0.0) & (d2 > 0.0) & (Det > MFX_PROFILE_CUT * pd);
+  const double u1 = fmax(Y1, 0.0) * i11, u2 = fmax(Y2, 0.0) * i22;   // single-atom weights
+  const double s1 = Y1 * u1, s2 = Y2 * u2;
+  const bool first = s1 >= s2;
+  const double iD = both ? 1.0 / Det : 0.0;
+  w1 = both ? d1 * iD : (first ? u1 : 0.0);
+  w2 = both ? d2 * iD : (first ? 0.0 : u2);
+  return both ? fma(Y2, d2, Y1 * d1) * iD : (first ? s1 : s2);
+}
+
+// statistics of an atom with the CSF column x projected out: A' = A - X^2 / xx, Y' = Y - X xy / xx; an atom
+// parallel to x (A' within the cut of 0) becomes a null atom
+__device__ __forceinline__ void prof_primed(double A, double Yv, double X, double ixx, double xy, double& Ap, double& Yp,
+                                            double& iAp) {
+  const double xs = X * ixx;
+  Ap = fma(-xs, X, A);
+  Yp = fma(-xs, xy, Yv);
+  const bool ok = Ap > MFX_PROFILE_CUT * A;
+  Ap = ok ? Ap : 0.0;
+  Yp = ok ? Yp : 0.0;
+  iAp = ok ? 1.0 / Ap : 0.0;
+}
+
+// NW waves per workgroup, TILES 16-atom column tiles per D_1 chunk, NBUF LDS buffers for the chunks (as fit_k2.hip):
+// (8, 2, 2) for exact-G protocols of M <= 200 without CSF where it fits; (4, 1, 2) and (4, 1, 1) - one wave per SIMD with the whole register
+// file - for the CSF form (whose scan keeps twice the per-row operands), G-bracketed rows, larger dictionaries and long protocols.
+template <int KSTEPS, bool BRACKET, bool CSF, bool LAND, int NW, int TILES, int NBUF>
+__global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void mfx_profile_k2_kernel(ProfArgs a) {
+  constexpr int WG = NW * 64;
+  constexpr int MP = KSTEPS * 4;              // padded measurement count
+  constexpr int MPS = MP;                     // rows of one LDS D_1 tile
+  constexpr int CW = 16 * TILES;              // atoms per chunk
+  constexpr int RS = WG / CW;                 // row stride of one generating thread
+  extern __shared__ double smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lg = lane >> 4, lc = lane & 15;
+  const int M = a.P.M, N = a.T.N, ldn = a.T.ldn;
+  const int NP = ldn;  // atoms padded to a multiple of 16 (padded atoms are zero columns)
+  const int ntiles = NP >> 4;
+  const double2* __restrict__ tab = a.T.tab;
+  const size_t vox = blockIdx.x;
+
+  // ---- LDS carve-up (prof_lds_bytes below mirrors it)
+  double* sB = smem;                              // [NBUF][TILES][MPS][16]
+  double* s_y = sB + NBUF * TILES * MPS * 16;     // [MP]
+  double* s_x = s_y + MP;                         // [MP] (CSF)
+  double* s_t0 = s_x + (CSF ? MP : 0);            // [2][MP]
+  double* s_t1 = s_t0 + 2 * MP;                   // [2][MP] (bracket only)
+  double* s_tG = s_t1 + (BRACKET ? 2 * MP : 0);   // [MP]
+  double* s_dG = s_tG + (BRACKET ? MP : 0);       // [MP]
+  double* s_A11 = s_dG + (BRACKET ? MP : 0);      // [NP] each: |d|^2 and d.y of both dictionaries
+  double* s_Y1 = s_A11 + NP;
+  double* s_A22 = s_Y1 + NP;
+  double* s_Y2 = s_A22 + NP;
+  double* s_X1 = s_Y2 + NP;                       // [NP] each: d.x (CSF)
+  double* s_X2 = s_X1 + (CSF ? NP : 0);
+  double* s_cp = s_X2 + (CSF ? NP : 0);           // [NP] each: running column best as a fraction (profile)
+  double* s_cq = s_cp + (LAND ? 0 : NP);
+  double* s_sp = s_cq + (LAND ? 0 : NP);          // [2][NW][CW] each: the waves' column bests of one chunk
+  double* s_sq = s_sp + (LAND ? 0 : 2 * NW * CW);
+  double* s_end = s_sq + (LAND ? 0 : 2 * NW * CW);
+  int* s_r0 = (int*)s_end;                        // [2][MP]
+  int* s_r1 = s_r0 + 2 * MP;                      // [2][MP] (bracket only)
+  int* s_ci = s_r1 + (BRACKET ? 2 * MP : 0);      // [NP]
+  int* s_si = s_ci + (LAND ? 0 : NP);             // [2][NW][CW]
+
+  // ---- phase 0: y, x, descriptors
+  const double* __restrict__ yv = a.Y + vox * M;
+  const double* __restrict__ pk = a.peaks + vox * 6;
+  for (int m = tid; m < MP; m += WG) {
+    s_y[m] = (m < M) ? yv[m] : 0.0;
+    if constexpr (CSF) s_x[m] = (m < M) ? a.xc[m] : 0.0;
+  }
+  for (int idx = tid; idx < 2 * MP; idx += WG) {
+    const int k = idx / MP, m = idx - k * MP;
+    RowDesc rd;
+    rd.r0 = a.T.P; rd.t0 = 0.0; rd.r1 = -1; rd.t1 = 0.0;  // padded rows -> the all-zero table row
+    if (m < M) rd = mfx_row_desc(a.T, a.P, m, pk[3 * k], pk[3 * k + 1], pk[3 * k + 2]);
+    s_r0[idx] = rd.r0;
+    s_t0[idx] = rd.t0;
+    if (BRACKET) {
+      s_r1[idx] = rd.r1;
+      s_t1[idx] = rd.t1;
+      if (k == 0) { s_tG[m] = (m < M) ? a.P.tG[m] : 0.0; s_dG[m] = (m < M) ? a.P.dG[m] : 1.0; }
+    }
+  }
+  if (tid < 2) mfx_check_dir(a.P, pk + 3 * tid, (int)vox);
+  if constexpr (!LAND) {
+    for (int n = tid; n < NP; n += WG) { s_cp[n] = 0.0; s_cq[n] = 1.0; s_ci[n] = 0; }
+  }
+  __syncthreads();
+
+  auto elem = [&](int k, int m, int n) -> double {
+    if (BRACKET) {
+      RowDesc rd;
+      rd.r0 = s_r0[k * MP + m]; rd.t0 = s_t0[k * MP + m];
+      rd.r1 = s_r1[k * MP + m]; rd.t1 = s_t1[k * MP + m];
+      return mfx_eval_br(tab, ldn, rd, s_tG[m], s_dG[m], n);
+    } else {
+      return mfx_eval(tab, ldn, s_r0[k * MP + m], s_t0[k * MP + m], n);
+    }
+  };
+
+  // ---- phase 1: column statistics, sequential over the measurements; ||y||^2, x.x, x.y likewise (every thread)
+  double y_sq = 0.0, xx = 0.0, xy = 0.0;
+  for (int m = 0; m < M; ++m) {
+    y_sq += s_y[m] * s_y[m];
+    if constexpr (CSF) { xx += s_x[m] * s_x[m]; xy += s_x[m] * s_y[m]; }
+  }
+  for (int col = tid; col < 2 * NP; col += WG) {
+    const int k = col >= NP, n = col - k * NP;
+    double a2 = 0.0, ay = 0.0, ax = 0.0;
+    if (n < N) {
+#pragma unroll 4
+      for (int m = 0; m < M; ++m) {
+        const double d = elem(k, m, n);
+        a2 += d * d;
+        ay += s_y[m] * d;
+        if constexpr (CSF) ax += s_x[m] * d;
+      }
+    }
+    (k ? s_A22 : s_A11)[n] = a2;
+    (k ? s_Y2 : s_Y1)[n] = ay;
+    if constexpr (CSF) (k ? s_X2 : s_X1)[n] = ax;
+  }
+  const double ixx = (CSF && xx > 0.0) ? 1.0 / xx : 0.0;
+  const double sx = xy * xy * ixx;   // what x alone explains: ||y||^2 - ||y'||^2
+
+  auto gen_chunk = [&](int ch, int buf) {
+    const int c = tid % CW, m0 = tid / CW;
+    const int n = ch * CW + c;
+    double* dst = sB + (size_t)buf * (TILES * MPS * 16) + (c >> 4) * (MPS * 16) + (c & 15);
+    if (n < NP) {
+      if constexpr (BRACKET) {   // not unrolled: a bracketed entry holds two table loads and six descriptors
+#pragma unroll 1
+        for (int m = m0; m < MP; m += RS) dst[m * 16] = elem(1, m, n);
+      } else {
+#pragma unroll 4
+        for (int m = m0; m < MP; m += RS) dst[m * 16] = elem(1, m, n);
+      }
+    } else {
+      for (int m = m0; m < MP; m += RS) dst[m * 16] = 0.0;
+    }
+  };
+
+  const int nchunks = (ntiles + TILES - 1) / TILES;
+  const int nrounds = (ntiles + NW - 1) / NW;
+  double* const out_land = LAND ? a.obj + vox * (size_t)N * N : nullptr;
+
+  for (int round = 0; round < nrounds; ++round) {
+    const int rt = round * NW + wave;
+    const bool rt_valid = rt < ntiles;  // wave-uniform
+    const int rtc = rt_valid ? rt : 0;
+    // A operand: this wave's 16 atoms of D_0, all KSTEPS k-steps, in registers
+    double afr[KSTEPS];
+#pragma unroll
+    for (int kk = 0; kk < KSTEPS; ++kk) {
+      afr[kk] = rt_valid ? elem(0, 4 * kk + lg, rtc * 16 + lc) : 0.0;
+      if (BRACKET && (kk & 3) == 3) __builtin_amdgcn_sched_barrier(0);   // keeps the loads of a long protocol from piling up in registers
+    }
+    __syncthreads();   // statistics complete (round 0); the previous sweep's last slab half folded before it is written again
+    gen_chunk(0, 0);
+    __syncthreads();
+
+    // per-row operands of the scan (row r of the lane: atom i = 16 rt + lg + 4 r)
+    double A11r[4], Y1r[4], p1r[4];   // CSF: the primed statistics
+    double X1s[4], X1r[4], A11u[4], Y1u[4], i11p[4], i11u[4];   // CSF only: X1 / xx, X1, the plain statistics, inverses
+    bool rowok[4];
+    double bp[4], bq[4];
+    int bj[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = rtc * 16 + lg + 4 * r;
+      rowok[r] = rt_valid && (i < N);
+      const double A = s_A11[i], Yv = s_Y1[i];
+      if constexpr (CSF) {
+        const double X = s_X1[i];
+        A11u[r] = A; Y1u[r] = Yv; X1r[r] = X; X1s[r] = X * ixx;
+        i11u[r] = A > 0.0 ? 1.0 / A : 0.0;
+        prof_primed(A, Yv, X, ixx, xy, A11r[r], Y1r[r], i11p[r]);
+        p1r[r] = 0.0;
+      } else {
+        A11r[r] = A; Y1r[r] = Yv;
+        const double yp = fmax(Yv, 0.0);
+        p1r[r] = yp * yp;
+      }
+      bp[r] = 0.0; bq[r] = 1.0; bj[r] = 0;
+    }
+
+    for (int ch = 0; ch < nchunks; ++ch) {
+      const int buf = (NBUF == 2) ? (ch & 1) : 0;
+      if constexpr (NBUF == 2) {
+        if (ch + 1 < nchunks) gen_chunk(ch + 1, buf ^ 1);
+      } else if (ch > 0) {
+        gen_chunk(ch, 0);   // single buffer: generate, barrier, consume, barrier
+        __syncthreads();
+      }
+      double cp[TILES], cq[TILES];
+      int ci[TILES];
+#pragma unroll
+      for (int t = 0; t < TILES; ++t) { cp[t] = 0.0; cq[t] = 1.0; ci[t] = 0; }
+      if (rt_valid) {
+        const double* b0p = sB + (size_t)buf * (TILES * MPS * 16) + lg * 16 + lc;
+        const double* b1p = b0p + (TILES == 2 ? MPS * 16 : 0);
+        d4 acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};
+#pragma unroll
+        for (int kk = 0; kk < KSTEPS; ++kk) {
+          const double b0 = b0p[kk * 64];
+          acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(afr[kk], b0, acc0, 0, 0, 0);
+          if constexpr (TILES == 2) {
+            const double b1 = b1p[kk * 64];
+            acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(afr[kk], b1, acc1, 0, 0, 0);
+          }
+        }
+#pragma unroll
+        for (int t = 0; t < TILES; ++t) {
+          const d4 acc = t ? acc1 : acc0;
+          const int j = ch * CW + t * 16 + lc;
+          const bool colok = j < N;
+          const int jq = colok ? j : 0;
+          double A22 = s_A22[jq], Y2 = s_Y2[jq];
+          double p2 = 0.0, X2 = 0.0, A22u = 0.0, Y2u = 0.0, i22p = 0.0, i22u = 0.0;
+          if constexpr (CSF) {
+            X2 = s_X2[jq]; A22u = A22; Y2u = Y2;
+            i22u = A22 > 0.0 ? 1.0 / A22 : 0.0;
+            prof_primed(A22u, Y2u, X2, ixx, xy, A22, Y2, i22p);
+          } else {
+            const double yp = fmax(Y2, 0.0);
+            p2 = yp * yp;
+          }
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            double p, q;
+            if constexpr (CSF) {
+              // x projected out: the two-variable form on the primed quantities, then the sign of w_x decides
+              double w1, w2, v1, v2;
+              const double A12p = fma(-X1s[r], X2, acc[r]);
+              const double sp = prof_pair_w(A11r[r], A22, A12p, Y1r[r], Y2, i11p[r], i22p, w1, w2);
+              const double wxn = fma(-w2, X2, fma(-w1, X1r[r], xy));   // w_x times x.x
+              const double su = prof_pair_w(A11u[r], A22u, acc[r], Y1u[r], Y2u, i11u[r], i22u, v1, v2);
+              p = (wxn >= 0.0) ? sx + sp : su;
+              q = 1.0;
+            } else {
+              prof_pair_frac(A11r[r], A22, acc[r], Y1r[r], Y2, p1r[r], p2, p, q);
+            }
+            const bool ok = rowok[r] & colok;
+            if constexpr (LAND) {
+              if (ok) out_land[(size_t)(rtc * 16 + lg + 4 * r) * N + j] = y_sq - (q > 0.0 ? p / q : 0.0);
+            } else {
+              p = ok ? p : 0.0;   // padded atoms never win (strict comparisons)
+              const bool brow = p * bq[r] > bp[r] * q;   // increasing j per lane: the first best stays
+              bp[r] = brow ? p : bp[r];
+              bq[r] = brow ? q : bq[r];
+              bj[r] = brow ? j : bj[r];
+              const bool bcol = p * cq[t] > cp[t] * q;   // increasing i with r
+              cp[t] = bcol ? p : cp[t];
+              cq[t] = bcol ? q : cq[t];
+              ci[t] = bcol ? rtc * 16 + lg + 4 * r : ci[t];
+            }
+          }
+        }
+      }
+      if constexpr (!LAND) {
+        // column bests: over the four lane groups (rows lg + 4 r), then one slab entry per wave and column
+#pragma unroll
+        for (int t = 0; t < TILES; ++t) {
+#pragma unroll
+          for (int o = 16; o <= 32; o <<= 1) {
+            const double p2 = __shfl_xor(cp[t], o), q2 = __shfl_xor(cq[t], o);
+            const int i2 = __shfl_xor(ci[t], o);
+            const double l = p2 * cq[t], rgt = cp[t] * q2;
+            const bool take = (l > rgt) || (l == rgt && i2 < ci[t]);
+            cp[t] = take ? p2 : cp[t];
+            cq[t] = take ? q2 : cq[t];
+            ci[t] = take ? i2 : ci[t];
+          }
+          if (lg == 0) {
+            const int s = ((ch & 1) * NW + wave) * CW + t * 16 + lc;
+            s_sp[s] = cp[t]; s_sq[s] = cq[t]; s_si[s] = ci[t];
+          }
+        }
+      }
+      __syncthreads();
+      if constexpr (!LAND) {
+        // over the waves (increasing atom index: the first best stays) into the running column best.  The slab has two
+        // halves: the waves that run ahead write the other one, and this half is rewritten only behind the next barrier.
+        if (tid < CW) {
+          const int j = ch * CW + tid;
+          if (j < NP) {
+            double p = s_cp[j], q = s_cq[j];
+            int i = s_ci[j];
+            for (int w = 0; w < NW; ++w) {
+              const int s = ((ch & 1) * NW + w) * CW + tid;
+              const double p2 = s_sp[s], q2 = s_sq[s];
+              const bool take = p2 * q > p * q2;
+              p = take ? p2 : p;
+              q = take ? q2 : q;
+              i = take ? s_si[s] : i;
+            }
+            s_cp[j] = p; s_cq[j] = q; s_ci[j] = i;
+          }
+        }
+      }
+    }
+    if constexpr (!LAND) {
+      // row bests of this sweep: one division per (lane, row), then over the 16 lanes of the row (ties: lowest j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        double v = bp[r] / bq[r];
+        int j = bj[r];
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) {
+          const double v2 = __shfl_xor(v, o);
+          const int j2 = __shfl_xor(j, o);
+          const bool take = (v2 > v) || (v2 == v && j2 < j);
+          v = take ? v2 : v;
+          j = take ? j2 : j;
+        }
+        const int i = rtc * 16 + lg + 4 * r;
+        if (lc == 0 && rowok[r]) {
+          a.obj[(vox * 2 + 0) * N + i] = y_sq - v;
+          if (a.partner) a.partner[(vox * 2 + 0) * N + i] = j;
+        }
+      }
+    }
+  }
+  if constexpr (!LAND) {
+    __syncthreads();
+    for (int j = tid; j < N; j += WG) {
+      a.obj[(vox * 2 + 1) * N + j] = y_sq - s_cp[j] / s_cq[j];
+      if (a.partner) a.partner[(vox * 2 + 1) * N + j] = s_ci[j];
+    }
+  }
+}
+
+// K = 1: one workgroup per voxel, one thread per atom
+template <bool CSF>
+__global__ __launch_bounds__(PROF_K1_WG) void mfx_profile_k1_kernel(ProfArgs a) {
+  extern __shared__ double smem[];
+  const int tid = threadIdx.x;
+  const int M = a.P.M, N = a.T.N, ldn = a.T.ldn;
+  const size_t vox = blockIdx.x;
+  double* s_y = smem;          // [M]
+  double* s_x = s_y + M;       // [M]
+  double* s_t0 = s_x + M;      // [M]
+  double* s_t1 = s_t0 + M;     // [M]
+  int* s_r0 = (int*)(s_t1 + M);  // [M]
+  int* s_r1 = s_r0 + M;        // [M]
+  const double* __restrict__ yv = a.Y + vox * M;
+  const double* __restrict__ pk = a.peaks + vox * 3;
+  for (int m = tid; m < M; m += PROF_K1_WG) {
+    s_y[m] = yv[m];
+    s_x[m] = CSF ? a.xc[m] : 0.0;
+    const RowDesc rd = mfx_row_desc(a.T, a.P, m, pk[0], pk[1], pk[2]);
+    s_r0[m] = rd.r0; s_t0[m] = rd.t0; s_r1[m] = rd.r1; s_t1[m] = rd.t1;
+  }
+  if (tid == 0) mfx_check_dir(a.P, pk, (int)vox);
+  __syncthreads();
+  double y_sq = 0.0, xx = 0.0, xy = 0.0;
+  for (int m = 0; m < M; ++m) {
+    y_sq += s_y[m] * s_y[m];
+    if constexpr (CSF) { xx += s_x[m] * s_x[m]; xy += s_x[m] * s_y[m]; }
+  }
+  const double ixx = (CSF && xx > 0.0) ? 1.0 / xx : 0.0;
+  for (int n = tid; n < N; n += PROF_K1_WG) {
+    double a2 = 0.0, ay = 0.0, ax = 0.0;
+    for (int m = 0; m < M; ++m) {
+      RowDesc rd;
+      rd.r0 = s_r0[m]; rd.t0 = s_t0[m]; rd.r1 = s_r1[m]; rd.t1 = s_t1[m];
+      const double d = mfx_eval_br(a.T.tab, ldn, rd, a.P.tG[m], a.P.dG[m], n);
+      a2 += d * d;
+      ay += s_y[m] * d;
+      if constexpr (CSF) ax += s_x[m] * d;
+    }
+    const double yp = fmax(ay, 0.0);
+    double s = a2 > 0.0 ? yp * yp / a2 : 0.0;
+    if constexpr (CSF) {
+      double Ap, Yp, iAp;
+      prof_primed(a2, ay, ax, ixx, xy, Ap, Yp, iAp);
+      const double w1 = fmax(Yp, 0.0) * iAp;
+      if (fma(-w1, ax, xy) >= 0.0) s = xy * xy * ixx + Yp * w1;
+    }
+    a.obj[vox * N + n] = y_sq - s;
+    if (a.partner) a.partner[vox * N + n] = -1;
+  }
+}
+
+size_t prof_lds_bytes(int ksteps, bool bracket, bool csf, bool land, int NP, int nw, int tiles, int nbuf) {
+  const size_t MP = (size_t)ksteps * 4, MPS = MP, cw = 16 * (size_t)tiles;
+  const size_t dbl = (size_t)nbuf * tiles * MPS * 16 + MP + (csf ? MP : 0) + 2 * MP + (bracket ? 4 * MP : 0) +
+                     (size_t)NP * (4 + (csf ? 2 : 0) + (land ? 0 : 2)) + (land ? 0 : 2 * 2 * nw * cw);
+  const size_t ints = 2 * MP + (bracket ? 2 * MP : 0) + (land ? 0 : (size_t)NP + 2 * nw * cw);
+  return dbl * 8 + ints * 4;
+}
+
+template <int KS, bool BR, bool CSF, bool LAND, int NW, int TILES, int NBUF>
+int prof_launch_t(const ProfArgs& a, int nvox, hipStream_t st) {
+  const size_t lds = prof_lds_bytes(KS, BR, CSF, LAND, a.T.ldn, NW, TILES, NBUF);
+  auto kern = mfx_profile_k2_kernel<KS, BR, CSF, LAND, NW, TILES, NBUF>;
+  HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kern, dim3(nvox), dim3(NW * 64), lds, st, a);
+  HIPCHK(hipGetLastError());
+  return MFX_OK;
+}
+
+// the configurations of M <= 200 in the order they are tried: {KSTEPS, NW, TILES, NBUF}; longer protocols: {140, 4, 1, 1}
+struct ProfCfg { int ks, nw, tiles, nbuf; };
+constexpr ProfCfg PROF_CFG_200[3] = {{50, 8, 2, 2}, {50, 4, 1, 2}, {50, 4, 1, 1}};
+
+int prof_pick(int M, bool br, bool csf, bool land, int NP) {   // index into PROF_CFG_200, 3: the long-protocol form, -1: none fits
+  if (M <= 200) {
+    for (int c = (csf || br) ? 1 : 0; c < 3; ++c)   // the CSF scan and bracketed rows do not fit the 256 registers of the 8-wave form
+      if (prof_lds_bytes(50, br, csf, land, NP, PROF_CFG_200[c].nw, PROF_CFG_200[c].tiles, PROF_CFG_200[c].nbuf) <= PROF_LDS_MAX) return c;
+    return -1;
+  }
+  return prof_lds_bytes(140, br, csf, land, NP, 4, 1, 1) <= PROF_LDS_MAX ? 3 : -1;
+}
+
+int prof_max_atoms(int M, bool br, bool csf, bool land) {
+  int n = 0;
+  while (n < (1 << 20) && prof_pick(M, br, csf, land, n + 16) >= 0) n += 16;
+  return n;
+}
+
+template <bool BR, bool CSF, bool LAND>
+int prof_launch_cfg(int cfg, const ProfArgs& a, int nvox, hipStream_t st) {
+  switch (cfg) {
+    case 0:
+      if constexpr (!CSF && !BR) return prof_launch_t<50, BR, CSF, LAND, 8, 2, 2>(a, nvox, st);
+      return mfx_fail(MFX_ERR_ARG, "profile: no such configuration");
+    case 1: return prof_launch_t<50, BR, CSF, LAND, 4, 1, 2>(a, nvox, st);
+    case 2: return prof_launch_t<50, BR, CSF, LAND, 4, 1, 1>(a, nvox, st);
+    default: return prof_launch_t<140, BR, CSF, LAND, 4, 1, 1>(a, nvox, st);
+  }
+}
+
+int prof_launch_k2(const ProfArgs& a, int nvox, bool csf, bool land, hipStream_t st, const char* fn) {
+  const int M = a.P.M;
+  const bool br = a.P.any_bracket != 0;
+  if (M > 560) return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: the K = 2 kernel supports M <= 560 (got %d)", fn, M);
+  const int cfg = prof_pick(M, br, csf, land, a.T.ldn);
+  if (cfg < 0)
+    return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: N = %d atoms exceed the %d that fit in LDS for this protocol (M = %d)", fn, a.T.N,
+                    prof_max_atoms(M, br, csf, land), M);
+  if (br) {
+    if (csf) return land ? prof_launch_cfg<true, true, true>(cfg, a, nvox, st) : prof_launch_cfg<true, true, false>(cfg, a, nvox, st);
+    return land ? prof_launch_cfg<true, false, true>(cfg, a, nvox, st) : prof_launch_cfg<true, false, false>(cfg, a, nvox, st);
+  }
+  if (csf) return land ? prof_launch_cfg<false, true, true>(cfg, a, nvox, st) : prof_launch_cfg<false, true, false>(cfg, a, nvox, st);
+  return land ? prof_launch_cfg<false, false, true>(cfg, a, nvox, st) : prof_launch_cfg<false, false, false>(cfg, a, nvox, st);
+}
+
+const char* NO_DEVICE = "no HIP device available (this library has no CPU path)";
+
+int prof_require_device(int device) {
+  const int n = mfx_device_count();
+  if (n <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
+  if (device < 0 || device >= n) return mfx_fail(MFX_ERR_ARG, "device %d out of range (have %d)", device, n);
+  HIPCHK(hipSetDevice(device));
+  return MFX_OK;
+}
+
+int prof_check_args(const char* fn, const mfx_plan* p, const void* Y, const void* peaks, int K, int csf_on, const void* sig_csf,
+                    int64_t V, const void* out) {
+  if (!p || V < 0 || (V > 0 && (!Y || !peaks || !out))) return mfx_fail(MFX_ERR_ARG, "%s: bad argument", fn);
+  if (K != 1 && K != 2)
+    return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: K must be 1 or 2 (got %d): three fascicles and voxels without one are out of scope", fn, K);
+  if (csf_on && !sig_csf) return mfx_fail(MFX_ERR_ARG, "%s: csf_on without sig_csf", fn);
+  if (V > 0x7fffffff) return mfx_fail(MFX_ERR_ARG, "%s: V too large for one call", fn);
+  return MFX_OK;
+}
+
+// shared body of the two device entry points
+int prof_enqueue(const char* fn, const mfx_plan* p, const double* d_Y, const double* d_peaks, int K, int csf_on,
+                 const double* d_sig_csf, int64_t V, double* d_obj, int32_t* d_partner, bool land, void* stream) {
+  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
+  if (int rc = prof_check_args(fn, p, d_Y, d_peaks, K, csf_on, d_sig_csf, V, d_obj)) return rc;
+  ProfArgs a{};
+  int device = 0;
+  mfx_plan_view(p, &a.T, &a.P, &device);
+  if (a.P.M > 560) return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: supports M <= 560 (got %d)", fn, a.P.M);
+  if (V == 0) return MFX_OK;
+  if (int rc = prof_require_device(device)) return rc;
+  a.Y = d_Y; a.peaks = d_peaks; a.xc = csf_on ? d_sig_csf : nullptr; a.obj = d_obj; a.partner = d_partner;
+  hipStream_t st = (hipStream_t)stream;
+  if (K == 2) return prof_launch_k2(a, (int)V, csf_on != 0, land, st, fn);
+  const size_t lds = (size_t)a.P.M * (4 * sizeof(double) + 2 * sizeof(int));
+  if (csf_on) hipLaunchKernelGGL(mfx_profile_k1_kernel<true>, dim3((unsigned)V), dim3(PROF_K1_WG), lds, st, a);
+  else hipLaunchKernelGGL(mfx_profile_k1_kernel<false>, dim3((unsigned)V), dim3(PROF_K1_WG), lds, st, a);
+  HIPCHK(hipGetLastError());
+  return MFX_OK;
+}
+
+// shared body of the two host entry points: out [V x rows x N] with rows = K (profile) or N (landscape)
+int prof_host(const char* fn, const mfx_plan* p, const double* Y, const double* peaks, int K, int csf_on, const double* sig_csf,
+              int64_t V, double* obj, int32_t* partner, bool land) {
+  if (int rc = prof_check_args(fn, p, Y, peaks, K, csf_on, sig_csf, V, obj)) return rc;
+  if (V == 0) return MFX_OK;
+  TablesDev T;
+  PlanDev P;
+  int device = 0;
+  mfx_plan_view(p, &T, &P, &device);
+  if (int rc = prof_require_device(device)) return rc;
+  const size_t M = P.M, N = T.N, nout = (size_t)V * (land ? N : (size_t)K) * N;
+  DevMem dY, dpk, dx, dobj, dpar;
+  HIPCHK(dY.alloc(sizeof(double) * V * M));
+  HIPCHK(dpk.alloc(sizeof(double) * V * 3 * K));
+  HIPCHK(dx.alloc(sizeof(double) * M));
+  HIPCHK(dobj.alloc(sizeof(double) * nout));
+  HIPCHK(dpar.alloc(partner ? sizeof(int32_t) * nout : 0));
+  HIPCHK(hipMemcpy(dY.p, Y, sizeof(double) * V * M, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dpk.p, peaks, sizeof(double) * V * 3 * K, hipMemcpyHostToDevice));
+  if (csf_on) HIPCHK(hipMemcpy(dx.p, sig_csf, sizeof(double) * M, hipMemcpyHostToDevice));
+  if (int rc = prof_enqueue(fn, p, dY.as<double>(), dpk.as<double>(), K, csf_on, csf_on ? dx.as<double>() : nullptr, V,
+                            dobj.as<double>(), partner ? dpar.as<int32_t>() : nullptr, land, nullptr)) return rc;
+  if (int rc = mfx_plan_status(p, nullptr)) return rc;   // waits; a direction that is not a unit vector
+  HIPCHK(hipMemcpy(obj, dobj.p, sizeof(double) * nout, hipMemcpyDeviceToHost));
+  if (partner) HIPCHK(hipMemcpy(partner, dpar.p, sizeof(int32_t) * nout, hipMemcpyDeviceToHost));
+  return MFX_OK;
+}
+
+}  // namespace
+
+extern "C" int mfx_profile_abi_version(void) { return 1; }
+
+extern "C" double mfx_profile_cut(void) { return MFX_PROFILE_CUT; }
+
+extern "C" int mfx_profile_max_atoms(const mfx_plan* p, int csf_on, int landscape) {
+  if (!p) return 0;
+  TablesDev T;
+  PlanDev P;
+  int device = 0;
+  mfx_plan_view(p, &T, &P, &device);
+  if (P.M > 560) return 0;
+  return prof_max_atoms(P.M, P.any_bracket != 0, csf_on != 0, landscape != 0);
+}
+
+extern "C" int mfx_profile_dev(const mfx_plan* p, const double* d_Y, const double* d_peaks, int K, int csf_on,
+                               const double* d_sig_csf, int64_t V, double* d_obj, int32_t* d_partner, void* stream) {
+  return prof_enqueue("mfx_profile_dev", p, d_Y, d_peaks, K, csf_on, d_sig_csf, V, d_obj, d_partner, false, stream);
+}
+
+extern "C" int mfx_profile(const mfx_plan* p, const double* Y, const double* peaks, int K, int csf_on, const double* sig_csf,
+                           int64_t V, double* obj, int32_t* partner) {
+  return prof_host("mfx_profile", p, Y, peaks, K, csf_on, sig_csf, V, obj, partner, false);
+}
+
+extern "C" int mfx_pair_objectives_dev(const mfx_plan* p, const double* d_Y, const double* d_peaks, int csf_on,
+                                       const double* d_sig_csf, int64_t V, double* d_out, void* stream) {
+  return prof_enqueue("mfx_pair_objectives_dev", p, d_Y, d_peaks, 2, csf_on, d_sig_csf, V, d_out, nullptr, true, stream);
+}
+
+extern "C" int mfx_pair_objectives(const mfx_plan* p, const double* Y, const double* peaks, int csf_on, const double* sig_csf,
+                                   int64_t V, double* out) {
+  return prof_host("mfx_pair_objectives", p, Y, peaks, 2, csf_on, sig_csf, V, out, nullptr, true);
+}

@@ -413,6 +413,136 @@ def sos_noise(S0, sigma_g, ncoils=1, seed=0, offset=0, device=0):
     return out
 
 
+def _profile_shapes(plan, y_shape, pk_shape, K, csf_on, M_csf):
+    """Argument checks shared by the profile entry points (before any device call); returns V."""
+    K = int(K)
+    if K not in (1, 2):
+        raise NotImplementedError("objective profiles serve K = 1 or 2 fascicles (got %d): three fascicles and voxels "
+                                  "without one are out of scope" % K)
+    if len(y_shape) != 2 or y_shape[1] != plan.M:
+        raise ValueError("data has shape %s, protocol has %d measurements" % (tuple(y_shape), plan.M))
+    V = y_shape[0]
+    if pk_shape is None or tuple(pk_shape) != (V, 3 * K):
+        raise ValueError("peaks should have shape (%d, %d)" % (V, 3 * K))
+    if csf_on and M_csf != plan.M:
+        raise ValueError("sig_csf has %s entries, protocol has %d" % (M_csf, plan.M))
+    return V
+
+
+def profile_dev(plan, d_Y, d_peaks, K, csf_on=False, d_sig_csf=None, partner=False, out=None):
+    """Objective profiles on the device (mfx_profile_dev) for torch CUDA float64 tensors of ONE voxel class (every
+    voxel: K fascicles, CSF or not, no EAR): ``obj`` [V x K x N], obj[v, k, i] the smallest sum of squared residuals
+    any partner atom reaches beside atom i of fascicle k (include/mfx_profile.h has the definitions), and with
+    ``partner=True`` also the int32 tensor of the arg-min partners (-1 for K = 1).  Enqueues on torch's current
+    stream and returns without waiting; a direction that is not a unit vector flags the plan's status word."""
+    import torch
+    assert d_Y.is_cuda and d_Y.dtype == torch.float64 and d_Y.is_contiguous()
+    assert d_peaks.is_cuda and d_peaks.dtype == torch.float64 and d_peaks.is_contiguous()
+    if csf_on:
+        if d_sig_csf is None:
+            raise ValueError("csf_on without d_sig_csf")
+        assert d_sig_csf.is_cuda and d_sig_csf.dtype == torch.float64 and d_sig_csf.is_contiguous()
+    V = _profile_shapes(plan, d_Y.shape, d_peaks.shape, K, csf_on, d_sig_csf.numel() if csf_on else None)
+    N = plan.tables.N
+    if out is None:
+        out = torch.empty((V, int(K), N), dtype=torch.float64, device=d_Y.device)
+    assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (V, int(K), N)
+    part = torch.empty((V, int(K), N), dtype=torch.int32, device=d_Y.device) if partner else None
+    st = torch.cuda.current_stream(d_Y.device).cuda_stream
+    L.check(L.lib().mfx_profile_dev(plan.handle(), d_Y.data_ptr(), d_peaks.data_ptr(), int(K), int(bool(csf_on)),
+                                    d_sig_csf.data_ptr() if csf_on else None, V, out.data_ptr(),
+                                    part.data_ptr() if partner else None, st))
+    return (out, part) if partner else out
+
+
+def pair_objectives_dev(plan, d_Y, d_peaks, csf_on=False, d_sig_csf=None):
+    """The objective of every atom pair (mfx_pair_objectives_dev): [V x N x N] torch tensor, two-fascicle voxels."""
+    import torch
+    assert d_Y.is_cuda and d_Y.dtype == torch.float64 and d_Y.is_contiguous()
+    assert d_peaks.is_cuda and d_peaks.dtype == torch.float64 and d_peaks.is_contiguous()
+    V = _profile_shapes(plan, d_Y.shape, d_peaks.shape, 2, csf_on, d_sig_csf.numel() if csf_on else None)
+    N = plan.tables.N
+    out = torch.empty((V, N, N), dtype=torch.float64, device=d_Y.device)
+    st = torch.cuda.current_stream(d_Y.device).cuda_stream
+    L.check(L.lib().mfx_pair_objectives_dev(plan.handle(), d_Y.data_ptr(), d_peaks.data_ptr(), int(bool(csf_on)),
+                                            d_sig_csf.data_ptr() if csf_on else None, V, out.data_ptr(), st))
+    return out
+
+
+def profile_classes(K, csf, ear, maxfasc):
+    """Bins the voxels of a mixed volume for the profile: ([(k, csf_flag, indices)], n_unsupported).  In scope: one or
+    two fascicles (k <= maxfasc), with or without CSF, no EAR."""
+    K = np.asarray(K).astype(np.int64)
+    V = K.shape[0]
+    csf = np.zeros(V, bool) if csf is None else np.asarray(csf).astype(bool)
+    ear = np.zeros(V, bool) if ear is None else np.asarray(ear).astype(bool)
+    if csf.shape != (V,) or ear.shape != (V,):
+        raise ValueError("K, csf and ear should have one entry per voxel")
+    if V and K.max() > maxfasc:
+        raise ValueError("K exceeds maxfasc = %d" % maxfasc)
+    ok = (K >= 1) & (K <= 2) & ~ear
+    bins = []
+    for k in (1, 2):
+        for c in (False, True):
+            ix = np.flatnonzero(ok & (K == k) & (csf == c))
+            if ix.size:
+                bins.append((k, c, ix))
+    return bins, int(V - np.count_nonzero(ok))
+
+
+def profile(plan, Y, K, csf, peaks, maxfasc, csf_on, sig_csf, partner=False, ear=None):
+    """Objective profiles of a mixed set of voxels on NumPy arrays (mfx_profile, one call per voxel class): Y [V x M],
+    per-voxel K, csf (and ear) flags, peaks [V x 3 maxfasc] as for ``fit_batch``.  Returns ``(obj, partner,
+    n_unsupported)``: obj [V x maxfasc x N] float64 (rows of absent fascicles and of the voxel classes out of scope -
+    EAR, no fascicle, three fascicles - are NaN), partner [V x maxfasc x N] int32 (-1 where there is none) or None,
+    and the number of voxels out of scope."""
+    Y = L.f64c(Y)
+    maxfasc = int(maxfasc)
+    if Y.ndim != 2 or Y.shape[1] != plan.M:
+        raise ValueError("data has shape %s, protocol has %d measurements" % (Y.shape, plan.M))
+    V = Y.shape[0]
+    if np.asarray(K).shape != (V,):
+        raise ValueError("K should have one entry per voxel")
+    pk = L.f64c(peaks).reshape(V, -1) if maxfasc > 0 else np.zeros((V, 0))
+    if pk.shape[1] != 3 * maxfasc:
+        raise ValueError("peaks should have %d columns" % (3 * maxfasc))
+    sc = L.f64c(sig_csf).reshape(-1) if sig_csf is not None else None
+    if np.any(csf) and (not csf_on or sc is None):
+        raise ValueError("voxels flagged CSF need csf_on and sig_csf")
+    if sc is not None and sc.shape[0] != plan.M:
+        raise ValueError("sig_csf has %d entries, protocol has %d" % (sc.shape[0], plan.M))
+    bins, n_uns = profile_classes(K, csf, ear, maxfasc)
+    N = plan.tables.N
+    obj = np.full((V, maxfasc, N), np.nan)
+    par = np.full((V, maxfasc, N), -1, dtype=np.int32) if partner else None
+    for k, c, ix in bins:
+        Yc, pc = np.ascontiguousarray(Y[ix]), np.ascontiguousarray(pk[ix, :3 * k])
+        o = np.zeros((ix.size, k, N))
+        p = np.zeros((ix.size, k, N), dtype=np.int32) if partner else None
+        L.check(L.lib().mfx_profile(plan.handle(), L.dptr(Yc), L.dptr(pc), k, int(c), L.dptr(sc) if c else None, ix.size,
+                                    L.dptr(o), L.iptr(p) if partner else None))
+        obj[ix, :k] = o
+        if partner:
+            par[ix, :k] = p
+    return obj, par, n_uns
+
+
+def pair_objectives(plan, Y, peaks, csf_on=False, sig_csf=None):
+    """The objective of every atom pair of two-fascicle voxels (mfx_pair_objectives): Y [V x M], peaks [V x 6] ->
+    [V x N x N], out[v, i, j] = min over non-negative weights of |y - w1 D_0[:, i] - w2 D_1[:, j] (- wx sig_csf)|^2."""
+    Y = L.f64c(Y)
+    pk = L.f64c(peaks)
+    sc = L.f64c(sig_csf).reshape(-1) if csf_on else None
+    if csf_on and sig_csf is None:
+        raise ValueError("csf_on without sig_csf")
+    V = _profile_shapes(plan, Y.shape, pk.shape, 2, csf_on, sc.shape[0] if sc is not None else None)
+    N = plan.tables.N
+    out = np.zeros((V, N, N))
+    L.check(L.lib().mfx_pair_objectives(plan.handle(), L.dptr(Y), L.dptr(pk), int(bool(csf_on)),
+                                        L.dptr(sc) if sc is not None else None, V, L.dptr(out)))
+    return out
+
+
 def rotate2d_dev(tables, d_dirs, d_cols=None):
     """Device-resident 2-D protocol rotation (mfx_rot2d_rotate_dev / mfx_rot2d_rotate_cols_dev) for a
     mf_utils.RotateAtom2DTables: torch CUDA tensors dirs [B,3] f64 (and cols [B] int: one atom per direction)

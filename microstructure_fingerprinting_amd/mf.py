@@ -304,7 +304,9 @@ class MFModel():
             print("Estimation performed in %g second(s)." % (time.time() - st))
         fitinfo = {'maxfasc': maxfasc, 'csf_on': csf_on, 'ear_on': ear_on, 'affine': nii_affine, 'mask': mask_arr,
                    'fasc_propnames': [x.strip() for x in self.dic['fasc_propnames']], 'peaks_roi': peaks_roi,
-                   'roi_index': roi_index, 'model': self, 'pgse_scheme': pgse_scheme}
+                   'roi_index': roi_index, 'model': self, 'pgse_scheme': pgse_scheme,
+                   'numfasc_roi': numfasc_roi, 'csf_roi': np.asarray(csf_mask, dtype=bool),
+                   'ear_roi': np.asarray(ear_mask, dtype=bool)}
         for n in fitinfo['fasc_propnames']:
             fitinfo['_dict_' + n] = self.dic[n]
         if ear_on:
@@ -464,6 +466,9 @@ class MFModelFit():
         self._model, self._pgse_scheme = fitinfo.get('model'), fitinfo.get('pgse_scheme')
         self._nf, self._csf_on, self._ear_on = nf, bool(csf_on), bool(ear_on)
         self._peaks_roi, self._roi_flat, self._grid = fitinfo.get('peaks_roi'), flat, tuple(mask.shape)
+        # per-voxel classes and per-atom properties (profile() and interval())
+        self._numfasc_roi, self._csf_roi, self._ear_roi = (fitinfo.get(k) for k in ('numfasc_roi', 'csf_roi', 'ear_roi'))
+        self._props = {n: np.asarray(fitinfo['_dict_' + n], dtype=np.float64).reshape(-1) for n in fitinfo['fasc_propnames']}
         whole = ROI_size == int(np.prod(mask.shape))
 
         def to_map(vals, extra=()):
@@ -560,6 +565,75 @@ class MFModelFit():
             rows[idx] = np.asarray(data_arr[np.unravel_index(idx, self._grid)], dtype=np.float64) - pred
         return vol
 
+    PROFILE_BYTES = 256 << 20   # largest [chunk x K x N] float64 buffer of interval()
+
+    def _profile_setup(self, data):
+        if self._model is None or self._pgse_scheme is None or self._numfasc_roi is None:
+            raise RuntimeError("this fit object was not made by MFModel.fit: it knows neither its model nor its protocol "
+                               "nor the voxels' classes")
+        data_arr, _ = _load_volume(data)
+        shape = self._grid + (self._pgse_scheme.shape[0],)
+        if data_arr.shape != shape:
+            raise ValueError("data should have shape (%s), got (%s)" % (" ".join("%d" % x for x in shape),
+                                                                        " ".join("%d" % x for x in data_arr.shape)))
+        m = self._model
+        sig_csf = m._extra_signals(self._pgse_scheme, self._csf_on, False)[0]
+        return data_arr, m.ms_interpolator.plan_for(self._pgse_scheme), sig_csf
+
+    def _data_rows(self, data_arr, idx):
+        return np.ascontiguousarray(data_arr[np.unravel_index(idx, self._grid)], dtype=np.float64)
+
+    def profile(self, data, voxels=None, partner=False):
+        """What the exhaustive search saw beside its arg-min: for every atom of each fascicle the smallest sum of
+        squared residuals any partner atom reaches with it (``engine.profile``).  ``data`` as given to ``fit``;
+        ``voxels``: positions in the ROI (default: all of it - [ROI x maxfasc x N] float64 on the host, meant for
+        regions, not for brains: see ``interval``).  Returns an object with ``obj`` [n x maxfasc x N], ``partner``
+        (int32, -1 where there is none; None unless asked for), ``n_unsupported`` (voxels with EAR or without a
+        fascicle: their rows are NaN) and ``by_property(name)`` -> (levels, obj_by_level)."""
+        data_arr, plan, sig_csf = self._profile_setup(data)
+        vox = np.arange(self._roi_flat.shape[0]) if voxels is None else np.asarray(voxels, dtype=np.int64).reshape(-1)
+        obj, par, n_uns = engine.profile(plan, self._data_rows(data_arr, self._roi_flat[vox]), self._numfasc_roi[vox],
+                                         self._csf_roi[vox], self._peaks_roi[vox], self._nf, self._csf_on, sig_csf,
+                                         partner=partner, ear=self._ear_roi[vox])
+        return ObjectiveProfile(obj, par, n_uns, vox, self._props)
+
+    def interval(self, data, name, rel=0.0, delta=0.0):
+        """The range of the fascicle property ``name`` (one of the dictionary's ``fasc_propnames``) that fits the data
+        within a margin of the optimum: per voxel and fascicle, over the atoms whose profile value is at most
+        ``min * (1 + rel) + delta``, the smallest and largest property value and the number of such atoms
+        (``mf_utils.profile_interval``).  Returns ``(lo, hi, count)`` volumes of shape ``mask.shape + (maxfasc,)``;
+        NaN / 0 outside the ROI, for absent fascicles and for voxels out of the profile's scope.  The profiles are
+        computed and reduced on the device, PROFILE_BYTES of them at a time; only the three numbers per voxel and
+        fascicle come back."""
+        import torch
+        if name not in self._props:
+            raise ValueError("unknown fascicle property %s (have: %s)" % (name, ", ".join(sorted(self._props))))
+        data_arr, plan, sig_csf = self._profile_setup(data)
+        nf, R = self._nf, self._roi_flat.shape[0]
+        N = plan.tables.N
+        dev = torch.device("cuda", plan.tables.device)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        d_csf = t(sig_csf) if self._csf_on else None
+        lo, hi = np.full((R, nf), np.nan), np.full((R, nf), np.nan)
+        cnt = np.zeros((R, nf), dtype=np.int64)
+        chunk = max(1, int(self.PROFILE_BYTES // (8 * 2 * N)))
+        bins, _ = engine.profile_classes(self._numfasc_roi, self._csf_roi, self._ear_roi, nf)
+        with torch.cuda.device(dev):
+            for k, c, ix in bins:
+                for i0 in range(0, ix.size, chunk):
+                    sub = ix[i0:i0 + chunk]
+                    obj = engine.profile_dev(plan, t(self._data_rows(data_arr, self._roi_flat[sub])),
+                                             t(self._peaks_roi[sub, :3 * k]), k, c, d_csf if c else None)
+                    l, h, n = mfu.profile_interval(obj, self._props[name], rel, delta)
+                    L.check(L.lib().mfx_plan_status(plan.handle(), torch.cuda.current_stream(dev).cuda_stream))
+                    lo[sub, :k], hi[sub, :k], cnt[sub, :k] = l.cpu().numpy(), h.cpu().numpy(), n.cpu().numpy()
+
+        def to_map(vals, fill):
+            m = np.full((int(np.prod(self._grid)), nf), fill, dtype=vals.dtype)
+            m[self._roi_flat] = vals
+            return m.reshape(self._grid + (nf,))
+        return to_map(lo, np.nan), to_map(hi, np.nan), to_map(cnt, 0)
+
     def write_nifti(self, output_basename, affine=None):
         """One NIfTI file per parameter map, ``<stem>_<param><ext>``; returns the file names (reference mf.py:1177-1229).
         ``output_basename`` may end in .nii.gz (kept), .nii or nothing (both give .nii); any other extension is refused."""
@@ -574,6 +648,20 @@ class MFModelFit():
             nifti.save(getattr(self, name), xfm, target)
             written.append(target)
         return written
+
+
+class ObjectiveProfile(object):
+    """Result of ``MFModelFit.profile``: ``obj`` [n x maxfasc x N], ``partner`` (or None), ``n_unsupported``, ``voxels``
+    (the ROI positions the rows stand for)."""
+
+    def __init__(self, obj, partner, n_unsupported, voxels, props):
+        self.obj, self.partner, self.n_unsupported, self.voxels, self._props = obj, partner, n_unsupported, voxels, props
+
+    def by_property(self, name):
+        """(levels, obj_by_level [n x maxfasc x len(levels)]): the profile as a function of the property ``name``."""
+        if name not in self._props:
+            raise ValueError("unknown fascicle property %s (have: %s)" % (name, ", ".join(sorted(self._props))))
+        return mfu.profile_by_property(self.obj, self._props[name])
 
 
 def _nifti_stem(output_basename):

@@ -40,7 +40,7 @@ __all__ = ["get_gyromagnetic_ratio", "solve_exhaustive_posweights", "init_PGSE_m
            "interp_PGSE_from_multishell", "rotate_atom", "RotateAtomTables", "import_PGSE_scheme",
            "get_PGSE_scheme_from_bval_bvec_dense", "loadmat", "MultiShellInterpolator",
            "rotate_atom_2Dprotocol", "RotateAtom2DTables", "rotate_scheme_mat", "vrrotvec2mat", "rotate_vector",
-           "get_perp_vector", "project_PGSE_scheme_xy_plane", "gen_SoS_MRI"]
+           "get_perp_vector", "project_PGSE_scheme_xy_plane", "gen_SoS_MRI", "profile_by_property", "profile_interval"]
 
 
 def get_gyromagnetic_ratio(element='H'):
@@ -1046,6 +1046,65 @@ def gen_SoS_MRI(S0, sigma_g, N=1, *, seed=None, device=0):
     out = engine.sos_noise(S0, sg.reshape(-1)[:1] if sg.size == 1 else sg, int(N), _sos_seed(seed), 0, device)
     # a sigma_g of shape (1, 1) beside an S0 of shape (N,) still gives shape (N,) (ref:2350-2353)
     return np.reshape(out, S0.shape)
+
+
+def _is_torch(x):
+    return type(x).__module__.split('.')[0] == 'torch'
+
+
+def _property_levels(obj, values):
+    """(levels, index of every atom's level, obj, torch or None) for the two profile helpers below."""
+    values = np.asarray(values.cpu() if _is_torch(values) else values, dtype=np.float64).reshape(-1)
+    if obj.shape[-1] != values.shape[0]:
+        raise ValueError("obj has %d atoms along its last axis, values has %d" % (obj.shape[-1], values.shape[0]))
+    if np.isnan(values).any():
+        raise ValueError("values should not hold NaN")
+    levels, inv = np.unique(values, return_inverse=True)
+    return levels, np.asarray(inv).reshape(-1), values
+
+
+def profile_by_property(obj, values):
+    """An objective profile over atoms (``engine.profile``: obj [..., N]) as a function of one per-atom property
+    (``values`` [N]: rad, fin, ... - the arrays named by the dictionary's ``fasc_propnames``).  Returns
+    ``(levels, obj_by_level)``: the sorted distinct property values and, along a last axis of that length, the minimum
+    of obj over the atoms at each level.  A row that holds NaN (a voxel class the profile does not serve) stays NaN.
+    NumPy in, NumPy out; a torch tensor in, tensors out on its device."""
+    levels, inv, _ = _property_levels(obj, values)
+    if _is_torch(obj):
+        import torch
+        cols = [obj[..., torch.as_tensor(np.flatnonzero(inv == p), device=obj.device)].amin(dim=-1) for p in range(levels.size)]
+        return torch.as_tensor(levels, device=obj.device), torch.stack(cols, dim=-1)
+    obj = np.asarray(obj, dtype=np.float64)
+    return levels, np.stack([obj[..., inv == p].min(axis=-1) for p in range(levels.size)], axis=-1)
+
+
+def profile_interval(obj, values, rel=0.0, delta=0.0):
+    """The range of a per-atom property that fits within a margin of the optimum: among the atoms with
+    ``obj <= obj_min * (1 + rel) + delta`` (obj_min the minimum of obj [..., N] along its last axis) the smallest and
+    the largest of ``values`` [N], and how many atoms that is: ``(lo, hi, count)`` of shape obj.shape[:-1].  NaN rows
+    give lo = hi = NaN and count 0.  NumPy in, NumPy out; a torch tensor in, tensors out on its device."""
+    if rel < 0 or delta < 0:
+        raise ValueError("rel and delta should not be negative")
+    _, _, values = _property_levels(obj, values)
+    if _is_torch(obj):
+        import torch
+        v = torch.as_tensor(values, device=obj.device)
+        bad = torch.isnan(obj).any(dim=-1, keepdim=True)
+        omin = obj.amin(dim=-1, keepdim=True)
+        sel = (obj <= omin * (1.0 + rel) + delta) & ~bad
+        inf = torch.tensor(float('inf'), dtype=torch.float64, device=obj.device)
+        lo = torch.where(sel, v, inf).amin(dim=-1)
+        hi = torch.where(sel, v, -inf).amax(dim=-1)
+        nan = torch.tensor(float('nan'), dtype=torch.float64, device=obj.device)
+        return torch.where(bad[..., 0], nan, lo), torch.where(bad[..., 0], nan, hi), sel.sum(dim=-1)
+    obj = np.asarray(obj, dtype=np.float64)
+    bad = np.isnan(obj).any(axis=-1, keepdims=True)
+    with np.errstate(invalid='ignore'):
+        omin = obj.min(axis=-1, keepdims=True)
+        sel = (obj <= omin * (1.0 + rel) + delta) & ~bad
+    lo = np.where(sel, values, np.inf).min(axis=-1)
+    hi = np.where(sel, values, -np.inf).max(axis=-1)
+    return np.where(bad[..., 0], np.nan, lo), np.where(bad[..., 0], np.nan, hi), sel.sum(axis=-1)
 
 
 def _sos_seed(seed):
