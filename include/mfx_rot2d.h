@@ -29,7 +29,8 @@
  * knot_y    [K x N]   perpendicular signals S_perp_ref at those knots
  *
  * Status record of each direction, int32[4]: {code, pair (0-based), value, value2}; code 0 = the
- * direction succeeded.  The codes name the first check that failed in the reference's order:
+ * direction succeeded.  The codes name the first check that failed in the reference's order.  The per-(direction, row)
+ * plan records behind these entry points are shared with the fit of mfx_fit2d.h, which takes the same handle:
  */
 #ifndef MFX_ROT2D_H
 #define MFX_ROT2D_H

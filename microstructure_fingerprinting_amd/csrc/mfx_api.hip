@@ -982,6 +982,66 @@ static int fit_class_generic(const mfx_plan* p, const double* d_Y, const double*
   return mfx_prof_end(st);
 }
 
+// The explicit-dictionary solver on a dictionary that already sits on the device (fit2d.hip's path for the voxel classes
+// without a fused kernel): d_A [M x Ntot] row-major, K blocks of N columns and then the CSF column if has_csf.  Gram,
+// scan, exact finalize and the params row are enqueued on `st`.  The caller owns the scratch (mfx_solve_dense_scratch_bytes)
+// and may hand the same block to one call after the other on one stream.  run_if: null, or a device flag - while it is 0
+// every kernel exits at once.
+static int dense_args(int M, int K, int N, int has_csf, SolveArgs& a, bool& k3, size_t off[11]) {
+  const int Kp = K + has_csf;
+  if (Kp < 1 || Kp > MFX_GK) return fail(MFX_ERR_UNSUPPORTED, "explicit solver: 1 to %d sub-dictionaries (got %d)", MFX_GK, Kp);
+  long Ntot = 0, ntup = 1;
+  for (int k = 0; k < Kp; ++k) {
+    const long sz = k < K ? N : 1;
+    a.sizes[k] = sz; a.start[k] = Ntot; Ntot += sz;
+    if (ntup > (1L << 42) / sz) return fail(MFX_ERR_UNSUPPORTED, "too many index tuples per voxel for the explicit solver");
+    ntup *= sz;
+  }
+  if (Ntot > 30000) return fail(MFX_ERR_UNSUPPORTED, "explicit solver supports up to 30000 columns (got %ld)", Ntot);
+  a.M = M; a.Kp = Kp; a.Ntot = (int)Ntot; a.lda = Ntot; a.ntuples = ntup;
+  a.nblocks = (int)std::min<long>(16384, (ntup + 255) / 256);
+  k3 = mfx_thread().k3_screen && k3_applies(a);
+  const size_t nlist = k3 ? (size_t)MFX_K3_CAP : (size_t)a.nblocks;
+  // G, Aty, ysq, blk_score, blk_tuple, w, sub, minobj, yrec, k3 buffers; off[10] = total
+  const size_t sz[10] = {sizeof(double) * (size_t)Ntot * Ntot, sizeof(double) * (size_t)Ntot, 16, sizeof(double) * nlist, sizeof(long) * nlist,
+                         sizeof(double) * MFX_GK, sizeof(long) * MFX_GK, 8, sizeof(double) * (size_t)M, k3_buf_bytes(N)};
+  size_t o = 0;
+  for (int q = 0; q < 10; ++q) { off[q] = o; o += (sz[q] + 255) / 256 * 256; }
+  off[10] = o;
+  return MFX_OK;
+}
+int mfx_solve_dense_scratch_bytes(int M, int K, int N, int has_csf, size_t* bytes) {
+  SolveArgs a{};
+  bool k3;
+  size_t off[11];
+  if (int rc = dense_args(M, K, N, has_csf, a, k3, off)) return rc;
+  *bytes = off[10];
+  return MFX_OK;
+}
+int mfx_solve_dense_dev(const double* d_A, int M, int K, int N, int has_csf, const double* d_y, int maxfasc, int csf_on,
+                        double* d_row, const int* run_if, void* d_scratch, hipStream_t st) {
+  SolveArgs a{};
+  bool k3;
+  size_t off[11];
+  if (int rc = dense_args(M, K, N, has_csf, a, k3, off)) return rc;
+  char* sc = (char*)d_scratch;
+  a.A = d_A; a.y = d_y; a.run_if = run_if;
+  a.G = (double*)(sc + off[0]); a.Aty = (double*)(sc + off[1]); a.ysq = (double*)(sc + off[2]); a.blk_score = (double*)(sc + off[3]);
+  a.blk_tuple = (long*)(sc + off[4]); a.w = (double*)(sc + off[5]); a.sub = (long*)(sc + off[6]); a.minobj = (double*)(sc + off[7]);
+  a.yrec = (double*)(sc + off[8]);
+  K3Bufs kb = k3_bufs(sc + off[9]);
+  if (int rc = launch_solver(a, k3 ? &kb : nullptr, st)) return rc;
+  PackArgs pa{};
+  pa.run_if = run_if;
+  pa.w = a.w; pa.sub = a.sub; pa.minobj = a.minobj; pa.yrec = a.yrec; pa.y = d_y;
+  pa.M = M; pa.K = K; pa.has_csf = has_csf; pa.E = 0; pa.maxfasc = maxfasc; pa.csf_on = csf_on; pa.ear_on = 0;
+  pa.num_params = 1 + 2 * maxfasc + csf_on + 2;
+  pa.out = d_row;
+  hipLaunchKernelGGL(mfx_pack_params_kernel, dim3(1), dim3(64), 0, st, pa);
+  HIPCHK(hipGetLastError());
+  return MFX_OK;
+}
+
 extern "C" int mfx_fit_batch_dev(const mfx_plan* p, const double* d_Y, const double* d_peaks, int maxfasc, int csf_on,
                                  int ear_on, const double* d_sig_csf, const double* d_sig_ear, int E, int64_t V,
                                  double* d_params_out, void* stream) {

@@ -132,6 +132,11 @@ int mfx_fb_end(hipStream_t st);
 // the device-side views of a plan and of its tables, and the device they live on (for translation units other than mfx_api.hip)
 void mfx_plan_view(const mfx_plan* p, TablesDev* T, PlanDev* P, int* device);
 
+// explicit-dictionary solver and params packing on a device-resident dictionary [M x (K N + has_csf)] (mfx_api.hip; for fit2d.hip)
+int mfx_solve_dense_scratch_bytes(int M, int K, int N, int has_csf, size_t* bytes);
+int mfx_solve_dense_dev(const double* d_A, int M, int K, int N, int has_csf, const double* d_y, int maxfasc, int csf_on,
+                        double* d_row, const int* run_if, void* d_scratch, hipStream_t st);
+
 // ---- kernel launchers, one translation unit each
 // FP64 two-fascicle kernel (tu_k2.hip).  With a.list_count set, a.vox_list is a device-side list whose length only the
 // device knows: the launch covers nvox blocks and those beyond *a.list_count exit at once.

@@ -16,8 +16,9 @@
 //                           then S_par_new * S_perp_new), or S_par * const row, or S_par * 0 (the reference's
 //                           zero-initialised S_perp_new).  Stores are coalesced over the atoms n.
 // plus mfx_rot2d_cols_kernel, the one-atom-per-direction evaluation.
-#include "mfx_host.h"
-#include "../../include/mfx_rot2d.h"
+// The handle's device view, the plan records and the expression that turns a record into an entry live in rot2d_shared.h:
+// fit2d.hip (the fit of 2-D protocols) launches the plan kernel through mfx_rot2d_plan_enqueue and evaluates the same function.
+#include "rot2d_shared.h"
 
 #include <cmath>
 #include <vector>
@@ -25,42 +26,8 @@
 namespace {
 
 constexpr int R2_PLAN_WG = 256;
-constexpr int R2_MAX_ROWS = 4000;   // perpendicular directions of every row in LDS: 2 x 4000 doubles
 constexpr int R2_EVAL_WG = 256;
 constexpr int R2_EVAL_ROWS = 8;
-constexpr int R2_OP_ZERO = -1;      // op >= 1: interpolate on knot interval [op-1, op]; op <= -2: constant row -2 - op
-
-struct Rot2dDev {
-  int M, P, N, C, T, K;
-  const double* sch;      // [M x 6]
-  const int* pair_off;    // [P + 1]
-  const int* pair_rows;   // [M]
-  const int* ref_info;    // [P x 3]
-  const double* ref_dirs; // [P x 5 x 2]
-  const int* ref_tab;     // [P x 5]
-  const int* row_const;   // [M]
-  const int* van_const;   // [P]
-  const double* cst;      // [C x N]
-  const int* tab_off;     // [T + 1]
-  const double* kx;       // [K]
-  const double* ky;       // [K x N]
-  const double* slope;    // [K x N], row k: interval [k-1, k] (unused for a table's first knot)
-  double gamma, diff;
-};
-
-struct Rot2dPlan {
-  int* op;        // [B x M]
-  double* x;      // [B x M] abscissa of interpolated rows
-  double* spar;   // [B x M] S_par_new
-  double* n2;     // [B x M] |g_perp| of the new side (before its normalisation)
-  int* status;    // [B x 4]
-};
-
-struct mfx_rot2d {
-  int device = 0;
-  Rot2dDev d{};
-  void* mem = nullptr;
-};
 
 // numpy.isclose(a, b) with rtol 1e-5, atol 1e-8
 __host__ __device__ inline bool r2_isclose(double a, double b) {
@@ -293,19 +260,19 @@ __global__ __launch_bounds__(R2_EVAL_WG) void mfx_rot2d_eval_kernel(Rot2dDev D, 
           const double2 a = *reinterpret_cast<const double2*>(sl + n);
           const double2 y = *reinterpret_cast<const double2*>(yl + n);
           double2 v;
-          v.x = s * (a.x * dx + y.x);
-          v.y = s * (a.y * dx + y.y);
+          v.x = r2_value(o, s, a.x, dx, y.x);
+          v.y = r2_value(o, s, a.y, dx, y.y);
           *reinterpret_cast<double2*>(dst + n) = v;
         }
       } else {
-        for (int n = threadIdx.x; n < N; n += R2_EVAL_WG) dst[n] = s * (sl[n] * dx + yl[n]);
+        for (int n = threadIdx.x; n < N; n += R2_EVAL_WG) dst[n] = r2_value(o, s, sl[n], dx, yl[n]);
       }
     } else if (o == R2_OP_ZERO) {
-      const double v = s * 0.0;
+      const double v = r2_value(o, s, 0.0, 0.0, 0.0);
       for (int n = threadIdx.x; n < N; n += R2_EVAL_WG) dst[n] = v;
     } else {
       const double* c = D.cst + (size_t)(-2 - o) * N;
-      for (int n = threadIdx.x; n < N; n += R2_EVAL_WG) dst[n] = s * c[n];
+      for (int n = threadIdx.x; n < N; n += R2_EVAL_WG) dst[n] = r2_value(o, s, 0.0, 0.0, c[n]);
     }
   }
 }
@@ -320,11 +287,7 @@ __global__ __launch_bounds__(256) void mfx_rot2d_cols_kernel(Rot2dDev D, Rot2dPl
   if (pl.status[4 * b] != MFX_ROT2D_OK || n < 0 || n >= D.N) { out[i] = __builtin_nan(""); return; }
   const int o = pl.op[i];
   const double x = pl.x[i], s = pl.spar[i];
-  double v;
-  if (o >= 1) v = s * (D.slope[(size_t)o * D.N + n] * (x - D.kx[o - 1]) + D.ky[(size_t)(o - 1) * D.N + n]);
-  else if (o == R2_OP_ZERO) v = s * 0.0;
-  else v = s * D.cst[(size_t)(-2 - o) * D.N + n];
-  out[i] = v;
+  out[i] = r2_elem(D, o, x, s, n);
 }
 
 int r2_require_device(int device) {
@@ -335,31 +298,12 @@ int r2_require_device(int device) {
   return MFX_OK;
 }
 
-// plan scratch of B directions, on the caller's stream
-struct PlanMem {
-  StreamMem mem;
-  Rot2dPlan pl{};
-  explicit PlanMem(hipStream_t s) : mem(s) {}
-  int alloc(int64_t B, int M, int* d_status) {
-    const size_t n = (size_t)B * M;
-    HIPCHK(mem.alloc(n * (sizeof(int) + 3 * sizeof(double)) + 64));
-    char* p = mem.as<char>();
-    pl.x = (double*)p;
-    pl.spar = (double*)(p + n * sizeof(double));
-    pl.n2 = (double*)(p + 2 * n * sizeof(double));
-    pl.op = (int*)(p + 3 * n * sizeof(double));
-    pl.status = d_status;
-    return MFX_OK;
-  }
-};
-
 int r2_launch(const mfx_rot2d* h, const double* d_dirs, const int* d_cols, int64_t B, double* d_out, int* d_status,
               hipStream_t st) {
   if (B > 0x7fffffff) return mfx_fail(MFX_ERR_UNSUPPORTED, "mfx_rot2d: more than 2^31 - 1 directions");
   PlanMem pm(st);
   if (int rc = pm.alloc(B, h->d.M, d_status)) return rc;
-  hipLaunchKernelGGL(mfx_rot2d_plan_kernel, dim3((unsigned)B), dim3(R2_PLAN_WG), 0, st, h->d, d_dirs, pm.pl);
-  HIPCHK(hipGetLastError());
+  if (int rc = mfx_rot2d_plan_enqueue(h, d_dirs, B, pm.pl, st)) return rc;
   if (d_cols) {
     const int64_t blocks = (B * h->d.M + 255) / 256;
     if (blocks > 0x7fffffff) return mfx_fail(MFX_ERR_UNSUPPORTED, "mfx_rot2d_rotate_cols: batch too large");
@@ -393,6 +337,12 @@ int r2_host(const mfx_rot2d* h, const double* dirs, const int32_t* cols, int64_t
 }
 
 }  // namespace
+
+int mfx_rot2d_plan_enqueue(const mfx_rot2d* h, const double* d_dirs, int64_t B, const Rot2dPlan& pl, hipStream_t st) {
+  hipLaunchKernelGGL(mfx_rot2d_plan_kernel, dim3((unsigned)B), dim3(R2_PLAN_WG), 0, st, h->d, d_dirs, pl);
+  HIPCHK(hipGetLastError());
+  return MFX_OK;
+}
 
 extern "C" int mfx_rot2d_abi_version(void) { return 1; }
 

@@ -567,6 +567,71 @@ def rotate2d_dev(tables, d_dirs, d_cols=None):
     return out, status
 
 
+def _fit2d_shapes(tables, y_shape, pk_shape, maxfasc):
+    """Argument checks shared by the 2-D protocol fit's entry points (before any device call); returns V."""
+    if maxfasc < 0 or maxfasc > 3:
+        raise NotImplementedError("the 2-D protocol fit serves 0 to 3 fascicles per voxel (maxfasc = %d)" % maxfasc)
+    if len(y_shape) != 2 or y_shape[1] != tables.M:
+        raise ValueError("data has shape %s, protocol has %d measurements" % (tuple(y_shape), tables.M))
+    V = y_shape[0]
+    if tuple(pk_shape) != (V, 3 * maxfasc):
+        raise ValueError("peaks should have shape (%d, %d)" % (V, 3 * maxfasc))
+    return V
+
+
+def fit2d_dev(tables, d_Y, d_peaks, maxfasc, out=None):
+    """Device-resident fit of voxels of a 2-D (AxCaliber-like) protocol (mfx_fit2d_batch_dev) for a
+    mf_utils.RotateAtom2DTables and ONE voxel class: every voxel has ``maxfasc`` fascicles and no CSF column.
+    torch CUDA float64 tensors d_Y [V, M], d_peaks [V, 3 maxfasc] -> (params [V, num_params(maxfasc, False, False)]
+    f64, status [V, 5] int32: the failing direction's record and fascicle index, zeros for a fitted voxel).
+    Enqueues on torch's current stream and returns without waiting; a voxel with a failing direction has a NaN row."""
+    import torch
+    maxfasc = int(maxfasc)
+    assert d_Y.is_cuda and d_Y.dtype == torch.float64 and d_Y.is_contiguous()
+    assert d_peaks.is_cuda and d_peaks.dtype == torch.float64 and d_peaks.is_contiguous()
+    V = _fit2d_shapes(tables, d_Y.shape, d_peaks.shape, maxfasc)
+    npar = num_params(maxfasc, False, False)
+    if out is None:
+        out = torch.empty((V, npar), dtype=torch.float64, device=d_Y.device)
+    assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (V, npar)
+    status = torch.empty((V, 5), dtype=torch.int32, device=d_Y.device)
+    st = torch.cuda.current_stream(d_Y.device).cuda_stream
+    L.check(L.lib().mfx_fit2d_batch_dev(tables.handle(), d_Y.data_ptr(), d_peaks.data_ptr(), maxfasc, V, out.data_ptr(),
+                                        status.data_ptr(), st))
+    return out, status
+
+
+def fit2d(tables, Y, K, csf, peaks, maxfasc, csf_on, sig_csf=None):
+    """Fit of a mixed set of voxels of a 2-D protocol on NumPy arrays (mfx_fit2d_batch): Y [V, M], per-voxel fascicle
+    counts K [V] in 0..maxfasc, CSF flags csf [V] (or None), peaks [V, 3 maxfasc] -> (params [V, num_params(maxfasc,
+    csf_on, False)], status [V, 5] int32).  A voxel with a failing direction has a NaN row and a non-zero record."""
+    Y = L.f64c(Y)
+    maxfasc = int(maxfasc)
+    pk = L.f64c(peaks).reshape(Y.shape[0], -1) if (maxfasc > 0 and Y.ndim == 2) else np.zeros((Y.shape[0], 0))
+    V = _fit2d_shapes(tables, Y.shape, pk.shape, maxfasc)
+    K = np.ascontiguousarray(np.asarray(K).reshape(-1), dtype=np.int32)
+    if K.shape != (V,):
+        raise ValueError("K should have one entry per voxel")
+    if V and (K.min() < 0 or K.max() > maxfasc):
+        raise ValueError("K should lie in 0..maxfasc = %d" % maxfasc)
+    cs = None
+    if csf is not None:
+        cs = np.ascontiguousarray(np.asarray(csf).reshape(-1).astype(bool), dtype=np.uint8)
+        if cs.shape != (V,):
+            raise ValueError("csf should have one entry per voxel")
+    sc = L.f64c(sig_csf).reshape(-1) if sig_csf is not None else None
+    if cs is not None and np.any(cs) and (not csf_on or sc is None):
+        raise ValueError("voxels flagged CSF need csf_on and sig_csf")
+    if sc is not None and sc.shape[0] != tables.M:
+        raise ValueError("sig_csf has %d entries, protocol has %d" % (sc.shape[0], tables.M))
+    params = np.zeros((V, num_params(maxfasc, bool(csf_on), False)))
+    status = np.zeros((V, 5), dtype=np.int32)
+    L.check(L.lib().mfx_fit2d_batch(tables.handle(), L.dptr(Y), L.iptr(K), L.bptr(cs) if cs is not None else None,
+                                    L.dptr(pk) if maxfasc > 0 else None, maxfasc, int(bool(csf_on)),
+                                    L.dptr(sc) if sc is not None else None, V, L.dptr(params), L.iptr(status)))
+    return params, status
+
+
 def cleanup_select(f1, f2, p1, p2, cos_min, ratio, w_keep, w_small, device=0):
     """Voxel loop of cleanup_2fascicles (mfx_cleanup_2fascicles; ref mf.py:170-335): weights f1, f2 [n] and directions p1, p2
     [n x 3] of the ROI voxels -> (peaks [n x 6], count [n])."""

@@ -40,7 +40,7 @@ __all__ = ["get_gyromagnetic_ratio", "solve_exhaustive_posweights", "init_PGSE_m
            "interp_PGSE_from_multishell", "rotate_atom", "RotateAtomTables", "import_PGSE_scheme",
            "get_PGSE_scheme_from_bval_bvec_dense", "loadmat", "MultiShellInterpolator",
            "rotate_atom_2Dprotocol", "RotateAtom2DTables", "rotate_scheme_mat", "vrrotvec2mat", "rotate_vector",
-           "get_perp_vector", "project_PGSE_scheme_xy_plane", "gen_SoS_MRI", "profile_by_property", "profile_interval"]
+           "get_perp_vector", "project_PGSE_scheme_xy_plane", "fit_2Dprotocol", "Fit2DResult", "gen_SoS_MRI", "profile_by_property", "profile_interval"]
 
 
 def get_gyromagnetic_ratio(element='H'):
@@ -602,6 +602,15 @@ class RotateAtom2DTables:
         self.raise_for_status(status)
         return out
 
+    def fit(self, data, peaks, numfasc, csf_mask=None, sig_csf=None, on_error='raise'):
+        """Fit ``data`` [V, M]: voxel v has ``numfasc[v]`` fascicles along ``peaks[v, 3k:3k+3]`` (unit vectors,
+        peaks [V, 3 maxfasc]) and, where ``csf_mask[v]``, a CSF column ``sig_csf`` [M].  Per voxel the dictionaries
+        ``rotate(peaks[v, 3k:3k+3])`` side by side go through ``solve_exhaustive_posweights`` on the device; returns
+        a :class:`Fit2DResult`.  ``on_error='raise'`` raises the reference's exception for the lowest voxel with a
+        failing direction (what a loop over the voxels would have raised first); ``'nan'`` returns NaN rows there
+        and the status records."""
+        return _fit2d(self, data, peaks, numfasc, csf_mask, sig_csf, on_error)
+
     def rotate_cols(self, newdirs, cols):
         """Atom ``cols[b]`` for a fascicle along ``newdirs[b]`` -> [B, M]."""
         d = L.f64c(np.asarray(newdirs, dtype=np.float64).reshape(-1, 3))
@@ -615,6 +624,77 @@ class RotateAtom2DTables:
                                                   L.iptr(status)))
         self.raise_for_status(status)
         return out
+
+
+class Fit2DResult:
+    """Parameters of voxels fitted with a 2-D protocol: ``params`` [V, num_params(maxfasc, csf_on, False)] and
+    its columns ``M0`` [V], ``frac`` [V, maxfasc], ``atoms`` [V, maxfasc] (int64 atom indices; 0 for an absent
+    fascicle or a voxel that was not fitted), ``frac_csf`` [V] (None without a CSF column), ``MSE``, ``R2`` [V];
+    ``status`` [V, 5] int32: {code, pair, value, value2, fascicle} of the voxel's lowest failing fascicle
+    direction, zeros for a fitted voxel (such a voxel's row is NaN)."""
+
+    def __init__(self, params, status, maxfasc, csf_on):
+        params = np.asarray(params, dtype=np.float64)
+        maxfasc = int(maxfasc)
+        if params.ndim != 2 or params.shape[1] != engine.num_params(maxfasc, bool(csf_on), False):
+            raise ValueError("params should have %d columns" % engine.num_params(maxfasc, bool(csf_on), False))
+        self.params, self.status = params, np.asarray(status, dtype=np.int32).reshape(params.shape[0], 5)
+        self.maxfasc, self.csf_on = maxfasc, bool(csf_on)
+        self.M0 = params[:, 0]
+        self.frac = params[:, 1:1 + maxfasc]
+        ids = params[:, 1 + maxfasc:1 + 2 * maxfasc]
+        self.atoms = np.where(np.isfinite(ids), ids, 0).astype(np.int64)
+        self.frac_csf = params[:, 1 + 2 * maxfasc] if csf_on else None
+        self.MSE, self.R2 = params[:, -2], params[:, -1]
+
+    @property
+    def failed(self):
+        """Indices of the voxels that were not fitted."""
+        return np.flatnonzero(self.status[:, 0])
+
+
+def _fit2d(T, data, peaks, numfasc, csf_mask, sig_csf, on_error):
+    if on_error not in ("raise", "nan"):
+        raise ValueError("on_error should be 'raise' or 'nan'")
+    data = np.asarray(data, dtype=np.float64)
+    if data.ndim != 2 or data.shape[1] != T.M:
+        raise ValueError("data has shape %s, protocol has %d measurements" % (data.shape, T.M))
+    V = data.shape[0]
+    numfasc = np.asarray(numfasc)
+    if numfasc.shape != (V,):
+        raise ValueError("numfasc should have one entry per voxel")
+    peaks = np.asarray(peaks, dtype=np.float64)
+    if peaks.ndim != 2 or peaks.shape[0] != V or peaks.shape[1] % 3 != 0:
+        raise ValueError("peaks should have shape (%d, 3 maxfasc)" % V)
+    maxfasc = peaks.shape[1] // 3
+    if maxfasc > 3:
+        raise NotImplementedError("the 2-D protocol fit serves at most 3 fascicles per voxel (peaks holds %d)" % maxfasc)
+    if V and (numfasc.min() < 0 or numfasc.max() > maxfasc):
+        raise ValueError("numfasc should lie in 0..%d (the directions peaks holds per voxel)" % maxfasc)
+    csf = None
+    if csf_mask is not None:
+        csf = np.asarray(csf_mask).astype(bool)
+        if csf.shape != (V,):
+            raise ValueError("csf_mask should have one entry per voxel")
+    csf_on = csf is not None
+    if csf is not None and np.any(csf):
+        if sig_csf is None:
+            raise ValueError("voxels flagged CSF need sig_csf")
+    if sig_csf is not None and np.asarray(sig_csf).size != T.M:
+        raise ValueError("sig_csf has %d entries, protocol has %d" % (np.asarray(sig_csf).size, T.M))
+    params, status = engine.fit2d(T, data, numfasc, csf, peaks, maxfasc, csf_on, sig_csf)
+    if on_error == "raise":
+        bad = np.flatnonzero(status[:, 0])
+        if bad.size:
+            raise T.error_for(status[bad[0], :4])
+    return Fit2DResult(params, status, maxfasc, csf_on)
+
+
+def fit_2Dprotocol(sig, sch_mat, refdir, DIFF, data, peaks, numfasc, csf_mask=None, sig_csf=None, on_error='raise',
+                   device=0):
+    """Fit voxels of a 2-D protocol: :class:`RotateAtom2DTables` of (sig, sch_mat, refdir, DIFF), then its ``fit``."""
+    return RotateAtom2DTables(sig, sch_mat, refdir, DIFF, device=device).fit(data, peaks, numfasc, csf_mask, sig_csf,
+                                                                            on_error)
 
 
 def rotate_atom_2Dprotocol(sig, sch_mat, refdir, newdir, DIFF):
