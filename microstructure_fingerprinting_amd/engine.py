@@ -4,6 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from . import nifti
 
 
 class DeviceTables:
@@ -96,7 +97,7 @@ class FileOrderVolume(object):
 
     @property
     def scaled(self):
-        return self.slope != 0.0 and not (self.slope == 1.0 and self.inter == 0.0) and np.isfinite(self.slope)
+        return nifti._scaled(self.slope, self.inter)
 
     def get_fdata(self):
         d = self.array.astype(np.float64)

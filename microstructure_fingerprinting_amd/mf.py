@@ -145,7 +145,7 @@ class MFModel():
                 data_arr = raw
             else:
                 data_arr = np.array(raw, dtype=np.float64)
-                if slope != 0.0 and not (slope == 1.0 and inter == 0.0) and np.isfinite(slope):
+                if nifti._scaled(slope, inter):
                     data_arr = data_arr * slope + inter
         else:
             data_arr, aff = data, None

@@ -59,7 +59,9 @@ def _header(hdr, path):
 
 
 def _scaled(slope, inter):
-    return slope != 0.0 and not (slope == 1.0 and inter == 0.0) and np.isfinite(slope)
+    """Whether a header's scl_slope / scl_inter change the data (nibabel's rule; the one copy on the Python side,
+    csrc/mfx_api.hip: volume_gather_launch has the library's)."""
+    return bool(slope != 0.0 and not (slope == 1.0 and inter == 0.0) and np.isfinite(slope))
 
 
 def load_raw(path):
