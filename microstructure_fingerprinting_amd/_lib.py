@@ -35,6 +35,10 @@ ROT2D_EXPORTS = ["mfx_rot2d_abi_version", "mfx_rot2d_create", "mfx_rot2d_destroy
 FIT2D_EXPORTS = ["mfx_fit2d_abi_version", "mfx_fit2d_max_atoms", "mfx_fit2d_batch_dev", "mfx_fit2d_batch",
                  "mfx_fit2d_debug_set_force_explicit"]
 
+# every symbol include/mfx_wfit.h declares (weighted fit: per-voxel measurement weights; versioned on its own)
+WFIT_EXPORTS = ["mfx_wfit_abi_version", "mfx_wfit_max_atoms", "mfx_wfit_batch_dev", "mfx_wfit_batch",
+                "mfx_wfit_debug_set_force_explicit"]
+
 # every symbol include/mfx_predict.h declares (forward model and magnitude noise; versioned on its own)
 PREDICT_EXPORTS = ["mfx_predict_abi_version", "mfx_predict_dev", "mfx_predict", "mfx_sos_noise_dev", "mfx_sos_noise"]
 
@@ -137,6 +141,12 @@ def lib():
     L.mfx_fit2d_batch.argtypes = [vp, dp, ip, bp, dp, C.c_int, C.c_int, dp, C.c_int64, dp, ip]
     L.mfx_fit2d_debug_set_force_explicit.argtypes = [C.c_int]
     L.mfx_fit2d_debug_set_force_explicit.restype = None
+    L.mfx_wfit_abi_version.restype = C.c_int
+    L.mfx_wfit_max_atoms.argtypes = [vp, C.c_int]
+    L.mfx_wfit_batch_dev.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int, C.c_int64, vp, vp, vp]
+    L.mfx_wfit_batch.argtypes = [vp, dp, dp, C.c_int64, ip, bp, dp, C.c_int, C.c_int, dp, C.c_int64, dp, ip]
+    L.mfx_wfit_debug_set_force_explicit.argtypes = [C.c_int]
+    L.mfx_wfit_debug_set_force_explicit.restype = None
     L.mfx_predict_abi_version.restype = C.c_int
     L.mfx_predict_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int64, vp, vp, C.c_int, C.c_int,
                                   C.c_uint64, C.c_uint64, vp, vp, vp, vp]

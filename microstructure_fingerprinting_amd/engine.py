@@ -633,6 +633,89 @@ def fit2d(tables, Y, K, csf, peaks, maxfasc, csf_on, sig_csf=None):
     return params, status
 
 
+def _wfit_shapes(plan, y_shape, w_shape, pk_shape, maxfasc):
+    """Argument checks shared by the weighted fit's entry points (before any device call); returns (V, w_stride)."""
+    if maxfasc < 0 or maxfasc > 3:
+        raise ValueError("the weighted fit is not served for maxfasc = %d: it takes 0 to 3 fascicles per voxel" % maxfasc)
+    if len(y_shape) != 2 or y_shape[1] != plan.M:
+        raise ValueError("data has shape %s, protocol has %d measurements" % (tuple(y_shape), plan.M))
+    V = y_shape[0]
+    if tuple(w_shape) == (plan.M,):
+        w_stride = 0
+    elif tuple(w_shape) == (V, plan.M):
+        w_stride = plan.M
+    else:
+        raise ValueError("weights should have shape (%d, %d) or (%d,), got %s (%d voxels)"
+                         % (V, plan.M, plan.M, tuple(w_shape), V))
+    if tuple(pk_shape) != (V, 3 * maxfasc):
+        raise ValueError("peaks should have shape (%d, %d)" % (V, 3 * maxfasc))
+    return V, w_stride
+
+
+def fit_weighted_dev(plan, d_Y, d_W, d_peaks, maxfasc, out=None):
+    """Device-resident weighted fit (mfx_wfit_batch_dev) of ONE voxel class: every voxel has ``maxfasc`` fascicles and
+    no CSF column.  torch CUDA float64 tensors d_Y [V, M], d_W [V, M] or [M] (weights >= 0 of the measurements),
+    d_peaks [V, 3 maxfasc] -> (params [V, num_params(maxfasc, False, False)] f64, status [V] int32: 0 fitted, 1 a
+    negative or non-finite weight, 2 no positive weight; a voxel with a non-zero status has a NaN row).  Enqueues on
+    torch's current stream and returns without waiting; a direction that is not a unit vector is reported by
+    mfx_plan_status as in fit_batch_dev."""
+    import torch
+    maxfasc = int(maxfasc)
+    for t in (d_Y, d_W, d_peaks):
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+    V, w_stride = _wfit_shapes(plan, d_Y.shape, d_W.shape, d_peaks.shape, maxfasc)
+    npar = num_params(maxfasc, False, False)
+    if out is None:
+        out = torch.empty((V, npar), dtype=torch.float64, device=d_Y.device)
+    assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (V, npar)
+    status = torch.empty((V,), dtype=torch.int32, device=d_Y.device)
+    st = torch.cuda.current_stream(d_Y.device).cuda_stream
+    L.check(L.lib().mfx_wfit_batch_dev(plan.handle(), d_Y.data_ptr(), d_W.data_ptr(), w_stride,
+                                       d_peaks.data_ptr() if maxfasc > 0 else None, maxfasc, V, out.data_ptr(),
+                                       status.data_ptr(), st))
+    return out, status
+
+
+def fit_weighted(plan, Y, W, K, csf, peaks, maxfasc, csf_on, sig_csf=None, ear=None):
+    """Weighted fit of a mixed set of voxels on NumPy arrays (mfx_wfit_batch): Y [V, M], weights W [V, M] or [M] (>= 0;
+    a 0/1 outlier mask, inverse noise variances, ...), fascicle counts K [V] in 0..maxfasc, CSF flags csf [V] (or None),
+    peaks [V, 3 maxfasc] -> (params [V, num_params(maxfasc, csf_on, False)], status [V] int32).  Minimises
+    sum_m W[v, m] (y_m - model_m)^2: the reference chain on rows scaled by sqrt(W).  status 1: a negative or non-finite
+    weight, 2: no positive weight; such a voxel has a NaN row.  EAR compartments are not served with weights."""
+    if ear is not None and np.any(ear):
+        raise ValueError("the weighted fit is not served for voxels with an EAR compartment (%d flagged)"
+                         % int(np.count_nonzero(ear)))
+    Y = L.f64c(Y)
+    W = L.f64c(W)
+    maxfasc = int(maxfasc)
+    pk = L.f64c(peaks).reshape(Y.shape[0], -1) if (maxfasc > 0 and Y.ndim == 2) else np.zeros((Y.shape[0], 0))
+    V, w_stride = _wfit_shapes(plan, Y.shape, W.shape, pk.shape, maxfasc)
+    K = np.ascontiguousarray(np.asarray(K).reshape(-1), dtype=np.int32)
+    if K.shape != (V,):
+        raise ValueError("K should have one entry per voxel")
+    if V and (K.min() < 0 or K.max() > maxfasc):
+        raise ValueError("K should lie in 0..maxfasc = %d" % maxfasc)
+    cs = None
+    if csf is not None:
+        cs = np.ascontiguousarray(np.asarray(csf).reshape(-1).astype(bool), dtype=np.uint8)
+        if cs.shape != (V,):
+            raise ValueError("csf should have one entry per voxel")
+    sc = L.f64c(sig_csf).reshape(-1) if sig_csf is not None else None
+    if cs is not None and np.any(cs) and (not csf_on or sc is None):
+        raise ValueError("voxels flagged CSF need csf_on and sig_csf")
+    if sc is not None and sc.shape[0] != plan.M:
+        raise ValueError("sig_csf has %d entries, protocol has %d" % (sc.shape[0], plan.M))
+    params = np.zeros((V, num_params(maxfasc, bool(csf_on), False)))
+    status = np.zeros(V, dtype=np.int32)
+    L.check(L.lib().mfx_wfit_batch(plan.handle(), L.dptr(Y), L.dptr(W), w_stride, L.iptr(K),
+                                   L.bptr(cs) if cs is not None else None, L.dptr(pk) if maxfasc > 0 else None, maxfasc,
+                                   int(bool(csf_on)), L.dptr(sc) if sc is not None else None, V, L.dptr(params),
+                                   L.iptr(status)))
+    if V:
+        L.check(L.lib().mfx_plan_status(plan.handle(), None))   # a direction that is not a unit vector: ValueError
+    return params, status
+
+
 def cleanup_select(f1, f2, p1, p2, cos_min, ratio, w_keep, w_small, device=0):
     """Voxel loop of cleanup_2fascicles (mfx_cleanup_2fascicles; ref mf.py:170-335): weights f1, f2 [n] and directions p1, p2
     [n x 3] of the ROI voxels -> (peaks [n x 6], count [n])."""

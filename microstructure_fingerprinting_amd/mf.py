@@ -128,8 +128,17 @@ class MFModel():
 
     # ------------------------------------------------------------------------------------------
     def fit(self, data, mask, numfasc, *, peaks=None, colat_longit=None, tensors=None, pgse_scheme=None,
-            bvals=None, bvecs=None, csf_mask=None, ear_mask=None, verbose=1, parallel=False):
-        r"""Fingerprinting on the pre-computed dictionary (ref:516-1051; same arguments)."""
+            bvals=None, bvecs=None, csf_mask=None, ear_mask=None, verbose=1, parallel=False, weights=None):
+        r"""Fingerprinting on the pre-computed dictionary (ref:516-1051; same arguments).
+
+        ``weights`` (keyword only, default None: the plain sum of squares, exactly the code path without it):
+        non-negative weights of the measurements, minimising ``sum_m W[v, m] (y_m - model_m)^2`` in every voxel
+        (``engine.fit_weighted``: the reference chain on rows scaled by ``sqrt(W)``).  An array or NIfTI path of the
+        data's shape (gathered to the ROI like the data) or one ``[M]`` vector shared by all voxels; bool (an outlier
+        mask: False drops the measurement) or any numeric type.  Negative or non-finite weights, a voxel without a
+        positive weight and weights together with ``ear_mask`` raise ValueError before anything is launched.  MSE is
+        ``min_obj / sum W`` and R2 the weighted correlation; ``param_names`` and the maps are unchanged, and the fit
+        keeps ``weights_roi`` in its fitinfo.  With ``parallel=True`` a weighted fit still runs on one device."""
         VRB = verbose
         nii_affine = None
         t0 = time.time()
@@ -272,6 +281,13 @@ class MFModel():
         if data_arr.shape[-1] != num_seq:
             raise ValueError("Data has %d measurements per voxel but the protocol has %d." % (data_arr.shape[-1],
                                                                                                 num_seq))
+        # ---- measurement weights: gathered to the ROI like the data and checked on the host before any launch
+        weights_roi = None
+        if weights is not None:
+            weights_roi = self._roi_weights(weights, roi_index, img_shape, num_seq, ROI_size)
+            if ear_on:
+                raise ValueError("weights are not served together with ear_mask: %d of %d voxel(s) in mask have an EAR "
+                                 "compartment." % (int(np.count_nonzero(ear_mask)), ROI_size))
         # ---- what the reference checks in every voxel with a fascicle, through interp_PGSE_from_multishell
         # (mf_utils.py:1786-1789 and 1804-1807), checked once per fit here: the protocol's timing must be the
         # dictionary's, its gradient directions zero or unit vectors
@@ -294,7 +310,15 @@ class MFModel():
             print("Starting estimation in %d voxel(s) on the GPU%s." % (ROI_size, "s (sharded)" if parallel else ""))
         args = (numfasc_roi, csf_mask, ear_mask, peaks_roi, maxfasc, csf_on, ear_on, sig_csf, sig_ear, num_ear)
         devs = list(range(L.lib().mfx_device_count())) if self.SHARD_DEVICES is None else list(self.SHARD_DEVICES)
-        if parallel and len(devs) > 1 and ROI_size >= 2 * len(devs):
+        if weights_roi is not None:   # one device: the ROI's rows on the host, then the weighted kernels
+            plan = self.ms_interpolator.plan_for(pgse_scheme)
+            Y_roi = (engine.volume_rows(vol, rows, device=self.ms_interpolator.device) if vol is not None
+                     else (Y[rows] if rows is not None else Y))
+            params_in_mask, wstat = engine.fit_weighted(plan, Y_roi, weights_roi, numfasc_roi, csf_mask, peaks_roi, maxfasc,
+                                                        csf_on, sig_csf)
+            if np.any(wstat):
+                raise ValueError("weighted fit: %d of %d voxel(s) have unusable weights." % (int(np.count_nonzero(wstat)), ROI_size))
+        elif parallel and len(devs) > 1 and ROI_size >= 2 * len(devs):
             params_in_mask = self._fit_sharded(pgse_scheme, Y, rows, args, devs)
         else:
             plan = self.ms_interpolator.plan_for(pgse_scheme)
@@ -307,6 +331,8 @@ class MFModel():
                    'roi_index': roi_index, 'model': self, 'pgse_scheme': pgse_scheme,
                    'numfasc_roi': numfasc_roi, 'csf_roi': np.asarray(csf_mask, dtype=bool),
                    'ear_roi': np.asarray(ear_mask, dtype=bool)}
+        if weights_roi is not None:
+            fitinfo['weights_roi'] = weights_roi
         for n in fitinfo['fasc_propnames']:
             fitinfo['_dict_' + n] = self.dic[n]
         if ear_on:
@@ -401,6 +427,33 @@ class MFModel():
                             N=N, seed=mfu._sos_seed(seed), offset=offset)
 
     @staticmethod
+    def _roi_weights(weights, roi_index, img_shape, num_seq, ROI_size):
+        """weights argument -> float64 [ROI_size x M] or [M], checked (every failure a ValueError naming the voxel count)."""
+        w = weights
+        if isinstance(w, str):
+            w, _ = _load_volume(w)
+        w = np.asarray(w)
+        if w.dtype == object or not (np.issubdtype(w.dtype, np.number) or w.dtype == np.bool_):
+            raise ValueError("weights should be boolean or numeric (%d voxel(s) in mask)." % ROI_size)
+        if w.shape == (num_seq,):
+            w_roi = np.ascontiguousarray(w, dtype=np.float64)
+        elif w.shape == tuple(img_shape) + (num_seq,):
+            w_roi = np.ascontiguousarray(w.reshape(-1, num_seq)[roi_index], dtype=np.float64)
+        else:
+            raise ValueError("weights not compatible with the data of %d voxel(s) in mask: expected shape (%s) or (%d), "
+                             "got (%s)." % (ROI_size, " ".join("%d" % x for x in tuple(img_shape) + (num_seq,)), num_seq,
+                                            " ".join("%d" % x for x in w.shape)))
+        bad = ~np.isfinite(w_roi) | (w_roi < 0)
+        if bad.any():
+            n_bad = ROI_size if w_roi.ndim == 1 else int(np.count_nonzero(bad.any(axis=1)))
+            raise ValueError("Detected %d of %d voxel(s) in mask with negative or non-finite weights." % (n_bad, ROI_size))
+        none = ~(w_roi > 0).any(axis=-1)
+        if np.any(none):
+            n_none = ROI_size if w_roi.ndim == 1 else int(np.count_nonzero(none))
+            raise ValueError("Detected %d of %d voxel(s) in mask without a positive weight." % (n_none, ROI_size))
+        return w_roi
+
+    @staticmethod
     def _roi_flags(m, roi, img_shape, ROI_size, name):
         """csf_mask / ear_mask argument -> bool[ROI_size] (ref:852-894)."""
         aff = None
@@ -469,6 +522,7 @@ class MFModelFit():
         # per-voxel classes and per-atom properties (profile() and interval())
         self._numfasc_roi, self._csf_roi, self._ear_roi = (fitinfo.get(k) for k in ('numfasc_roi', 'csf_roi', 'ear_roi'))
         self._props = {n: np.asarray(fitinfo['_dict_' + n], dtype=np.float64).reshape(-1) for n in fitinfo['fasc_propnames']}
+        self.weights_roi = fitinfo.get('weights_roi')   # float64 [ROI x M] or [M] of a weighted fit, else None (not a map)
         whole = ROI_size == int(np.prod(mask.shape))
 
         def to_map(vals, extra=()):
