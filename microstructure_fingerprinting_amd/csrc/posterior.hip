@@ -1,0 +1,628 @@
+// posterior.hip -- soft fits (include/mfx_post.h): per atom of each fascicle the sum over every partner atom of
+// exp(-(F - shift) / T), normalised per voxel, and the log of the whole sum.
+//
+// mfx_post_k2_kernel   one workgroup per voxel; phases 0-2 are those of mfx_profile_k2_kernel (profile.hip): knot
+//                      descriptors and y in LDS, column statistics of both rotated dictionaries (one thread per atom),
+//                      the cross-Gram D_0^T D_1 on v_mfma_f64_16x16x4_f64 with the wave's 16 atoms of D_0 in registers
+//                      and D_1 generated chunk by chunk into LDS.  The scan keeps a sum of exponentials per row and per
+//                      column where the profile keeps a minimum:
+//                        per pair  the score ||y||^2 - F (p / q, or the CSF value), t = exp((score - (||y||^2 - shift)) / T):
+//                                  one division and one FP64 exp per pair.  FP64 MFMA and VALU instructions do not
+//                                  overlap on a SIMD, so the scan adds to the matrix work: about 2 900 cycles of
+//                                  VALU beside 6 400 of MFMA per wave and pair of tiles.
+//                        rows      4 running sums per lane and sweep (C/D layout: col = lane & 15, row = (lane >> 4) +
+//                                  4 reg), folded over the 16 lanes of a row once per sweep, one lane stores;
+//                        columns   added in the lane over its 4 rows, over the 4 lane groups by two shuffles, then one
+//                                  entry per wave and column in a two-half LDS slab; the chunk's first CW threads add
+//                                  the waves' entries in wave order into an [NP] LDS array behind the barrier that ends
+//                                  the chunk anyway.
+//                      No indices, no tie rules, no fraction compare, no global atomics.  Z is the index-order sum of the
+//                      row sums; the division by Z and log_sum happen in the kernel's last phase.
+// mfx_post_k1_kernel   one workgroup per voxel, one thread per atom (mfx_profile_k1_kernel's scoring).
+//
+// The status codes come from the kernels themselves: T and shift are checked in phase 0 (code 1, workgroup-uniform
+// exit), an exponent above 700 raises an LDS flag and Z is tested in the last phase (code 2).
+//
+// The scoring helpers restate those of profile.hip word for word (F is the profile's value by definition); profile.hip
+// itself is left alone so that its kernels' register allocation stays what it is.
+#include "mfx_host.h"
+#include "../../include/mfx_post.h"
+#include "../../include/mfx_profile.h"
+
+#include <algorithm>
+
+// profile.hip's MFX_PROFILE_CUT restated as a compile-time constant (the 8-wave form has no register to spare for a kernel
+// argument); the entry points refuse to launch unless it equals mfx_profile_cut()
+#define MFX_POST_CUT 1e-8
+
+namespace {
+
+constexpr size_t POST_LDS_MAX = 160 * 1024;
+constexpr int POST_K1_WG = 256;
+constexpr double POST_EXP_MAX = 700.0;   // exponents above this make the shift unusable (status 2)
+
+struct PostArgs {
+  TablesDev T;
+  PlanDev P;
+  const double* Y;      // [V x M]
+  const double* peaks;  // [V x 3 K]
+  const double* xc;     // [M] the CSF column (CSF variants)
+  const double* temp;   // [V]
+  const double* shift;  // [V]
+  double* w;            // [V x K x N]
+  double* log_sum;      // [V]
+  int* status;          // [V]
+};
+
+// score s = ||y||^2 - F of one atom pair as the fraction p / q (profile.hip: prof_pair_frac)
+__device__ __forceinline__ void post_pair_frac(double cut, double A11, double A22, double A12, double Y1, double Y2, double p1,
+                                               double p2, double& p, double& q) {
+  const double d1 = fma(-A12, Y2, A22 * Y1);
+  const double d2 = fma(-A12, Y1, A11 * Y2);
+  const double pd = A11 * A22;
+  const double Det = fma(-A12, A12, pd);
+  const double num = fma(Y2, d2, Y1 * d1);
+  const bool both = (d1 > 0.0) & (d2 > 0.0) & (Det > cut * pd);
+  const bool first = p1 * A22 >= p2 * A11;
+  p = both ? num : (first ? p1 : p2);
+  q = both ? Det : (first ? A11 : A22);
+}
+
+// the same with the weights (CSF form; profile.hip: prof_pair_w)
+__device__ __forceinline__ double post_pair_w(double cut, double A11, double A22, double A12, double Y1, double Y2, double i11,
+                                              double i22, double& w1, double& w2) {
+  const double d1 = fma(-A12, Y2, A22 * Y1);
+  const double d2 = fma(-A12, Y1, A11 * Y2);
+  const double pd = A11 * A22;
+  const double Det = fma(-A12, A12, pd);
+  const bool both = (d1 > 0.0) & (d2 > 0.0) & (Det > cut * pd);
+  const double u1 = fmax(Y1, 0.0) * i11, u2 = fmax(Y2, 0.0) * i22;
+  const double s1 = Y1 * u1, s2 = Y2 * u2;
+  const bool first = s1 >= s2;
+  const double iD = both ? 1.0 / Det : 0.0;
+  w1 = both ? d1 * iD : (first ? u1 : 0.0);
+  w2 = both ? d2 * iD : (first ? 0.0 : u2);
+  return both ? fma(Y2, d2, Y1 * d1) * iD : (first ? s1 : s2);
+}
+
+// statistics of an atom with the CSF column x projected out (profile.hip: prof_primed)
+__device__ __forceinline__ void post_primed(double cut, double A, double Yv, double X, double ixx, double xy, double& Ap,
+                                            double& Yp, double& iAp) {
+  const double xs = X * ixx;
+  Ap = fma(-xs, X, A);
+  Yp = fma(-xs, xy, Yv);
+  const bool ok = Ap > cut * A;
+  Ap = ok ? Ap : 0.0;
+  Yp = ok ? Yp : 0.0;
+  iAp = ok ? 1.0 / Ap : 0.0;
+}
+
+__device__ __forceinline__ bool post_finite(double x) { return fabs(x) <= 1.79769313486231570815e308; }   // false for NaN
+
+// status 1: the voxel's rows and log_sum become NaN (every thread of the workgroup takes part)
+__device__ __forceinline__ void post_nan_rows(const PostArgs& a, size_t vox, int K, int N, int code, int tid, int wg) {
+  const double nan = __builtin_nan("");
+  for (int n = tid; n < K * N; n += wg) a.w[vox * K * N + n] = nan;
+  if (tid == 0) { a.log_sum[vox] = nan; a.status[vox] = code; }
+}
+
+// NW waves per workgroup, TILES 16-atom column tiles per D_1 chunk, NBUF LDS buffers for the chunks: the profile's
+// configurations (profile.hip).
+template <int KSTEPS, bool BRACKET, bool CSF, int NW, int TILES, int NBUF>
+__global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void mfx_post_k2_kernel(PostArgs a) {
+  constexpr int WG = NW * 64;
+  constexpr int MP = KSTEPS * 4;              // padded measurement count
+  constexpr int MPS = MP;                     // rows of one LDS D_1 tile
+  constexpr int CW = 16 * TILES;              // atoms per chunk
+  constexpr int RS = WG / CW;                 // row stride of one generating thread
+  extern __shared__ double smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lg = lane >> 4, lc = lane & 15;
+  const int M = a.P.M, N = a.T.N, ldn = a.T.ldn;
+  const int NP = ldn;  // atoms padded to a multiple of 16 (padded atoms are zero columns)
+  const int ntiles = NP >> 4;
+  const double2* __restrict__ tab = a.T.tab;
+  const size_t vox = blockIdx.x;
+  constexpr double cut = MFX_POST_CUT;
+
+  // ---- LDS carve-up (post_lds_bytes below mirrors it)
+  double* sB = smem;                              // [NBUF][TILES][MPS][16]
+  double* s_y = sB + NBUF * TILES * MPS * 16;     // [MP]
+  double* s_x = s_y + MP;                         // [MP] (CSF)
+  double* s_t0 = s_x + (CSF ? MP : 0);            // [2][MP]
+  double* s_t1 = s_t0 + 2 * MP;                   // [2][MP] (bracket only)
+  double* s_tG = s_t1 + (BRACKET ? 2 * MP : 0);   // [MP]
+  double* s_dG = s_tG + (BRACKET ? MP : 0);       // [MP]
+  double* s_A11 = s_dG + (BRACKET ? MP : 0);      // [NP] each: |d|^2 and d.y of both dictionaries
+  double* s_Y1 = s_A11 + NP;
+  double* s_A22 = s_Y1 + NP;
+  double* s_Y2 = s_A22 + NP;
+  double* s_X1 = s_Y2 + NP;                       // [NP] each: d.x (CSF)
+  double* s_X2 = s_X1 + (CSF ? NP : 0);
+  double* s_rs = s_X2 + (CSF ? NP : 0);           // [NP] row sums R0 (written once per atom)
+  double* s_cs = s_rs + NP;                       // [NP] running column sums R1
+  double* s_sl = s_cs + NP;                       // [2][NW][CW] the waves' column sums of one chunk
+  double* s_end = s_sl + 2 * NW * CW;
+  int* s_r0 = (int*)s_end;                        // [2][MP]
+  int* s_r1 = s_r0 + 2 * MP;                      // [2][MP] (bracket only)
+  int* s_flag = s_r1 + (BRACKET ? 2 * MP : 0);    // [2] an exponent above POST_EXP_MAX was met
+
+  // ---- phase 0: temperature and shift (status 1 leaves here, workgroup-uniform), y, x, descriptors
+  const double* __restrict__ yv = a.Y + vox * M;
+  const double* __restrict__ pk = a.peaks + vox * 6;
+  const double Tv = a.temp[vox], shift = a.shift[vox];
+  if (tid < 2) mfx_check_dir(a.P, pk + 3 * tid, (int)vox);
+  if (!(Tv > 0.0) || !post_finite(Tv) || !post_finite(shift)) {
+    post_nan_rows(a, vox, 2, N, 1, tid, WG);
+    return;
+  }
+  const double iT = 1.0 / Tv;
+  for (int m = tid; m < MP; m += WG) {
+    s_y[m] = (m < M) ? yv[m] : 0.0;
+    if constexpr (CSF) s_x[m] = (m < M) ? a.xc[m] : 0.0;
+  }
+  for (int idx = tid; idx < 2 * MP; idx += WG) {
+    const int k = idx / MP, m = idx - k * MP;
+    RowDesc rd;
+    rd.r0 = a.T.P; rd.t0 = 0.0; rd.r1 = -1; rd.t1 = 0.0;  // padded rows -> the all-zero table row
+    if (m < M) rd = mfx_row_desc(a.T, a.P, m, pk[3 * k], pk[3 * k + 1], pk[3 * k + 2]);
+    s_r0[idx] = rd.r0;
+    s_t0[idx] = rd.t0;
+    if (BRACKET) {
+      s_r1[idx] = rd.r1;
+      s_t1[idx] = rd.t1;
+      if (k == 0) { s_tG[m] = (m < M) ? a.P.tG[m] : 0.0; s_dG[m] = (m < M) ? a.P.dG[m] : 1.0; }
+    }
+  }
+  for (int n = tid; n < NP; n += WG) { s_rs[n] = 0.0; s_cs[n] = 0.0; }
+  if (tid == 0) s_flag[0] = 0;
+  __syncthreads();
+
+  auto elem = [&](int k, int m, int n) -> double {
+    if (BRACKET) {
+      RowDesc rd;
+      rd.r0 = s_r0[k * MP + m]; rd.t0 = s_t0[k * MP + m];
+      rd.r1 = s_r1[k * MP + m]; rd.t1 = s_t1[k * MP + m];
+      return mfx_eval_br(tab, ldn, rd, s_tG[m], s_dG[m], n);
+    } else {
+      return mfx_eval(tab, ldn, s_r0[k * MP + m], s_t0[k * MP + m], n);
+    }
+  };
+
+  // ---- phase 1: column statistics, sequential over the measurements; ||y||^2, x.x, x.y likewise (every thread)
+  double y_sq = 0.0, xx = 0.0, xy = 0.0;
+  for (int m = 0; m < M; ++m) {
+    y_sq += s_y[m] * s_y[m];
+    if constexpr (CSF) { xx += s_x[m] * s_x[m]; xy += s_x[m] * s_y[m]; }
+  }
+  for (int col = tid; col < 2 * NP; col += WG) {
+    const int k = col >= NP, n = col - k * NP;
+    double a2 = 0.0, ay = 0.0, ax = 0.0;
+    if (n < N) {
+#pragma unroll 4
+      for (int m = 0; m < M; ++m) {
+        const double d = elem(k, m, n);
+        a2 += d * d;
+        ay += s_y[m] * d;
+        if constexpr (CSF) ax += s_x[m] * d;
+      }
+    }
+    (k ? s_A22 : s_A11)[n] = a2;
+    (k ? s_Y2 : s_Y1)[n] = ay;
+    if constexpr (CSF) (k ? s_X2 : s_X1)[n] = ax;
+  }
+  const double ixx = (CSF && xx > 0.0) ? 1.0 / xx : 0.0;
+  const double sx = xy * xy * ixx;   // what x alone explains: ||y||^2 - ||y'||^2
+  const double c0 = y_sq - shift;    // exponent of a pair: (score - c0) / T = -(F - shift) / T
+
+  auto gen_chunk = [&](int ch, int buf) {
+    const int c = tid % CW, m0 = tid / CW;
+    const int n = ch * CW + c;
+    double* dst = sB + (size_t)buf * (TILES * MPS * 16) + (c >> 4) * (MPS * 16) + (c & 15);
+    if (n < NP) {
+      if constexpr (BRACKET) {   // not unrolled: a bracketed entry holds two table loads and six descriptors
+#pragma unroll 1
+        for (int m = m0; m < MP; m += RS) dst[m * 16] = elem(1, m, n);
+      } else {
+#pragma unroll 4
+        for (int m = m0; m < MP; m += RS) dst[m * 16] = elem(1, m, n);
+      }
+    } else {
+      for (int m = m0; m < MP; m += RS) dst[m * 16] = 0.0;
+    }
+  };
+
+  const int nchunks = (ntiles + TILES - 1) / TILES;
+  const int nrounds = (ntiles + NW - 1) / NW;
+  // largest exponent this lane met over the pairs of two real atoms
+  double emax = -POST_EXP_MAX;
+
+  for (int round = 0; round < nrounds; ++round) {
+    const int rt = round * NW + wave;
+    const bool rt_valid = rt < ntiles;  // wave-uniform
+    const int rtc = rt_valid ? rt : 0;
+    // A operand: this wave's 16 atoms of D_0, all KSTEPS k-steps, in registers
+    double afr[KSTEPS];
+#pragma unroll
+    for (int kk = 0; kk < KSTEPS; ++kk) {
+      afr[kk] = rt_valid ? elem(0, 4 * kk + lg, rtc * 16 + lc) : 0.0;
+      if (BRACKET && (kk & 3) == 3) __builtin_amdgcn_sched_barrier(0);   // keeps the loads of a long protocol from piling up in registers
+    }
+    __syncthreads();   // statistics complete (round 0); the previous sweep's last slab half folded before it is written again
+    gen_chunk(0, 0);
+    __syncthreads();
+
+    // per-row operands of the scan (row r of the lane: atom i = 16 rt + lg + 4 r)
+    double A11r[4], Y1r[4], p1r[4];   // CSF: the primed statistics
+    double X1s[4], X1r[4], A11u[4], Y1u[4], i11p[4], i11u[4];   // CSF only: X1 / xx, X1, the plain statistics, inverses
+    const int nrow = rt_valid ? N - (rtc * 16 + lg) : 0;   // row r of the lane is an atom iff 4 r < nrow
+    double rs[4];   // running row sums of this sweep
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = rtc * 16 + lg + 4 * r;
+      const double A = s_A11[i], Yv = s_Y1[i];
+      if constexpr (CSF) {
+        const double X = s_X1[i];
+        A11u[r] = A; Y1u[r] = Yv; X1r[r] = X; X1s[r] = X * ixx;
+        i11u[r] = A > 0.0 ? 1.0 / A : 0.0;
+        post_primed(cut, A, Yv, X, ixx, xy, A11r[r], Y1r[r], i11p[r]);
+        p1r[r] = 0.0;
+      } else {
+        A11r[r] = A; Y1r[r] = Yv;
+        const double yp = fmax(Yv, 0.0);
+        p1r[r] = yp * yp;
+      }
+      rs[r] = 0.0;
+    }
+
+    for (int ch = 0; ch < nchunks; ++ch) {
+      const int buf = (NBUF == 2) ? (ch & 1) : 0;
+      if constexpr (NBUF == 2) {
+        if (ch + 1 < nchunks) gen_chunk(ch + 1, buf ^ 1);
+      } else if (ch > 0) {
+        gen_chunk(ch, 0);   // single buffer: generate, barrier, consume, barrier
+        __syncthreads();
+      }
+      double cs[TILES];   // this lane's column sums of the chunk (a wave without a row tile contributes zeros)
+#pragma unroll
+      for (int t = 0; t < TILES; ++t) cs[t] = 0.0;
+      if (rt_valid) {
+        const double* b0p = sB + (size_t)buf * (TILES * MPS * 16) + lg * 16 + lc;
+        const double* b1p = b0p + (TILES == 2 ? MPS * 16 : 0);
+        d4 acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};
+#pragma unroll
+        for (int kk = 0; kk < KSTEPS; ++kk) {
+          const double b0 = b0p[kk * 64];
+          acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(afr[kk], b0, acc0, 0, 0, 0);
+          if constexpr (TILES == 2) {
+            const double b1 = b1p[kk * 64];
+            acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(afr[kk], b1, acc1, 0, 0, 0);
+          }
+        }
+#pragma unroll
+        for (int t = 0; t < TILES; ++t) {
+          const d4 acc = t ? acc1 : acc0;
+          const int j = ch * CW + t * 16 + lc;
+          const bool colok = j < N;
+          const int jq = colok ? j : 0;
+          // a padded column is a null atom
+          double A22 = colok ? s_A22[jq] : 0.0, Y2 = colok ? s_Y2[jq] : 0.0;
+          double p2 = 0.0, X2 = 0.0, A22u = 0.0, Y2u = 0.0, i22p = 0.0, i22u = 0.0;
+          if constexpr (CSF) {
+            X2 = colok ? s_X2[jq] : 0.0; A22u = A22; Y2u = Y2;
+            i22u = A22 > 0.0 ? 1.0 / A22 : 0.0;
+            post_primed(cut, A22u, Y2u, X2, ixx, xy, A22, Y2, i22p);
+          } else {
+            const double yp = fmax(Y2, 0.0);
+            p2 = yp * yp;
+          }
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            double s;
+            if constexpr (CSF) {
+              // x projected out: the two-variable form on the primed quantities, then the sign of w_x decides
+              double w1, w2, v1, v2;
+              const double A12p = fma(-X1s[r], X2, acc[r]);
+              const double sp = post_pair_w(cut, A11r[r], A22, A12p, Y1r[r], Y2, i11p[r], i22p, w1, w2);
+              const double wxn = fma(-w2, X2, fma(-w1, X1r[r], xy));   // w_x times x.x
+              const double su = post_pair_w(cut, A11u[r], A22u, acc[r], Y1u[r], Y2u, i11u[r], i22u, v1, v2);
+              s = (wxn >= 0.0) ? sx + sp : su;
+            } else {
+              double p, q;
+              post_pair_frac(cut, A11r[r], A22, acc[r], Y1r[r], Y2, p1r[r], p2, p, q);
+              s = q > 0.0 ? p / q : 0.0;
+            }
+            const bool ok = (4 * r < nrow) & colok;
+            const double e = fma(s - c0, iT, 0.0);
+            emax = fmax(emax, ok ? e : emax);
+            const double tv = ok ? exp(e) : 0.0;   // padded atoms contribute nothing
+            rs[r] += tv;    // increasing j per lane
+            cs[t] += tv;    // increasing i with r
+          }
+        }
+      }
+      // column sums: over the four lane groups (rows lg + 4 r), then one slab entry per wave and column
+#pragma unroll
+      for (int t = 0; t < TILES; ++t) {
+        cs[t] += __shfl_xor(cs[t], 16);
+        cs[t] += __shfl_xor(cs[t], 32);
+        if (lg == 0) s_sl[((ch & 1) * NW + wave) * CW + t * 16 + lc] = cs[t];
+      }
+      __syncthreads();
+      // over the waves in wave order into the running column sum.  The slab has two halves: the waves that run ahead
+      // write the other one, and this half is rewritten only behind the next barrier.
+      if (tid < CW) {
+        const int j = ch * CW + tid;
+        if (j < NP) {
+          double c = s_cs[j];
+          for (int w = 0; w < NW; ++w) c += s_sl[((ch & 1) * NW + w) * CW + tid];
+          s_cs[j] = c;
+        }
+      }
+    }
+    // row sums of this sweep: over the 16 lanes of the row (a butterfly: every lane ends with the same value)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      double v = rs[r];
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o);
+      if (lc == 0 && 4 * r < nrow) s_rs[rtc * 16 + lg + 4 * r] = v;
+    }
+  }
+  if (emax > POST_EXP_MAX) s_flag[0] = 1;
+  __syncthreads();
+
+  // ---- last phase: Z in index order (every thread, the same value), status, normalisation, log_sum
+  double Z = 0.0;
+  for (int i = 0; i < N; ++i) Z += s_rs[i];
+  if (s_flag[0] != 0 || !(Z > 0.0) || !post_finite(Z)) {
+    post_nan_rows(a, vox, 2, N, 2, tid, WG);
+    return;
+  }
+  for (int n = tid; n < N; n += WG) {
+    a.w[(vox * 2 + 0) * N + n] = s_rs[n] / Z;
+    a.w[(vox * 2 + 1) * N + n] = s_cs[n] / Z;
+  }
+  if (tid == 0) {
+    a.log_sum[vox] = log(Z) - shift / Tv;
+    a.status[vox] = 0;
+  }
+}
+
+// K = 1: one workgroup per voxel, one thread per atom; the unnormalised t(i) wait in the output row for Z
+template <bool CSF>
+__global__ __launch_bounds__(POST_K1_WG) void mfx_post_k1_kernel(PostArgs a) {
+  extern __shared__ double smem[];
+  const int tid = threadIdx.x;
+  const int M = a.P.M, N = a.T.N, ldn = a.T.ldn;
+  const size_t vox = blockIdx.x;
+  constexpr double cut = MFX_POST_CUT;
+  double* s_y = smem;          // [M]
+  double* s_x = s_y + M;       // [M]
+  double* s_t0 = s_x + M;      // [M]
+  double* s_t1 = s_t0 + M;     // [M]
+  int* s_r0 = (int*)(s_t1 + M);  // [M]
+  int* s_r1 = s_r0 + M;        // [M]
+  int* s_flag = s_r1 + M;      // [2]
+  const double* __restrict__ yv = a.Y + vox * M;
+  const double* __restrict__ pk = a.peaks + vox * 3;
+  const double Tv = a.temp[vox], shift = a.shift[vox];
+  if (tid == 0) mfx_check_dir(a.P, pk, (int)vox);
+  if (!(Tv > 0.0) || !post_finite(Tv) || !post_finite(shift)) {
+    post_nan_rows(a, vox, 1, N, 1, tid, POST_K1_WG);
+    return;
+  }
+  const double iT = 1.0 / Tv;
+  for (int m = tid; m < M; m += POST_K1_WG) {
+    s_y[m] = yv[m];
+    s_x[m] = CSF ? a.xc[m] : 0.0;
+    const RowDesc rd = mfx_row_desc(a.T, a.P, m, pk[0], pk[1], pk[2]);
+    s_r0[m] = rd.r0; s_t0[m] = rd.t0; s_r1[m] = rd.r1; s_t1[m] = rd.t1;
+  }
+  if (tid == 0) s_flag[0] = 0;
+  __syncthreads();
+  double y_sq = 0.0, xx = 0.0, xy = 0.0;
+  for (int m = 0; m < M; ++m) {
+    y_sq += s_y[m] * s_y[m];
+    if constexpr (CSF) { xx += s_x[m] * s_x[m]; xy += s_x[m] * s_y[m]; }
+  }
+  const double ixx = (CSF && xx > 0.0) ? 1.0 / xx : 0.0;
+  const double c0 = y_sq - shift;
+  double* wrow = a.w + vox * N;
+  bool over = false;
+  for (int n = tid; n < N; n += POST_K1_WG) {
+    double a2 = 0.0, ay = 0.0, ax = 0.0;
+    for (int m = 0; m < M; ++m) {
+      RowDesc rd;
+      rd.r0 = s_r0[m]; rd.t0 = s_t0[m]; rd.r1 = s_r1[m]; rd.t1 = s_t1[m];
+      const double d = mfx_eval_br(a.T.tab, ldn, rd, a.P.tG[m], a.P.dG[m], n);
+      a2 += d * d;
+      ay += s_y[m] * d;
+      if constexpr (CSF) ax += s_x[m] * d;
+    }
+    const double yp = fmax(ay, 0.0);
+    double s = a2 > 0.0 ? yp * yp / a2 : 0.0;
+    if constexpr (CSF) {
+      double Ap, Yp, iAp;
+      post_primed(cut, a2, ay, ax, ixx, xy, Ap, Yp, iAp);
+      const double w1 = fmax(Yp, 0.0) * iAp;
+      if (fma(-w1, ax, xy) >= 0.0) s = xy * xy * ixx + Yp * w1;
+    }
+    const double e = fma(s - c0, iT, 0.0);
+    over |= e > POST_EXP_MAX;
+    wrow[n] = exp(e);
+  }
+  if (over) s_flag[0] = 1;
+  __syncthreads();   // the row is written and visible to the workgroup
+  double Z = 0.0;
+  for (int i = 0; i < N; ++i) Z += wrow[i];   // index order, every thread the same value
+  __syncthreads();   // every thread has read the unnormalised row before it is overwritten
+  if (s_flag[0] != 0 || !(Z > 0.0) || !post_finite(Z)) {
+    post_nan_rows(a, vox, 1, N, 2, tid, POST_K1_WG);
+    return;
+  }
+  for (int n = tid; n < N; n += POST_K1_WG) wrow[n] = wrow[n] / Z;
+  if (tid == 0) {
+    a.log_sum[vox] = log(Z) - shift / Tv;
+    a.status[vox] = 0;
+  }
+}
+
+size_t post_lds_bytes(int ksteps, bool bracket, bool csf, int NP, int nw, int tiles, int nbuf) {
+  const size_t MP = (size_t)ksteps * 4, MPS = MP, cw = 16 * (size_t)tiles;
+  const size_t dbl = (size_t)nbuf * tiles * MPS * 16 + MP + (csf ? MP : 0) + 2 * MP + (bracket ? 4 * MP : 0) +
+                     (size_t)NP * (4 + (csf ? 2 : 0) + 2) + 2 * nw * cw;
+  const size_t ints = 2 * MP + (bracket ? 2 * MP : 0) + 2;
+  return dbl * 8 + ints * 4;
+}
+
+template <int KS, bool BR, bool CSF, int NW, int TILES, int NBUF>
+int post_launch_t(const PostArgs& a, int nvox, hipStream_t st) {
+  const size_t lds = post_lds_bytes(KS, BR, CSF, a.T.ldn, NW, TILES, NBUF);
+  auto kern = mfx_post_k2_kernel<KS, BR, CSF, NW, TILES, NBUF>;
+  HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kern, dim3(nvox), dim3(NW * 64), lds, st, a);
+  HIPCHK(hipGetLastError());
+  return MFX_OK;
+}
+
+// the configurations of M <= 200 in the order they are tried: {KSTEPS, NW, TILES, NBUF}; longer protocols: {140, 4, 1, 1}
+struct PostCfg { int ks, nw, tiles, nbuf; };
+constexpr PostCfg POST_CFG_200[3] = {{50, 8, 2, 2}, {50, 4, 1, 2}, {50, 4, 1, 1}};
+
+int post_pick(int M, bool br, bool csf, int NP) {   // index into POST_CFG_200, 3: the long-protocol form, -1: none fits
+  if (M <= 200) {
+    for (int c = (csf || br) ? 1 : 0; c < 3; ++c)   // the CSF scan and bracketed rows take one wave per SIMD, as in the profile
+      if (post_lds_bytes(50, br, csf, NP, POST_CFG_200[c].nw, POST_CFG_200[c].tiles, POST_CFG_200[c].nbuf) <= POST_LDS_MAX) return c;
+    return -1;
+  }
+  return post_lds_bytes(140, br, csf, NP, 4, 1, 1) <= POST_LDS_MAX ? 3 : -1;
+}
+
+int post_max_atoms(int M, bool br, bool csf) {
+  int n = 0;
+  while (n < (1 << 20) && post_pick(M, br, csf, n + 16) >= 0) n += 16;
+  return n;
+}
+
+template <bool BR, bool CSF>
+int post_launch_cfg(int cfg, const PostArgs& a, int nvox, hipStream_t st) {
+  switch (cfg) {
+    case 0:
+      if constexpr (!CSF && !BR) return post_launch_t<50, BR, CSF, 8, 2, 2>(a, nvox, st);
+      return mfx_fail(MFX_ERR_ARG, "posterior: no such configuration");
+    case 1: return post_launch_t<50, BR, CSF, 4, 1, 2>(a, nvox, st);
+    case 2: return post_launch_t<50, BR, CSF, 4, 1, 1>(a, nvox, st);
+    default: return post_launch_t<140, BR, CSF, 4, 1, 1>(a, nvox, st);
+  }
+}
+
+int post_launch_k2(const PostArgs& a, int nvox, bool csf, hipStream_t st, const char* fn) {
+  const int M = a.P.M;
+  const bool br = a.P.any_bracket != 0;
+  const int cfg = post_pick(M, br, csf, a.T.ldn);
+  if (cfg < 0)
+    return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: N = %d atoms exceed the %d that fit in LDS for this protocol (M = %d)", fn, a.T.N,
+                    post_max_atoms(M, br, csf), M);
+  if (br) return csf ? post_launch_cfg<true, true>(cfg, a, nvox, st) : post_launch_cfg<true, false>(cfg, a, nvox, st);
+  return csf ? post_launch_cfg<false, true>(cfg, a, nvox, st) : post_launch_cfg<false, false>(cfg, a, nvox, st);
+}
+
+const char* POST_NO_DEVICE = "no HIP device available (this library has no CPU path)";
+
+int post_require_device(int device) {
+  const int n = mfx_device_count();
+  if (n <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", POST_NO_DEVICE);
+  if (device < 0 || device >= n) return mfx_fail(MFX_ERR_ARG, "device %d out of range (have %d)", device, n);
+  HIPCHK(hipSetDevice(device));
+  return MFX_OK;
+}
+
+int post_check_args(const char* fn, const mfx_plan* p, const void* Y, const void* peaks, int K, int csf_on, const void* sig_csf,
+                    const void* T, const void* shift, int64_t V, const void* w, const void* log_sum, const void* status) {
+  if (!p || V < 0 || (V > 0 && (!Y || !peaks || !T || !shift || !w || !log_sum || !status)))
+    return mfx_fail(MFX_ERR_ARG, "%s: bad argument", fn);
+  if (K != 1 && K != 2)
+    return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: K must be 1 or 2 (got %d): three fascicles and voxels without one are out of scope", fn, K);
+  if (csf_on && !sig_csf) return mfx_fail(MFX_ERR_ARG, "%s: csf_on without sig_csf", fn);
+  if (V > 0x7fffffff) return mfx_fail(MFX_ERR_ARG, "%s: V too large for one call", fn);
+  return MFX_OK;
+}
+
+int post_enqueue(const char* fn, const mfx_plan* p, const double* d_Y, const double* d_peaks, int K, int csf_on,
+                 const double* d_sig_csf, const double* d_T, const double* d_shift, int64_t V, double* d_w, double* d_log_sum,
+                 int32_t* d_status, void* stream) {
+  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", POST_NO_DEVICE);
+  if (int rc = post_check_args(fn, p, d_Y, d_peaks, K, csf_on, d_sig_csf, d_T, d_shift, V, d_w, d_log_sum, d_status)) return rc;
+  PostArgs a{};
+  int device = 0;
+  mfx_plan_view(p, &a.T, &a.P, &device);
+  if (a.P.M > 560) return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: supports M <= 560 (got %d)", fn, a.P.M);
+  if (mfx_profile_cut() != MFX_POST_CUT) return mfx_fail(MFX_ERR_HIP, "%s: built with a cut other than the profile's", fn);
+  if (V == 0) return MFX_OK;
+  if (int rc = post_require_device(device)) return rc;
+  a.Y = d_Y; a.peaks = d_peaks; a.xc = csf_on ? d_sig_csf : nullptr; a.temp = d_T; a.shift = d_shift;
+  a.w = d_w; a.log_sum = d_log_sum; a.status = d_status;
+  hipStream_t st = (hipStream_t)stream;
+  if (K == 2) return post_launch_k2(a, (int)V, csf_on != 0, st, fn);
+  const size_t lds = (size_t)a.P.M * (4 * sizeof(double) + 2 * sizeof(int)) + 2 * sizeof(int);
+  if (csf_on) hipLaunchKernelGGL(mfx_post_k1_kernel<true>, dim3((unsigned)V), dim3(POST_K1_WG), lds, st, a);
+  else hipLaunchKernelGGL(mfx_post_k1_kernel<false>, dim3((unsigned)V), dim3(POST_K1_WG), lds, st, a);
+  HIPCHK(hipGetLastError());
+  return MFX_OK;
+}
+
+}  // namespace
+
+extern "C" int mfx_post_abi_version(void) { return 1; }
+
+extern "C" int mfx_post_max_atoms(const mfx_plan* p, int csf_on) {
+  if (!p) return 0;
+  TablesDev T;
+  PlanDev P;
+  int device = 0;
+  mfx_plan_view(p, &T, &P, &device);
+  if (P.M > 560) return 0;
+  return post_max_atoms(P.M, P.any_bracket != 0, csf_on != 0);
+}
+
+extern "C" int mfx_post_dev(const mfx_plan* p, const double* d_Y, const double* d_peaks, int K, int csf_on,
+                            const double* d_sig_csf, const double* d_T, const double* d_shift, int64_t V, double* d_w,
+                            double* d_log_sum, int32_t* d_status, void* stream) {
+  return post_enqueue("mfx_post_dev", p, d_Y, d_peaks, K, csf_on, d_sig_csf, d_T, d_shift, V, d_w, d_log_sum, d_status, stream);
+}
+
+extern "C" int mfx_post(const mfx_plan* p, const double* Y, const double* peaks, int K, int csf_on, const double* sig_csf,
+                        const double* T, const double* shift, int64_t V, double* w, double* log_sum, int32_t* status) {
+  const char* fn = "mfx_post";
+  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", POST_NO_DEVICE);   // before the plan is looked at
+  if (int rc = post_check_args(fn, p, Y, peaks, K, csf_on, sig_csf, T, shift, V, w, log_sum, status)) return rc;
+  if (V == 0) return MFX_OK;
+  TablesDev Td;
+  PlanDev P;
+  int device = 0;
+  mfx_plan_view(p, &Td, &P, &device);
+  if (int rc = post_require_device(device)) return rc;
+  const size_t M = P.M, N = Td.N, nout = (size_t)V * K * N;
+  DevMem dY, dpk, dx, dT, dsh, dw, dls, dst;
+  HIPCHK(dY.alloc(sizeof(double) * V * M));
+  HIPCHK(dpk.alloc(sizeof(double) * V * 3 * K));
+  HIPCHK(dx.alloc(sizeof(double) * M));
+  HIPCHK(dT.alloc(sizeof(double) * V));
+  HIPCHK(dsh.alloc(sizeof(double) * V));
+  HIPCHK(dw.alloc(sizeof(double) * nout));
+  HIPCHK(dls.alloc(sizeof(double) * V));
+  HIPCHK(dst.alloc(sizeof(int32_t) * V));
+  HIPCHK(hipMemcpy(dY.p, Y, sizeof(double) * V * M, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dpk.p, peaks, sizeof(double) * V * 3 * K, hipMemcpyHostToDevice));
+  if (csf_on) HIPCHK(hipMemcpy(dx.p, sig_csf, sizeof(double) * M, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dT.p, T, sizeof(double) * V, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dsh.p, shift, sizeof(double) * V, hipMemcpyHostToDevice));
+  if (int rc = post_enqueue(fn, p, dY.as<double>(), dpk.as<double>(), K, csf_on, csf_on ? dx.as<double>() : nullptr, dT.as<double>(),
+                            dsh.as<double>(), V, dw.as<double>(), dls.as<double>(), dst.as<int32_t>(), nullptr)) return rc;
+  if (int rc = mfx_plan_status(p, nullptr)) return rc;   // waits; a direction that is not a unit vector
+  HIPCHK(hipMemcpy(w, dw.p, sizeof(double) * nout, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(log_sum, dls.p, sizeof(double) * V, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(status, dst.p, sizeof(int32_t) * V, hipMemcpyDeviceToHost));
+  return MFX_OK;
+}

@@ -544,6 +544,88 @@ def pair_objectives(plan, Y, peaks, csf_on=False, sig_csf=None):
     return out
 
 
+def _per_voxel(x, V, what):
+    """A scalar or a [V] array as a float64 [V] array."""
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim == 0:
+        return np.full(V, float(x))
+    if x.shape != (V,):
+        raise ValueError("%s should be a scalar or have one entry per voxel (%d), got shape %s" % (what, V, x.shape))
+    return np.ascontiguousarray(x)
+
+
+def posterior_dev(plan, d_Y, d_peaks, K, T, shift, csf_on=False, d_sig_csf=None):
+    """Soft fit on the device (mfx_post_dev) for torch CUDA float64 tensors of ONE voxel class (every voxel: K
+    fascicles, CSF or not, no EAR).  ``T`` [V] the temperatures (2 sigma^2), ``shift`` [V] a value near each voxel's
+    smallest objective (include/mfx_post.h has the definitions).  Returns ``(w, log_sum, status)``: w [V x K x N]
+    the posterior weight of every atom of each fascicle, log_sum [V] = log sum exp(-F / T), status [V] int32 (0 ok,
+    1 unusable T or shift, 2 unusable shift: an exponent above 700 or a vanishing sum; rows of such voxels are NaN).
+    Enqueues on torch's current stream and returns without waiting."""
+    import torch
+    if csf_on and d_sig_csf is None:
+        raise ValueError("csf_on without d_sig_csf")
+    V = _profile_shapes(plan, d_Y.shape, d_peaks.shape, K, csf_on, d_sig_csf.numel() if csf_on else None)
+    for t, what in ((T, "T"), (shift, "shift")):
+        if not torch.is_tensor(t) or tuple(t.shape) != (V,):
+            raise ValueError("%s should be a tensor with one entry per voxel (%d)" % (what, V))
+    for t in (d_Y, d_peaks, T, shift) + ((d_sig_csf,) if csf_on else ()):
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+    N = plan.tables.N
+    w = torch.empty((V, int(K), N), dtype=torch.float64, device=d_Y.device)
+    log_sum = torch.empty((V,), dtype=torch.float64, device=d_Y.device)
+    status = torch.empty((V,), dtype=torch.int32, device=d_Y.device)
+    st = torch.cuda.current_stream(d_Y.device).cuda_stream
+    L.check(L.lib().mfx_post_dev(plan.handle(), d_Y.data_ptr(), d_peaks.data_ptr(), int(K), int(bool(csf_on)),
+                                 d_sig_csf.data_ptr() if csf_on else None, T.data_ptr(), shift.data_ptr(), V, w.data_ptr(),
+                                 log_sum.data_ptr(), status.data_ptr(), st))
+    return w, log_sum, status
+
+
+def posterior(plan, Y, K, csf, peaks, maxfasc, csf_on, sig_csf, sigma, shift=None, ear=None):
+    """Soft fit of a mixed set of voxels on NumPy arrays (mfx_post, one call per voxel class): Y [V x M], per-voxel K,
+    csf (and ear) flags, peaks [V x 3 maxfasc] as for ``fit_batch``; ``sigma`` the noise standard deviation (a scalar
+    or [V]; the temperature is 2 sigma^2); ``shift`` [V] a value near each voxel's smallest objective, default: MSE * M
+    of the library's own fit of the same voxels.  Returns ``(w, log_sum, status, n_unsupported)``: w [V x maxfasc x N]
+    float64, log_sum [V], status [V] int32 (the codes of include/mfx_post.h, and -1 for a voxel class out of scope: EAR,
+    no fascicle, three fascicles - counted in n_unsupported); rows of absent fascicles and of voxels with a non-zero
+    status are NaN."""
+    Y = L.f64c(Y)
+    maxfasc = int(maxfasc)
+    if Y.ndim != 2 or Y.shape[1] != plan.M:
+        raise ValueError("data has shape %s, protocol has %d measurements" % (Y.shape, plan.M))
+    V = Y.shape[0]
+    if np.asarray(K).shape != (V,):
+        raise ValueError("K should have one entry per voxel")
+    pk = L.f64c(peaks).reshape(V, -1) if maxfasc > 0 else np.zeros((V, 0))
+    if pk.shape[1] != 3 * maxfasc:
+        raise ValueError("peaks should have %d columns" % (3 * maxfasc))
+    sc = L.f64c(sig_csf).reshape(-1) if sig_csf is not None else None
+    if np.any(csf) and (not csf_on or sc is None):
+        raise ValueError("voxels flagged CSF need csf_on and sig_csf")
+    if sc is not None and sc.shape[0] != plan.M:
+        raise ValueError("sig_csf has %d entries, protocol has %d" % (sc.shape[0], plan.M))
+    sig = _per_voxel(sigma, V, "sigma")
+    sh = _per_voxel(shift, V, "shift") if shift is not None else None
+    bins, n_uns = profile_classes(K, csf, ear, maxfasc)
+    N = plan.tables.N
+    w = np.full((V, maxfasc, N), np.nan)
+    log_sum = np.full(V, np.nan)
+    status = np.full(V, -1, dtype=np.int32)
+    for k, c, ix in bins:
+        Yc, pc = np.ascontiguousarray(Y[ix]), np.ascontiguousarray(pk[ix, :3 * k])
+        if sh is None:
+            fit = fit_batch(plan, Yc, np.full(ix.size, k), np.full(ix.size, c), None, pc, k, c, False, sc if c else None)
+            shc = np.ascontiguousarray(fit[:, -2] * plan.M)
+        else:
+            shc = np.ascontiguousarray(sh[ix])
+        Tc = np.ascontiguousarray(2.0 * sig[ix] ** 2)
+        wc, lc, stc = np.zeros((ix.size, k, N)), np.zeros(ix.size), np.zeros(ix.size, dtype=np.int32)
+        L.check(L.lib().mfx_post(plan.handle(), L.dptr(Yc), L.dptr(pc), k, int(c), L.dptr(sc) if c else None, L.dptr(Tc),
+                                 L.dptr(shc), ix.size, L.dptr(wc), L.dptr(lc), L.iptr(stc)))
+        w[ix, :k], log_sum[ix], status[ix] = wc, lc, stc
+    return w, log_sum, status, n_uns
+
+
 def rotate2d_dev(tables, d_dirs, d_cols=None):
     """Device-resident 2-D protocol rotation (mfx_rot2d_rotate_dev / mfx_rot2d_rotate_cols_dev) for a
     mf_utils.RotateAtom2DTables: torch CUDA tensors dirs [B,3] f64 (and cols [B] int: one atom per direction)

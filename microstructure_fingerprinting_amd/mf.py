@@ -688,6 +688,80 @@ class MFModelFit():
             return m.reshape(self._grid + (nf,))
         return to_map(lo, np.nan), to_map(hi, np.nan), to_map(cnt, 0)
 
+    def _posterior_inputs(self, sigma, vox):
+        """(sigma [n], shift [n]) of the ROI positions ``vox``: the shift is the fit's own objective MSE * M; ``sigma``
+        None means sigma^2 = MSE * M / (M - K - csf), the residual variance of the fit."""
+        if self.weights_roi is not None:
+            raise NotImplementedError("posterior weights of a weighted fit are not served")
+        M = self._pgse_scheme.shape[0]
+        sse = np.asarray(self.params_in_mask[vox, -2], dtype=np.float64) * M
+        if sigma is None:
+            dof = M - self._numfasc_roi[vox].astype(np.float64) - self._csf_roi[vox].astype(np.float64)
+            with np.errstate(invalid='ignore', divide='ignore'):
+                sig = np.sqrt(sse / dof)
+        else:
+            sig = np.asarray(sigma, dtype=np.float64)
+            if sig.ndim == 0:
+                sig = np.full(vox.shape[0], float(sig))
+            elif sig.shape == (self._roi_flat.shape[0],):
+                sig = sig[vox]
+            else:
+                raise ValueError("sigma should be a scalar or have one entry per ROI voxel (%d), got shape %s"
+                                 % (self._roi_flat.shape[0], sig.shape))
+        return np.ascontiguousarray(sig), np.ascontiguousarray(sse)
+
+    def posterior(self, data, sigma=None, voxels=None):
+        """The soft answer beside the arg-min: for every atom of each fascicle its posterior weight given the noise
+        level, w proportional to the sum over all partner atoms of exp(-F / 2 sigma^2) (``engine.posterior``).  ``data``
+        as given to ``fit``; ``sigma``: the noise standard deviation, a scalar or one value per ROI voxel (default: the
+        fit's residual variance, sigma^2 = MSE * M / (M - K - csf) per voxel; a voxel with MSE = 0 gets status 1);
+        ``voxels``: positions in the ROI (default: all of it - [ROI x maxfasc x N] float64 on the host, meant for
+        regions: see ``posterior_moments``).  Returns a ``Posterior``."""
+        data_arr, plan, sig_csf = self._profile_setup(data)
+        vox = np.arange(self._roi_flat.shape[0]) if voxels is None else np.asarray(voxels, dtype=np.int64).reshape(-1)
+        sig, shift = self._posterior_inputs(sigma, vox)
+        w, log_sum, status, n_uns = engine.posterior(plan, self._data_rows(data_arr, self._roi_flat[vox]),
+                                                     self._numfasc_roi[vox], self._csf_roi[vox], self._peaks_roi[vox],
+                                                     self._nf, self._csf_on, sig_csf, sig, shift=shift, ear=self._ear_roi[vox])
+        return Posterior(w, log_sum, status, n_uns, vox, self._props, self._numfasc_roi[vox], 2.0 * sig ** 2, plan.M)
+
+    def posterior_moments(self, data, name, sigma=None):
+        """Posterior mean and standard deviation of the fascicle property ``name`` (one of the dictionary's
+        ``fasc_propnames``) per voxel and fascicle (``mf_utils.posterior_moments`` of the weights of ``posterior``):
+        ``(mean, std)`` volumes of shape ``mask.shape + (maxfasc,)``; NaN outside the ROI, for absent fascicles, for
+        voxels out of the posterior's scope (EAR, no fascicle) and for voxels with a non-zero status.  The weights are
+        computed and reduced on the device, PROFILE_BYTES of them at a time; only the two numbers per voxel and
+        fascicle come back."""
+        import torch
+        if name not in self._props:
+            raise ValueError("unknown fascicle property %s (have: %s)" % (name, ", ".join(sorted(self._props))))
+        data_arr, plan, sig_csf = self._profile_setup(data)
+        nf, R = self._nf, self._roi_flat.shape[0]
+        N = plan.tables.N
+        sig, shift = self._posterior_inputs(sigma, np.arange(R))
+        dev = torch.device("cuda", plan.tables.device)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        d_csf = t(sig_csf) if self._csf_on else None
+        mean, std = np.full((R, nf), np.nan), np.full((R, nf), np.nan)
+        chunk = max(1, int(self.PROFILE_BYTES // (8 * 2 * N)))
+        bins, _ = engine.profile_classes(self._numfasc_roi, self._csf_roi, self._ear_roi, nf)
+        with torch.cuda.device(dev):
+            for k, c, ix in bins:
+                for i0 in range(0, ix.size, chunk):
+                    sub = ix[i0:i0 + chunk]
+                    w, _, _ = engine.posterior_dev(plan, t(self._data_rows(data_arr, self._roi_flat[sub])),
+                                                   t(self._peaks_roi[sub, :3 * k]), k, t(2.0 * sig[sub] ** 2), t(shift[sub]),
+                                                   c, d_csf if c else None)
+                    m, sd = mfu.posterior_moments(w, self._props[name])
+                    L.check(L.lib().mfx_plan_status(plan.handle(), torch.cuda.current_stream(dev).cuda_stream))
+                    mean[sub, :k], std[sub, :k] = m.cpu().numpy(), sd.cpu().numpy()
+
+        def to_map(vals):
+            m = np.full((int(np.prod(self._grid)), nf), np.nan)
+            m[self._roi_flat] = vals
+            return m.reshape(self._grid + (nf,))
+        return to_map(mean), to_map(std)
+
     def write_nifti(self, output_basename, affine=None):
         """One NIfTI file per parameter map, ``<stem>_<param><ext>``; returns the file names (reference mf.py:1177-1229).
         ``output_basename`` may end in .nii.gz (kept), .nii or nothing (both give .nii); any other extension is refused."""
@@ -716,6 +790,47 @@ class ObjectiveProfile(object):
         if name not in self._props:
             raise ValueError("unknown fascicle property %s (have: %s)" % (name, ", ".join(sorted(self._props))))
         return mfu.profile_by_property(self.obj, self._props[name])
+
+
+class Posterior(object):
+    """Result of ``MFModelFit.posterior``: ``weights`` [n x maxfasc x N] (each present fascicle's row sums to 1; NaN rows
+    for absent fascicles, voxels out of scope and voxels with a non-zero status), ``log_sum`` [n] = log of the sum of
+    exp(-F / T) over all atoms (pairs), ``status`` [n] (0 ok, 1 unusable temperature, 2 unusable shift, -1 a voxel class out of scope),
+    ``n_unsupported``, ``voxels`` (the ROI positions the rows stand for)."""
+
+    def __init__(self, weights, log_sum, status, n_unsupported, voxels, props, numfasc, T, M):
+        self.weights, self.log_sum, self.status, self.n_unsupported, self.voxels = weights, log_sum, status, n_unsupported, voxels
+        self._props, self._K, self._T, self._M = props, np.asarray(numfasc, dtype=np.float64), np.asarray(T, dtype=np.float64), int(M)
+
+    def _values(self, name):
+        if name not in self._props:
+            raise ValueError("unknown fascicle property %s (have: %s)" % (name, ", ".join(sorted(self._props))))
+        return self._props[name]
+
+    def mean(self, name):
+        """Posterior mean of the property ``name`` [n x maxfasc]."""
+        return mfu.posterior_moments(self.weights, self._values(name))[0]
+
+    def std(self, name):
+        """Posterior standard deviation of the property ``name`` [n x maxfasc]."""
+        return mfu.posterior_moments(self.weights, self._values(name))[1]
+
+    def quantile(self, name, q):
+        """Lower weighted quantile of the property ``name`` [n x maxfasc] (``mf_utils.posterior_quantile``)."""
+        return mfu.posterior_quantile(self.weights, self._values(name), q)
+
+    def by_property(self, name):
+        """(levels, weight_by_level [n x maxfasc x len(levels)]): the posterior as a distribution over ``name``."""
+        return mfu.posterior_by_property(self.weights, self._values(name))
+
+    def log_evidence(self):
+        """log_sum - K log N - (M / 2) log(pi T) per voxel: the log of the Gaussian likelihood averaged over a uniform
+        prior on the K-tuples of atoms, which lets a one-fascicle and a two-fascicle explanation of the same voxel be
+        compared.  It is a profile-likelihood evidence: the fascicle (and CSF) weights are maximised for every tuple,
+        not integrated over.  NaN where log_sum is."""
+        N = self.weights.shape[-1]
+        with np.errstate(invalid='ignore', divide='ignore'):
+            return self.log_sum - self._K * np.log(N) - 0.5 * self._M * np.log(np.pi * self._T)
 
 
 def _nifti_stem(output_basename):

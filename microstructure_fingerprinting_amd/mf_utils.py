@@ -40,7 +40,8 @@ __all__ = ["get_gyromagnetic_ratio", "solve_exhaustive_posweights", "init_PGSE_m
            "interp_PGSE_from_multishell", "rotate_atom", "RotateAtomTables", "import_PGSE_scheme",
            "get_PGSE_scheme_from_bval_bvec_dense", "loadmat", "MultiShellInterpolator",
            "rotate_atom_2Dprotocol", "RotateAtom2DTables", "rotate_scheme_mat", "vrrotvec2mat", "rotate_vector",
-           "get_perp_vector", "project_PGSE_scheme_xy_plane", "fit_2Dprotocol", "Fit2DResult", "gen_SoS_MRI", "profile_by_property", "profile_interval"]
+           "get_perp_vector", "project_PGSE_scheme_xy_plane", "fit_2Dprotocol", "Fit2DResult", "gen_SoS_MRI", "profile_by_property", "profile_interval",
+           "posterior_moments", "posterior_quantile", "posterior_by_property"]
 
 
 def get_gyromagnetic_ratio(element='H'):
@@ -1185,6 +1186,60 @@ def profile_interval(obj, values, rel=0.0, delta=0.0):
     lo = np.where(sel, values, np.inf).min(axis=-1)
     hi = np.where(sel, values, -np.inf).max(axis=-1)
     return np.where(bad[..., 0], np.nan, lo), np.where(bad[..., 0], np.nan, hi), sel.sum(axis=-1)
+
+
+def posterior_moments(w, values):
+    """Mean and standard deviation of one per-atom property (``values`` [N]) under posterior weights over atoms
+    (``engine.posterior``: w [..., N], each row summing to 1): ``(mean, std)`` of shape w.shape[:-1], std the square
+    root of sum w (values - mean)^2.  A row that holds NaN (an absent fascicle, a voxel out of scope or with a non-zero
+    status) gives NaN.  NumPy in, NumPy out; a torch tensor in, tensors out on its device."""
+    _, _, values = _property_levels(w, values)
+    if _is_torch(w):
+        import torch
+        v = torch.as_tensor(values, device=w.device)
+        mean = (w * v).sum(dim=-1)
+        return mean, torch.sqrt((w * (v - mean[..., None]) ** 2).sum(dim=-1))
+    w = np.asarray(w, dtype=np.float64)
+    mean = (w * values).sum(axis=-1)
+    return mean, np.sqrt((w * (values - mean[..., None]) ** 2).sum(axis=-1))
+
+
+def posterior_quantile(w, values, q):
+    """The lower weighted quantile of a per-atom property under posterior weights w [..., N]: with the atoms sorted by
+    value, the smallest value whose cumulative weight reaches ``q`` times the row's total (0 <= q <= 1).  NaN rows give
+    NaN.  NumPy in, NumPy out; a torch tensor in, a tensor out on its device."""
+    q = float(q)
+    if not 0.0 <= q <= 1.0:
+        raise ValueError("q should lie in [0, 1]")
+    _, _, values = _property_levels(w, values)
+    order = np.argsort(values, kind='stable')
+    vs = values[order]
+    if _is_torch(w):
+        import torch
+        c = torch.cumsum(w[..., torch.as_tensor(order, device=w.device)], dim=-1)
+        reach = c >= q * c[..., -1:]
+        first = torch.argmax(reach.to(torch.int8), dim=-1)      # the first True
+        out = torch.as_tensor(vs, device=w.device)[first]
+        return torch.where(reach.any(dim=-1), out, torch.full_like(out, float('nan')))
+    w = np.asarray(w, dtype=np.float64)
+    c = np.cumsum(w[..., order], axis=-1)
+    with np.errstate(invalid='ignore'):
+        reach = c >= q * c[..., -1:]
+    return np.where(reach.any(axis=-1), vs[np.argmax(reach, axis=-1)], np.nan)
+
+
+def posterior_by_property(w, values):
+    """Posterior weights over atoms (w [..., N]) as a distribution over one per-atom property: ``(levels,
+    weight_by_level)``, the sorted distinct property values and, along a last axis of that length, the sum of w over the
+    atoms at each level - the counterpart of ``profile_by_property`` with sums in place of minima.  NaN rows stay NaN.
+    NumPy in, NumPy out; a torch tensor in, tensors out on its device."""
+    levels, inv, _ = _property_levels(w, values)
+    if _is_torch(w):
+        import torch
+        cols = [w[..., torch.as_tensor(np.flatnonzero(inv == p), device=w.device)].sum(dim=-1) for p in range(levels.size)]
+        return torch.as_tensor(levels, device=w.device), torch.stack(cols, dim=-1)
+    w = np.asarray(w, dtype=np.float64)
+    return levels, np.stack([w[..., inv == p].sum(axis=-1) for p in range(levels.size)], axis=-1)
 
 
 def _sos_seed(seed):
