@@ -696,34 +696,45 @@ static int fit_class_fused(const mfx_plan* p, const double* d_Y, const double* d
 }
 
 // Launch sequence of the explicit-dictionary solver on device buffers.  Three sub-dictionaries with many triples go
-// through solve_k3.hip (Gram on FP64 MFMA, relaxed-bound screen, candidate list); k3 = its extra buffers (thr, ncand,
-// nblocks_dev), or null for the plain one-thread-per-tuple scan.
-struct K3Bufs { unsigned long long* thr; int* ncand; int* nblocks_dev; double2* st3; };
-static size_t k3_buf_bytes(long N3) { return 64 + sizeof(double2) * (size_t)N3; }
-static K3Bufs k3_bufs(char* p) { return K3Bufs{(unsigned long long*)p, (int*)(p + 16), (int*)(p + 32), (double2*)(p + 64)}; }
+// through solve_k3.hip (Gram on FP64 MFMA, relaxed-bound screen, candidate list), everything else through the plain
+// one-thread-per-tuple scan.  kb = the small buffers of both: the scan's running maximum, the best of every scan block
+// and the device-side length of the candidate list (nblocks_dev: the plain scan's counter, or what the screen publishes);
+// thr, ncand, st3 of the three-dictionary screen.
+struct K3Bufs { unsigned long long* thr; unsigned long long* smax; int* ncand; int* nblocks_dev; double* blk_max; double2* st3; };
+static size_t k3_buf_bytes(long N3, int nblocks) { return 64 + sizeof(double) * (size_t)((nblocks + 1) & ~1) + sizeof(double2) * (size_t)N3; }
+static K3Bufs k3_bufs(char* p, int nblocks) {
+  return K3Bufs{(unsigned long long*)p, (unsigned long long*)(p + 8), (int*)(p + 16), (int*)(p + 32), (double*)(p + 64),
+                (double2*)(p + 64 + sizeof(double) * (size_t)((nblocks + 1) & ~1))};
+}
 static bool k3_applies(const SolveArgs& a) { return a.Kp == 3 && a.ntuples >= (1L << 18) && a.sizes[0] >= 16 && a.sizes[1] >= 16 && a.sizes[2] >= 16; }
-static int launch_solver(SolveArgs a, const K3Bufs* k3, hipStream_t st) {
+// entries the caller allocates for blk_score / blk_tuple
+static size_t solver_list_entries(const SolveArgs& a, bool k3) { return k3 ? (size_t)MFX_K3_CAP : (size_t)std::min<long>(a.ntuples, MFX_SCAN_CAP); }
+static int launch_solver(SolveArgs a, const K3Bufs& kb, bool k3, hipStream_t st) {
+  if (a.nblocks > MFX_SCAN_CAP) return fail(MFX_ERR_ARG, "explicit solver: scan grid of %d blocks", a.nblocks);
+  a.list_cap = (int)std::min<long>(a.ntuples, MFX_SCAN_CAP);   // >= nblocks = min(cap, ceil(ntuples / 256))
+  a.smax = kb.smax; a.blk_max = kb.blk_max; a.ncand = kb.nblocks_dev; a.nblocks_dev = kb.nblocks_dev;
   if (k3) {
     K3Args k{};
-    a.nblocks_dev = k3->nblocks_dev; a.scan_enable = k3->ncand + 1; a.gram_ranking_only = 1;
-    k.s = a; k.thr = k3->thr; k.ncand = k3->ncand; k.st3 = k3->st3; k.cand_score = a.blk_score; k.cand_tuple = a.blk_tuple;
-    HIPCHK(hipMemsetAsync(k3->thr, 0, sizeof(unsigned long long), st));
-    HIPCHK(hipMemsetAsync(k3->ncand, 0, 2 * sizeof(int), st));
+    a.scan_enable = kb.ncand + 1; a.gram_ranking_only = 1;
+    k.s = a; k.thr = kb.thr; k.ncand = kb.ncand; k.st3 = kb.st3; k.cand_score = a.blk_score; k.cand_tuple = a.blk_tuple;
+    HIPCHK(hipMemsetAsync(kb.thr, 0, sizeof(unsigned long long), st));
+    HIPCHK(hipMemsetAsync(kb.ncand, 0, 2 * sizeof(int), st));
     const int nt = (a.Ntot + 63) / 64;
     hipLaunchKernelGGL(mfx_k3_gram_kernel, dim3(nt, nt), dim3(256), 0, st, a);
     hipLaunchKernelGGL(mfx_k3_aty_kernel, dim3((a.Ntot + 2 + 255) / 256), dim3(256), 0, st, a);
     hipLaunchKernelGGL(mfx_k3_st3_kernel, dim3((unsigned)((a.sizes[2] + 255) / 256)), dim3(256), 0, st, k);
     hipLaunchKernelGGL(mfx_k3_pairs_kernel, dim3(2048), dim3(256), 0, st, k);
     hipLaunchKernelGGL(mfx_k3_screen_kernel, dim3((unsigned)((a.sizes[1] + 31) / 32), (unsigned)((a.sizes[0] + 31) / 32)), dim3(256), 0, st, k);
-    hipLaunchKernelGGL(mfx_k3_publish_kernel, dim3(1), dim3(64), 0, st, k, k3->nblocks_dev);
-    hipLaunchKernelGGL(mfx_tuple_scan, dim3(a.nblocks), dim3(256), 0, st, a);   // exits at once unless the list overflowed
-    hipLaunchKernelGGL(mfx_tuple_finalize, dim3(1), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(mfx_k3_publish_kernel, dim3(1), dim3(64), 0, st, k, kb.nblocks_dev);
   } else {
     const long work = (long)a.Ntot * a.Ntot + a.Ntot + 2;
     hipLaunchKernelGGL(mfx_gram_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(mfx_tuple_scan, dim3(a.nblocks), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(mfx_tuple_finalize, dim3(1), dim3(256), 0, st, a);
   }
+  // (three dictionaries: the three passes of the scan exit at once unless the screen's list overflowed)
+  hipLaunchKernelGGL(mfx_tuple_scan, dim3(a.nblocks), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(mfx_tuple_collect, dim3(a.nblocks), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(mfx_tuple_overflow, dim3(a.nblocks), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(mfx_tuple_finalize, dim3(1), dim3(256), 0, st, a);
   HIPCHK(hipGetLastError());
   return MFX_OK;
 }
@@ -818,12 +829,12 @@ static int fit_k3_batched(const mfx_plan* p, const double* d_Y, const double* d_
     HIPCHK(S.fbs.alloc(sizeof(double) * (size_t)MFX_K3_CAP));
     HIPCHK(S.fbt.alloc(sizeof(long) * (size_t)MFX_K3_CAP));
     HIPCHK(S.fout.alloc(sizeof(double) * (MFX_GK + MFX_GK + 1 + (size_t)M)));
-    HIPCHK(S.fk3.alloc(k3_buf_bytes(N)));
+    HIPCHK(S.fk3.alloc(k3_buf_bytes(N, fa.nblocks)));
     fa.G = S.fG.as<double>(); fa.Aty = S.fcol.as<double>(); fa.ysq = fa.Aty + LD;
     fa.blk_score = S.fbs.as<double>(); fa.blk_tuple = S.fbt.as<long>();
     fa.w = S.fout.as<double>(); fa.sub = (long*)(fa.w + MFX_GK); fa.minobj = (double*)(fa.sub + MFX_GK); fa.yrec = fa.minobj + 1;
     fav[l] = fa;
-    fkbv[l] = k3_bufs(S.fk3.as<char>());
+    fkbv[l] = k3_bufs(S.fk3.as<char>(), fa.nblocks);
   }
   if (int rc = mfx_prof_begin(st)) return rc;
   for (int q0 = 0; q0 < nvox; q0 += BT) {
@@ -853,7 +864,7 @@ static int fit_k3_batched(const mfx_plan* p, const double* d_Y, const double* d_
       fa.A = dA.as<double>() + (size_t)b * M * LD;
       fa.y = d_Y + (size_t)v * M;
       fa.run_if = k.ncand + 2 * b + 1;
-      rc_fb = launch_solver(fa, &fkbv[l], TT.s_lane[l]);
+      rc_fb = launch_solver(fa, fkbv[l], true, TT.s_lane[l]);
       if (rc_fb != MFX_OK) break;
       PackArgs pa = pk;
       pa.run_if = fa.run_if;
@@ -909,7 +920,7 @@ static int fit_class_generic(const mfx_plan* p, const double* d_Y, const double*
   a.M = M; a.Kp = Kp; a.Ntot = (int)Ntot; a.lda = Ntot; a.ntuples = ntup;
   a.nblocks = (int)std::min<long>(16384, (ntup + 255) / 256);
   const bool k3 = mfx_thread().k3_screen && k3_applies(a);
-  const size_t nlist = k3 ? (size_t)MFX_K3_CAP : (size_t)a.nblocks;
+  const size_t nlist = solver_list_entries(a, k3);
   // two voxels in flight on two internal streams, each with its own set of buffers (at config 5: 162 MB of Gram, 11 MB
   // of dictionary, 16 MB of candidate list per set)
   constexpr int LANES = 2;   // (3: no further gain, 4: slower - measured at config 5)
@@ -926,8 +937,8 @@ static int fit_class_generic(const mfx_plan* p, const double* d_Y, const double*
   K3Bufs kbv[LANES];
   for (int l = 0; l < nl; ++l) {
     Set& S = *sets[l];
-    HIPCHK(S.dk3.alloc(k3_buf_bytes(N)));
-    kbv[l] = k3_bufs(S.dk3.as<char>());
+    HIPCHK(S.dk3.alloc(k3_buf_bytes(std::max<long>(N, Kp > 0 ? a.sizes[Kp - 1] : 0), a.nblocks)));
+    kbv[l] = k3_bufs(S.dk3.as<char>(), a.nblocks);
     HIPCHK(S.dA.alloc(sizeof(double) * (size_t)M * Ntot));
     HIPCHK(S.dG.alloc(sizeof(double) * (size_t)Ntot * Ntot));
     HIPCHK(S.dAty.alloc(sizeof(double) * Ntot));
@@ -962,7 +973,7 @@ static int fit_class_generic(const mfx_plan* p, const double* d_Y, const double*
       hipLaunchKernelGGL(mfx_rotate_kernel, grid, dim3(MFX_ROT_WG), 0, ls[l], p->t->d, p->d, d_peaks + (size_t)v * peaks_ld, 0,
                          sets[l]->dA.as<double>(), (long)N, Ntot);   // (an explicit plan normalises the direction inside mfx_row_desc)
     av[l].y = d_Y + (size_t)v * M;
-    rc_loop = launch_solver(av[l], k3 ? &kbv[l] : nullptr, ls[l]);
+    rc_loop = launch_solver(av[l], kbv[l], k3, ls[l]);
     if (rc_loop != MFX_OK) break;
     PackArgs pa{};
     pa.w = av[l].w; pa.sub = av[l].sub; pa.minobj = av[l].minobj; pa.yrec = av[l].yrec; pa.y = av[l].y;
@@ -1001,10 +1012,10 @@ static int dense_args(int M, int K, int N, int has_csf, SolveArgs& a, bool& k3, 
   a.M = M; a.Kp = Kp; a.Ntot = (int)Ntot; a.lda = Ntot; a.ntuples = ntup;
   a.nblocks = (int)std::min<long>(16384, (ntup + 255) / 256);
   k3 = mfx_thread().k3_screen && k3_applies(a);
-  const size_t nlist = k3 ? (size_t)MFX_K3_CAP : (size_t)a.nblocks;
-  // G, Aty, ysq, blk_score, blk_tuple, w, sub, minobj, yrec, k3 buffers; off[10] = total
+  const size_t nlist = solver_list_entries(a, k3);
+  // G, Aty, ysq, blk_score, blk_tuple, w, sub, minobj, yrec, the scan's and the screen's small buffers; off[10] = total
   const size_t sz[10] = {sizeof(double) * (size_t)Ntot * Ntot, sizeof(double) * (size_t)Ntot, 16, sizeof(double) * nlist, sizeof(long) * nlist,
-                         sizeof(double) * MFX_GK, sizeof(long) * MFX_GK, 8, sizeof(double) * (size_t)M, k3_buf_bytes(N)};
+                         sizeof(double) * MFX_GK, sizeof(long) * MFX_GK, 8, sizeof(double) * (size_t)M, k3_buf_bytes(N, a.nblocks)};
   size_t o = 0;
   for (int q = 0; q < 10; ++q) { off[q] = o; o += (sz[q] + 255) / 256 * 256; }
   off[10] = o;
@@ -1029,8 +1040,8 @@ int mfx_solve_dense_dev(const double* d_A, int M, int K, int N, int has_csf, con
   a.G = (double*)(sc + off[0]); a.Aty = (double*)(sc + off[1]); a.ysq = (double*)(sc + off[2]); a.blk_score = (double*)(sc + off[3]);
   a.blk_tuple = (long*)(sc + off[4]); a.w = (double*)(sc + off[5]); a.sub = (long*)(sc + off[6]); a.minobj = (double*)(sc + off[7]);
   a.yrec = (double*)(sc + off[8]);
-  K3Bufs kb = k3_bufs(sc + off[9]);
-  if (int rc = launch_solver(a, k3 ? &kb : nullptr, st)) return rc;
+  const K3Bufs kb = k3_bufs(sc + off[9], a.nblocks);
+  if (int rc = launch_solver(a, kb, k3, st)) return rc;
   PackArgs pa{};
   pa.run_if = run_if;
   pa.w = a.w; pa.sub = a.sub; pa.minobj = a.minobj; pa.yrec = a.yrec; pa.y = d_y;
@@ -1574,7 +1585,7 @@ extern "C" int mfx_solve_exhaustive(const double* A, int64_t lda, int M, const i
   a.M = M; a.Kp = Kp; a.Ntot = (int)Ntot; a.lda = Ntot; a.ntuples = ntup;
   a.nblocks = (int)std::min<long>(8192, (ntup + 255) / 256);
   const bool k3 = mfx_thread().k3_screen && k3_applies(a);
-  const size_t nlist = k3 ? (size_t)MFX_K3_CAP : (size_t)a.nblocks;
+  const size_t nlist = solver_list_entries(a, k3);
   std::vector<double> Ac((size_t)M * Ntot);
   for (int k = 0; k < M; ++k) std::memcpy(&Ac[(size_t)k * Ntot], A + (size_t)k * lda, sizeof(double) * Ntot);
   double *dA = nullptr, *dy = nullptr, *dG = nullptr, *dAty = nullptr, *dysq = nullptr, *dbs = nullptr, *dw = nullptr,
@@ -1597,14 +1608,14 @@ extern "C" int mfx_solve_exhaustive(const double* A, int64_t lda, int M, const i
   SCHK(hipMalloc(&dsub, sizeof(long) * MFX_GK));
   SCHK(hipMalloc(&dobj, sizeof(double)));
   SCHK(hipMalloc(&dyrec, sizeof(double) * M));
-  SCHK(hipMalloc(&dk3, k3_buf_bytes(dicsizes[Kp - 1])));
+  SCHK(hipMalloc(&dk3, k3_buf_bytes(dicsizes[Kp - 1], a.nblocks)));
   SCHK(hipMemcpy(dA, Ac.data(), sizeof(double) * Ac.size(), hipMemcpyHostToDevice));
   SCHK(hipMemcpy(dy, y, sizeof(double) * M, hipMemcpyHostToDevice));
   a.A = dA; a.y = dy; a.G = dG; a.Aty = dAty; a.ysq = dysq; a.blk_score = dbs; a.blk_tuple = dbt;
   a.w = dw; a.sub = dsub; a.minobj = dobj; a.yrec = dyrec;
   {
-    K3Bufs kb = k3_bufs(dk3);
-    if (int rc = launch_solver(a, k3 ? &kb : nullptr, nullptr)) { cleanup(); return rc; }
+    const K3Bufs kb = k3_bufs(dk3, a.nblocks);
+    if (int rc = launch_solver(a, kb, k3, nullptr)) { cleanup(); return rc; }
   }
   SCHK(hipGetLastError());
   SCHK(hipDeviceSynchronize());

@@ -2,12 +2,23 @@
 // (mf_utils.py:115-214) for ONE problem with arbitrary sub-dictionary sizes.
 //
 // The fused fit kernels never see an explicit dictionary; this path backs the drop-in mf_utils entry
-// point (and reproduces the reference's own solver tests).  Three launches:
+// point (and reproduces the reference's own solver tests).  The launches:
 //   1. mfx_gram_kernel     G = A^T A and A^T y, every entry summed sequentially over the rows exactly as
 //                          the reference's precompute loops (mf_utils.py:307-325, 503-535)  -> HBM
-//   2. mfx_tuple_scan      all prod(sizes) index tuples, one thread per tuple (grid-stride); ranks by
-//                          the NNLS optimum of the tuple's tiny Gram system; per-block best -> HBM
-//   3. mfx_tuple_finalize  candidates within 1e-9*||y||^2 of the best are re-evaluated with the
+//   2. mfx_tuple_scan      all prod(sizes) index tuples, one thread per tuple (grid-stride); scores a tuple
+//                          by the NNLS optimum of its tiny Gram system; the best score of every block -> HBM,
+//                          the best score of all (atomicMax)
+//   3. mfx_tuple_collect   the blocks whose best lies within 1e-9*||y||^2 of the best of all (the finalize
+//                          stage's tie window) score their tuples again and append EVERY tuple inside the
+//                          window to a candidate list (atomic counter); every other block exits at once.
+//                          Two tuples whose scores differ by rounding only - the same columns in two
+//                          orders, (i, j) and (j, i) of two identical sub-dictionaries - both reach the
+//                          finalize stage, whatever block they sit in.
+//   4. mfx_tuple_overflow  only when the list overflowed (more than MFX_SCAN_CAP tuples inside the window:
+//                          massive exact ties), exits at once otherwise: every block keeps, of its tuples
+//                          inside the window, the first in the reference's scan order - the first hit of
+//                          all tuples inside the window is among them.
+//   5. mfx_tuple_finalize  the listed candidates are re-evaluated with the
 //                          reference's exact per-tuple arithmetic (_1/_2 closed forms, _3 Cramer +
 //                          explicit residual, _4up active-set optimum + explicit residual), first-hit
 //                          rule in the reference's scan order, outputs written.
@@ -17,6 +28,8 @@
 #include "nnls_small.h"
 
 #define MFX_GK 8  // max sub-dictionaries supported by the explicit solver
+#define MFX_SCAN_CAP 16384   // candidate list entries of the plain scan (>= the largest grid of the scan: the overflow pass
+                             // stores one entry per block in the same arrays)
 
 struct SolveArgs {
   const double* A;  // [M x lda] device copy
@@ -28,11 +41,15 @@ struct SolveArgs {
   double* Aty;      // [Ntot]
   double* ysq;      // [2]: sequential, pairwise
   long ntuples;
-  double* blk_score;  // [nblocks]
-  long* blk_tuple;    // [nblocks]
-  int nblocks;
+  double* blk_score;  // [list_cap] candidate list: score ...
+  long* blk_tuple;    // [list_cap] ... and tuple number (after an overflow: one entry per scan block, tuple -1 = none)
+  int nblocks;        // grid of the scan
+  int list_cap;       // min(ntuples, MFX_SCAN_CAP) >= nblocks
+  double* blk_max;    // [nblocks] best score of every scan block
+  unsigned long long* smax;   // [1] bits of the best score of all tuples (a non-negative double)
+  int* ncand;         // [1] tuples appended to the list; negative once it has overflowed
   // three-dictionary fast path (solve_k3.hip); all null / 0 otherwise
-  const int* nblocks_dev;   // device-side number of entries in blk_score / blk_tuple (< 0: use nblocks)
+  const int* nblocks_dev;   // device-side number of entries in blk_score / blk_tuple (< 0: use nblocks); the plain scan: ncand
   const int* scan_enable;   // the full scan below runs only when this device flag is set
   int gram_ranking_only;    // G was summed on the matrix pipe: the finalize stage re-sums what it needs sequentially
   const int* run_if;        // null, or a device flag: every kernel of the launch sequence exits at once while it is 0 (fit_k3.hip
@@ -64,6 +81,8 @@ __global__ void mfx_gram_kernel(SolveArgs a) {
     a.ysq[0] = s;
   } else if (idx == nn + a.Ntot + 1) {
     a.ysq[1] = mfx_np_sumsq(a.y, a.M);
+    *a.smax = 0ull;   // the scan's running maximum and candidate counter start from zero in every launch sequence
+    *a.ncand = 0;
   }
 }
 
@@ -138,29 +157,33 @@ __device__ inline double mfx_tuple_score(const SolveArgs& a, const int col[MFX_G
   return mfx_score_general(n, g, y);
 }
 
+// ||y||^2 as the reference's kernel for this number of sub-dictionaries sums it: np.sum(y**2) in _1/_4up, sequential in _2/_3
+__device__ __forceinline__ double mfx_ref_ysq(const SolveArgs& a) { return (a.Kp == 1 || a.Kp >= 4) ? a.ysq[1] : a.ysq[0]; }
+
+// lower edge of the tie window: what the finalize stage computes from the best listed score
+__device__ __forceinline__ double mfx_tie_threshold(const SolveArgs& a) {
+  return __longlong_as_double((long long)*a.smax) - 1e-9 * mfx_ref_ysq(a);
+}
+
+// pass 1: the best score of every block and of all tuples.  Nothing is selected here: which tuples reach the finalize
+// stage is decided against the maximum of ALL tuples, in mfx_tuple_collect.
 __global__ __launch_bounds__(256) void mfx_tuple_scan(SolveArgs a) {
   __shared__ double s_sc[256];
-  __shared__ long s_t[256];
   if (a.run_if && !*a.run_if) return;
   if (a.scan_enable && !*a.scan_enable) return;   // (three-dictionary fast path: only after a candidate-list overflow)
   double best = 0.0;
-  long bt = -1;
   for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < a.ntuples; t += (long)gridDim.x * 256) {
     int col[MFX_GK];
     mfx_decode(a, t, col);
     const double s = mfx_tuple_score(a, col);
-    if (s > best) { best = s; bt = t; }
+    if (s > best) best = s;
   }
   s_sc[threadIdx.x] = best;
-  s_t[threadIdx.x] = bt;
   __syncthreads();
-  // keep EVERY thread's best that is within the tie window of the block maximum?  One per block is
-  // enough for generic data; exact ties inside a block resolve to the smaller tuple number below.
   if (threadIdx.x == 0) {
-    for (int i = 1; i < 256; ++i)
-      if (s_sc[i] > best || (s_sc[i] == best && s_t[i] >= 0 && (bt < 0 || s_t[i] < bt))) { best = s_sc[i]; bt = s_t[i]; }
-    a.blk_score[blockIdx.x] = best;
-    a.blk_tuple[blockIdx.x] = bt;
+    for (int i = 1; i < 256; ++i) best = fmax(best, s_sc[i]);
+    a.blk_max[blockIdx.x] = best;
+    if (best > 0.0) atomicMax(a.smax, (unsigned long long)__double_as_longlong(best));
   }
 }
 
@@ -170,6 +193,67 @@ __device__ __forceinline__ long mfx_order_key(const SolveArgs& a, long t) {
   if (a.Kp != 3) return t;
   const long i3 = t % a.sizes[2], i2 = (t / a.sizes[2]) % a.sizes[1], i1 = t / (a.sizes[2] * a.sizes[1]);
   return (i3 * a.sizes[0] + i1) * a.sizes[1] + i2;
+}
+
+// pass 2: every tuple inside the tie window goes to the candidate list.  Same grid as pass 1 (a block sees the tuples it
+// scored there, and scores them to the same bits: the build does not contract floating point); a block whose best lies
+// below the window has none and exits.  More than list_cap candidates: the counter's sign bit is set and stays.
+__global__ __launch_bounds__(256) void mfx_tuple_collect(SolveArgs a) {
+  if (a.run_if && !*a.run_if) return;
+  if (a.scan_enable && !*a.scan_enable) return;
+  const double thr = mfx_tie_threshold(a);
+  const double bm = a.blk_max[blockIdx.x];
+  if (!(bm > 0.0) || bm < thr) return;
+  for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < a.ntuples; t += (long)gridDim.x * 256) {
+    int col[MFX_GK];
+    mfx_decode(a, t, col);
+    const double s = mfx_tuple_score(a, col);
+    if (!(s > 0.0) || s < thr) continue;
+    if (*(volatile int*)a.ncand < 0) return;   // overflowed: mfx_tuple_overflow takes over
+    const int slot = atomicAdd(a.ncand, 1);
+    if (slot >= 0 && slot < a.list_cap) {
+      a.blk_score[slot] = s;
+      a.blk_tuple[slot] = t;
+    } else {
+      atomicOr(a.ncand, (int)0x80000000);
+      return;
+    }
+  }
+}
+
+// pass 3, only after an overflow of the list (exits at once otherwise): one entry per block - of the block's tuples
+// inside the tie window the first in the reference's scan order.  The first hit among ALL tuples inside the window is
+// the first of its own block, so it is kept; the finalize stage reads nblocks entries (nblocks_dev < 0).
+__global__ __launch_bounds__(256) void mfx_tuple_overflow(SolveArgs a) {
+  __shared__ double s_sc[256];
+  __shared__ long s_key[256], s_t[256];
+  if (a.run_if && !*a.run_if) return;
+  if (a.scan_enable && !*a.scan_enable) return;
+  if (*a.ncand >= 0) return;
+  const double thr = mfx_tie_threshold(a);
+  const double bm = a.blk_max[blockIdx.x];
+  double bs = 0.0;
+  long bkey = -1, bt = -1;
+  if (bm > 0.0 && !(bm < thr)) {   // (uniform over the block)
+    for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < a.ntuples; t += (long)gridDim.x * 256) {
+      int col[MFX_GK];
+      mfx_decode(a, t, col);
+      const double s = mfx_tuple_score(a, col);
+      if (!(s > 0.0) || s < thr) continue;
+      const long key = mfx_order_key(a, t);
+      if (bt < 0 || key < bkey) { bs = s; bkey = key; bt = t; }
+    }
+  }
+  s_sc[threadIdx.x] = bs;
+  s_key[threadIdx.x] = bkey;
+  s_t[threadIdx.x] = bt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < 256; ++i)
+      if (s_t[i] >= 0 && (bt < 0 || s_key[i] < bkey)) { bs = s_sc[i]; bkey = s_key[i]; bt = s_t[i]; }
+    a.blk_score[blockIdx.x] = bs;
+    a.blk_tuple[blockIdx.x] = bt;
+  }
 }
 
 __global__ __launch_bounds__(256) void mfx_tuple_finalize(SolveArgs a) {

@@ -20,8 +20,8 @@
 //   4. mfx_tuple_finalize     (solve_generic.hip) on the candidate list: exact _3 arithmetic, first hit in the
 //                             reference's i3 -> i1 -> i2 order.
 // A candidate list that overflows (massive ties: e.g. a single-fascicle signal fitted with three - every (i2, i3)
-// ties) raises a device flag; the one-thread-per-tuple scan of solve_generic.hip then runs as before (it is launched
-// unconditionally and exits at once when the flag is clear), so nothing is dropped silently.
+// ties) raises a device flag; the one-thread-per-tuple scan of solve_generic.hip (scan, collect, overflow pass) then
+// runs instead (it is launched unconditionally and exits at once when the flag is clear), so nothing is dropped silently.
 #pragma once
 #include "solve_generic.hip"
 
@@ -89,6 +89,7 @@ __global__ void mfx_k3_aty_kernel(SolveArgs a) {
     a.ysq[0] = s;
   } else if (idx == a.Ntot + 1) {
     a.ysq[1] = mfx_np_sumsq(a.y, a.M);
+    *a.smax = 0ull;   // the full scan's running maximum (its candidate counter: mfx_k3_publish_kernel)
   }
 }
 
@@ -269,6 +270,7 @@ __global__ void mfx_k3_publish_kernel(K3Args k, int* nblocks_dev) {
   if (k.s.run_if && !*k.s.run_if) return;
   if (threadIdx.x == 0) {
     const int n = k.ncand[0];
-    nblocks_dev[0] = (k.ncand[1] || n > MFX_K3_CAP) ? -1 : n;   // -1: overflow, the full scan's per-block results are used
+    // overflow: 0 - the full scan starts its own list in the same arrays, with this word as its counter (SolveArgs::ncand)
+    nblocks_dev[0] = (k.ncand[1] || n > MFX_K3_CAP) ? 0 : n;
   }
 }

@@ -1,0 +1,177 @@
+"""The explicit-dictionary solver (csrc/solve_generic.hip: mfx_solve_exhaustive, the generic and fallback classes of
+fit_batch, mfx_solve_dense_dev behind the 2-D and weighted fits) on inputs whose best index tuples tie: the answer
+must be the reference's - its atom indices, first hit in its scan order.  The referee is the CPU oracle everywhere;
+problems and oracle answers come from tests/_ties_cases.py (guarded without a GPU in test_solver_ties_host.py)."""
+import ctypes as ct
+
+import numpy as np
+import pytest
+
+import _ties_cases as C
+import _wfit_ref as R
+from microstructure_fingerprinting_amd import _lib, engine
+from microstructure_fingerprinting_amd import mf_utils as mfu
+from oracle import oracle as orc
+
+pytestmark = pytest.mark.gpu
+
+
+def assert_bit_equal(got, ref, what):
+    """(w, sub, tot, min_obj, y_rec) of K' <= 3: same arithmetic, same order as the reference - bit for bit."""
+    assert np.array_equal(got[1], ref[1]), "%s: sub %s, oracle %s" % (what, got[1], ref[1])
+    assert np.array_equal(got[2], ref[2]), "%s: tot %s, oracle %s" % (what, got[2], ref[2])
+    assert np.array_equal(got[0], ref[0]), "%s: w %s, oracle %s" % (what, got[0], ref[0])
+    assert got[3] == ref[3], "%s: min_obj %r, oracle %r" % (what, got[3], ref[3])
+
+
+# ---- a. two bit-identical sub-dictionaries: (i, j) and (j, i) hold the same columns
+@pytest.mark.parametrize("sizes,M", C.ONE_BLOCK + C.SEVERAL_BLOCKS, ids=C.shape_id)
+def test_symmetric_subdictionaries(sizes, M):
+    bad = []
+    for seed, (A, y, ds, ref) in zip(C.SEEDS, C.symmetric_reference(sizes, M)):
+        got = mfu.solve_exhaustive_posweights(A, y, ds)
+        if not (np.array_equal(got[1], ref[1]) and np.array_equal(got[2], ref[2]) and np.array_equal(got[0], ref[0]) and got[3] == ref[3]):
+            bad.append((seed, tuple(got[1]), tuple(ref[1])))
+    print("%s: %d of %d problems differ from the oracle (seed, got, oracle): %s" % (sizes, len(bad), len(C.SEEDS), bad[:6]))
+    assert not bad
+
+
+# ---- b. the same through the fit paths: both fascicles along one direction
+@pytest.mark.parametrize("csf_on", [False, True])
+def test_identical_peaks_forced_generic_fit_batch(csf_on):
+    sch, dic, T, sig_csf = C.c2_model(16)
+    V = 24
+    peaks, Y = C.identical_peak_voxels(sch, T, V, 3, sig_csf if csf_on else None)
+    plan = mfu.init_PGSE_multishell_interp(dic, sch, R.Z).plan_for(sch)
+    Kv, cm, z = np.full(V, 2), np.full(V, csf_on), np.zeros(V, bool)
+    sc = sig_csf if csf_on else None
+    ref = orc.fit_batch(T, sch, Y, Kv, cm, z, peaks, 2, csf_on, False, sc, None, 0, nthreads=8)
+    _lib.lib().mfx_debug_set_force_generic(1)
+    try:
+        got = engine.fit_batch(plan, Y, Kv, cm, z, peaks, 2, csf_on, False, sc, None, 0)
+    finally:
+        _lib.lib().mfx_debug_set_force_generic(0)
+    bad = np.flatnonzero(np.any(got[:, 3:5] != ref[:, 3:5], axis=1))
+    print("csf %s: atom indices differ in %d of %d voxels" % (csf_on, bad.size, V))
+    assert bad.size == 0, "voxels %s: %s vs oracle %s" % (bad[:8], got[bad[:8], 3:5], ref[bad[:8], 3:5])
+    assert np.allclose(got, ref, rtol=1e-7, atol=1e-9)
+
+
+def test_identical_peaks_fit2d_with_csf():
+    import os
+    import test_fit2d_gpu as F2
+    sch = np.load(os.path.join(F2.G, "rot2d_cases.npz"))["syn2_sch"]
+    T = mfu.RotateAtom2DTables(F2.atoms(sch, 16, 14), sch, F2.Z, F2.DIFF)
+    sig_csf = F2.csf_signal(sch)
+    rng = np.random.default_rng(15)
+    V = 24
+    d = F2.random_dirs(rng, V, 0.3)
+    peaks = np.ascontiguousarray(np.hstack([d, d]))
+    Y = np.zeros((V, T.M))
+    for v in range(V):
+        ids = rng.choice(T.N, 2, replace=False)
+        cols = T.rotate_cols(peaks[v].reshape(2, 3), ids)
+        Y[v] = F2.rician(rng, 0.6 * cols[0] + 0.3 * cols[1] + 0.1 * sig_csf, snr=50.0)
+    got, st = engine.fit2d(T, Y, np.full(V, 2), np.ones(V, bool), peaks, 2, True, sig_csf)
+    assert np.all(st == 0)
+    ref = np.array([F2.oracle_row(T, Y[v], peaks[v].reshape(2, 3), True, sig_csf, 2, True) for v in range(V)])
+    print("fit2d: the oracle returns (larger, smaller) in %d of %d voxels" % (np.count_nonzero(ref[:, 3] > ref[:, 4]), V))
+    assert np.count_nonzero(ref[:, 3] > ref[:, 4]) >= 5                   # the test's power, on the oracle alone (measured: 13)
+    F2.assert_rows(got, ref, 2, "identical peaks + CSF")
+
+
+def test_identical_peaks_weighted_fit_with_csf():
+    sch, dic, T, sig_csf = C.c2_model(16)
+    V = 24
+    peaks, Y = C.identical_peak_voxels(sch, T, V, 4, sig_csf)
+    W = np.random.default_rng(16).uniform(0.05, 2.0, Y.shape)
+    plan = mfu.init_PGSE_multishell_interp(dic, sch, R.Z).plan_for(sch)
+    got, st = engine.fit_weighted(plan, Y, W, np.full(V, 2), np.ones(V, bool), peaks, 2, True, sig_csf)
+    assert np.all(st == 0)
+    ref = np.array([R.ref_row(T, sch, Y[v], W[v], peaks[v].reshape(2, 3), True, sig_csf, 2, True) for v in range(V)])
+    print("wfit: the oracle returns (larger, smaller) in %d of %d voxels" % (np.count_nonzero(ref[:, 3] > ref[:, 4]), V))
+    assert np.count_nonzero(ref[:, 3] > ref[:, 4]) >= 5                   # the test's power, on the oracle alone (measured: 10)
+    R.assert_rows(got, ref, 2, "identical peaks + CSF")
+
+
+# ---- c. exact ties, the reference's K' = 3 order (i3 -> i1 -> i2), and a K' = 2 tie across scan blocks
+@pytest.mark.parametrize("kind", ["within", "cross"])
+def test_k3_ties_follow_the_reference_order(kind):
+    for seed in range(8):
+        A, y, ds = C.k3_order_problem(kind, seed)
+        assert_bit_equal(mfu.solve_exhaustive_posweights(A, y, ds), orc.solve_exhaustive_posweights(A, y, ds), "%s %d" % (kind, seed))
+
+
+def test_k2_tie_across_scan_blocks():
+    A, y, ds = C.two_block_tie_problem()
+    ref = orc.solve_exhaustive_posweights(A, y, ds)
+    assert tuple(ref[1]) == (0, 5)
+    assert_bit_equal(mfu.solve_exhaustive_posweights(A, y, ds), ref, "two blocks")
+
+
+# ---- d. more exact ties than any candidate list holds
+def test_every_tuple_ties():
+    A, y, ds = C.all_tied_problem()
+    ref = orc.solve_exhaustive_posweights(A, y, ds)
+    assert tuple(ref[1]) == (0, 0) and ref[0][1] == 0.0
+    assert_bit_equal(mfu.solve_exhaustive_posweights(A, y, ds), ref, "2 250 000 ties")
+
+
+def test_every_triple_ties_beyond_the_screen_list():
+    """2 080 768 exactly tied triples: the three-dictionary screen (solve_k3.hip) lists more than its 2^20 entries and
+    hands over to the plain scan, whose own list overflows in turn."""
+    A, y, ds = C.all_tied_triples_problem()
+    ref = orc.solve_exhaustive_posweights(A, y, ds)
+    assert tuple(ref[1]) == (1, 0, 0) and np.all(ref[0] > 0.1)
+    assert_bit_equal(mfu.solve_exhaustive_posweights(A, y, ds), ref, "2 080 768 tied triples")
+
+
+# ---- e. the optimum beyond the scan's first sweep of 8192 x 256 tuples
+def test_optimum_in_the_second_grid_stride_trip():
+    A, y, ds = C.grid_stride_problem()
+    ref = orc.solve_exhaustive_posweights(A, y, ds)
+    assert tuple(ref[1]) == C.PLANTED
+    assert_bit_equal(mfu.solve_exhaustive_posweights(A, y, ds), ref, "grid stride")
+
+
+# ---- f. K' = 6, 7, 8 (the reference's _4up: SciPy's NNLS per tuple), and the limit
+@pytest.mark.parametrize("Kp", [6, 7, 8])
+def test_six_to_eight_subdictionaries(Kp):
+    A, y, sizes = C.many_dictionaries_problem(Kp)
+    gap, _ = C.top2_gap(A, y, sizes)
+    assert gap > 1e-6, "pick another seed: top-2 gap %.2e |y|^2" % gap          # no case is excused from the index check
+    ref = orc.solve_exhaustive_posweights(A, y, sizes)
+    got = mfu.solve_exhaustive_posweights(A, y, sizes)
+    assert np.array_equal(got[1], ref[1]) and np.array_equal(got[2], ref[2])
+    assert tuple(got[1]) == tuple(sizes - 1)
+    assert np.allclose(got[0], ref[0], rtol=1e-5, atol=1e-10)
+    assert np.isclose(got[3], ref[3], rtol=1e-5, atol=1e-10)
+    assert np.allclose(got[4], ref[4], rtol=1e-5, atol=1e-10)
+
+
+def test_nine_subdictionaries_are_refused():
+    A = np.abs(np.random.default_rng(9).standard_normal((12, 9))) + 0.2
+    with pytest.raises(NotImplementedError, match="at most 8 sub-dictionaries"):
+        mfu.solve_exhaustive_posweights(A, A[:, 0].copy(), np.ones(9, dtype=np.int64))
+
+
+# ---- g. a row stride larger than the number of columns
+def test_lda_larger_than_ntot():
+    rng = np.random.default_rng(10)
+    M, sizes, off = 14, np.array([9, 7, 1], dtype=np.int64), 3
+    Ntot = int(sizes.sum())
+    wide = np.abs(rng.standard_normal((M, Ntot + 8))) + 0.2
+    Ac = np.ascontiguousarray(wide[:, off:off + Ntot])
+    y = 0.5 * Ac[:, 4] + 0.3 * Ac[:, 9 + 2] + 0.2 * Ac[:, 16] + 0.01 * rng.standard_normal(M)
+    dp, lp = ct.POINTER(ct.c_double), ct.POINTER(ct.c_int64)
+
+    def call(ptr, lda):
+        w, sub, tot, obj, yrec = np.zeros(3), np.zeros(3, np.int64), np.zeros(3, np.int64), np.zeros(1), np.zeros(M)
+        _lib.check(_lib.lib().mfx_solve_exhaustive(ptr, lda, M, sizes.ctypes.data_as(lp), 3, y.ctypes.data_as(dp), w.ctypes.data_as(dp),
+                                                   sub.ctypes.data_as(lp), tot.ctypes.data_as(lp), obj.ctypes.data_as(dp), yrec.ctypes.data_as(dp)))
+        return w, sub, tot, obj[0], yrec
+    strided = call(ct.cast(wide.ctypes.data + 8 * off, dp), wide.shape[1])
+    dense = call(Ac.ctypes.data_as(dp), Ntot)
+    for s, d in zip(strided, dense):
+        assert np.array_equal(s, d)
+    assert_bit_equal(strided, orc.solve_exhaustive_posweights(Ac, y, sizes), "lda")
