@@ -49,6 +49,10 @@ PROFILE_EXPORTS = ["mfx_profile_abi_version", "mfx_profile_cut", "mfx_profile_ma
 # every symbol include/mfx_post.h declares (soft fits: posterior weights per atom; versioned on its own)
 POST_EXPORTS = ["mfx_post_abi_version", "mfx_post_max_atoms", "mfx_post_dev", "mfx_post"]
 
+# every symbol include/mfx_wsoft.h declares (profiles and soft fits of a weighted fit; versioned on its own)
+WSOFT_EXPORTS = ["mfx_wsoft_abi_version", "mfx_wsoft_max_atoms", "mfx_wpost_dev", "mfx_wpost", "mfx_wprofile_dev", "mfx_wprofile",
+                 "mfx_wpair_objectives_dev", "mfx_wpair_objectives"]
+
 
 class MfxError(RuntimeError):
     pass
@@ -168,6 +172,14 @@ def lib():
     L.mfx_post_max_atoms.argtypes = [vp, C.c_int]
     L.mfx_post_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int64, vp, vp, vp, vp]
     L.mfx_post.argtypes = [vp, dp, dp, C.c_int, C.c_int, dp, dp, dp, C.c_int64, dp, dp, ip]
+    L.mfx_wsoft_abi_version.restype = C.c_int
+    L.mfx_wsoft_max_atoms.argtypes = [vp, C.c_int, C.c_int]
+    L.mfx_wpost_dev.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int64, vp, vp, vp, vp]
+    L.mfx_wpost.argtypes = [vp, dp, dp, C.c_int64, dp, C.c_int, C.c_int, dp, dp, dp, C.c_int64, dp, dp, ip]
+    L.mfx_wprofile_dev.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int, C.c_int, vp, C.c_int64, vp, vp, vp]
+    L.mfx_wprofile.argtypes = [vp, dp, dp, C.c_int64, dp, C.c_int, C.c_int, dp, C.c_int64, dp, ip]
+    L.mfx_wpair_objectives_dev.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int, vp, C.c_int64, vp, vp]
+    L.mfx_wpair_objectives.argtypes = [vp, dp, dp, C.c_int64, dp, C.c_int, dp, C.c_int64, dp]
     _lib = L
     return L
 

@@ -28,8 +28,10 @@
 #include "mfx_host.h"
 #include "../../include/mfx_post.h"
 #include "../../include/mfx_profile.h"
+#include "../../include/mfx_wsoft.h"
 
 #include <algorithm>
+#include <type_traits>
 
 // profile.hip's MFX_PROFILE_CUT restated as a compile-time constant (the 8-wave form has no register to spare for a kernel
 // argument); the entry points refuse to launch unless it equals mfx_profile_cut()
@@ -53,6 +55,24 @@ struct PostArgs {
   double* log_sum;      // [V]
   int* status;          // [V]
 };
+// the weighted variants (include/mfx_wsoft.h) take two more arguments; the unweighted kernels keep PostArgs as it is
+struct PostArgsW : PostArgs {
+  const double* W;      // [V x M] (wstride = M) or [M] (wstride = 0)
+  long long wstride;
+};
+template <bool WGT> using PostArgsT = std::conditional_t<WGT, PostArgsW, PostArgs>;
+
+// weights of a voxel: 3 one is negative or not finite, 4 none is positive, 0 usable.  Every thread reads all M weights
+// (the address does not depend on the lane), so the answer is workgroup-uniform without a barrier.
+__device__ __forceinline__ int post_weights_status(const double* __restrict__ wv, int M) {
+  bool bad = false, pos = false;
+  for (int m = 0; m < M; ++m) {
+    const double w = wv[m];
+    bad |= !(w >= 0.0) || !(w <= 1.79769313486231570815e308);
+    pos |= w > 0.0;
+  }
+  return bad ? 3 : (pos ? 0 : 4);
+}
 
 // score s = ||y||^2 - F of one atom pair as the fraction p / q (profile.hip: prof_pair_frac)
 __device__ __forceinline__ void post_pair_frac(double cut, double A11, double A22, double A12, double Y1, double Y2, double p1,
@@ -107,9 +127,10 @@ __device__ __forceinline__ void post_nan_rows(const PostArgs& a, size_t vox, int
 }
 
 // NW waves per workgroup, TILES 16-atom column tiles per D_1 chunk, NBUF LDS buffers for the chunks: the profile's
-// configurations (profile.hip).
-template <int KSTEPS, bool BRACKET, bool CSF, int NW, int TILES, int NBUF>
-__global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void mfx_post_k2_kernel(PostArgs a) {
+// configurations (profile.hip).  WGT: rows scaled by s = sqrt(W) as they are generated (include/mfx_wsoft.h): one more
+// [MP] array in LDS, y and x stored scaled, every generated entry multiplied by s_w[m]; all else is the same code.
+template <int KSTEPS, bool BRACKET, bool CSF, int NW, int TILES, int NBUF, bool WGT = false>
+__global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void mfx_post_k2_kernel(PostArgsT<WGT> a) {
   constexpr int WG = NW * 64;
   constexpr int MP = KSTEPS * 4;              // padded measurement count
   constexpr int MPS = MP;                     // rows of one LDS D_1 tile
@@ -129,7 +150,8 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void mfx_post_k2_kernel(P
   double* sB = smem;                              // [NBUF][TILES][MPS][16]
   double* s_y = sB + NBUF * TILES * MPS * 16;     // [MP]
   double* s_x = s_y + MP;                         // [MP] (CSF)
-  double* s_t0 = s_x + (CSF ? MP : 0);            // [2][MP]
+  double* s_w = s_x + (CSF ? MP : 0);             // [MP] sqrt(W) (WGT)
+  double* s_t0 = s_w + (WGT ? MP : 0);            // [2][MP]
   double* s_t1 = s_t0 + 2 * MP;                   // [2][MP] (bracket only)
   double* s_tG = s_t1 + (BRACKET ? 2 * MP : 0);   // [MP]
   double* s_dG = s_tG + (BRACKET ? MP : 0);       // [MP]
@@ -156,10 +178,23 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void mfx_post_k2_kernel(P
     post_nan_rows(a, vox, 2, N, 1, tid, WG);
     return;
   }
+  if constexpr (WGT) {   // status 3 / 4 leave here, workgroup-uniform
+    if (const int code = post_weights_status(a.W + vox * a.wstride, M)) {
+      post_nan_rows(a, vox, 2, N, code, tid, WG);
+      return;
+    }
+  }
   const double iT = 1.0 / Tv;
   for (int m = tid; m < MP; m += WG) {
-    s_y[m] = (m < M) ? yv[m] : 0.0;
-    if constexpr (CSF) s_x[m] = (m < M) ? a.xc[m] : 0.0;
+    if constexpr (WGT) {
+      const double s = (m < M) ? sqrt(a.W[vox * a.wstride + m]) : 0.0;
+      s_w[m] = s;
+      s_y[m] = (m < M) ? s * yv[m] : 0.0;
+      if constexpr (CSF) s_x[m] = (m < M) ? s * a.xc[m] : 0.0;
+    } else {
+      s_y[m] = (m < M) ? yv[m] : 0.0;
+      if constexpr (CSF) s_x[m] = (m < M) ? a.xc[m] : 0.0;
+    }
   }
   for (int idx = tid; idx < 2 * MP; idx += WG) {
     const int k = idx / MP, m = idx - k * MP;
@@ -183,9 +218,11 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void mfx_post_k2_kernel(P
       RowDesc rd;
       rd.r0 = s_r0[k * MP + m]; rd.t0 = s_t0[k * MP + m];
       rd.r1 = s_r1[k * MP + m]; rd.t1 = s_t1[k * MP + m];
-      return mfx_eval_br(tab, ldn, rd, s_tG[m], s_dG[m], n);
+      if constexpr (WGT) return s_w[m] * mfx_eval_br(tab, ldn, rd, s_tG[m], s_dG[m], n);
+      else return mfx_eval_br(tab, ldn, rd, s_tG[m], s_dG[m], n);
     } else {
-      return mfx_eval(tab, ldn, s_r0[k * MP + m], s_t0[k * MP + m], n);
+      if constexpr (WGT) return s_w[m] * mfx_eval(tab, ldn, s_r0[k * MP + m], s_t0[k * MP + m], n);
+      else return mfx_eval(tab, ldn, s_r0[k * MP + m], s_t0[k * MP + m], n);
     }
   };
 
@@ -390,8 +427,8 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void mfx_post_k2_kernel(P
 }
 
 // K = 1: one workgroup per voxel, one thread per atom; the unnormalised t(i) wait in the output row for Z
-template <bool CSF>
-__global__ __launch_bounds__(POST_K1_WG) void mfx_post_k1_kernel(PostArgs a) {
+template <bool CSF, bool WGT = false>
+__global__ __launch_bounds__(POST_K1_WG) void mfx_post_k1_kernel(PostArgsT<WGT> a) {
   extern __shared__ double smem[];
   const int tid = threadIdx.x;
   const int M = a.P.M, N = a.T.N, ldn = a.T.ldn;
@@ -401,7 +438,8 @@ __global__ __launch_bounds__(POST_K1_WG) void mfx_post_k1_kernel(PostArgs a) {
   double* s_x = s_y + M;       // [M]
   double* s_t0 = s_x + M;      // [M]
   double* s_t1 = s_t0 + M;     // [M]
-  int* s_r0 = (int*)(s_t1 + M);  // [M]
+  double* s_w = s_t1 + M;      // [M] sqrt(W) (WGT)
+  int* s_r0 = (int*)(s_w + (WGT ? M : 0));  // [M]
   int* s_r1 = s_r0 + M;        // [M]
   int* s_flag = s_r1 + M;      // [2]
   const double* __restrict__ yv = a.Y + vox * M;
@@ -412,10 +450,23 @@ __global__ __launch_bounds__(POST_K1_WG) void mfx_post_k1_kernel(PostArgs a) {
     post_nan_rows(a, vox, 1, N, 1, tid, POST_K1_WG);
     return;
   }
+  if constexpr (WGT) {
+    if (const int code = post_weights_status(a.W + vox * a.wstride, M)) {
+      post_nan_rows(a, vox, 1, N, code, tid, POST_K1_WG);
+      return;
+    }
+  }
   const double iT = 1.0 / Tv;
   for (int m = tid; m < M; m += POST_K1_WG) {
-    s_y[m] = yv[m];
-    s_x[m] = CSF ? a.xc[m] : 0.0;
+    if constexpr (WGT) {
+      const double s = sqrt(a.W[vox * a.wstride + m]);
+      s_w[m] = s;
+      s_y[m] = s * yv[m];
+      s_x[m] = CSF ? s * a.xc[m] : 0.0;
+    } else {
+      s_y[m] = yv[m];
+      s_x[m] = CSF ? a.xc[m] : 0.0;
+    }
     const RowDesc rd = mfx_row_desc(a.T, a.P, m, pk[0], pk[1], pk[2]);
     s_r0[m] = rd.r0; s_t0[m] = rd.t0; s_r1[m] = rd.r1; s_t1[m] = rd.t1;
   }
@@ -435,7 +486,8 @@ __global__ __launch_bounds__(POST_K1_WG) void mfx_post_k1_kernel(PostArgs a) {
     for (int m = 0; m < M; ++m) {
       RowDesc rd;
       rd.r0 = s_r0[m]; rd.t0 = s_t0[m]; rd.r1 = s_r1[m]; rd.t1 = s_t1[m];
-      const double d = mfx_eval_br(a.T.tab, ldn, rd, a.P.tG[m], a.P.dG[m], n);
+      double d = mfx_eval_br(a.T.tab, ldn, rd, a.P.tG[m], a.P.dG[m], n);
+      if constexpr (WGT) d = s_w[m] * d;
       a2 += d * d;
       ay += s_y[m] * d;
       if constexpr (CSF) ax += s_x[m] * d;
@@ -468,20 +520,21 @@ __global__ __launch_bounds__(POST_K1_WG) void mfx_post_k1_kernel(PostArgs a) {
   }
 }
 
-size_t post_lds_bytes(int ksteps, bool bracket, bool csf, int NP, int nw, int tiles, int nbuf) {
+size_t post_lds_bytes(int ksteps, bool bracket, bool csf, int NP, int nw, int tiles, int nbuf, bool wgt = false) {
   const size_t MP = (size_t)ksteps * 4, MPS = MP, cw = 16 * (size_t)tiles;
-  const size_t dbl = (size_t)nbuf * tiles * MPS * 16 + MP + (csf ? MP : 0) + 2 * MP + (bracket ? 4 * MP : 0) +
+  const size_t dbl = (size_t)nbuf * tiles * MPS * 16 + MP + (csf ? MP : 0) + (wgt ? MP : 0) + 2 * MP + (bracket ? 4 * MP : 0) +
                      (size_t)NP * (4 + (csf ? 2 : 0) + 2) + 2 * nw * cw;
   const size_t ints = 2 * MP + (bracket ? 2 * MP : 0) + 2;
   return dbl * 8 + ints * 4;
 }
 
-template <int KS, bool BR, bool CSF, int NW, int TILES, int NBUF>
-int post_launch_t(const PostArgs& a, int nvox, hipStream_t st) {
-  const size_t lds = post_lds_bytes(KS, BR, CSF, a.T.ldn, NW, TILES, NBUF);
-  auto kern = mfx_post_k2_kernel<KS, BR, CSF, NW, TILES, NBUF>;
+template <int KS, bool BR, bool CSF, int NW, int TILES, int NBUF, bool WGT>
+int post_launch_t(const PostArgsW& a, int nvox, hipStream_t st) {
+  const size_t lds = post_lds_bytes(KS, BR, CSF, a.T.ldn, NW, TILES, NBUF, WGT);
+  auto kern = mfx_post_k2_kernel<KS, BR, CSF, NW, TILES, NBUF, WGT>;
+  const PostArgsT<WGT> ka = a;   // the unweighted kernels take the PostArgs part
   HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3(nvox), dim3(NW * 64), lds, st, a);
+  hipLaunchKernelGGL(kern, dim3(nvox), dim3(NW * 64), lds, st, ka);
   HIPCHK(hipGetLastError());
   return MFX_OK;
 }
@@ -490,42 +543,53 @@ int post_launch_t(const PostArgs& a, int nvox, hipStream_t st) {
 struct PostCfg { int ks, nw, tiles, nbuf; };
 constexpr PostCfg POST_CFG_200[3] = {{50, 8, 2, 2}, {50, 4, 1, 2}, {50, 4, 1, 1}};
 
-int post_pick(int M, bool br, bool csf, int NP) {   // index into POST_CFG_200, 3: the long-protocol form, -1: none fits
+int post_pick(int M, bool br, bool csf, int NP, bool wgt = false) {   // index into POST_CFG_200, 3: the long-protocol form, -1: none fits
   if (M <= 200) {
     for (int c = (csf || br) ? 1 : 0; c < 3; ++c)   // the CSF scan and bracketed rows take one wave per SIMD, as in the profile
-      if (post_lds_bytes(50, br, csf, NP, POST_CFG_200[c].nw, POST_CFG_200[c].tiles, POST_CFG_200[c].nbuf) <= POST_LDS_MAX) return c;
+      if (post_lds_bytes(50, br, csf, NP, POST_CFG_200[c].nw, POST_CFG_200[c].tiles, POST_CFG_200[c].nbuf, wgt) <= POST_LDS_MAX) return c;
     return -1;
   }
-  return post_lds_bytes(140, br, csf, NP, 4, 1, 1) <= POST_LDS_MAX ? 3 : -1;
+  return post_lds_bytes(140, br, csf, NP, 4, 1, 1, wgt) <= POST_LDS_MAX ? 3 : -1;
 }
 
-int post_max_atoms(int M, bool br, bool csf) {
+int post_max_atoms(int M, bool br, bool csf, bool wgt = false) {
   int n = 0;
-  while (n < (1 << 20) && post_pick(M, br, csf, n + 16) >= 0) n += 16;
+  while (n < (1 << 20) && post_pick(M, br, csf, n + 16, wgt) >= 0) n += 16;
   return n;
 }
 
-template <bool BR, bool CSF>
-int post_launch_cfg(int cfg, const PostArgs& a, int nvox, hipStream_t st) {
+template <bool BR, bool CSF, bool WGT>
+int post_launch_cfg(int cfg, const PostArgsW& a, int nvox, hipStream_t st) {
   switch (cfg) {
     case 0:
-      if constexpr (!CSF && !BR) return post_launch_t<50, BR, CSF, 8, 2, 2>(a, nvox, st);
+      if constexpr (!CSF && !BR) return post_launch_t<50, BR, CSF, 8, 2, 2, WGT>(a, nvox, st);
       return mfx_fail(MFX_ERR_ARG, "posterior: no such configuration");
-    case 1: return post_launch_t<50, BR, CSF, 4, 1, 2>(a, nvox, st);
-    case 2: return post_launch_t<50, BR, CSF, 4, 1, 1>(a, nvox, st);
-    default: return post_launch_t<140, BR, CSF, 4, 1, 1>(a, nvox, st);
+    case 1: return post_launch_t<50, BR, CSF, 4, 1, 2, WGT>(a, nvox, st);
+    case 2: return post_launch_t<50, BR, CSF, 4, 1, 1, WGT>(a, nvox, st);
+    default: return post_launch_t<140, BR, CSF, 4, 1, 1, WGT>(a, nvox, st);
   }
 }
 
-int post_launch_k2(const PostArgs& a, int nvox, bool csf, hipStream_t st, const char* fn) {
+template <bool WGT>
+int post_launch_k2(const PostArgsW& a, int nvox, bool csf, hipStream_t st, const char* fn) {
   const int M = a.P.M;
   const bool br = a.P.any_bracket != 0;
-  const int cfg = post_pick(M, br, csf, a.T.ldn);
+  const int cfg = post_pick(M, br, csf, a.T.ldn, WGT);
   if (cfg < 0)
     return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: N = %d atoms exceed the %d that fit in LDS for this protocol (M = %d)", fn, a.T.N,
-                    post_max_atoms(M, br, csf), M);
-  if (br) return csf ? post_launch_cfg<true, true>(cfg, a, nvox, st) : post_launch_cfg<true, false>(cfg, a, nvox, st);
-  return csf ? post_launch_cfg<false, true>(cfg, a, nvox, st) : post_launch_cfg<false, false>(cfg, a, nvox, st);
+                    post_max_atoms(M, br, csf, WGT), M);
+  if (br) return csf ? post_launch_cfg<true, true, WGT>(cfg, a, nvox, st) : post_launch_cfg<true, false, WGT>(cfg, a, nvox, st);
+  return csf ? post_launch_cfg<false, true, WGT>(cfg, a, nvox, st) : post_launch_cfg<false, false, WGT>(cfg, a, nvox, st);
+}
+
+template <bool WGT>
+int post_launch_k1(const PostArgsW& a, int nvox, bool csf, hipStream_t st) {
+  const size_t lds = (size_t)a.P.M * ((WGT ? 5 : 4) * sizeof(double) + 2 * sizeof(int)) + 2 * sizeof(int);
+  const PostArgsT<WGT> ka = a;
+  if (csf) hipLaunchKernelGGL((mfx_post_k1_kernel<true, WGT>), dim3((unsigned)nvox), dim3(POST_K1_WG), lds, st, ka);
+  else hipLaunchKernelGGL((mfx_post_k1_kernel<false, WGT>), dim3((unsigned)nvox), dim3(POST_K1_WG), lds, st, ka);
+  HIPCHK(hipGetLastError());
+  return MFX_OK;
 }
 
 const char* POST_NO_DEVICE = "no HIP device available (this library has no CPU path)";
@@ -549,26 +613,69 @@ int post_check_args(const char* fn, const mfx_plan* p, const void* Y, const void
   return MFX_OK;
 }
 
+// shared body of the device entry points; wgt: d_W [V x M] (w_stride = M) or [M] (w_stride = 0) scales the rows
 int post_enqueue(const char* fn, const mfx_plan* p, const double* d_Y, const double* d_peaks, int K, int csf_on,
                  const double* d_sig_csf, const double* d_T, const double* d_shift, int64_t V, double* d_w, double* d_log_sum,
-                 int32_t* d_status, void* stream) {
+                 int32_t* d_status, void* stream, bool wgt = false, const double* d_W = nullptr, int64_t w_stride = 0) {
   if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", POST_NO_DEVICE);
   if (int rc = post_check_args(fn, p, d_Y, d_peaks, K, csf_on, d_sig_csf, d_T, d_shift, V, d_w, d_log_sum, d_status)) return rc;
-  PostArgs a{};
+  PostArgsW a{};
   int device = 0;
   mfx_plan_view(p, &a.T, &a.P, &device);
   if (a.P.M > 560) return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: supports M <= 560 (got %d)", fn, a.P.M);
+  if (wgt && V > 0 && !d_W) return mfx_fail(MFX_ERR_ARG, "%s: bad argument", fn);
+  if (wgt && w_stride != 0 && w_stride != a.P.M)
+    return mfx_fail(MFX_ERR_ARG, "%s: w_stride should be M = %d or 0 (got %lld)", fn, a.P.M, (long long)w_stride);
   if (mfx_profile_cut() != MFX_POST_CUT) return mfx_fail(MFX_ERR_HIP, "%s: built with a cut other than the profile's", fn);
   if (V == 0) return MFX_OK;
   if (int rc = post_require_device(device)) return rc;
   a.Y = d_Y; a.peaks = d_peaks; a.xc = csf_on ? d_sig_csf : nullptr; a.temp = d_T; a.shift = d_shift;
   a.w = d_w; a.log_sum = d_log_sum; a.status = d_status;
+  a.W = d_W; a.wstride = w_stride;
   hipStream_t st = (hipStream_t)stream;
-  if (K == 2) return post_launch_k2(a, (int)V, csf_on != 0, st, fn);
-  const size_t lds = (size_t)a.P.M * (4 * sizeof(double) + 2 * sizeof(int)) + 2 * sizeof(int);
-  if (csf_on) hipLaunchKernelGGL(mfx_post_k1_kernel<true>, dim3((unsigned)V), dim3(POST_K1_WG), lds, st, a);
-  else hipLaunchKernelGGL(mfx_post_k1_kernel<false>, dim3((unsigned)V), dim3(POST_K1_WG), lds, st, a);
-  HIPCHK(hipGetLastError());
+  if (K == 2) return wgt ? post_launch_k2<true>(a, (int)V, csf_on != 0, st, fn) : post_launch_k2<false>(a, (int)V, csf_on != 0, st, fn);
+  return wgt ? post_launch_k1<true>(a, (int)V, csf_on != 0, st) : post_launch_k1<false>(a, (int)V, csf_on != 0, st);
+}
+
+// shared body of the host entry points
+int post_host(const char* fn, const mfx_plan* p, const double* Y, const double* peaks, int K, int csf_on, const double* sig_csf,
+              const double* T, const double* shift, int64_t V, double* w, double* log_sum, int32_t* status, bool wgt = false,
+              const double* W = nullptr, int64_t w_stride = 0) {
+  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", POST_NO_DEVICE);   // before the plan is looked at
+  if (int rc = post_check_args(fn, p, Y, peaks, K, csf_on, sig_csf, T, shift, V, w, log_sum, status)) return rc;
+  if (V == 0) return MFX_OK;
+  TablesDev Td;
+  PlanDev P;
+  int device = 0;
+  mfx_plan_view(p, &Td, &P, &device);
+  if (wgt && (!W || (w_stride != 0 && w_stride != P.M)))
+    return mfx_fail(MFX_ERR_ARG, "%s: W should be given with w_stride M = %d or 0 (got %lld)", fn, P.M, (long long)w_stride);
+  if (int rc = post_require_device(device)) return rc;
+  const size_t M = P.M, N = Td.N, nout = (size_t)V * K * N;
+  const size_t nW = wgt ? (w_stride ? (size_t)V * M : M) : 0;
+  DevMem dY, dpk, dx, dT, dsh, dw, dls, dst, dW;
+  HIPCHK(dY.alloc(sizeof(double) * V * M));
+  HIPCHK(dpk.alloc(sizeof(double) * V * 3 * K));
+  HIPCHK(dx.alloc(sizeof(double) * M));
+  HIPCHK(dT.alloc(sizeof(double) * V));
+  HIPCHK(dsh.alloc(sizeof(double) * V));
+  HIPCHK(dw.alloc(sizeof(double) * nout));
+  HIPCHK(dls.alloc(sizeof(double) * V));
+  HIPCHK(dst.alloc(sizeof(int32_t) * V));
+  HIPCHK(dW.alloc(sizeof(double) * nW));
+  HIPCHK(hipMemcpy(dY.p, Y, sizeof(double) * V * M, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dpk.p, peaks, sizeof(double) * V * 3 * K, hipMemcpyHostToDevice));
+  if (csf_on) HIPCHK(hipMemcpy(dx.p, sig_csf, sizeof(double) * M, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dT.p, T, sizeof(double) * V, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dsh.p, shift, sizeof(double) * V, hipMemcpyHostToDevice));
+  if (wgt) HIPCHK(hipMemcpy(dW.p, W, sizeof(double) * nW, hipMemcpyHostToDevice));
+  if (int rc = post_enqueue(fn, p, dY.as<double>(), dpk.as<double>(), K, csf_on, csf_on ? dx.as<double>() : nullptr, dT.as<double>(),
+                            dsh.as<double>(), V, dw.as<double>(), dls.as<double>(), dst.as<int32_t>(), nullptr, wgt,
+                            dW.as<double>(), w_stride)) return rc;
+  if (int rc = mfx_plan_status(p, nullptr)) return rc;   // waits; a direction that is not a unit vector
+  HIPCHK(hipMemcpy(w, dw.p, sizeof(double) * nout, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(log_sum, dls.p, sizeof(double) * V, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(status, dst.p, sizeof(int32_t) * V, hipMemcpyDeviceToHost));
   return MFX_OK;
 }
 
@@ -594,35 +701,34 @@ extern "C" int mfx_post_dev(const mfx_plan* p, const double* d_Y, const double* 
 
 extern "C" int mfx_post(const mfx_plan* p, const double* Y, const double* peaks, int K, int csf_on, const double* sig_csf,
                         const double* T, const double* shift, int64_t V, double* w, double* log_sum, int32_t* status) {
-  const char* fn = "mfx_post";
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", POST_NO_DEVICE);   // before the plan is looked at
-  if (int rc = post_check_args(fn, p, Y, peaks, K, csf_on, sig_csf, T, shift, V, w, log_sum, status)) return rc;
-  if (V == 0) return MFX_OK;
-  TablesDev Td;
+  return post_host("mfx_post", p, Y, peaks, K, csf_on, sig_csf, T, shift, V, w, log_sum, status);
+}
+
+// ---- include/mfx_wsoft.h: the weighted forms (the profile's are in profile.hip)
+int mfx_wsoft_prof_max_atoms(int M, bool br, bool csf, bool land);   // profile.hip
+
+extern "C" int mfx_wsoft_abi_version(void) { return 1; }
+
+extern "C" int mfx_wsoft_max_atoms(const mfx_plan* p, int csf_on, int what) {
+  if (!p || what < 0 || what > 2) return 0;
+  TablesDev T;
   PlanDev P;
   int device = 0;
-  mfx_plan_view(p, &Td, &P, &device);
-  if (int rc = post_require_device(device)) return rc;
-  const size_t M = P.M, N = Td.N, nout = (size_t)V * K * N;
-  DevMem dY, dpk, dx, dT, dsh, dw, dls, dst;
-  HIPCHK(dY.alloc(sizeof(double) * V * M));
-  HIPCHK(dpk.alloc(sizeof(double) * V * 3 * K));
-  HIPCHK(dx.alloc(sizeof(double) * M));
-  HIPCHK(dT.alloc(sizeof(double) * V));
-  HIPCHK(dsh.alloc(sizeof(double) * V));
-  HIPCHK(dw.alloc(sizeof(double) * nout));
-  HIPCHK(dls.alloc(sizeof(double) * V));
-  HIPCHK(dst.alloc(sizeof(int32_t) * V));
-  HIPCHK(hipMemcpy(dY.p, Y, sizeof(double) * V * M, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dpk.p, peaks, sizeof(double) * V * 3 * K, hipMemcpyHostToDevice));
-  if (csf_on) HIPCHK(hipMemcpy(dx.p, sig_csf, sizeof(double) * M, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dT.p, T, sizeof(double) * V, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dsh.p, shift, sizeof(double) * V, hipMemcpyHostToDevice));
-  if (int rc = post_enqueue(fn, p, dY.as<double>(), dpk.as<double>(), K, csf_on, csf_on ? dx.as<double>() : nullptr, dT.as<double>(),
-                            dsh.as<double>(), V, dw.as<double>(), dls.as<double>(), dst.as<int32_t>(), nullptr)) return rc;
-  if (int rc = mfx_plan_status(p, nullptr)) return rc;   // waits; a direction that is not a unit vector
-  HIPCHK(hipMemcpy(w, dw.p, sizeof(double) * nout, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(log_sum, dls.p, sizeof(double) * V, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(status, dst.p, sizeof(int32_t) * V, hipMemcpyDeviceToHost));
-  return MFX_OK;
+  mfx_plan_view(p, &T, &P, &device);
+  if (P.M > 560) return 0;
+  if (what == 0) return post_max_atoms(P.M, P.any_bracket != 0, csf_on != 0, true);
+  return mfx_wsoft_prof_max_atoms(P.M, P.any_bracket != 0, csf_on != 0, what == 2);
+}
+
+extern "C" int mfx_wpost_dev(const mfx_plan* p, const double* d_Y, const double* d_W, int64_t w_stride, const double* d_peaks, int K,
+                             int csf_on, const double* d_sig_csf, const double* d_T, const double* d_shift, int64_t V, double* d_w,
+                             double* d_log_sum, int32_t* d_status, void* stream) {
+  return post_enqueue("mfx_wpost_dev", p, d_Y, d_peaks, K, csf_on, d_sig_csf, d_T, d_shift, V, d_w, d_log_sum, d_status, stream, true,
+                      d_W, w_stride);
+}
+
+extern "C" int mfx_wpost(const mfx_plan* p, const double* Y, const double* W, int64_t w_stride, const double* peaks, int K, int csf_on,
+                         const double* sig_csf, const double* T, const double* shift, int64_t V, double* w, double* log_sum,
+                         int32_t* status) {
+  return post_host("mfx_wpost", p, Y, peaks, K, csf_on, sig_csf, T, shift, V, w, log_sum, status, true, W, w_stride);
 }

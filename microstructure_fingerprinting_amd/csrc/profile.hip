@@ -29,8 +29,10 @@
 // 16 M eps ||y||^2 / (1 - c^2).
 #include "mfx_host.h"
 #include "../../include/mfx_profile.h"
+#include "../../include/mfx_wsoft.h"
 
 #include <algorithm>
+#include <type_traits>
 
 #define MFX_PROFILE_CUT 1e-8   // pairs with 1 - c^2 <= this are scored as their better single atom (the fit's MFX_DET_REL)
 
@@ -48,6 +50,32 @@ struct ProfArgs {
   double* obj;          // profile: [V x K x N]; landscape: [V x N x N]
   int* partner;         // [V x K x N] or null
 };
+// the weighted variants (include/mfx_wsoft.h) take two more arguments; the unweighted kernels keep ProfArgs as it is
+struct ProfArgsW : ProfArgs {
+  const double* W;      // [V x M] (wstride = M) or [M] (wstride = 0)
+  long long wstride;
+};
+template <bool WGT> using ProfArgsT = std::conditional_t<WGT, ProfArgsW, ProfArgs>;
+
+// true when the voxel's weights are unusable (one negative or not finite, or none positive).  Every thread reads all M
+// weights (the address does not depend on the lane), so the answer is workgroup-uniform without a barrier.
+__device__ __forceinline__ bool prof_weights_unusable(const double* __restrict__ wv, int M) {
+  bool bad = false, pos = false;
+  for (int m = 0; m < M; ++m) {
+    const double w = wv[m];
+    bad |= !(w >= 0.0) || !(w <= 1.79769313486231570815e308);
+    pos |= w > 0.0;
+  }
+  return bad || !pos;
+}
+// such a voxel: NaN values, partner -1 (every thread of the workgroup takes part)
+__device__ __forceinline__ void prof_nan_rows(const ProfArgs& a, size_t vox, size_t n_out, int tid, int wg) {
+  const double nan = __builtin_nan("");
+  for (size_t n = tid; n < n_out; n += wg) {
+    a.obj[vox * n_out + n] = nan;
+    if (a.partner) a.partner[vox * n_out + n] = -1;
+  }
+}
 
 // score s = ||y||^2 - F of one atom pair as the fraction p / q (q > 0 whenever p > 0).  p1 = max(Y1, 0)^2 and
 // p2 likewise are the single atoms' numerators (denominators A11, A22).
@@ -97,8 +125,10 @@ __device__ __forceinline__ void prof_primed(double A, double Yv, double X, doubl
 // NW waves per workgroup, TILES 16-atom column tiles per D_1 chunk, NBUF LDS buffers for the chunks (as fit_k2.hip):
 // (8, 2, 2) for exact-G protocols of M <= 200 without CSF where it fits; (4, 1, 2) and (4, 1, 1) - one wave per SIMD with the whole register
 // file - for the CSF form (whose scan keeps twice the per-row operands), G-bracketed rows, larger dictionaries and long protocols.
-template <int KSTEPS, bool BRACKET, bool CSF, bool LAND, int NW, int TILES, int NBUF>
-__global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void mfx_profile_k2_kernel(ProfArgs a) {
+// WGT: rows scaled by s = sqrt(W) as they are generated (include/mfx_wsoft.h): one more [MP] array in LDS, y and x stored scaled,
+// every generated entry multiplied by s_w[m]; all else is the same code.
+template <int KSTEPS, bool BRACKET, bool CSF, bool LAND, int NW, int TILES, int NBUF, bool WGT = false>
+__global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void mfx_profile_k2_kernel(ProfArgsT<WGT> a) {
   constexpr int WG = NW * 64;
   constexpr int MP = KSTEPS * 4;              // padded measurement count
   constexpr int MPS = MP;                     // rows of one LDS D_1 tile
@@ -117,7 +147,8 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void mfx_profile_k2_kerne
   double* sB = smem;                              // [NBUF][TILES][MPS][16]
   double* s_y = sB + NBUF * TILES * MPS * 16;     // [MP]
   double* s_x = s_y + MP;                         // [MP] (CSF)
-  double* s_t0 = s_x + (CSF ? MP : 0);            // [2][MP]
+  double* s_w = s_x + (CSF ? MP : 0);             // [MP] sqrt(W) (WGT)
+  double* s_t0 = s_w + (WGT ? MP : 0);            // [2][MP]
   double* s_t1 = s_t0 + 2 * MP;                   // [2][MP] (bracket only)
   double* s_tG = s_t1 + (BRACKET ? 2 * MP : 0);   // [MP]
   double* s_dG = s_tG + (BRACKET ? MP : 0);       // [MP]
@@ -140,9 +171,23 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void mfx_profile_k2_kerne
   // ---- phase 0: y, x, descriptors
   const double* __restrict__ yv = a.Y + vox * M;
   const double* __restrict__ pk = a.peaks + vox * 6;
+  if constexpr (WGT) {   // unusable weights leave here, workgroup-uniform
+    if (prof_weights_unusable(a.W + vox * a.wstride, M)) {
+      if (tid < 2) mfx_check_dir(a.P, pk + 3 * tid, (int)vox);
+      prof_nan_rows(a, vox, (size_t)(LAND ? N : 2) * N, tid, WG);
+      return;
+    }
+  }
   for (int m = tid; m < MP; m += WG) {
-    s_y[m] = (m < M) ? yv[m] : 0.0;
-    if constexpr (CSF) s_x[m] = (m < M) ? a.xc[m] : 0.0;
+    if constexpr (WGT) {
+      const double s = (m < M) ? sqrt(a.W[vox * a.wstride + m]) : 0.0;
+      s_w[m] = s;
+      s_y[m] = (m < M) ? s * yv[m] : 0.0;
+      if constexpr (CSF) s_x[m] = (m < M) ? s * a.xc[m] : 0.0;
+    } else {
+      s_y[m] = (m < M) ? yv[m] : 0.0;
+      if constexpr (CSF) s_x[m] = (m < M) ? a.xc[m] : 0.0;
+    }
   }
   for (int idx = tid; idx < 2 * MP; idx += WG) {
     const int k = idx / MP, m = idx - k * MP;
@@ -168,9 +213,11 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void mfx_profile_k2_kerne
       RowDesc rd;
       rd.r0 = s_r0[k * MP + m]; rd.t0 = s_t0[k * MP + m];
       rd.r1 = s_r1[k * MP + m]; rd.t1 = s_t1[k * MP + m];
-      return mfx_eval_br(tab, ldn, rd, s_tG[m], s_dG[m], n);
+      if constexpr (WGT) return s_w[m] * mfx_eval_br(tab, ldn, rd, s_tG[m], s_dG[m], n);
+      else return mfx_eval_br(tab, ldn, rd, s_tG[m], s_dG[m], n);
     } else {
-      return mfx_eval(tab, ldn, s_r0[k * MP + m], s_t0[k * MP + m], n);
+      if constexpr (WGT) return s_w[m] * mfx_eval(tab, ldn, s_r0[k * MP + m], s_t0[k * MP + m], n);
+      else return mfx_eval(tab, ldn, s_r0[k * MP + m], s_t0[k * MP + m], n);
     }
   };
 
@@ -407,8 +454,8 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void mfx_profile_k2_kerne
 }
 
 // K = 1: one workgroup per voxel, one thread per atom
-template <bool CSF>
-__global__ __launch_bounds__(PROF_K1_WG) void mfx_profile_k1_kernel(ProfArgs a) {
+template <bool CSF, bool WGT = false>
+__global__ __launch_bounds__(PROF_K1_WG) void mfx_profile_k1_kernel(ProfArgsT<WGT> a) {
   extern __shared__ double smem[];
   const int tid = threadIdx.x;
   const int M = a.P.M, N = a.T.N, ldn = a.T.ldn;
@@ -417,13 +464,28 @@ __global__ __launch_bounds__(PROF_K1_WG) void mfx_profile_k1_kernel(ProfArgs a) 
   double* s_x = s_y + M;       // [M]
   double* s_t0 = s_x + M;      // [M]
   double* s_t1 = s_t0 + M;     // [M]
-  int* s_r0 = (int*)(s_t1 + M);  // [M]
+  double* s_w = s_t1 + M;      // [M] sqrt(W) (WGT)
+  int* s_r0 = (int*)(s_w + (WGT ? M : 0));  // [M]
   int* s_r1 = s_r0 + M;        // [M]
   const double* __restrict__ yv = a.Y + vox * M;
   const double* __restrict__ pk = a.peaks + vox * 3;
+  if constexpr (WGT) {
+    if (prof_weights_unusable(a.W + vox * a.wstride, M)) {
+      if (tid == 0) mfx_check_dir(a.P, pk, (int)vox);
+      prof_nan_rows(a, vox, (size_t)N, tid, PROF_K1_WG);
+      return;
+    }
+  }
   for (int m = tid; m < M; m += PROF_K1_WG) {
-    s_y[m] = yv[m];
-    s_x[m] = CSF ? a.xc[m] : 0.0;
+    if constexpr (WGT) {
+      const double s = sqrt(a.W[vox * a.wstride + m]);
+      s_w[m] = s;
+      s_y[m] = s * yv[m];
+      s_x[m] = CSF ? s * a.xc[m] : 0.0;
+    } else {
+      s_y[m] = yv[m];
+      s_x[m] = CSF ? a.xc[m] : 0.0;
+    }
     const RowDesc rd = mfx_row_desc(a.T, a.P, m, pk[0], pk[1], pk[2]);
     s_r0[m] = rd.r0; s_t0[m] = rd.t0; s_r1[m] = rd.r1; s_t1[m] = rd.t1;
   }
@@ -440,7 +502,8 @@ __global__ __launch_bounds__(PROF_K1_WG) void mfx_profile_k1_kernel(ProfArgs a) 
     for (int m = 0; m < M; ++m) {
       RowDesc rd;
       rd.r0 = s_r0[m]; rd.t0 = s_t0[m]; rd.r1 = s_r1[m]; rd.t1 = s_t1[m];
-      const double d = mfx_eval_br(a.T.tab, ldn, rd, a.P.tG[m], a.P.dG[m], n);
+      double d = mfx_eval_br(a.T.tab, ldn, rd, a.P.tG[m], a.P.dG[m], n);
+      if constexpr (WGT) d = s_w[m] * d;
       a2 += d * d;
       ay += s_y[m] * d;
       if constexpr (CSF) ax += s_x[m] * d;
@@ -458,20 +521,21 @@ __global__ __launch_bounds__(PROF_K1_WG) void mfx_profile_k1_kernel(ProfArgs a) 
   }
 }
 
-size_t prof_lds_bytes(int ksteps, bool bracket, bool csf, bool land, int NP, int nw, int tiles, int nbuf) {
+size_t prof_lds_bytes(int ksteps, bool bracket, bool csf, bool land, int NP, int nw, int tiles, int nbuf, bool wgt = false) {
   const size_t MP = (size_t)ksteps * 4, MPS = MP, cw = 16 * (size_t)tiles;
-  const size_t dbl = (size_t)nbuf * tiles * MPS * 16 + MP + (csf ? MP : 0) + 2 * MP + (bracket ? 4 * MP : 0) +
+  const size_t dbl = (size_t)nbuf * tiles * MPS * 16 + MP + (csf ? MP : 0) + (wgt ? MP : 0) + 2 * MP + (bracket ? 4 * MP : 0) +
                      (size_t)NP * (4 + (csf ? 2 : 0) + (land ? 0 : 2)) + (land ? 0 : 2 * 2 * nw * cw);
   const size_t ints = 2 * MP + (bracket ? 2 * MP : 0) + (land ? 0 : (size_t)NP + 2 * nw * cw);
   return dbl * 8 + ints * 4;
 }
 
-template <int KS, bool BR, bool CSF, bool LAND, int NW, int TILES, int NBUF>
-int prof_launch_t(const ProfArgs& a, int nvox, hipStream_t st) {
-  const size_t lds = prof_lds_bytes(KS, BR, CSF, LAND, a.T.ldn, NW, TILES, NBUF);
-  auto kern = mfx_profile_k2_kernel<KS, BR, CSF, LAND, NW, TILES, NBUF>;
+template <int KS, bool BR, bool CSF, bool LAND, int NW, int TILES, int NBUF, bool WGT>
+int prof_launch_t(const ProfArgsW& a, int nvox, hipStream_t st) {
+  const size_t lds = prof_lds_bytes(KS, BR, CSF, LAND, a.T.ldn, NW, TILES, NBUF, WGT);
+  auto kern = mfx_profile_k2_kernel<KS, BR, CSF, LAND, NW, TILES, NBUF, WGT>;
+  const ProfArgsT<WGT> ka = a;   // the unweighted kernels take the ProfArgs part
   HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3(nvox), dim3(NW * 64), lds, st, a);
+  hipLaunchKernelGGL(kern, dim3(nvox), dim3(NW * 64), lds, st, ka);
   HIPCHK(hipGetLastError());
   return MFX_OK;
 }
@@ -480,47 +544,58 @@ int prof_launch_t(const ProfArgs& a, int nvox, hipStream_t st) {
 struct ProfCfg { int ks, nw, tiles, nbuf; };
 constexpr ProfCfg PROF_CFG_200[3] = {{50, 8, 2, 2}, {50, 4, 1, 2}, {50, 4, 1, 1}};
 
-int prof_pick(int M, bool br, bool csf, bool land, int NP) {   // index into PROF_CFG_200, 3: the long-protocol form, -1: none fits
+int prof_pick(int M, bool br, bool csf, bool land, int NP, bool wgt = false) {   // index into PROF_CFG_200, 3: the long-protocol form, -1: none fits
   if (M <= 200) {
     for (int c = (csf || br) ? 1 : 0; c < 3; ++c)   // the CSF scan and bracketed rows do not fit the 256 registers of the 8-wave form
-      if (prof_lds_bytes(50, br, csf, land, NP, PROF_CFG_200[c].nw, PROF_CFG_200[c].tiles, PROF_CFG_200[c].nbuf) <= PROF_LDS_MAX) return c;
+      if (prof_lds_bytes(50, br, csf, land, NP, PROF_CFG_200[c].nw, PROF_CFG_200[c].tiles, PROF_CFG_200[c].nbuf, wgt) <= PROF_LDS_MAX) return c;
     return -1;
   }
-  return prof_lds_bytes(140, br, csf, land, NP, 4, 1, 1) <= PROF_LDS_MAX ? 3 : -1;
+  return prof_lds_bytes(140, br, csf, land, NP, 4, 1, 1, wgt) <= PROF_LDS_MAX ? 3 : -1;
 }
 
-int prof_max_atoms(int M, bool br, bool csf, bool land) {
+int prof_max_atoms(int M, bool br, bool csf, bool land, bool wgt = false) {
   int n = 0;
-  while (n < (1 << 20) && prof_pick(M, br, csf, land, n + 16) >= 0) n += 16;
+  while (n < (1 << 20) && prof_pick(M, br, csf, land, n + 16, wgt) >= 0) n += 16;
   return n;
 }
 
-template <bool BR, bool CSF, bool LAND>
-int prof_launch_cfg(int cfg, const ProfArgs& a, int nvox, hipStream_t st) {
+template <bool BR, bool CSF, bool LAND, bool WGT>
+int prof_launch_cfg(int cfg, const ProfArgsW& a, int nvox, hipStream_t st) {
   switch (cfg) {
     case 0:
-      if constexpr (!CSF && !BR) return prof_launch_t<50, BR, CSF, LAND, 8, 2, 2>(a, nvox, st);
+      if constexpr (!CSF && !BR) return prof_launch_t<50, BR, CSF, LAND, 8, 2, 2, WGT>(a, nvox, st);
       return mfx_fail(MFX_ERR_ARG, "profile: no such configuration");
-    case 1: return prof_launch_t<50, BR, CSF, LAND, 4, 1, 2>(a, nvox, st);
-    case 2: return prof_launch_t<50, BR, CSF, LAND, 4, 1, 1>(a, nvox, st);
-    default: return prof_launch_t<140, BR, CSF, LAND, 4, 1, 1>(a, nvox, st);
+    case 1: return prof_launch_t<50, BR, CSF, LAND, 4, 1, 2, WGT>(a, nvox, st);
+    case 2: return prof_launch_t<50, BR, CSF, LAND, 4, 1, 1, WGT>(a, nvox, st);
+    default: return prof_launch_t<140, BR, CSF, LAND, 4, 1, 1, WGT>(a, nvox, st);
   }
 }
 
-int prof_launch_k2(const ProfArgs& a, int nvox, bool csf, bool land, hipStream_t st, const char* fn) {
+template <bool WGT>
+int prof_launch_k2(const ProfArgsW& a, int nvox, bool csf, bool land, hipStream_t st, const char* fn) {
   const int M = a.P.M;
   const bool br = a.P.any_bracket != 0;
   if (M > 560) return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: the K = 2 kernel supports M <= 560 (got %d)", fn, M);
-  const int cfg = prof_pick(M, br, csf, land, a.T.ldn);
+  const int cfg = prof_pick(M, br, csf, land, a.T.ldn, WGT);
   if (cfg < 0)
     return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: N = %d atoms exceed the %d that fit in LDS for this protocol (M = %d)", fn, a.T.N,
-                    prof_max_atoms(M, br, csf, land), M);
+                    prof_max_atoms(M, br, csf, land, WGT), M);
   if (br) {
-    if (csf) return land ? prof_launch_cfg<true, true, true>(cfg, a, nvox, st) : prof_launch_cfg<true, true, false>(cfg, a, nvox, st);
-    return land ? prof_launch_cfg<true, false, true>(cfg, a, nvox, st) : prof_launch_cfg<true, false, false>(cfg, a, nvox, st);
+    if (csf) return land ? prof_launch_cfg<true, true, true, WGT>(cfg, a, nvox, st) : prof_launch_cfg<true, true, false, WGT>(cfg, a, nvox, st);
+    return land ? prof_launch_cfg<true, false, true, WGT>(cfg, a, nvox, st) : prof_launch_cfg<true, false, false, WGT>(cfg, a, nvox, st);
   }
-  if (csf) return land ? prof_launch_cfg<false, true, true>(cfg, a, nvox, st) : prof_launch_cfg<false, true, false>(cfg, a, nvox, st);
-  return land ? prof_launch_cfg<false, false, true>(cfg, a, nvox, st) : prof_launch_cfg<false, false, false>(cfg, a, nvox, st);
+  if (csf) return land ? prof_launch_cfg<false, true, true, WGT>(cfg, a, nvox, st) : prof_launch_cfg<false, true, false, WGT>(cfg, a, nvox, st);
+  return land ? prof_launch_cfg<false, false, true, WGT>(cfg, a, nvox, st) : prof_launch_cfg<false, false, false, WGT>(cfg, a, nvox, st);
+}
+
+template <bool WGT>
+int prof_launch_k1(const ProfArgsW& a, int nvox, bool csf, hipStream_t st) {
+  const size_t lds = (size_t)a.P.M * ((WGT ? 5 : 4) * sizeof(double) + 2 * sizeof(int));
+  const ProfArgsT<WGT> ka = a;
+  if (csf) hipLaunchKernelGGL((mfx_profile_k1_kernel<true, WGT>), dim3((unsigned)nvox), dim3(PROF_K1_WG), lds, st, ka);
+  else hipLaunchKernelGGL((mfx_profile_k1_kernel<false, WGT>), dim3((unsigned)nvox), dim3(PROF_K1_WG), lds, st, ka);
+  HIPCHK(hipGetLastError());
+  return MFX_OK;
 }
 
 const char* NO_DEVICE = "no HIP device available (this library has no CPU path)";
@@ -543,49 +618,58 @@ int prof_check_args(const char* fn, const mfx_plan* p, const void* Y, const void
   return MFX_OK;
 }
 
-// shared body of the two device entry points
+// shared body of the device entry points; wgt: d_W [V x M] (w_stride = M) or [M] (w_stride = 0) scales the rows
 int prof_enqueue(const char* fn, const mfx_plan* p, const double* d_Y, const double* d_peaks, int K, int csf_on,
-                 const double* d_sig_csf, int64_t V, double* d_obj, int32_t* d_partner, bool land, void* stream) {
+                 const double* d_sig_csf, int64_t V, double* d_obj, int32_t* d_partner, bool land, void* stream, bool wgt = false,
+                 const double* d_W = nullptr, int64_t w_stride = 0) {
   if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
   if (int rc = prof_check_args(fn, p, d_Y, d_peaks, K, csf_on, d_sig_csf, V, d_obj)) return rc;
-  ProfArgs a{};
+  ProfArgsW a{};
   int device = 0;
   mfx_plan_view(p, &a.T, &a.P, &device);
   if (a.P.M > 560) return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: supports M <= 560 (got %d)", fn, a.P.M);
+  if (wgt && V > 0 && !d_W) return mfx_fail(MFX_ERR_ARG, "%s: bad argument", fn);
+  if (wgt && w_stride != 0 && w_stride != a.P.M)
+    return mfx_fail(MFX_ERR_ARG, "%s: w_stride should be M = %d or 0 (got %lld)", fn, a.P.M, (long long)w_stride);
   if (V == 0) return MFX_OK;
   if (int rc = prof_require_device(device)) return rc;
   a.Y = d_Y; a.peaks = d_peaks; a.xc = csf_on ? d_sig_csf : nullptr; a.obj = d_obj; a.partner = d_partner;
+  a.W = d_W; a.wstride = w_stride;
   hipStream_t st = (hipStream_t)stream;
-  if (K == 2) return prof_launch_k2(a, (int)V, csf_on != 0, land, st, fn);
-  const size_t lds = (size_t)a.P.M * (4 * sizeof(double) + 2 * sizeof(int));
-  if (csf_on) hipLaunchKernelGGL(mfx_profile_k1_kernel<true>, dim3((unsigned)V), dim3(PROF_K1_WG), lds, st, a);
-  else hipLaunchKernelGGL(mfx_profile_k1_kernel<false>, dim3((unsigned)V), dim3(PROF_K1_WG), lds, st, a);
-  HIPCHK(hipGetLastError());
-  return MFX_OK;
+  if (K == 2)
+    return wgt ? prof_launch_k2<true>(a, (int)V, csf_on != 0, land, st, fn) : prof_launch_k2<false>(a, (int)V, csf_on != 0, land, st, fn);
+  return wgt ? prof_launch_k1<true>(a, (int)V, csf_on != 0, st) : prof_launch_k1<false>(a, (int)V, csf_on != 0, st);
 }
 
-// shared body of the two host entry points: out [V x rows x N] with rows = K (profile) or N (landscape)
+// shared body of the host entry points: out [V x rows x N] with rows = K (profile) or N (landscape)
 int prof_host(const char* fn, const mfx_plan* p, const double* Y, const double* peaks, int K, int csf_on, const double* sig_csf,
-              int64_t V, double* obj, int32_t* partner, bool land) {
+              int64_t V, double* obj, int32_t* partner, bool land, bool wgt = false, const double* W = nullptr, int64_t w_stride = 0) {
+  if (wgt && mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);   // before the plan is looked at
   if (int rc = prof_check_args(fn, p, Y, peaks, K, csf_on, sig_csf, V, obj)) return rc;
   if (V == 0) return MFX_OK;
   TablesDev T;
   PlanDev P;
   int device = 0;
   mfx_plan_view(p, &T, &P, &device);
+  if (wgt && (!W || (w_stride != 0 && w_stride != P.M)))
+    return mfx_fail(MFX_ERR_ARG, "%s: W should be given with w_stride M = %d or 0 (got %lld)", fn, P.M, (long long)w_stride);
   if (int rc = prof_require_device(device)) return rc;
   const size_t M = P.M, N = T.N, nout = (size_t)V * (land ? N : (size_t)K) * N;
-  DevMem dY, dpk, dx, dobj, dpar;
+  const size_t nW = wgt ? (w_stride ? (size_t)V * M : M) : 0;
+  DevMem dY, dpk, dx, dobj, dpar, dW;
   HIPCHK(dY.alloc(sizeof(double) * V * M));
   HIPCHK(dpk.alloc(sizeof(double) * V * 3 * K));
   HIPCHK(dx.alloc(sizeof(double) * M));
   HIPCHK(dobj.alloc(sizeof(double) * nout));
   HIPCHK(dpar.alloc(partner ? sizeof(int32_t) * nout : 0));
+  HIPCHK(dW.alloc(sizeof(double) * nW));
   HIPCHK(hipMemcpy(dY.p, Y, sizeof(double) * V * M, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(dpk.p, peaks, sizeof(double) * V * 3 * K, hipMemcpyHostToDevice));
   if (csf_on) HIPCHK(hipMemcpy(dx.p, sig_csf, sizeof(double) * M, hipMemcpyHostToDevice));
+  if (wgt) HIPCHK(hipMemcpy(dW.p, W, sizeof(double) * nW, hipMemcpyHostToDevice));
   if (int rc = prof_enqueue(fn, p, dY.as<double>(), dpk.as<double>(), K, csf_on, csf_on ? dx.as<double>() : nullptr, V,
-                            dobj.as<double>(), partner ? dpar.as<int32_t>() : nullptr, land, nullptr)) return rc;
+                            dobj.as<double>(), partner ? dpar.as<int32_t>() : nullptr, land, nullptr, wgt, dW.as<double>(),
+                            w_stride)) return rc;
   if (int rc = mfx_plan_status(p, nullptr)) return rc;   // waits; a direction that is not a unit vector
   HIPCHK(hipMemcpy(obj, dobj.p, sizeof(double) * nout, hipMemcpyDeviceToHost));
   if (partner) HIPCHK(hipMemcpy(partner, dpar.p, sizeof(int32_t) * nout, hipMemcpyDeviceToHost));
@@ -626,4 +710,28 @@ extern "C" int mfx_pair_objectives_dev(const mfx_plan* p, const double* d_Y, con
 extern "C" int mfx_pair_objectives(const mfx_plan* p, const double* Y, const double* peaks, int csf_on, const double* sig_csf,
                                    int64_t V, double* out) {
   return prof_host("mfx_pair_objectives", p, Y, peaks, 2, csf_on, sig_csf, V, out, nullptr, true);
+}
+
+// ---- include/mfx_wsoft.h: the weighted forms (the posterior's are in posterior.hip)
+int mfx_wsoft_prof_max_atoms(int M, bool br, bool csf, bool land) { return prof_max_atoms(M, br, csf, land, true); }
+
+extern "C" int mfx_wprofile_dev(const mfx_plan* p, const double* d_Y, const double* d_W, int64_t w_stride, const double* d_peaks, int K,
+                                int csf_on, const double* d_sig_csf, int64_t V, double* d_obj, int32_t* d_partner, void* stream) {
+  return prof_enqueue("mfx_wprofile_dev", p, d_Y, d_peaks, K, csf_on, d_sig_csf, V, d_obj, d_partner, false, stream, true, d_W, w_stride);
+}
+
+extern "C" int mfx_wprofile(const mfx_plan* p, const double* Y, const double* W, int64_t w_stride, const double* peaks, int K,
+                            int csf_on, const double* sig_csf, int64_t V, double* obj, int32_t* partner) {
+  return prof_host("mfx_wprofile", p, Y, peaks, K, csf_on, sig_csf, V, obj, partner, false, true, W, w_stride);
+}
+
+extern "C" int mfx_wpair_objectives_dev(const mfx_plan* p, const double* d_Y, const double* d_W, int64_t w_stride, const double* d_peaks,
+                                        int csf_on, const double* d_sig_csf, int64_t V, double* d_out, void* stream) {
+  return prof_enqueue("mfx_wpair_objectives_dev", p, d_Y, d_peaks, 2, csf_on, d_sig_csf, V, d_out, nullptr, true, stream, true, d_W,
+                      w_stride);
+}
+
+extern "C" int mfx_wpair_objectives(const mfx_plan* p, const double* Y, const double* W, int64_t w_stride, const double* peaks,
+                                    int csf_on, const double* sig_csf, int64_t V, double* out) {
+  return prof_host("mfx_wpair_objectives", p, Y, peaks, 2, csf_on, sig_csf, V, out, nullptr, true, true, W, w_stride);
 }

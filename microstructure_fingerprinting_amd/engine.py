@@ -430,43 +430,70 @@ def _profile_shapes(plan, y_shape, pk_shape, K, csf_on, M_csf):
     return V
 
 
-def profile_dev(plan, d_Y, d_peaks, K, csf_on=False, d_sig_csf=None, partner=False, out=None):
+def _soft_weights(plan, V, w_shape):
+    """w_stride of measurement weights given to a profile or posterior entry point (before any device call): M for
+    [V x M], 0 for one [M] vector shared by the voxels."""
+    if tuple(w_shape) == (plan.M,):
+        return 0
+    if tuple(w_shape) == (V, plan.M):
+        return plan.M
+    raise ValueError("weights should have shape (%d, %d) or (%d,), got %s (%d voxels)"
+                     % (V, plan.M, plan.M, tuple(w_shape), V))
+
+
+def profile_dev(plan, d_Y, d_peaks, K, csf_on=False, d_sig_csf=None, partner=False, out=None, d_W=None):
     """Objective profiles on the device (mfx_profile_dev) for torch CUDA float64 tensors of ONE voxel class (every
     voxel: K fascicles, CSF or not, no EAR): ``obj`` [V x K x N], obj[v, k, i] the smallest sum of squared residuals
     any partner atom reaches beside atom i of fascicle k (include/mfx_profile.h has the definitions), and with
     ``partner=True`` also the int32 tensor of the arg-min partners (-1 for K = 1).  Enqueues on torch's current
-    stream and returns without waiting; a direction that is not a unit vector flags the plan's status word."""
+    stream and returns without waiting; a direction that is not a unit vector flags the plan's status word.
+    ``d_W``: measurement weights [V x M] or [M] of a weighted fit (mfx_wprofile_dev, include/mfx_wsoft.h): the profile of
+    sum_m W (y_m - model_m)^2; a voxel whose weights are unusable (one negative or not finite, none positive) gets NaN
+    values and partner -1."""
     import torch
-    assert d_Y.is_cuda and d_Y.dtype == torch.float64 and d_Y.is_contiguous()
-    assert d_peaks.is_cuda and d_peaks.dtype == torch.float64 and d_peaks.is_contiguous()
-    if csf_on:
-        if d_sig_csf is None:
-            raise ValueError("csf_on without d_sig_csf")
-        assert d_sig_csf.is_cuda and d_sig_csf.dtype == torch.float64 and d_sig_csf.is_contiguous()
+    if csf_on and d_sig_csf is None:
+        raise ValueError("csf_on without d_sig_csf")
     V = _profile_shapes(plan, d_Y.shape, d_peaks.shape, K, csf_on, d_sig_csf.numel() if csf_on else None)
+    w_stride = _soft_weights(plan, V, d_W.shape) if d_W is not None else None
+    for t in (d_Y, d_peaks) + ((d_sig_csf,) if csf_on else ()) + ((d_W,) if d_W is not None else ()):
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
     N = plan.tables.N
     if out is None:
         out = torch.empty((V, int(K), N), dtype=torch.float64, device=d_Y.device)
     assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (V, int(K), N)
     part = torch.empty((V, int(K), N), dtype=torch.int32, device=d_Y.device) if partner else None
     st = torch.cuda.current_stream(d_Y.device).cuda_stream
-    L.check(L.lib().mfx_profile_dev(plan.handle(), d_Y.data_ptr(), d_peaks.data_ptr(), int(K), int(bool(csf_on)),
-                                    d_sig_csf.data_ptr() if csf_on else None, V, out.data_ptr(),
-                                    part.data_ptr() if partner else None, st))
+    if d_W is None:
+        L.check(L.lib().mfx_profile_dev(plan.handle(), d_Y.data_ptr(), d_peaks.data_ptr(), int(K), int(bool(csf_on)),
+                                        d_sig_csf.data_ptr() if csf_on else None, V, out.data_ptr(),
+                                        part.data_ptr() if partner else None, st))
+    else:
+        L.check(L.lib().mfx_wprofile_dev(plan.handle(), d_Y.data_ptr(), d_W.data_ptr(), w_stride, d_peaks.data_ptr(), int(K),
+                                         int(bool(csf_on)), d_sig_csf.data_ptr() if csf_on else None, V, out.data_ptr(),
+                                         part.data_ptr() if partner else None, st))
     return (out, part) if partner else out
 
 
-def pair_objectives_dev(plan, d_Y, d_peaks, csf_on=False, d_sig_csf=None):
-    """The objective of every atom pair (mfx_pair_objectives_dev): [V x N x N] torch tensor, two-fascicle voxels."""
+def pair_objectives_dev(plan, d_Y, d_peaks, csf_on=False, d_sig_csf=None, d_W=None):
+    """The objective of every atom pair (mfx_pair_objectives_dev): [V x N x N] torch tensor, two-fascicle voxels.
+    ``d_W``: measurement weights [V x M] or [M] (mfx_wpair_objectives_dev)."""
     import torch
-    assert d_Y.is_cuda and d_Y.dtype == torch.float64 and d_Y.is_contiguous()
-    assert d_peaks.is_cuda and d_peaks.dtype == torch.float64 and d_peaks.is_contiguous()
+    if csf_on and d_sig_csf is None:
+        raise ValueError("csf_on without d_sig_csf")
     V = _profile_shapes(plan, d_Y.shape, d_peaks.shape, 2, csf_on, d_sig_csf.numel() if csf_on else None)
+    w_stride = _soft_weights(plan, V, d_W.shape) if d_W is not None else None
+    for t in (d_Y, d_peaks) + ((d_sig_csf,) if csf_on else ()) + ((d_W,) if d_W is not None else ()):
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
     N = plan.tables.N
     out = torch.empty((V, N, N), dtype=torch.float64, device=d_Y.device)
     st = torch.cuda.current_stream(d_Y.device).cuda_stream
-    L.check(L.lib().mfx_pair_objectives_dev(plan.handle(), d_Y.data_ptr(), d_peaks.data_ptr(), int(bool(csf_on)),
-                                            d_sig_csf.data_ptr() if csf_on else None, V, out.data_ptr(), st))
+    if d_W is None:
+        L.check(L.lib().mfx_pair_objectives_dev(plan.handle(), d_Y.data_ptr(), d_peaks.data_ptr(), int(bool(csf_on)),
+                                                d_sig_csf.data_ptr() if csf_on else None, V, out.data_ptr(), st))
+    else:
+        L.check(L.lib().mfx_wpair_objectives_dev(plan.handle(), d_Y.data_ptr(), d_W.data_ptr(), w_stride, d_peaks.data_ptr(),
+                                                 int(bool(csf_on)), d_sig_csf.data_ptr() if csf_on else None, V,
+                                                 out.data_ptr(), st))
     return out
 
 
@@ -491,12 +518,14 @@ def profile_classes(K, csf, ear, maxfasc):
     return bins, int(V - np.count_nonzero(ok))
 
 
-def profile(plan, Y, K, csf, peaks, maxfasc, csf_on, sig_csf, partner=False, ear=None):
+def profile(plan, Y, K, csf, peaks, maxfasc, csf_on, sig_csf, partner=False, ear=None, W=None):
     """Objective profiles of a mixed set of voxels on NumPy arrays (mfx_profile, one call per voxel class): Y [V x M],
     per-voxel K, csf (and ear) flags, peaks [V x 3 maxfasc] as for ``fit_batch``.  Returns ``(obj, partner,
     n_unsupported)``: obj [V x maxfasc x N] float64 (rows of absent fascicles and of the voxel classes out of scope -
     EAR, no fascicle, three fascicles - are NaN), partner [V x maxfasc x N] int32 (-1 where there is none) or None,
-    and the number of voxels out of scope."""
+    and the number of voxels out of scope.  ``W``: measurement weights [V x M] or [M] of a weighted fit (mfx_wprofile):
+    the profile of sum_m W (y_m - model_m)^2, whose minimum is ``fit_weighted``'s MSE * sum_m W; a voxel whose weights are
+    unusable (one negative or not finite, none positive) gets NaN values and partner -1."""
     Y = L.f64c(Y)
     maxfasc = int(maxfasc)
     if Y.ndim != 2 or Y.shape[1] != plan.M:
@@ -504,6 +533,9 @@ def profile(plan, Y, K, csf, peaks, maxfasc, csf_on, sig_csf, partner=False, ear
     V = Y.shape[0]
     if np.asarray(K).shape != (V,):
         raise ValueError("K should have one entry per voxel")
+    if W is not None:
+        W = L.f64c(W)
+        w_stride = _soft_weights(plan, V, W.shape)
     pk = L.f64c(peaks).reshape(V, -1) if maxfasc > 0 else np.zeros((V, 0))
     if pk.shape[1] != 3 * maxfasc:
         raise ValueError("peaks should have %d columns" % (3 * maxfasc))
@@ -520,27 +552,40 @@ def profile(plan, Y, K, csf, peaks, maxfasc, csf_on, sig_csf, partner=False, ear
         Yc, pc = np.ascontiguousarray(Y[ix]), np.ascontiguousarray(pk[ix, :3 * k])
         o = np.zeros((ix.size, k, N))
         p = np.zeros((ix.size, k, N), dtype=np.int32) if partner else None
-        L.check(L.lib().mfx_profile(plan.handle(), L.dptr(Yc), L.dptr(pc), k, int(c), L.dptr(sc) if c else None, ix.size,
-                                    L.dptr(o), L.iptr(p) if partner else None))
+        if W is None:
+            L.check(L.lib().mfx_profile(plan.handle(), L.dptr(Yc), L.dptr(pc), k, int(c), L.dptr(sc) if c else None, ix.size,
+                                        L.dptr(o), L.iptr(p) if partner else None))
+        else:
+            Wc = np.ascontiguousarray(W[ix]) if w_stride else W
+            L.check(L.lib().mfx_wprofile(plan.handle(), L.dptr(Yc), L.dptr(Wc), w_stride, L.dptr(pc), k, int(c),
+                                         L.dptr(sc) if c else None, ix.size, L.dptr(o), L.iptr(p) if partner else None))
         obj[ix, :k] = o
         if partner:
             par[ix, :k] = p
     return obj, par, n_uns
 
 
-def pair_objectives(plan, Y, peaks, csf_on=False, sig_csf=None):
+def pair_objectives(plan, Y, peaks, csf_on=False, sig_csf=None, W=None):
     """The objective of every atom pair of two-fascicle voxels (mfx_pair_objectives): Y [V x M], peaks [V x 6] ->
-    [V x N x N], out[v, i, j] = min over non-negative weights of |y - w1 D_0[:, i] - w2 D_1[:, j] (- wx sig_csf)|^2."""
+    [V x N x N], out[v, i, j] = min over non-negative weights of |y - w1 D_0[:, i] - w2 D_1[:, j] (- wx sig_csf)|^2.
+    ``W``: measurement weights [V x M] or [M] (mfx_wpair_objectives): the weighted sum of squares."""
     Y = L.f64c(Y)
     pk = L.f64c(peaks)
     sc = L.f64c(sig_csf).reshape(-1) if csf_on else None
     if csf_on and sig_csf is None:
         raise ValueError("csf_on without sig_csf")
     V = _profile_shapes(plan, Y.shape, pk.shape, 2, csf_on, sc.shape[0] if sc is not None else None)
+    if W is not None:
+        W = L.f64c(W)
+        w_stride = _soft_weights(plan, V, W.shape)
     N = plan.tables.N
     out = np.zeros((V, N, N))
-    L.check(L.lib().mfx_pair_objectives(plan.handle(), L.dptr(Y), L.dptr(pk), int(bool(csf_on)),
-                                        L.dptr(sc) if sc is not None else None, V, L.dptr(out)))
+    if W is None:
+        L.check(L.lib().mfx_pair_objectives(plan.handle(), L.dptr(Y), L.dptr(pk), int(bool(csf_on)),
+                                            L.dptr(sc) if sc is not None else None, V, L.dptr(out)))
+    else:
+        L.check(L.lib().mfx_wpair_objectives(plan.handle(), L.dptr(Y), L.dptr(W), w_stride, L.dptr(pk), int(bool(csf_on)),
+                                             L.dptr(sc) if sc is not None else None, V, L.dptr(out)))
     return out
 
 
@@ -554,13 +599,15 @@ def _per_voxel(x, V, what):
     return np.ascontiguousarray(x)
 
 
-def posterior_dev(plan, d_Y, d_peaks, K, T, shift, csf_on=False, d_sig_csf=None):
+def posterior_dev(plan, d_Y, d_peaks, K, T, shift, csf_on=False, d_sig_csf=None, d_W=None):
     """Soft fit on the device (mfx_post_dev) for torch CUDA float64 tensors of ONE voxel class (every voxel: K
     fascicles, CSF or not, no EAR).  ``T`` [V] the temperatures (2 sigma^2), ``shift`` [V] a value near each voxel's
     smallest objective (include/mfx_post.h has the definitions).  Returns ``(w, log_sum, status)``: w [V x K x N]
     the posterior weight of every atom of each fascicle, log_sum [V] = log sum exp(-F / T), status [V] int32 (0 ok,
     1 unusable T or shift, 2 unusable shift: an exponent above 700 or a vanishing sum; rows of such voxels are NaN).
-    Enqueues on torch's current stream and returns without waiting."""
+    Enqueues on torch's current stream and returns without waiting.  ``d_W``: measurement weights [V x M] or [M] of a
+    weighted fit (mfx_wpost_dev, include/mfx_wsoft.h): F is the weighted sum of squares and T = 2 sigma^2 means that
+    measurement m has noise variance sigma^2 / W_m; status 3: a weight is negative or not finite, 4: none is positive."""
     import torch
     if csf_on and d_sig_csf is None:
         raise ValueError("csf_on without d_sig_csf")
@@ -568,27 +615,35 @@ def posterior_dev(plan, d_Y, d_peaks, K, T, shift, csf_on=False, d_sig_csf=None)
     for t, what in ((T, "T"), (shift, "shift")):
         if not torch.is_tensor(t) or tuple(t.shape) != (V,):
             raise ValueError("%s should be a tensor with one entry per voxel (%d)" % (what, V))
-    for t in (d_Y, d_peaks, T, shift) + ((d_sig_csf,) if csf_on else ()):
+    w_stride = _soft_weights(plan, V, d_W.shape) if d_W is not None else None
+    for t in (d_Y, d_peaks, T, shift) + ((d_sig_csf,) if csf_on else ()) + ((d_W,) if d_W is not None else ()):
         assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
     N = plan.tables.N
     w = torch.empty((V, int(K), N), dtype=torch.float64, device=d_Y.device)
     log_sum = torch.empty((V,), dtype=torch.float64, device=d_Y.device)
     status = torch.empty((V,), dtype=torch.int32, device=d_Y.device)
     st = torch.cuda.current_stream(d_Y.device).cuda_stream
-    L.check(L.lib().mfx_post_dev(plan.handle(), d_Y.data_ptr(), d_peaks.data_ptr(), int(K), int(bool(csf_on)),
-                                 d_sig_csf.data_ptr() if csf_on else None, T.data_ptr(), shift.data_ptr(), V, w.data_ptr(),
-                                 log_sum.data_ptr(), status.data_ptr(), st))
+    if d_W is None:
+        L.check(L.lib().mfx_post_dev(plan.handle(), d_Y.data_ptr(), d_peaks.data_ptr(), int(K), int(bool(csf_on)),
+                                     d_sig_csf.data_ptr() if csf_on else None, T.data_ptr(), shift.data_ptr(), V, w.data_ptr(),
+                                     log_sum.data_ptr(), status.data_ptr(), st))
+    else:
+        L.check(L.lib().mfx_wpost_dev(plan.handle(), d_Y.data_ptr(), d_W.data_ptr(), w_stride, d_peaks.data_ptr(), int(K),
+                                      int(bool(csf_on)), d_sig_csf.data_ptr() if csf_on else None, T.data_ptr(),
+                                      shift.data_ptr(), V, w.data_ptr(), log_sum.data_ptr(), status.data_ptr(), st))
     return w, log_sum, status
 
 
-def posterior(plan, Y, K, csf, peaks, maxfasc, csf_on, sig_csf, sigma, shift=None, ear=None):
+def posterior(plan, Y, K, csf, peaks, maxfasc, csf_on, sig_csf, sigma, shift=None, ear=None, W=None):
     """Soft fit of a mixed set of voxels on NumPy arrays (mfx_post, one call per voxel class): Y [V x M], per-voxel K,
     csf (and ear) flags, peaks [V x 3 maxfasc] as for ``fit_batch``; ``sigma`` the noise standard deviation (a scalar
     or [V]; the temperature is 2 sigma^2); ``shift`` [V] a value near each voxel's smallest objective, default: MSE * M
     of the library's own fit of the same voxels.  Returns ``(w, log_sum, status, n_unsupported)``: w [V x maxfasc x N]
     float64, log_sum [V], status [V] int32 (the codes of include/mfx_post.h, and -1 for a voxel class out of scope: EAR,
     no fascicle, three fascicles - counted in n_unsupported); rows of absent fascicles and of voxels with a non-zero
-    status are NaN."""
+    status are NaN.  ``W``: measurement weights [V x M] or [M] of a weighted fit (mfx_wpost): F is the weighted sum of
+    squares, ``sigma`` the noise of a measurement of weight 1 (measurement m has variance sigma^2 / W_m), the default
+    shift ``fit_weighted``'s objective MSE * sum_m W; status 3: a weight is negative or not finite, 4: none is positive."""
     Y = L.f64c(Y)
     maxfasc = int(maxfasc)
     if Y.ndim != 2 or Y.shape[1] != plan.M:
@@ -596,6 +651,9 @@ def posterior(plan, Y, K, csf, peaks, maxfasc, csf_on, sig_csf, sigma, shift=Non
     V = Y.shape[0]
     if np.asarray(K).shape != (V,):
         raise ValueError("K should have one entry per voxel")
+    if W is not None:
+        W = L.f64c(W)
+        w_stride = _soft_weights(plan, V, W.shape)
     pk = L.f64c(peaks).reshape(V, -1) if maxfasc > 0 else np.zeros((V, 0))
     if pk.shape[1] != 3 * maxfasc:
         raise ValueError("peaks should have %d columns" % (3 * maxfasc))
@@ -613,15 +671,28 @@ def posterior(plan, Y, K, csf, peaks, maxfasc, csf_on, sig_csf, sigma, shift=Non
     status = np.full(V, -1, dtype=np.int32)
     for k, c, ix in bins:
         Yc, pc = np.ascontiguousarray(Y[ix]), np.ascontiguousarray(pk[ix, :3 * k])
-        if sh is None:
+        if W is not None:
+            Wc = np.ascontiguousarray(W[ix]) if w_stride else W
+        if sh is not None:
+            shc = np.ascontiguousarray(sh[ix])
+        elif W is None:
             fit = fit_batch(plan, Yc, np.full(ix.size, k), np.full(ix.size, c), None, pc, k, c, False, sc if c else None)
             shc = np.ascontiguousarray(fit[:, -2] * plan.M)
-        else:
-            shc = np.ascontiguousarray(sh[ix])
+        else:   # the weighted fit's objective; a voxel with unusable weights has a NaN row there and status 3 / 4 here
+            fit, fst = fit_weighted(plan, Yc, Wc, np.full(ix.size, k), np.full(ix.size, c), pc, k, c, sc if c else None)
+            with np.errstate(invalid='ignore', over='ignore'):
+                sw = np.sum(Wc, axis=-1) if w_stride else np.full(ix.size, np.sum(Wc))
+                shc = np.ascontiguousarray(fit[:, -2] * sw)
+            shc[fst != 0] = 0.0
         Tc = np.ascontiguousarray(2.0 * sig[ix] ** 2)
         wc, lc, stc = np.zeros((ix.size, k, N)), np.zeros(ix.size), np.zeros(ix.size, dtype=np.int32)
-        L.check(L.lib().mfx_post(plan.handle(), L.dptr(Yc), L.dptr(pc), k, int(c), L.dptr(sc) if c else None, L.dptr(Tc),
-                                 L.dptr(shc), ix.size, L.dptr(wc), L.dptr(lc), L.iptr(stc)))
+        if W is None:
+            L.check(L.lib().mfx_post(plan.handle(), L.dptr(Yc), L.dptr(pc), k, int(c), L.dptr(sc) if c else None, L.dptr(Tc),
+                                     L.dptr(shc), ix.size, L.dptr(wc), L.dptr(lc), L.iptr(stc)))
+        else:
+            L.check(L.lib().mfx_wpost(plan.handle(), L.dptr(Yc), L.dptr(Wc), w_stride, L.dptr(pc), k, int(c),
+                                      L.dptr(sc) if c else None, L.dptr(Tc), L.dptr(shc), ix.size, L.dptr(wc), L.dptr(lc),
+                                      L.iptr(stc)))
         w[ix, :k], log_sum[ix], status[ix] = wc, lc, stc
     return w, log_sum, status, n_uns
 

@@ -637,18 +637,29 @@ class MFModelFit():
     def _data_rows(self, data_arr, idx):
         return np.ascontiguousarray(data_arr[np.unravel_index(idx, self._grid)], dtype=np.float64)
 
+    def _weights_rows(self, vox):
+        """The measurement weights of the ROI positions ``vox`` for the profile and posterior entry points: None for an
+        unweighted fit, the shared [M] vector as it is, else the voxels' rows [n x M]."""
+        W = self.weights_roi
+        if W is None:
+            return None
+        W = np.asarray(W, dtype=np.float64)
+        return W if W.ndim == 1 else np.ascontiguousarray(W[vox])
+
     def profile(self, data, voxels=None, partner=False):
         """What the exhaustive search saw beside its arg-min: for every atom of each fascicle the smallest sum of
         squared residuals any partner atom reaches with it (``engine.profile``).  ``data`` as given to ``fit``;
         ``voxels``: positions in the ROI (default: all of it - [ROI x maxfasc x N] float64 on the host, meant for
         regions, not for brains: see ``interval``).  Returns an object with ``obj`` [n x maxfasc x N], ``partner``
         (int32, -1 where there is none; None unless asked for), ``n_unsupported`` (voxels with EAR or without a
-        fascicle: their rows are NaN) and ``by_property(name)`` -> (levels, obj_by_level)."""
+        fascicle: their rows are NaN) and ``by_property(name)`` -> (levels, obj_by_level).  After a weighted fit the
+        values are those of the weighted objective sum_m W (y_m - model_m)^2 (``weights_roi``), so that the smallest one
+        is the fit's own MSE * sum_m W."""
         data_arr, plan, sig_csf = self._profile_setup(data)
         vox = np.arange(self._roi_flat.shape[0]) if voxels is None else np.asarray(voxels, dtype=np.int64).reshape(-1)
         obj, par, n_uns = engine.profile(plan, self._data_rows(data_arr, self._roi_flat[vox]), self._numfasc_roi[vox],
                                          self._csf_roi[vox], self._peaks_roi[vox], self._nf, self._csf_on, sig_csf,
-                                         partner=partner, ear=self._ear_roi[vox])
+                                         partner=partner, ear=self._ear_roi[vox], W=self._weights_rows(vox))
         return ObjectiveProfile(obj, par, n_uns, vox, self._props)
 
     def interval(self, data, name, rel=0.0, delta=0.0):
@@ -668,6 +679,8 @@ class MFModelFit():
         dev = torch.device("cuda", plan.tables.device)
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         d_csf = t(sig_csf) if self._csf_on else None
+        shared_W = self.weights_roi is not None and np.ndim(self.weights_roi) == 1
+        d_Ws = t(self._weights_rows(None)) if shared_W else None   # a shared [M] vector is passed once
         lo, hi = np.full((R, nf), np.nan), np.full((R, nf), np.nan)
         cnt = np.zeros((R, nf), dtype=np.int64)
         chunk = max(1, int(self.PROFILE_BYTES // (8 * 2 * N)))
@@ -676,8 +689,9 @@ class MFModelFit():
             for k, c, ix in bins:
                 for i0 in range(0, ix.size, chunk):
                     sub = ix[i0:i0 + chunk]
+                    d_W = d_Ws if (shared_W or self.weights_roi is None) else t(self._weights_rows(sub))
                     obj = engine.profile_dev(plan, t(self._data_rows(data_arr, self._roi_flat[sub])),
-                                             t(self._peaks_roi[sub, :3 * k]), k, c, d_csf if c else None)
+                                             t(self._peaks_roi[sub, :3 * k]), k, c, d_csf if c else None, d_W=d_W)
                     l, h, n = mfu.profile_interval(obj, self._props[name], rel, delta)
                     L.check(L.lib().mfx_plan_status(plan.handle(), torch.cuda.current_stream(dev).cuda_stream))
                     lo[sub, :k], hi[sub, :k], cnt[sub, :k] = l.cpu().numpy(), h.cpu().numpy(), n.cpu().numpy()
@@ -690,15 +704,23 @@ class MFModelFit():
 
     def _posterior_inputs(self, sigma, vox):
         """(sigma [n], shift [n]) of the ROI positions ``vox``: the shift is the fit's own objective MSE * M; ``sigma``
-        None means sigma^2 = MSE * M / (M - K - csf), the residual variance of the fit."""
-        if self.weights_roi is not None:
-            raise NotImplementedError("posterior weights of a weighted fit are not served")
+        None means sigma^2 = MSE * M / (M - K - csf), the residual variance of the fit.  After a weighted fit the
+        objective is MSE * sum_m W and M becomes the number of positive weights; no degree of freedom left gives NaN."""
         M = self._pgse_scheme.shape[0]
-        sse = np.asarray(self.params_in_mask[vox, -2], dtype=np.float64) * M
+        W = self._weights_rows(vox)
+        if W is None:
+            sse = np.asarray(self.params_in_mask[vox, -2], dtype=np.float64) * M
+            n_pos = M
+        else:
+            with np.errstate(invalid='ignore', over='ignore'):
+                sse = np.asarray(self.params_in_mask[vox, -2], dtype=np.float64) * np.sum(W, axis=-1)
+                n_pos = np.count_nonzero(W > 0, axis=-1).astype(np.float64)
         if sigma is None:
-            dof = M - self._numfasc_roi[vox].astype(np.float64) - self._csf_roi[vox].astype(np.float64)
+            dof = n_pos - self._numfasc_roi[vox].astype(np.float64) - self._csf_roi[vox].astype(np.float64)
             with np.errstate(invalid='ignore', divide='ignore'):
                 sig = np.sqrt(sse / dof)
+            if W is not None:
+                sig = np.where(dof > 0, sig, np.nan)
         else:
             sig = np.asarray(sigma, dtype=np.float64)
             if sig.ndim == 0:
@@ -716,14 +738,18 @@ class MFModelFit():
         as given to ``fit``; ``sigma``: the noise standard deviation, a scalar or one value per ROI voxel (default: the
         fit's residual variance, sigma^2 = MSE * M / (M - K - csf) per voxel; a voxel with MSE = 0 gets status 1);
         ``voxels``: positions in the ROI (default: all of it - [ROI x maxfasc x N] float64 on the host, meant for
-        regions: see ``posterior_moments``).  Returns a ``Posterior``."""
+        regions: see ``posterior_moments``).  Returns a ``Posterior``.  After a weighted fit F is the weighted objective
+        (``weights_roi``) and ``sigma`` the noise of a measurement of weight 1: measurement m has variance sigma^2 / W_m;
+        the default is sigma^2 = MSE * sum_m W / (n_pos - K - csf) with n_pos the number of positive weights."""
         data_arr, plan, sig_csf = self._profile_setup(data)
         vox = np.arange(self._roi_flat.shape[0]) if voxels is None else np.asarray(voxels, dtype=np.int64).reshape(-1)
         sig, shift = self._posterior_inputs(sigma, vox)
+        W = self._weights_rows(vox)
         w, log_sum, status, n_uns = engine.posterior(plan, self._data_rows(data_arr, self._roi_flat[vox]),
                                                      self._numfasc_roi[vox], self._csf_roi[vox], self._peaks_roi[vox],
-                                                     self._nf, self._csf_on, sig_csf, sig, shift=shift, ear=self._ear_roi[vox])
-        return Posterior(w, log_sum, status, n_uns, vox, self._props, self._numfasc_roi[vox], 2.0 * sig ** 2, plan.M)
+                                                     self._nf, self._csf_on, sig_csf, sig, shift=shift, ear=self._ear_roi[vox],
+                                                     W=W)
+        return Posterior(w, log_sum, status, n_uns, vox, self._props, self._numfasc_roi[vox], 2.0 * sig ** 2, plan.M, W=W)
 
     def posterior_moments(self, data, name, sigma=None):
         """Posterior mean and standard deviation of the fascicle property ``name`` (one of the dictionary's
@@ -742,6 +768,8 @@ class MFModelFit():
         dev = torch.device("cuda", plan.tables.device)
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         d_csf = t(sig_csf) if self._csf_on else None
+        shared_W = self.weights_roi is not None and np.ndim(self.weights_roi) == 1
+        d_Ws = t(self._weights_rows(None)) if shared_W else None   # a shared [M] vector is passed once
         mean, std = np.full((R, nf), np.nan), np.full((R, nf), np.nan)
         chunk = max(1, int(self.PROFILE_BYTES // (8 * 2 * N)))
         bins, _ = engine.profile_classes(self._numfasc_roi, self._csf_roi, self._ear_roi, nf)
@@ -749,9 +777,10 @@ class MFModelFit():
             for k, c, ix in bins:
                 for i0 in range(0, ix.size, chunk):
                     sub = ix[i0:i0 + chunk]
+                    d_W = d_Ws if (shared_W or self.weights_roi is None) else t(self._weights_rows(sub))
                     w, _, _ = engine.posterior_dev(plan, t(self._data_rows(data_arr, self._roi_flat[sub])),
                                                    t(self._peaks_roi[sub, :3 * k]), k, t(2.0 * sig[sub] ** 2), t(shift[sub]),
-                                                   c, d_csf if c else None)
+                                                   c, d_csf if c else None, d_W=d_W)
                     m, sd = mfu.posterior_moments(w, self._props[name])
                     L.check(L.lib().mfx_plan_status(plan.handle(), torch.cuda.current_stream(dev).cuda_stream))
                     mean[sub, :k], std[sub, :k] = m.cpu().numpy(), sd.cpu().numpy()
@@ -795,12 +824,22 @@ class ObjectiveProfile(object):
 class Posterior(object):
     """Result of ``MFModelFit.posterior``: ``weights`` [n x maxfasc x N] (each present fascicle's row sums to 1; NaN rows
     for absent fascicles, voxels out of scope and voxels with a non-zero status), ``log_sum`` [n] = log of the sum of
-    exp(-F / T) over all atoms (pairs), ``status`` [n] (0 ok, 1 unusable temperature, 2 unusable shift, -1 a voxel class out of scope),
-    ``n_unsupported``, ``voxels`` (the ROI positions the rows stand for)."""
+    exp(-F / T) over all atoms (pairs), ``status`` [n] (0 ok, 1 unusable temperature, 2 unusable shift, 3 a measurement
+    weight that is negative or not finite, 4 no positive measurement weight - the last two after a weighted fit only -,
+    -1 a voxel class out of scope), ``n_unsupported``, ``voxels`` (the ROI positions the rows stand for).  ``W``: the
+    measurement weights [n x M] or [M] the posterior was computed with (None: an unweighted fit)."""
 
-    def __init__(self, weights, log_sum, status, n_unsupported, voxels, props, numfasc, T, M):
+    def __init__(self, weights, log_sum, status, n_unsupported, voxels, props, numfasc, T, M, W=None):
         self.weights, self.log_sum, self.status, self.n_unsupported, self.voxels = weights, log_sum, status, n_unsupported, voxels
         self._props, self._K, self._T, self._M = props, np.asarray(numfasc, dtype=np.float64), np.asarray(T, dtype=np.float64), int(M)
+        # of a weighted posterior: the number of positive weights and the sum of their logarithms, per voxel (or shared)
+        self._n_pos, self._sum_log_w = None, None
+        if W is not None:
+            W = np.asarray(W, dtype=np.float64)
+            pos = W > 0
+            self._n_pos = np.count_nonzero(pos, axis=-1).astype(np.float64)
+            with np.errstate(invalid='ignore', divide='ignore'):
+                self._sum_log_w = np.sum(np.log(np.where(pos, W, 1.0)), axis=-1)
 
     def _values(self, name):
         if name not in self._props:
@@ -827,10 +866,14 @@ class Posterior(object):
         """log_sum - K log N - (M / 2) log(pi T) per voxel: the log of the Gaussian likelihood averaged over a uniform
         prior on the K-tuples of atoms, which lets a one-fascicle and a two-fascicle explanation of the same voxel be
         compared.  It is a profile-likelihood evidence: the fascicle (and CSF) weights are maximised for every tuple,
-        not integrated over.  NaN where log_sum is."""
+        not integrated over.  NaN where log_sum is.  For a weighted posterior measurement m has variance T / (2 W_m), and
+        the expression is log_sum - K log N - (n_pos / 2) log(pi T) + (1 / 2) sum over the positive weights of log W_m,
+        n_pos their number: the same value when every weight is 1."""
         N = self.weights.shape[-1]
         with np.errstate(invalid='ignore', divide='ignore'):
-            return self.log_sum - self._K * np.log(N) - 0.5 * self._M * np.log(np.pi * self._T)
+            if self._n_pos is None:
+                return self.log_sum - self._K * np.log(N) - 0.5 * self._M * np.log(np.pi * self._T)
+            return self.log_sum - self._K * np.log(N) - 0.5 * self._n_pos * np.log(np.pi * self._T) + 0.5 * self._sum_log_w
 
 
 def _nifti_stem(output_basename):
