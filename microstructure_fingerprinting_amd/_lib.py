@@ -53,6 +53,10 @@ POST_EXPORTS = ["mfx_post_abi_version", "mfx_post_max_atoms", "mfx_post_dev", "m
 WSOFT_EXPORTS = ["mfx_wsoft_abi_version", "mfx_wsoft_max_atoms", "mfx_wpost_dev", "mfx_wpost", "mfx_wprofile_dev", "mfx_wprofile",
                  "mfx_wpair_objectives_dev", "mfx_wpair_objectives"]
 
+# every symbol include/mfx_soft2d.h declares (soft fits and objective profiles of 2-D protocols; versioned on its own)
+SOFT2D_EXPORTS = ["mfx_soft2d_abi_version", "mfx_soft2d_max_atoms", "mfx_post2d_dev", "mfx_post2d", "mfx_profile2d_dev",
+                  "mfx_profile2d"]
+
 
 class MfxError(RuntimeError):
     pass
@@ -180,6 +184,12 @@ def lib():
     L.mfx_wprofile.argtypes = [vp, dp, dp, C.c_int64, dp, C.c_int, C.c_int, dp, C.c_int64, dp, ip]
     L.mfx_wpair_objectives_dev.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int, vp, C.c_int64, vp, vp]
     L.mfx_wpair_objectives.argtypes = [vp, dp, dp, C.c_int64, dp, C.c_int, dp, C.c_int64, dp]
+    L.mfx_soft2d_abi_version.restype = C.c_int
+    L.mfx_soft2d_max_atoms.argtypes = [vp, C.c_int]
+    L.mfx_post2d_dev.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int64, vp, vp, vp, vp, vp]
+    L.mfx_post2d.argtypes = [vp, dp, dp, C.c_int, dp, dp, C.c_int64, dp, dp, ip, ip]
+    L.mfx_profile2d_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int64, vp, vp, vp, vp]
+    L.mfx_profile2d.argtypes = [vp, dp, dp, C.c_int, C.c_int64, dp, ip, ip]
     _lib = L
     return L
 

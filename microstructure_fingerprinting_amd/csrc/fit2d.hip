@@ -29,7 +29,7 @@
 // every other class     dictionaries materialised by fit2d_mat_kernel (the same expression) in voxel chunks, then the
 //                       explicit solver of mfx_api.hip per voxel on the device.
 // A voxel with a failing direction is skipped by every kernel (fit2d_status_kernel wrote its NaN row and record).
-#include "rot2d_shared.h"
+#include "fit2d_shared.h"   // F2Rec, fit2d_rec_kernel, f2_value, the Gram block geometry (shared with soft2d.hip)
 #include "../../include/mfx_fit2d.h"
 #include "fit_small.hip"   // mfx_np_sumsq
 
@@ -39,26 +39,11 @@
 
 namespace {
 
-constexpr int F2_WG = 256;                 // 4 waves, one per SIMD and workgroup
-constexpr int F2_NW = 4;
-constexpr int F2_BLK = 128;                // atoms per side of a workgroup's Gram block (2 x 2 waves of 64 x 64)
-constexpr int F2_MC = 8;                   // protocol rows per chunk (2 k-steps)
-constexpr int F2_TS = F2_MC * 16 + 16;     // doubles per LDS tile: 16 atoms x F2_MC rows, padded (bank spread of the writers)
-constexpr int F2_NT = 2 * F2_BLK / 16;     // tiles per buffer: 8 of D_0, 8 of D_1
 constexpr int F2_MAXC = 512;               // short-list entries
 constexpr size_t F2_LDS_MAX = 160 * 1024;
 constexpr int F2_K1_WG = 256;
 
 thread_local int g_force_explicit = 0;
-
-// What the kernels read of a direction, per (direction, row): the operation, S_par, the abscissa's distance to the knot
-// below it, and the offsets (in doubles, relative to the knot values `base` = Rot2dDev::ky; the handle's tables sit in one
-// allocation) of the row's two operands: slope and knot value, or the constant row twice, or any readable row for the
-// reference's zero.  fit2d_rec_kernel derives them from the plan records once, so that an entry is two loads and r2_value.
-struct __attribute__((aligned(16))) F2Rec {
-  double s, dx;
-  int o, a, b, pad;
-};
 
 struct F2Args {
   int M, N;
@@ -70,35 +55,9 @@ struct F2Args {
   int num_params, maxfasc;
 };
 
-// entry (record, atom n): the expression of mfx_rot2d_eval_kernel
-__device__ __forceinline__ double f2_value(const double* __restrict__ base, const F2Rec& r, int n) {
-  return r2_value(r.o, r.s, base[r.a + n], r.dx, base[r.b + n]);
-}
 __device__ __forceinline__ double f2_elem(const F2Args& a, size_t i, int n) {
   const F2Rec r = a.rec[i];
   return f2_value(a.base, r, n);
-}
-
-// records of B directions from their plan records; a failing direction gets harmless ones (its voxel is skipped)
-__global__ void fit2d_rec_kernel(Rot2dDev D, Rot2dPlan pl, int64_t n, F2Rec* __restrict__ rec) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  F2Rec r;
-  r.s = 0.0; r.dx = 0.0; r.o = R2_OP_ZERO; r.a = 0; r.b = 0; r.pad = 0;
-  if (pl.status[4 * (i / D.M)] == MFX_ROT2D_OK) {
-    const int o = pl.op[i];
-    r.s = pl.spar[i];
-    if (o >= 1 && o < D.K) {
-      r.o = o;
-      r.a = (int)((D.slope - D.ky) + (int64_t)o * D.N);
-      r.b = (o - 1) * D.N;
-      r.dx = pl.x[i] - D.kx[o - 1];
-    } else if (o <= -2 && -2 - o < D.C) {
-      r.o = o;
-      r.a = r.b = (int)((D.cst - D.ky) + (int64_t)(-2 - o) * D.N);
-    }
-  }
-  rec[i] = r;
 }
 
 // voxel status from the directions' records: the lowest failing fascicle; NaN row for such a voxel, ok[v] = 0
@@ -160,8 +119,6 @@ __device__ __forceinline__ double f2_r2(const double* __restrict__ yv, const dou
   }
   return r2;
 }
-
-constexpr int F2_REC = 2 * 2 * F2_MC;   // staged records: [chunk parity][side][row]
 
 size_t f2_lds_bytes(int NP) {
   return ((size_t)2 * F2_NT * F2_TS + 4 * (size_t)NP + 32) * sizeof(double) + F2_REC * sizeof(F2Rec) + F2_MAXC * sizeof(Cand) +

@@ -1,0 +1,54 @@
+// fit2d_shared.h -- what fit2d.hip (the fit of 2-D protocols) and soft2d.hip (their soft fits and objective profiles) share:
+// the 32-byte record of a (direction, row), the kernel that derives the records from the plan records of rotate2d.hip, the
+// expression that turns a record into a dictionary entry, and the geometry of the blocked cross-Gram (128 x 128 atoms per
+// workgroup, rows accumulated in chunks of 8).  Every translation unit gets its own copy (anonymous namespace).
+#pragma once
+#include "rot2d_shared.h"
+
+namespace {
+
+constexpr int F2_WG = 256;                 // 4 waves, one per SIMD and workgroup
+constexpr int F2_NW = 4;
+constexpr int F2_BLK = 128;                // atoms per side of a workgroup's Gram block (2 x 2 waves of 64 x 64)
+constexpr int F2_MC = 8;                   // protocol rows per chunk (2 k-steps)
+constexpr int F2_TS = F2_MC * 16 + 16;     // doubles per LDS tile: 16 atoms x F2_MC rows, padded (bank spread of the writers)
+constexpr int F2_NT = 2 * F2_BLK / 16;     // tiles per buffer: 8 of D_0, 8 of D_1
+constexpr int F2_REC = 2 * 2 * F2_MC;      // staged records: [chunk parity][side][row]
+
+// What the kernels read of a direction, per (direction, row): the operation, S_par, the abscissa's distance to the knot
+// below it, and the offsets (in doubles, relative to the knot values `base` = Rot2dDev::ky; the handle's tables sit in one
+// allocation) of the row's two operands: slope and knot value, or the constant row twice, or any readable row for the
+// reference's zero.  fit2d_rec_kernel derives them from the plan records once, so that an entry is two loads and r2_value.
+struct __attribute__((aligned(16))) F2Rec {
+  double s, dx;
+  int o, a, b, pad;
+};
+
+// entry (record, atom n): the expression of mfx_rot2d_eval_kernel
+__device__ __forceinline__ double f2_value(const double* __restrict__ base, const F2Rec& r, int n) {
+  return r2_value(r.o, r.s, base[r.a + n], r.dx, base[r.b + n]);
+}
+
+// records of B directions from their plan records; a failing direction gets harmless ones (its voxel is skipped)
+__global__ void fit2d_rec_kernel(Rot2dDev D, Rot2dPlan pl, int64_t n, F2Rec* __restrict__ rec) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  F2Rec r;
+  r.s = 0.0; r.dx = 0.0; r.o = R2_OP_ZERO; r.a = 0; r.b = 0; r.pad = 0;
+  if (pl.status[4 * (i / D.M)] == MFX_ROT2D_OK) {
+    const int o = pl.op[i];
+    r.s = pl.spar[i];
+    if (o >= 1 && o < D.K) {
+      r.o = o;
+      r.a = (int)((D.slope - D.ky) + (int64_t)o * D.N);
+      r.b = (o - 1) * D.N;
+      r.dx = pl.x[i] - D.kx[o - 1];
+    } else if (o <= -2 && -2 - o < D.C) {
+      r.o = o;
+      r.a = r.b = (int)((D.cst - D.ky) + (int64_t)(-2 - o) * D.N);
+    }
+  }
+  rec[i] = r;
+}
+
+}  // namespace

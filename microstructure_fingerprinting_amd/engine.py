@@ -786,6 +786,148 @@ def fit2d(tables, Y, K, csf, peaks, maxfasc, csf_on, sig_csf=None):
     return params, status
 
 
+def _soft2d_shapes(tables, y_shape, pk_shape, K):
+    """Argument checks shared by the device entry points of the 2-D protocols' soft fits and profiles (before any device
+    call); returns V."""
+    K = int(K)
+    if K not in (1, 2):
+        raise NotImplementedError("soft fits and profiles of 2-D protocols serve K = 1 or 2 fascicles (got %d): three "
+                                  "fascicles and voxels without one are out of scope" % K)
+    if len(y_shape) != 2 or y_shape[1] != tables.M:
+        raise ValueError("data has shape %s, protocol has %d measurements" % (tuple(y_shape), tables.M))
+    V = y_shape[0]
+    if pk_shape is None or tuple(pk_shape) != (V, 3 * K):
+        raise ValueError("peaks should have shape (%d, %d)" % (V, 3 * K))
+    return V
+
+
+def posterior2d_dev(tables, d_Y, d_peaks, K, T, shift):
+    """Soft fit of voxels of a 2-D (AxCaliber-like) protocol on the device (mfx_post2d_dev, include/mfx_soft2d.h) for a
+    mf_utils.RotateAtom2DTables and torch CUDA float64 tensors of ONE voxel class (every voxel: K fascicles, no CSF):
+    d_Y [V, M], d_peaks [V, 3 K], ``T`` [V] the temperatures (2 sigma^2), ``shift`` [V] a value near each voxel's smallest
+    objective.  Returns ``(w, log_sum, status, dir_status)``: w [V, K, N] the posterior weight of every atom of each
+    fascicle, log_sum [V] = log sum exp(-F / T), status [V] int32 (0 ok, 1 unusable T or shift, 2 unusable shift, 5 a
+    failing fascicle direction; rows of such voxels are NaN), dir_status [V, 5] int32 the failing direction's record as
+    ``fit2d_dev`` gives it.  Enqueues on torch's current stream and returns without waiting."""
+    import torch
+    V = _soft2d_shapes(tables, d_Y.shape, d_peaks.shape, K)
+    for t, what in ((T, "T"), (shift, "shift")):
+        if not torch.is_tensor(t) or tuple(t.shape) != (V,):
+            raise ValueError("%s should be a tensor with one entry per voxel (%d)" % (what, V))
+    for t in (d_Y, d_peaks, T, shift):
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+    N = tables.N
+    w = torch.empty((V, int(K), N), dtype=torch.float64, device=d_Y.device)
+    log_sum = torch.empty((V,), dtype=torch.float64, device=d_Y.device)
+    status = torch.empty((V,), dtype=torch.int32, device=d_Y.device)
+    dir_status = torch.empty((V, 5), dtype=torch.int32, device=d_Y.device)
+    st = torch.cuda.current_stream(d_Y.device).cuda_stream
+    L.check(L.lib().mfx_post2d_dev(tables.handle(), d_Y.data_ptr(), d_peaks.data_ptr(), int(K), T.data_ptr(), shift.data_ptr(), V,
+                                   w.data_ptr(), log_sum.data_ptr(), status.data_ptr(), dir_status.data_ptr(), st))
+    return w, log_sum, status, dir_status
+
+
+def profile2d_dev(tables, d_Y, d_peaks, K, partner=False, out=None):
+    """Objective profiles of voxels of a 2-D protocol on the device (mfx_profile2d_dev) for ONE voxel class, arguments
+    as ``posterior2d_dev``.  Returns ``(obj, partner, dir_status)``: obj [V, K, N] float64, obj[v, k, i] the smallest sum
+    of squared residuals any partner atom reaches beside atom i of fascicle k; the int32 tensor of the arg-min partners
+    (-1 for K = 1) with ``partner=True``, else None; dir_status [V, 5] int32.  A voxel with a failing direction has NaN
+    values and partner -1.  Enqueues on torch's current stream and returns without waiting."""
+    import torch
+    V = _soft2d_shapes(tables, d_Y.shape, d_peaks.shape, K)
+    for t in (d_Y, d_peaks):
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+    N = tables.N
+    if out is None:
+        out = torch.empty((V, int(K), N), dtype=torch.float64, device=d_Y.device)
+    assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (V, int(K), N)
+    part = torch.empty((V, int(K), N), dtype=torch.int32, device=d_Y.device) if partner else None
+    dir_status = torch.empty((V, 5), dtype=torch.int32, device=d_Y.device)
+    st = torch.cuda.current_stream(d_Y.device).cuda_stream
+    L.check(L.lib().mfx_profile2d_dev(tables.handle(), d_Y.data_ptr(), d_peaks.data_ptr(), int(K), V, out.data_ptr(),
+                                      part.data_ptr() if partner else None, dir_status.data_ptr(), st))
+    return out, part, dir_status
+
+
+def _soft2d_host_args(tables, Y, K, peaks, maxfasc, csf):
+    """Argument checks of ``posterior2d`` and ``profile2d`` (before any device call): (Y, peaks [V x 3 maxfasc], maxfasc,
+    bins [(k, indices)], n_unsupported).  In scope: one or two fascicles without a CSF column."""
+    Y = L.f64c(Y)
+    maxfasc = int(maxfasc)
+    if Y.ndim != 2 or Y.shape[1] != tables.M:
+        raise ValueError("data has shape %s, protocol has %d measurements" % (Y.shape, tables.M))
+    V = Y.shape[0]
+    K = np.asarray(K)
+    if K.shape != (V,):
+        raise ValueError("K should have one entry per voxel")
+    pk = L.f64c(peaks).reshape(V, -1) if maxfasc > 0 else np.zeros((V, 0))
+    if pk.shape[1] != 3 * maxfasc:
+        raise ValueError("peaks should have %d columns" % (3 * maxfasc))
+    K = K.astype(np.int64)
+    if V and (K.min() < 0 or K.max() > maxfasc):
+        raise ValueError("K should lie in 0..maxfasc = %d" % maxfasc)
+    csf = np.zeros(V, bool) if csf is None else np.asarray(csf).astype(bool)
+    if csf.shape != (V,):
+        raise ValueError("csf should have one entry per voxel")
+    ok = (K >= 1) & (K <= 2) & ~csf
+    bins = [(k, np.flatnonzero(ok & (K == k))) for k in (1, 2)]
+    return Y, pk, maxfasc, [(k, ix) for k, ix in bins if ix.size], int(V - np.count_nonzero(ok))
+
+
+def posterior2d(tables, Y, K, peaks, maxfasc, sigma, shift=None, csf=None):
+    """Soft fit of a mixed set of voxels of a 2-D protocol on NumPy arrays (mfx_post2d, one call per fascicle count):
+    Y [V, M], per-voxel K, peaks [V, 3 maxfasc] as for ``fit2d``; ``sigma`` the noise standard deviation (a scalar or
+    [V]; the temperature is 2 sigma^2); ``shift`` [V] a value near each voxel's smallest objective, default: MSE * M of
+    ``fit2d`` on the same voxels.  Returns ``(w, log_sum, status, dir_status, n_unsupported)``: w [V, maxfasc, N] float64,
+    log_sum [V], status [V] int32 (the codes of include/mfx_soft2d.h, and -1 for a voxel out of scope: no fascicle, three
+    fascicles, a CSF flag - counted in n_unsupported), dir_status [V, 5] int32 (the failing direction's record of a voxel
+    with status 5); rows of absent fascicles and of voxels with a non-zero status are NaN."""
+    Y, pk, maxfasc, bins, n_uns = _soft2d_host_args(tables, Y, K, peaks, maxfasc, csf)
+    V, N = Y.shape[0], tables.N
+    sig = _per_voxel(sigma, V, "sigma")
+    sh = _per_voxel(shift, V, "shift") if shift is not None else None
+    w = np.full((V, maxfasc, N), np.nan)
+    log_sum = np.full(V, np.nan)
+    status = np.full(V, -1, dtype=np.int32)
+    dir_status = np.zeros((V, 5), dtype=np.int32)
+    for k, ix in bins:
+        Yc, pc = np.ascontiguousarray(Y[ix]), np.ascontiguousarray(pk[ix, :3 * k])
+        if sh is not None:
+            shc = np.ascontiguousarray(sh[ix])
+        else:   # a voxel with a failing direction has a NaN row there and status 5 here
+            fit, fst = fit2d(tables, Yc, np.full(ix.size, k), None, pc, k, False)
+            shc = np.ascontiguousarray(np.where(fst[:, 0] == 0, fit[:, -2] * tables.M, 0.0))
+        Tc = np.ascontiguousarray(2.0 * sig[ix] ** 2)
+        wc, lc = np.zeros((ix.size, k, N)), np.zeros(ix.size)
+        stc, dsc = np.zeros(ix.size, dtype=np.int32), np.zeros((ix.size, 5), dtype=np.int32)
+        L.check(L.lib().mfx_post2d(tables.handle(), L.dptr(Yc), L.dptr(pc), k, L.dptr(Tc), L.dptr(shc), ix.size, L.dptr(wc),
+                                   L.dptr(lc), L.iptr(stc), L.iptr(dsc)))
+        w[ix, :k], log_sum[ix], status[ix], dir_status[ix] = wc, lc, stc, dsc
+    return w, log_sum, status, dir_status, n_uns
+
+
+def profile2d(tables, Y, K, peaks, maxfasc, partner=False, csf=None):
+    """Objective profiles of a mixed set of voxels of a 2-D protocol on NumPy arrays (mfx_profile2d, one call per
+    fascicle count), arguments as ``posterior2d``.  Returns ``(obj, partner, dir_status, n_unsupported)``: obj
+    [V, maxfasc, N] float64 (rows of absent fascicles, of voxels out of scope and of voxels with a failing direction are
+    NaN), partner [V, maxfasc, N] int32 (-1 where there is none) or None, dir_status [V, 5] int32."""
+    Y, pk, maxfasc, bins, n_uns = _soft2d_host_args(tables, Y, K, peaks, maxfasc, csf)
+    V, N = Y.shape[0], tables.N
+    obj = np.full((V, maxfasc, N), np.nan)
+    par = np.full((V, maxfasc, N), -1, dtype=np.int32) if partner else None
+    dir_status = np.zeros((V, 5), dtype=np.int32)
+    for k, ix in bins:
+        Yc, pc = np.ascontiguousarray(Y[ix]), np.ascontiguousarray(pk[ix, :3 * k])
+        o, dsc = np.zeros((ix.size, k, N)), np.zeros((ix.size, 5), dtype=np.int32)
+        p = np.zeros((ix.size, k, N), dtype=np.int32) if partner else None
+        L.check(L.lib().mfx_profile2d(tables.handle(), L.dptr(Yc), L.dptr(pc), k, ix.size, L.dptr(o),
+                                      L.iptr(p) if partner else None, L.iptr(dsc)))
+        obj[ix, :k], dir_status[ix] = o, dsc
+        if partner:
+            par[ix, :k] = p
+    return obj, par, dir_status, n_uns
+
+
 def _wfit_shapes(plan, y_shape, w_shape, pk_shape, maxfasc):
     """Argument checks shared by the weighted fit's entry points (before any device call); returns (V, w_stride)."""
     if maxfasc < 0 or maxfasc > 3:

@@ -612,6 +612,69 @@ class RotateAtom2DTables:
         and the status records."""
         return _fit2d(self, data, peaks, numfasc, csf_mask, sig_csf, on_error)
 
+    def posterior(self, data, peaks, numfasc, sigma=None, fit=None, props=None, on_error='raise'):
+        """The soft answer beside ``fit``'s arg-min (``engine.posterior2d``, include/mfx_soft2d.h): for every atom of each
+        fascicle its posterior weight given the noise level, proportional to the sum over all partner atoms of
+        exp(-F / 2 sigma^2).  ``data``, ``peaks``, ``numfasc`` as for ``fit`` (voxels of one or two fascicles are served;
+        the others get NaN rows, status -1 and are counted).  ``sigma``: the noise standard deviation, a scalar or one
+        value per voxel; default: the fit's residual variance, sigma^2 = MSE * M / (M - K) per voxel, from ``fit`` (a
+        :class:`Fit2DResult` of the same voxels) or from a fit made here; a voxel with MSE = 0 gets status 1.  ``props``:
+        a dict mapping a name to an [N] array of atom properties, for the result's ``mean``, ``std``, ``quantile`` and
+        ``by_property``.  Returns a ``mf.Posterior`` (its ``dir_status`` [V, 5] holds the failing directions' records:
+        such voxels have status 5 and NaN rows with ``on_error='nan'``; ``'raise'`` raises the reference's exception for
+        the lowest of them)."""
+        from .mf import Posterior
+        data, peaks, numfasc, maxfasc = _soft2d_args(self, data, peaks, numfasc, on_error)
+        props = _soft2d_props(self, props)
+        V = data.shape[0]
+        scope = (numfasc >= 1) & (numfasc <= 2)
+        if fit is None:
+            mse = np.full(V, np.nan)
+            ix = np.flatnonzero(scope)
+            if ix.size:
+                mse[ix] = engine.fit2d(self, data[ix], numfasc[ix], None, peaks[ix], maxfasc, False)[0][:, -2]
+        else:
+            mse = np.asarray(fit.MSE, dtype=np.float64)
+            if mse.shape != (V,):
+                raise ValueError("fit should hold the same %d voxels" % V)
+        sse = mse * self.M
+        if sigma is None:
+            with np.errstate(invalid='ignore', divide='ignore'):
+                sig = np.sqrt(sse / (self.M - numfasc.astype(np.float64)))
+        else:
+            sig = engine._per_voxel(sigma, V, "sigma")
+        w, log_sum, status, dstat, n_uns = engine.posterior2d(self, data, numfasc, peaks, maxfasc, sig,
+                                                              shift=np.where(np.isfinite(sse), sse, 0.0))
+        _soft2d_raise(self, dstat, on_error)
+        r = Posterior(w, log_sum, status, n_uns, np.arange(V), props, numfasc, 2.0 * sig ** 2, self.M)
+        r.dir_status = dstat
+        return r
+
+    def profile(self, data, peaks, numfasc, partner=False, props=None, on_error='raise'):
+        """What the exhaustive search of ``fit`` saw beside its arg-min (``engine.profile2d``): for every atom of each
+        fascicle the smallest sum of squared residuals any partner atom reaches with it.  Arguments as ``posterior``.
+        Returns a ``mf.ObjectiveProfile``: ``obj`` [V, maxfasc, N], ``partner`` (int32, -1 where there is none; None
+        unless asked for), ``n_unsupported``, ``by_property(name)``, and ``dir_status`` [V, 5]."""
+        from .mf import ObjectiveProfile
+        data, peaks, numfasc, maxfasc = _soft2d_args(self, data, peaks, numfasc, on_error)
+        props = _soft2d_props(self, props)
+        obj, par, dstat, n_uns = engine.profile2d(self, data, numfasc, peaks, maxfasc, partner=partner)
+        _soft2d_raise(self, dstat, on_error)
+        r = ObjectiveProfile(obj, par, n_uns, np.arange(data.shape[0]), props)
+        r.dir_status = dstat
+        return r
+
+    def interval(self, data, peaks, numfasc, values, rel=0.0, delta=0.0):
+        """The range of the atom property ``values`` [N] that fits the data within a margin of the optimum
+        (``profile_interval`` of ``profile``): ``(lo, hi, count)`` of shape [V, maxfasc]; NaN / 0 for absent fascicles
+        and voxels out of scope."""
+        return profile_interval(self.profile(data, peaks, numfasc).obj, values, rel, delta)
+
+    def posterior_moments(self, data, peaks, numfasc, values, sigma=None):
+        """Posterior mean and standard deviation of the atom property ``values`` [N] per voxel and fascicle
+        (``posterior_moments`` of the weights of ``posterior``): ``(mean, std)`` of shape [V, maxfasc]."""
+        return posterior_moments(self.posterior(data, peaks, numfasc, sigma=sigma).weights, values)
+
     def rotate_cols(self, newdirs, cols):
         """Atom ``cols[b]`` for a fascicle along ``newdirs[b]`` -> [B, M]."""
         d = L.f64c(np.asarray(newdirs, dtype=np.float64).reshape(-1, 3))
@@ -689,6 +752,43 @@ def _fit2d(T, data, peaks, numfasc, csf_mask, sig_csf, on_error):
         if bad.size:
             raise T.error_for(status[bad[0], :4])
     return Fit2DResult(params, status, maxfasc, csf_on)
+
+
+def _soft2d_args(T, data, peaks, numfasc, on_error):
+    """Argument checks of RotateAtom2DTables.posterior / .profile (before any device call)."""
+    if on_error not in ("raise", "nan"):
+        raise ValueError("on_error should be 'raise' or 'nan'")
+    data = np.asarray(data, dtype=np.float64)
+    if data.ndim != 2 or data.shape[1] != T.M:
+        raise ValueError("data has shape %s, protocol has %d measurements" % (data.shape, T.M))
+    V = data.shape[0]
+    numfasc = np.asarray(numfasc)
+    if numfasc.shape != (V,):
+        raise ValueError("numfasc should have one entry per voxel")
+    peaks = np.asarray(peaks, dtype=np.float64)
+    if peaks.ndim != 2 or peaks.shape[0] != V or peaks.shape[1] % 3 != 0:
+        raise ValueError("peaks should have shape (%d, 3 maxfasc)" % V)
+    maxfasc = peaks.shape[1] // 3
+    if V and (numfasc.min() < 0 or numfasc.max() > maxfasc):
+        raise ValueError("numfasc should lie in 0..%d (the directions peaks holds per voxel)" % maxfasc)
+    return data, peaks, numfasc.astype(np.int64), maxfasc
+
+
+def _soft2d_props(T, props):
+    out = {}
+    for name, v in (props or {}).items():
+        v = np.asarray(v, dtype=np.float64).reshape(-1)
+        if v.shape[0] != T.N:
+            raise ValueError("property %s has %d entries, the dictionary has %d atoms" % (name, v.shape[0], T.N))
+        out[name] = v
+    return out
+
+
+def _soft2d_raise(T, dir_status, on_error):
+    if on_error == "raise":
+        bad = np.flatnonzero(dir_status[:, 0])
+        if bad.size:
+            raise T.error_for(dir_status[bad[0], :4])
 
 
 def fit_2Dprotocol(sig, sch_mat, refdir, DIFF, data, peaks, numfasc, csf_mask=None, sig_csf=None, on_error='raise',
