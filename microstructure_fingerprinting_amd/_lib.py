@@ -57,6 +57,10 @@ WSOFT_EXPORTS = ["mfx_wsoft_abi_version", "mfx_wsoft_max_atoms", "mfx_wpost_dev"
 SOFT2D_EXPORTS = ["mfx_soft2d_abi_version", "mfx_soft2d_max_atoms", "mfx_post2d_dev", "mfx_post2d", "mfx_profile2d_dev",
                   "mfx_profile2d"]
 
+# every symbol include/mfx_w2d.h declares (measurement weights for 2-D protocols: fit, posterior, profile; versioned on its own)
+W2D_EXPORTS = ["mfx_w2d_abi_version", "mfx_w2d_max_atoms", "mfx_wfit2d_batch_dev", "mfx_wfit2d_batch", "mfx_wpost2d_dev",
+               "mfx_wpost2d", "mfx_wprofile2d_dev", "mfx_wprofile2d", "mfx_w2d_debug_set_force_explicit"]
+
 
 class MfxError(RuntimeError):
     pass
@@ -190,6 +194,16 @@ def lib():
     L.mfx_post2d.argtypes = [vp, dp, dp, C.c_int, dp, dp, C.c_int64, dp, dp, ip, ip]
     L.mfx_profile2d_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int64, vp, vp, vp, vp]
     L.mfx_profile2d.argtypes = [vp, dp, dp, C.c_int, C.c_int64, dp, ip, ip]
+    L.mfx_w2d_abi_version.restype = C.c_int
+    L.mfx_w2d_max_atoms.argtypes = [vp, C.c_int]
+    L.mfx_wfit2d_batch_dev.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int, C.c_int64, vp, vp, vp, vp]
+    L.mfx_wfit2d_batch.argtypes = [vp, dp, dp, C.c_int64, ip, bp, dp, C.c_int, C.c_int, dp, C.c_int64, dp, ip, ip]
+    L.mfx_wpost2d_dev.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int, vp, vp, C.c_int64, vp, vp, vp, vp, vp]
+    L.mfx_wpost2d.argtypes = [vp, dp, dp, C.c_int64, dp, C.c_int, dp, dp, C.c_int64, dp, dp, ip, ip]
+    L.mfx_wprofile2d_dev.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int, C.c_int64, vp, vp, vp, vp]
+    L.mfx_wprofile2d.argtypes = [vp, dp, dp, C.c_int64, dp, C.c_int, C.c_int64, dp, ip, ip]
+    L.mfx_w2d_debug_set_force_explicit.argtypes = [C.c_int]
+    L.mfx_w2d_debug_set_force_explicit.restype = None
     _lib = L
     return L
 

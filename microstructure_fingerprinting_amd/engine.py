@@ -786,6 +786,78 @@ def fit2d(tables, Y, K, csf, peaks, maxfasc, csf_on, sig_csf=None):
     return params, status
 
 
+def _w2d_stride(tables, V, w_shape):
+    """w_stride of measurement weights given to an entry point of include/mfx_w2d.h (before any device call): M for
+    [V, M], 0 for one [M] vector shared by the voxels."""
+    if tuple(w_shape) == (tables.M,):
+        return 0
+    if tuple(w_shape) == (V, tables.M):
+        return tables.M
+    raise ValueError("weights should have shape (%d, %d) or (%d,), got %s (%d voxels)"
+                     % (V, tables.M, tables.M, tuple(w_shape), V))
+
+
+def fit2d_weighted_dev(tables, d_Y, d_W, d_peaks, maxfasc, out=None):
+    """Device-resident weighted fit of voxels of a 2-D protocol (mfx_wfit2d_batch_dev, include/mfx_w2d.h) for ONE voxel
+    class, arguments as ``fit2d_dev`` and d_W [V, M] or [M] the weights >= 0 of the measurements: minimises
+    sum_m W[v, m] (y_m - model_m)^2.  Returns (params, status [V, 5] int32, wstatus [V] int32: 0 fitted, 1 a negative or
+    non-finite weight, 2 no positive weight; such a voxel has a NaN row).  MSE = min_obj / sum_m W, R2 the squared
+    weighted correlation.  Enqueues on torch's current stream and returns without waiting."""
+    import torch
+    maxfasc = int(maxfasc)
+    V = _fit2d_shapes(tables, d_Y.shape, d_peaks.shape, maxfasc)
+    w_stride = _w2d_stride(tables, V, d_W.shape)
+    for t in (d_Y, d_W, d_peaks):
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+    npar = num_params(maxfasc, False, False)
+    if out is None:
+        out = torch.empty((V, npar), dtype=torch.float64, device=d_Y.device)
+    assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (V, npar)
+    status = torch.empty((V, 5), dtype=torch.int32, device=d_Y.device)
+    wstatus = torch.empty((V,), dtype=torch.int32, device=d_Y.device)
+    st = torch.cuda.current_stream(d_Y.device).cuda_stream
+    L.check(L.lib().mfx_wfit2d_batch_dev(tables.handle(), d_Y.data_ptr(), d_W.data_ptr(), w_stride,
+                                         d_peaks.data_ptr() if maxfasc > 0 else None, maxfasc, V, out.data_ptr(),
+                                         status.data_ptr(), wstatus.data_ptr(), st))
+    return out, status, wstatus
+
+
+def fit2d_weighted(tables, Y, W, K, csf, peaks, maxfasc, csf_on, sig_csf=None):
+    """Weighted fit of a mixed set of voxels of a 2-D protocol on NumPy arrays (mfx_wfit2d_batch): arguments as ``fit2d``
+    and W [V, M] or [M] the weights >= 0 of the measurements (a 0/1 outlier mask, inverse noise variances, ...).
+    Returns (params, status [V, 5] int32, wstatus [V] int32: 1 a negative or non-finite weight, 2 no positive weight;
+    such a voxel, like one with a failing direction, has a NaN row)."""
+    Y = L.f64c(Y)
+    W = L.f64c(W)
+    maxfasc = int(maxfasc)
+    pk = L.f64c(peaks).reshape(Y.shape[0], -1) if (maxfasc > 0 and Y.ndim == 2) else np.zeros((Y.shape[0], 0))
+    V = _fit2d_shapes(tables, Y.shape, pk.shape, maxfasc)
+    w_stride = _w2d_stride(tables, V, W.shape)
+    K = np.ascontiguousarray(np.asarray(K).reshape(-1), dtype=np.int32)
+    if K.shape != (V,):
+        raise ValueError("K should have one entry per voxel")
+    if V and (K.min() < 0 or K.max() > maxfasc):
+        raise ValueError("K should lie in 0..maxfasc = %d" % maxfasc)
+    cs = None
+    if csf is not None:
+        cs = np.ascontiguousarray(np.asarray(csf).reshape(-1).astype(bool), dtype=np.uint8)
+        if cs.shape != (V,):
+            raise ValueError("csf should have one entry per voxel")
+    sc = L.f64c(sig_csf).reshape(-1) if sig_csf is not None else None
+    if cs is not None and np.any(cs) and (not csf_on or sc is None):
+        raise ValueError("voxels flagged CSF need csf_on and sig_csf")
+    if sc is not None and sc.shape[0] != tables.M:
+        raise ValueError("sig_csf has %d entries, protocol has %d" % (sc.shape[0], tables.M))
+    params = np.zeros((V, num_params(maxfasc, bool(csf_on), False)))
+    status = np.zeros((V, 5), dtype=np.int32)
+    wstatus = np.zeros(V, dtype=np.int32)
+    L.check(L.lib().mfx_wfit2d_batch(tables.handle(), L.dptr(Y), L.dptr(W), w_stride, L.iptr(K),
+                                     L.bptr(cs) if cs is not None else None, L.dptr(pk) if maxfasc > 0 else None, maxfasc,
+                                     int(bool(csf_on)), L.dptr(sc) if sc is not None else None, V, L.dptr(params),
+                                     L.iptr(status), L.iptr(wstatus)))
+    return params, status, wstatus
+
+
 def _soft2d_shapes(tables, y_shape, pk_shape, K):
     """Argument checks shared by the device entry points of the 2-D protocols' soft fits and profiles (before any device
     call); returns V."""
@@ -801,20 +873,24 @@ def _soft2d_shapes(tables, y_shape, pk_shape, K):
     return V
 
 
-def posterior2d_dev(tables, d_Y, d_peaks, K, T, shift):
+def posterior2d_dev(tables, d_Y, d_peaks, K, T, shift, d_W=None):
     """Soft fit of voxels of a 2-D (AxCaliber-like) protocol on the device (mfx_post2d_dev, include/mfx_soft2d.h) for a
     mf_utils.RotateAtom2DTables and torch CUDA float64 tensors of ONE voxel class (every voxel: K fascicles, no CSF):
     d_Y [V, M], d_peaks [V, 3 K], ``T`` [V] the temperatures (2 sigma^2), ``shift`` [V] a value near each voxel's smallest
     objective.  Returns ``(w, log_sum, status, dir_status)``: w [V, K, N] the posterior weight of every atom of each
     fascicle, log_sum [V] = log sum exp(-F / T), status [V] int32 (0 ok, 1 unusable T or shift, 2 unusable shift, 5 a
     failing fascicle direction; rows of such voxels are NaN), dir_status [V, 5] int32 the failing direction's record as
-    ``fit2d_dev`` gives it.  Enqueues on torch's current stream and returns without waiting."""
+    ``fit2d_dev`` gives it.  Enqueues on torch's current stream and returns without waiting.  ``d_W``: measurement weights
+    [V, M] or [M] of a weighted fit (mfx_wpost2d_dev, include/mfx_w2d.h): F is the weighted sum of squares and
+    T = 2 sigma^2 means that measurement m has variance sigma^2 / W_m; status 3: a weight is negative or not finite,
+    4: none is positive."""
     import torch
     V = _soft2d_shapes(tables, d_Y.shape, d_peaks.shape, K)
     for t, what in ((T, "T"), (shift, "shift")):
         if not torch.is_tensor(t) or tuple(t.shape) != (V,):
             raise ValueError("%s should be a tensor with one entry per voxel (%d)" % (what, V))
-    for t in (d_Y, d_peaks, T, shift):
+    w_stride = _w2d_stride(tables, V, d_W.shape) if d_W is not None else None
+    for t in (d_Y, d_peaks, T, shift) + ((d_W,) if d_W is not None else ()):
         assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
     N = tables.N
     w = torch.empty((V, int(K), N), dtype=torch.float64, device=d_Y.device)
@@ -822,20 +898,28 @@ def posterior2d_dev(tables, d_Y, d_peaks, K, T, shift):
     status = torch.empty((V,), dtype=torch.int32, device=d_Y.device)
     dir_status = torch.empty((V, 5), dtype=torch.int32, device=d_Y.device)
     st = torch.cuda.current_stream(d_Y.device).cuda_stream
-    L.check(L.lib().mfx_post2d_dev(tables.handle(), d_Y.data_ptr(), d_peaks.data_ptr(), int(K), T.data_ptr(), shift.data_ptr(), V,
-                                   w.data_ptr(), log_sum.data_ptr(), status.data_ptr(), dir_status.data_ptr(), st))
+    if d_W is None:
+        L.check(L.lib().mfx_post2d_dev(tables.handle(), d_Y.data_ptr(), d_peaks.data_ptr(), int(K), T.data_ptr(), shift.data_ptr(), V,
+                                       w.data_ptr(), log_sum.data_ptr(), status.data_ptr(), dir_status.data_ptr(), st))
+    else:
+        L.check(L.lib().mfx_wpost2d_dev(tables.handle(), d_Y.data_ptr(), d_W.data_ptr(), w_stride, d_peaks.data_ptr(), int(K),
+                                        T.data_ptr(), shift.data_ptr(), V, w.data_ptr(), log_sum.data_ptr(), status.data_ptr(),
+                                        dir_status.data_ptr(), st))
     return w, log_sum, status, dir_status
 
 
-def profile2d_dev(tables, d_Y, d_peaks, K, partner=False, out=None):
+def profile2d_dev(tables, d_Y, d_peaks, K, partner=False, out=None, d_W=None):
     """Objective profiles of voxels of a 2-D protocol on the device (mfx_profile2d_dev) for ONE voxel class, arguments
     as ``posterior2d_dev``.  Returns ``(obj, partner, dir_status)``: obj [V, K, N] float64, obj[v, k, i] the smallest sum
     of squared residuals any partner atom reaches beside atom i of fascicle k; the int32 tensor of the arg-min partners
     (-1 for K = 1) with ``partner=True``, else None; dir_status [V, 5] int32.  A voxel with a failing direction has NaN
-    values and partner -1.  Enqueues on torch's current stream and returns without waiting."""
+    values and partner -1.  Enqueues on torch's current stream and returns without waiting.  ``d_W``: measurement weights
+    [V, M] or [M] (mfx_wprofile2d_dev): obj is the weighted sum of squares; a voxel with unusable weights has NaN values
+    and partner -1."""
     import torch
     V = _soft2d_shapes(tables, d_Y.shape, d_peaks.shape, K)
-    for t in (d_Y, d_peaks):
+    w_stride = _w2d_stride(tables, V, d_W.shape) if d_W is not None else None
+    for t in (d_Y, d_peaks) + ((d_W,) if d_W is not None else ()):
         assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
     N = tables.N
     if out is None:
@@ -844,8 +928,12 @@ def profile2d_dev(tables, d_Y, d_peaks, K, partner=False, out=None):
     part = torch.empty((V, int(K), N), dtype=torch.int32, device=d_Y.device) if partner else None
     dir_status = torch.empty((V, 5), dtype=torch.int32, device=d_Y.device)
     st = torch.cuda.current_stream(d_Y.device).cuda_stream
-    L.check(L.lib().mfx_profile2d_dev(tables.handle(), d_Y.data_ptr(), d_peaks.data_ptr(), int(K), V, out.data_ptr(),
-                                      part.data_ptr() if partner else None, dir_status.data_ptr(), st))
+    if d_W is None:
+        L.check(L.lib().mfx_profile2d_dev(tables.handle(), d_Y.data_ptr(), d_peaks.data_ptr(), int(K), V, out.data_ptr(),
+                                          part.data_ptr() if partner else None, dir_status.data_ptr(), st))
+    else:
+        L.check(L.lib().mfx_wprofile2d_dev(tables.handle(), d_Y.data_ptr(), d_W.data_ptr(), w_stride, d_peaks.data_ptr(), int(K), V,
+                                           out.data_ptr(), part.data_ptr() if partner else None, dir_status.data_ptr(), st))
     return out, part, dir_status
 
 
@@ -874,16 +962,22 @@ def _soft2d_host_args(tables, Y, K, peaks, maxfasc, csf):
     return Y, pk, maxfasc, [(k, ix) for k, ix in bins if ix.size], int(V - np.count_nonzero(ok))
 
 
-def posterior2d(tables, Y, K, peaks, maxfasc, sigma, shift=None, csf=None):
+def posterior2d(tables, Y, K, peaks, maxfasc, sigma, shift=None, csf=None, W=None):
     """Soft fit of a mixed set of voxels of a 2-D protocol on NumPy arrays (mfx_post2d, one call per fascicle count):
     Y [V, M], per-voxel K, peaks [V, 3 maxfasc] as for ``fit2d``; ``sigma`` the noise standard deviation (a scalar or
     [V]; the temperature is 2 sigma^2); ``shift`` [V] a value near each voxel's smallest objective, default: MSE * M of
     ``fit2d`` on the same voxels.  Returns ``(w, log_sum, status, dir_status, n_unsupported)``: w [V, maxfasc, N] float64,
     log_sum [V], status [V] int32 (the codes of include/mfx_soft2d.h, and -1 for a voxel out of scope: no fascicle, three
     fascicles, a CSF flag - counted in n_unsupported), dir_status [V, 5] int32 (the failing direction's record of a voxel
-    with status 5); rows of absent fascicles and of voxels with a non-zero status are NaN."""
+    with status 5); rows of absent fascicles and of voxels with a non-zero status are NaN.  ``W``: measurement weights
+    [V, M] or [M] of a weighted fit (mfx_wpost2d): F is the weighted sum of squares, ``sigma`` the noise of a measurement
+    of weight 1 (measurement m has variance sigma^2 / W_m), the default shift ``fit2d_weighted``'s objective
+    MSE * sum_m W; status 3: a weight is negative or not finite, 4: none is positive."""
     Y, pk, maxfasc, bins, n_uns = _soft2d_host_args(tables, Y, K, peaks, maxfasc, csf)
     V, N = Y.shape[0], tables.N
+    if W is not None:
+        W = L.f64c(W)
+        w_stride = _w2d_stride(tables, V, W.shape)
     sig = _per_voxel(sigma, V, "sigma")
     sh = _per_voxel(shift, V, "shift") if shift is not None else None
     w = np.full((V, maxfasc, N), np.nan)
@@ -892,27 +986,42 @@ def posterior2d(tables, Y, K, peaks, maxfasc, sigma, shift=None, csf=None):
     dir_status = np.zeros((V, 5), dtype=np.int32)
     for k, ix in bins:
         Yc, pc = np.ascontiguousarray(Y[ix]), np.ascontiguousarray(pk[ix, :3 * k])
+        if W is not None:
+            Wc = np.ascontiguousarray(W[ix]) if w_stride else W
         if sh is not None:
             shc = np.ascontiguousarray(sh[ix])
-        else:   # a voxel with a failing direction has a NaN row there and status 5 here
+        elif W is None:   # a voxel with a failing direction has a NaN row there and status 5 here
             fit, fst = fit2d(tables, Yc, np.full(ix.size, k), None, pc, k, False)
             shc = np.ascontiguousarray(np.where(fst[:, 0] == 0, fit[:, -2] * tables.M, 0.0))
+        else:             # the weighted fit's objective; unusable weights: a NaN row there, status 3 / 4 here
+            fit, fst, wst = fit2d_weighted(tables, Yc, Wc, np.full(ix.size, k), None, pc, k, False)
+            with np.errstate(invalid='ignore', over='ignore'):
+                sw = np.sum(Wc, axis=-1) if w_stride else np.full(ix.size, np.sum(Wc))
+                shc = np.ascontiguousarray(np.where((fst[:, 0] == 0) & (wst == 0), fit[:, -2] * sw, 0.0))
         Tc = np.ascontiguousarray(2.0 * sig[ix] ** 2)
         wc, lc = np.zeros((ix.size, k, N)), np.zeros(ix.size)
         stc, dsc = np.zeros(ix.size, dtype=np.int32), np.zeros((ix.size, 5), dtype=np.int32)
-        L.check(L.lib().mfx_post2d(tables.handle(), L.dptr(Yc), L.dptr(pc), k, L.dptr(Tc), L.dptr(shc), ix.size, L.dptr(wc),
-                                   L.dptr(lc), L.iptr(stc), L.iptr(dsc)))
+        if W is None:
+            L.check(L.lib().mfx_post2d(tables.handle(), L.dptr(Yc), L.dptr(pc), k, L.dptr(Tc), L.dptr(shc), ix.size, L.dptr(wc),
+                                       L.dptr(lc), L.iptr(stc), L.iptr(dsc)))
+        else:
+            L.check(L.lib().mfx_wpost2d(tables.handle(), L.dptr(Yc), L.dptr(Wc), w_stride, L.dptr(pc), k, L.dptr(Tc), L.dptr(shc),
+                                        ix.size, L.dptr(wc), L.dptr(lc), L.iptr(stc), L.iptr(dsc)))
         w[ix, :k], log_sum[ix], status[ix], dir_status[ix] = wc, lc, stc, dsc
     return w, log_sum, status, dir_status, n_uns
 
 
-def profile2d(tables, Y, K, peaks, maxfasc, partner=False, csf=None):
+def profile2d(tables, Y, K, peaks, maxfasc, partner=False, csf=None, W=None):
     """Objective profiles of a mixed set of voxels of a 2-D protocol on NumPy arrays (mfx_profile2d, one call per
     fascicle count), arguments as ``posterior2d``.  Returns ``(obj, partner, dir_status, n_unsupported)``: obj
     [V, maxfasc, N] float64 (rows of absent fascicles, of voxels out of scope and of voxels with a failing direction are
-    NaN), partner [V, maxfasc, N] int32 (-1 where there is none) or None, dir_status [V, 5] int32."""
+    NaN), partner [V, maxfasc, N] int32 (-1 where there is none) or None, dir_status [V, 5] int32.  ``W``: measurement
+    weights [V, M] or [M] (mfx_wprofile2d): obj is the weighted sum of squares; a voxel with unusable weights has NaN rows."""
     Y, pk, maxfasc, bins, n_uns = _soft2d_host_args(tables, Y, K, peaks, maxfasc, csf)
     V, N = Y.shape[0], tables.N
+    if W is not None:
+        W = L.f64c(W)
+        w_stride = _w2d_stride(tables, V, W.shape)
     obj = np.full((V, maxfasc, N), np.nan)
     par = np.full((V, maxfasc, N), -1, dtype=np.int32) if partner else None
     dir_status = np.zeros((V, 5), dtype=np.int32)
@@ -920,8 +1029,13 @@ def profile2d(tables, Y, K, peaks, maxfasc, partner=False, csf=None):
         Yc, pc = np.ascontiguousarray(Y[ix]), np.ascontiguousarray(pk[ix, :3 * k])
         o, dsc = np.zeros((ix.size, k, N)), np.zeros((ix.size, 5), dtype=np.int32)
         p = np.zeros((ix.size, k, N), dtype=np.int32) if partner else None
-        L.check(L.lib().mfx_profile2d(tables.handle(), L.dptr(Yc), L.dptr(pc), k, ix.size, L.dptr(o),
-                                      L.iptr(p) if partner else None, L.iptr(dsc)))
+        if W is None:
+            L.check(L.lib().mfx_profile2d(tables.handle(), L.dptr(Yc), L.dptr(pc), k, ix.size, L.dptr(o),
+                                          L.iptr(p) if partner else None, L.iptr(dsc)))
+        else:
+            Wc = np.ascontiguousarray(W[ix]) if w_stride else W
+            L.check(L.lib().mfx_wprofile2d(tables.handle(), L.dptr(Yc), L.dptr(Wc), w_stride, L.dptr(pc), k, ix.size, L.dptr(o),
+                                           L.iptr(p) if partner else None, L.iptr(dsc)))
         obj[ix, :k], dir_status[ix] = o, dsc
         if partner:
             par[ix, :k] = p

@@ -603,16 +603,20 @@ class RotateAtom2DTables:
         self.raise_for_status(status)
         return out
 
-    def fit(self, data, peaks, numfasc, csf_mask=None, sig_csf=None, on_error='raise'):
+    def fit(self, data, peaks, numfasc, csf_mask=None, sig_csf=None, on_error='raise', *, weights=None):
         """Fit ``data`` [V, M]: voxel v has ``numfasc[v]`` fascicles along ``peaks[v, 3k:3k+3]`` (unit vectors,
         peaks [V, 3 maxfasc]) and, where ``csf_mask[v]``, a CSF column ``sig_csf`` [M].  Per voxel the dictionaries
         ``rotate(peaks[v, 3k:3k+3])`` side by side go through ``solve_exhaustive_posweights`` on the device; returns
         a :class:`Fit2DResult`.  ``on_error='raise'`` raises the reference's exception for the lowest voxel with a
         failing direction (what a loop over the voxels would have raised first); ``'nan'`` returns NaN rows there
-        and the status records."""
-        return _fit2d(self, data, peaks, numfasc, csf_mask, sig_csf, on_error)
+        and the status records.  ``weights``: measurement weights [V, M] or [M], boolean or numeric, >= 0 (a 0/1 outlier
+        mask, inverse noise variances): the fit minimises sum_m W[v, m] (y_m - model_m)^2 (``engine.fit2d_weighted``,
+        include/mfx_w2d.h), MSE = min_obj / sum_m W and R2 the squared weighted correlation; the result keeps them in
+        ``weights``.  Negative or non-finite weights, or a voxel without a positive weight, raise ValueError before any
+        device call; ``on_error`` is about directions only."""
+        return _fit2d(self, data, peaks, numfasc, csf_mask, sig_csf, on_error, weights)
 
-    def posterior(self, data, peaks, numfasc, sigma=None, fit=None, props=None, on_error='raise'):
+    def posterior(self, data, peaks, numfasc, sigma=None, fit=None, props=None, on_error='raise', *, weights=None):
         """The soft answer beside ``fit``'s arg-min (``engine.posterior2d``, include/mfx_soft2d.h): for every atom of each
         fascicle its posterior weight given the noise level, proportional to the sum over all partner atoms of
         exp(-F / 2 sigma^2).  ``data``, ``peaks``, ``numfasc`` as for ``fit`` (voxels of one or two fascicles are served;
@@ -622,58 +626,80 @@ class RotateAtom2DTables:
         a dict mapping a name to an [N] array of atom properties, for the result's ``mean``, ``std``, ``quantile`` and
         ``by_property``.  Returns a ``mf.Posterior`` (its ``dir_status`` [V, 5] holds the failing directions' records:
         such voxels have status 5 and NaN rows with ``on_error='nan'``; ``'raise'`` raises the reference's exception for
-        the lowest of them)."""
+        the lowest of them).  ``weights``: the measurement weights of a weighted fit, as for ``fit`` (default: those of
+        ``fit``, a result of ``fit(weights=...)``; ValueError when both are given and differ).  F is then the weighted
+        sum of squares and ``sigma`` the noise of a measurement of weight 1: measurement m has variance sigma^2 / W_m;
+        the default is sigma^2 = MSE * sum_m W / (n_pos - K) with n_pos the number of positive weights."""
         from .mf import Posterior
         data, peaks, numfasc, maxfasc = _soft2d_args(self, data, peaks, numfasc, on_error)
         props = _soft2d_props(self, props)
         V = data.shape[0]
+        W = _w2d_weights(self, weights, V) if weights is not None else None
+        if fit is not None:
+            if np.asarray(fit.MSE).shape != (V,):
+                raise ValueError("fit should hold the same %d voxels" % V)
+            fw = getattr(fit, "weights", None)
+            if W is None:
+                W = fw
+            elif fw is None or not np.array_equal(np.broadcast_to(fw, (V, self.M)), np.broadcast_to(W, (V, self.M))):
+                raise ValueError("weights differ from those of fit (%d voxels): give one of them" % V)
         scope = (numfasc >= 1) & (numfasc <= 2)
         if fit is None:
             mse = np.full(V, np.nan)
             ix = np.flatnonzero(scope)
-            if ix.size:
+            if ix.size and W is None:
                 mse[ix] = engine.fit2d(self, data[ix], numfasc[ix], None, peaks[ix], maxfasc, False)[0][:, -2]
+            elif ix.size:
+                mse[ix] = engine.fit2d_weighted(self, data[ix], W[ix] if W.ndim == 2 else W, numfasc[ix], None, peaks[ix],
+                                                maxfasc, False)[0][:, -2]
         else:
             mse = np.asarray(fit.MSE, dtype=np.float64)
-            if mse.shape != (V,):
-                raise ValueError("fit should hold the same %d voxels" % V)
-        sse = mse * self.M
+        if W is None:
+            sse, n_meas = mse * self.M, float(self.M)
+        else:
+            sse, n_meas = mse * np.sum(W, axis=-1), np.count_nonzero(W > 0, axis=-1).astype(np.float64)
         if sigma is None:
+            dof = n_meas - numfasc.astype(np.float64)
             with np.errstate(invalid='ignore', divide='ignore'):
-                sig = np.sqrt(sse / (self.M - numfasc.astype(np.float64)))
+                sig = np.sqrt(sse / dof)
+            if W is not None:
+                sig = np.where(dof > 0, sig, np.nan)
         else:
             sig = engine._per_voxel(sigma, V, "sigma")
         w, log_sum, status, dstat, n_uns = engine.posterior2d(self, data, numfasc, peaks, maxfasc, sig,
-                                                              shift=np.where(np.isfinite(sse), sse, 0.0))
+                                                              shift=np.where(np.isfinite(sse), sse, 0.0), W=W)
         _soft2d_raise(self, dstat, on_error)
-        r = Posterior(w, log_sum, status, n_uns, np.arange(V), props, numfasc, 2.0 * sig ** 2, self.M)
+        r = Posterior(w, log_sum, status, n_uns, np.arange(V), props, numfasc, 2.0 * sig ** 2, self.M, W=W)
         r.dir_status = dstat
         return r
 
-    def profile(self, data, peaks, numfasc, partner=False, props=None, on_error='raise'):
+    def profile(self, data, peaks, numfasc, partner=False, props=None, on_error='raise', *, weights=None):
         """What the exhaustive search of ``fit`` saw beside its arg-min (``engine.profile2d``): for every atom of each
         fascicle the smallest sum of squared residuals any partner atom reaches with it.  Arguments as ``posterior``.
         Returns a ``mf.ObjectiveProfile``: ``obj`` [V, maxfasc, N], ``partner`` (int32, -1 where there is none; None
-        unless asked for), ``n_unsupported``, ``by_property(name)``, and ``dir_status`` [V, 5]."""
+        unless asked for), ``n_unsupported``, ``by_property(name)``, and ``dir_status`` [V, 5].  ``weights``: measurement
+        weights as for ``fit``: ``obj`` is the weighted sum of squares, whose minimum is the weighted fit's MSE * sum_m W."""
         from .mf import ObjectiveProfile
         data, peaks, numfasc, maxfasc = _soft2d_args(self, data, peaks, numfasc, on_error)
         props = _soft2d_props(self, props)
-        obj, par, dstat, n_uns = engine.profile2d(self, data, numfasc, peaks, maxfasc, partner=partner)
+        W = _w2d_weights(self, weights, data.shape[0]) if weights is not None else None
+        obj, par, dstat, n_uns = engine.profile2d(self, data, numfasc, peaks, maxfasc, partner=partner, W=W)
         _soft2d_raise(self, dstat, on_error)
         r = ObjectiveProfile(obj, par, n_uns, np.arange(data.shape[0]), props)
         r.dir_status = dstat
         return r
 
-    def interval(self, data, peaks, numfasc, values, rel=0.0, delta=0.0):
+    def interval(self, data, peaks, numfasc, values, rel=0.0, delta=0.0, *, weights=None):
         """The range of the atom property ``values`` [N] that fits the data within a margin of the optimum
         (``profile_interval`` of ``profile``): ``(lo, hi, count)`` of shape [V, maxfasc]; NaN / 0 for absent fascicles
-        and voxels out of scope."""
-        return profile_interval(self.profile(data, peaks, numfasc).obj, values, rel, delta)
+        and voxels out of scope.  ``weights``: measurement weights as for ``fit``."""
+        return profile_interval(self.profile(data, peaks, numfasc, weights=weights).obj, values, rel, delta)
 
-    def posterior_moments(self, data, peaks, numfasc, values, sigma=None):
+    def posterior_moments(self, data, peaks, numfasc, values, sigma=None, *, weights=None):
         """Posterior mean and standard deviation of the atom property ``values`` [N] per voxel and fascicle
-        (``posterior_moments`` of the weights of ``posterior``): ``(mean, std)`` of shape [V, maxfasc]."""
-        return posterior_moments(self.posterior(data, peaks, numfasc, sigma=sigma).weights, values)
+        (``posterior_moments`` of the weights of ``posterior``): ``(mean, std)`` of shape [V, maxfasc].  ``weights``:
+        measurement weights as for ``fit``."""
+        return posterior_moments(self.posterior(data, peaks, numfasc, sigma=sigma, weights=weights).weights, values)
 
     def rotate_cols(self, newdirs, cols):
         """Atom ``cols[b]`` for a fascicle along ``newdirs[b]`` -> [B, M]."""
@@ -695,15 +721,17 @@ class Fit2DResult:
     its columns ``M0`` [V], ``frac`` [V, maxfasc], ``atoms`` [V, maxfasc] (int64 atom indices; 0 for an absent
     fascicle or a voxel that was not fitted), ``frac_csf`` [V] (None without a CSF column), ``MSE``, ``R2`` [V];
     ``status`` [V, 5] int32: {code, pair, value, value2, fascicle} of the voxel's lowest failing fascicle
-    direction, zeros for a fitted voxel (such a voxel's row is NaN)."""
+    direction, zeros for a fitted voxel (such a voxel's row is NaN).  ``weights``: the measurement weights [V, M] or [M]
+    (float64) of a weighted fit, None for an unweighted one."""
 
-    def __init__(self, params, status, maxfasc, csf_on):
+    def __init__(self, params, status, maxfasc, csf_on, weights=None):
         params = np.asarray(params, dtype=np.float64)
         maxfasc = int(maxfasc)
         if params.ndim != 2 or params.shape[1] != engine.num_params(maxfasc, bool(csf_on), False):
             raise ValueError("params should have %d columns" % engine.num_params(maxfasc, bool(csf_on), False))
         self.params, self.status = params, np.asarray(status, dtype=np.int32).reshape(params.shape[0], 5)
         self.maxfasc, self.csf_on = maxfasc, bool(csf_on)
+        self.weights = weights
         self.M0 = params[:, 0]
         self.frac = params[:, 1:1 + maxfasc]
         ids = params[:, 1 + maxfasc:1 + 2 * maxfasc]
@@ -717,7 +745,28 @@ class Fit2DResult:
         return np.flatnonzero(self.status[:, 0])
 
 
-def _fit2d(T, data, peaks, numfasc, csf_mask, sig_csf, on_error):
+def _w2d_weights(T, weights, V):
+    """weights argument of the 2-D protocols' entry points -> float64 [V, M] or [M], checked before any device call (every
+    failure a ValueError naming the voxel count, as MFModel.fit's)."""
+    w = np.asarray(weights)
+    if w.dtype == object or not (np.issubdtype(w.dtype, np.number) or w.dtype == np.bool_) or np.iscomplexobj(w):
+        raise ValueError("weights should be boolean or real numbers (%d voxel(s))." % V)
+    if w.shape != (T.M,) and w.shape != (V, T.M):
+        raise ValueError("weights not compatible with the data of %d voxel(s): expected shape (%d, %d) or (%d,), got %s."
+                         % (V, V, T.M, T.M, w.shape))
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    bad = ~np.isfinite(w) | (w < 0)
+    if bad.any():
+        n_bad = V if w.ndim == 1 else int(np.count_nonzero(bad.any(axis=1)))
+        raise ValueError("Detected %d of %d voxel(s) with negative or non-finite weights." % (n_bad, V))
+    none = ~(w > 0).any(axis=-1)
+    if np.any(none):
+        n_none = V if w.ndim == 1 else int(np.count_nonzero(none))
+        raise ValueError("Detected %d of %d voxel(s) without a positive weight." % (n_none, V))
+    return w
+
+
+def _fit2d(T, data, peaks, numfasc, csf_mask, sig_csf, on_error, weights=None):
     if on_error not in ("raise", "nan"):
         raise ValueError("on_error should be 'raise' or 'nan'")
     data = np.asarray(data, dtype=np.float64)
@@ -746,12 +795,16 @@ def _fit2d(T, data, peaks, numfasc, csf_mask, sig_csf, on_error):
             raise ValueError("voxels flagged CSF need sig_csf")
     if sig_csf is not None and np.asarray(sig_csf).size != T.M:
         raise ValueError("sig_csf has %d entries, protocol has %d" % (np.asarray(sig_csf).size, T.M))
-    params, status = engine.fit2d(T, data, numfasc, csf, peaks, maxfasc, csf_on, sig_csf)
+    W = _w2d_weights(T, weights, V) if weights is not None else None
+    if W is None:
+        params, status = engine.fit2d(T, data, numfasc, csf, peaks, maxfasc, csf_on, sig_csf)
+    else:
+        params, status, _ = engine.fit2d_weighted(T, data, W, numfasc, csf, peaks, maxfasc, csf_on, sig_csf)
     if on_error == "raise":
         bad = np.flatnonzero(status[:, 0])
         if bad.size:
             raise T.error_for(status[bad[0], :4])
-    return Fit2DResult(params, status, maxfasc, csf_on)
+    return Fit2DResult(params, status, maxfasc, csf_on, W)
 
 
 def _soft2d_args(T, data, peaks, numfasc, on_error):
@@ -792,10 +845,11 @@ def _soft2d_raise(T, dir_status, on_error):
 
 
 def fit_2Dprotocol(sig, sch_mat, refdir, DIFF, data, peaks, numfasc, csf_mask=None, sig_csf=None, on_error='raise',
-                   device=0):
-    """Fit voxels of a 2-D protocol: :class:`RotateAtom2DTables` of (sig, sch_mat, refdir, DIFF), then its ``fit``."""
+                   device=0, *, weights=None):
+    """Fit voxels of a 2-D protocol: :class:`RotateAtom2DTables` of (sig, sch_mat, refdir, DIFF), then its ``fit``
+    (``weights``: its measurement weights)."""
     return RotateAtom2DTables(sig, sch_mat, refdir, DIFF, device=device).fit(data, peaks, numfasc, csf_mask, sig_csf,
-                                                                            on_error)
+                                                                            on_error, weights=weights)
 
 
 def rotate_atom_2Dprotocol(sig, sch_mat, refdir, newdir, DIFF):

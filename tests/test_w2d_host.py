@@ -1,0 +1,290 @@
+"""Measurement weights for 2-D protocols, the parts that need no GPU: the C ABI of include/mfx_w2d.h, the argument and
+weight checks that come before any device call, the golden's own conditions (tests/golden/wfit2d_cases.npz, written by
+gen_golden_wfit2d.py), the weighted R2 restated against np.corrcoef, and the default noise level and evidence count."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+import _wfit_ref as WR
+from microstructure_fingerprinting_amd import _lib, engine
+from microstructure_fingerprinting_amd import mf_utils as U
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+G = os.path.join(ROOT, "tests", "golden")
+Z = np.array([0.0, 0.0, 1.0])
+
+
+@pytest.fixture(scope="module")
+def rot():
+    return np.load(os.path.join(G, "rot2d_cases.npz"))
+
+
+def _declared(header):
+    src = open(os.path.join(ROOT, "include", header)).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    return sorted(set(re.findall(r"\b(mfx_[a-z_0-9]+)\s*\(", src)))
+
+
+def test_header_binding_and_library_are_in_step():
+    lib = _lib.lib()
+    decl = _declared("mfx_w2d.h")
+    assert decl == sorted(_lib.W2D_EXPORTS) and len(decl) == 9
+    for name in decl:
+        assert hasattr(lib, name), "libmfx.so lacks %s declared in include/mfx_w2d.h" % name
+    assert lib.mfx_w2d_abi_version() == 1
+    others = (_lib.EXPORTS, _lib.MCF_EXPORTS, _lib.ROT2D_EXPORTS, _lib.FIT2D_EXPORTS, _lib.WFIT_EXPORTS, _lib.PREDICT_EXPORTS,
+              _lib.PROFILE_EXPORTS, _lib.POST_EXPORTS, _lib.WSOFT_EXPORTS, _lib.SOFT2D_EXPORTS)
+    for other in others:
+        assert not set(_lib.W2D_EXPORTS) & set(other)
+    # the other headers, their binding lists and versions are as they were
+    for header, lst, version in (("mfx.h", _lib.EXPORTS, (lib.mfx_abi_version, 3)),
+                                 ("mfx_fit2d.h", _lib.FIT2D_EXPORTS, (lib.mfx_fit2d_abi_version, 1)),
+                                 ("mfx_soft2d.h", _lib.SOFT2D_EXPORTS, (lib.mfx_soft2d_abi_version, 1)),
+                                 ("mfx_wfit.h", _lib.WFIT_EXPORTS, (lib.mfx_wfit_abi_version, 1)),
+                                 ("mfx_wsoft.h", _lib.WSOFT_EXPORTS, (lib.mfx_wsoft_abi_version, 1)),
+                                 ("mfx_rot2d.h", _lib.ROT2D_EXPORTS, (lib.mfx_rot2d_abi_version, 1)),
+                                 ("mfx_post.h", _lib.POST_EXPORTS, (lib.mfx_post_abi_version, 1)),
+                                 ("mfx_profile.h", _lib.PROFILE_EXPORTS, (lib.mfx_profile_abi_version, 1))):
+        assert _declared(header) == sorted(lst), header
+        assert version[0]() == version[1], header
+    assert [len(x) for x in others] == [41, 3, 7, 5, 5, 5, 7, 4, 8, 6]
+
+
+def test_header_states_the_definitions():
+    src = re.sub(r"\s*\n \*\s*|\s+", " ", open(os.path.join(ROOT, "include", "mfx_w2d.h")).read())   # the comment's line breaks
+    for word in ("sqrt(W", "bit for bit", "mfx_rot2d_rotate", "mfx_profile_cut", "sum_m W", "weighted Pearson", "w_stride",
+                 "tested first", "NaN", "MFX_ERR_UNSUPPORTED", "fixed order", "c W, c T, c shift", "masked rows deleted",
+                 "mfx_w2d_max_atoms", "launch nothing", "no floating-point atomics"):
+        assert word.lower() in src.lower(), word
+
+
+def test_max_atoms_needs_no_device():
+    lib = _lib.lib()
+    assert lib.mfx_w2d_max_atoms(None, 0) == 0
+    h = 1                                      # any non-null handle: the limits do not depend on the protocol
+    n_fit, n_post, n_prof = (lib.mfx_w2d_max_atoms(h, k) for k in range(3))
+    assert n_fit >= n_post >= n_prof >= 1024 and all(n % 16 == 0 for n in (n_fit, n_post, n_prof))
+    # the staged s costs 128 bytes of LDS: at most one tile of 16 atoms below the unweighted kernels
+    assert 0 <= lib.mfx_fit2d_max_atoms(h, 2) - n_fit <= 16
+    assert 0 <= lib.mfx_soft2d_max_atoms(h, 0) - n_post <= 16 and 0 <= lib.mfx_soft2d_max_atoms(h, 1) - n_prof <= 16
+    assert lib.mfx_w2d_max_atoms(h, 3) == 0 and lib.mfx_w2d_max_atoms(h, -1) == 0
+
+
+def test_without_a_device_the_entry_points_say_so(rot):
+    lib = _lib.lib()
+    if lib.mfx_device_count() > 0:
+        pytest.skip("a GPU is present")
+    fake = C.c_void_p(8)   # never dereferenced: the device check comes first
+    one = np.ones(1)
+    d = _lib.dptr(one)
+    st, ds, k1 = np.zeros(1, dtype=np.int32), np.zeros(5, dtype=np.int32), np.ones(1, dtype=np.int32)
+    calls = [lambda: lib.mfx_wfit2d_batch_dev(fake, fake, fake, 0, fake, 2, 1, fake, fake, fake, None),
+             lambda: lib.mfx_wfit2d_batch(fake, d, d, 0, _lib.iptr(k1), None, d, 1, 0, None, 1, d, _lib.iptr(ds), _lib.iptr(st)),
+             lambda: lib.mfx_wpost2d_dev(fake, fake, fake, 0, fake, 2, fake, fake, 1, fake, fake, fake, fake, None),
+             lambda: lib.mfx_wpost2d(fake, d, d, 0, d, 2, d, d, 1, d, d, _lib.iptr(st), _lib.iptr(ds)),
+             lambda: lib.mfx_wprofile2d_dev(fake, fake, fake, 0, fake, 2, 1, fake, None, fake, None),
+             lambda: lib.mfx_wprofile2d(fake, d, d, 0, d, 1, 1, d, None, _lib.iptr(ds))]
+    for c in calls:
+        assert c() == _lib.MFX_ERR_NO_DEVICE
+        assert b"no HIP device" in lib.mfx_last_error()
+    lib.mfx_w2d_debug_set_force_explicit(1)
+    lib.mfx_w2d_debug_set_force_explicit(0)
+    T = U.RotateAtom2DTables(rot["syn2_sig"], rot["syn2_sch"], Z, 2.2e-9)
+    pk, K, w = np.array([[0.0, 0.0, 1.0]]), np.ones(1, dtype=np.int32), np.ones(T.M)
+    with pytest.raises(_lib.MfxError, match="no CPU path"):
+        T.fit(np.ones((1, T.M)), pk, K, weights=w)
+    with pytest.raises(_lib.MfxError, match="no CPU path"):
+        T.posterior(np.ones((1, T.M)), pk, K, sigma=0.1, weights=w)
+    with pytest.raises(_lib.MfxError, match="no CPU path"):
+        T.profile(np.ones((1, T.M)), pk, K, weights=w)
+
+
+class _Tables:
+    """Stands for a RotateAtom2DTables of M rows; the argument checks must be done before its handle is asked for."""
+    M, N, device = 66, 14, 0
+
+    def handle(self):
+        raise AssertionError("the device handle was touched before the arguments were checked")
+
+    fit, posterior, profile = U.RotateAtom2DTables.fit, U.RotateAtom2DTables.posterior, U.RotateAtom2DTables.profile
+    interval, posterior_moments = U.RotateAtom2DTables.interval, U.RotateAtom2DTables.posterior_moments
+
+
+def test_engine_argument_errors_come_before_the_device():
+    import torch
+    T = _Tables()
+    V = 5
+    Y, pk, K, W = np.zeros((V, 66)), np.zeros((V, 6)), np.full(V, 2), np.ones((V, 66))
+    with pytest.raises(ValueError, match="protocol has 66"):
+        engine.fit2d_weighted(T, np.zeros((V, 63)), W, K, None, pk, 2, False)
+    with pytest.raises(ValueError, match=r"peaks should have shape \(5, 6\)"):
+        engine.fit2d_weighted(T, Y, W, K, None, np.zeros((V, 3)), 2, False)
+    with pytest.raises(NotImplementedError, match="0 to 3 fascicles"):
+        engine.fit2d_weighted(T, Y, W, K, None, np.zeros((V, 12)), 4, False)
+    with pytest.raises(ValueError, match="K should have one entry per voxel"):
+        engine.fit2d_weighted(T, Y, W, np.full(V + 1, 2), None, pk, 2, False)
+    with pytest.raises(ValueError, match="need csf_on and sig_csf"):
+        engine.fit2d_weighted(T, Y, W, K, np.ones(V, bool), pk, 2, True)
+    for bad in (np.ones((V, 65)), np.ones(65), np.ones((V + 1, 66)), np.ones((66, 1))):
+        for call in (lambda w: engine.fit2d_weighted(T, Y, w, K, None, pk, 2, False),
+                     lambda w: engine.posterior2d(T, Y, K, pk, 2, 1.0, W=w), lambda w: engine.profile2d(T, Y, K, pk, 2, W=w)):
+            with pytest.raises(ValueError, match=r"weights should have shape \(5, 66\) or \(66,\)"):
+                call(bad)
+    tY, tpk, tT = torch.zeros((V, 66), dtype=torch.float64), torch.zeros((V, 6), dtype=torch.float64), torch.ones(V, dtype=torch.float64)
+    tW = torch.ones((V, 60), dtype=torch.float64)
+    for call in (lambda: engine.fit2d_weighted_dev(T, tY, tW, tpk, 2), lambda: engine.posterior2d_dev(T, tY, tpk, 2, tT, tT, d_W=tW),
+                 lambda: engine.profile2d_dev(T, tY, tpk, 2, d_W=tW)):
+        with pytest.raises(ValueError, match="weights should have shape"):
+            call()
+    # a CPU tensor or another dtype is refused before the handle is asked for
+    for tWb in (torch.ones((V, 66), dtype=torch.float64), torch.ones((V, 66), dtype=torch.float32)):
+        for call in (lambda: engine.fit2d_weighted_dev(T, tY, tWb, tpk, 2), lambda: engine.profile2d_dev(T, tY, tpk, 2, d_W=tWb)):
+            with pytest.raises(AssertionError) as e:
+                call()
+            assert "device handle" not in str(e.value)
+
+
+def test_tables_weight_errors_come_before_the_device():
+    T = _Tables()
+    V = 4
+    Y, pk, K = np.ones((V, 66)), np.tile([0.0, 0.0, 1.0, 1.0, 0.0, 0.0], (V, 1)), np.full(V, 2)
+    Wneg, Wnan, Wzero = np.ones((V, 66)), np.ones((V, 66)), np.ones((V, 66))
+    Wneg[1, 3], Wneg[2, 5] = -1.0, -0.5
+    Wnan[3, 0] = np.nan
+    Wzero[0] = 0.0
+    calls = (lambda w: T.fit(Y, pk, K, weights=w), lambda w: T.posterior(Y, pk, K, sigma=1.0, weights=w),
+             lambda w: T.profile(Y, pk, K, weights=w), lambda w: T.interval(Y, pk, K, np.arange(14.0), weights=w),
+             lambda w: T.posterior_moments(Y, pk, K, np.arange(14.0), sigma=1.0, weights=w))
+    for call in calls:
+        with pytest.raises(ValueError, match="Detected 2 of 4 voxel.s. with negative or non-finite weights"):
+            call(Wneg)
+        with pytest.raises(ValueError, match="Detected 1 of 4 voxel.s. with negative or non-finite weights"):
+            call(Wnan)
+        with pytest.raises(ValueError, match="Detected 1 of 4 voxel.s. without a positive weight"):
+            call(Wzero)
+        with pytest.raises(ValueError, match="Detected 4 of 4 voxel.s. with negative"):
+            call(np.where(np.arange(66) == 7, np.inf, 1.0))
+        with pytest.raises(ValueError, match="Detected 4 of 4 voxel.s. without a positive weight"):
+            call(np.zeros(66, bool))
+        with pytest.raises(ValueError, match="expected shape .4, 66. or .66,."):
+            call(np.ones((V, 65)))
+        with pytest.raises(ValueError, match="boolean or real numbers .4 voxel"):
+            call(np.full((V, 66), "1"))
+        with pytest.raises(ValueError, match="boolean or real numbers"):
+            call(np.ones((V, 66), dtype=complex))
+    # fit= and weights= in conflict; a fit of other voxels
+    W = np.ones((V, 66))
+    W[:, ::7] = 0.0
+    params = np.zeros((V, engine.num_params(2, False, False)))
+    r_w = U.Fit2DResult(params, np.zeros((V, 5), dtype=np.int32), 2, False, W)
+    r_plain = U.Fit2DResult(params, np.zeros((V, 5), dtype=np.int32), 2, False)
+    assert r_plain.weights is None and r_w.weights is W
+    with pytest.raises(ValueError, match="weights differ from those of fit"):
+        T.posterior(Y, pk, K, fit=r_w, weights=np.ones((V, 66)))
+    with pytest.raises(ValueError, match="weights differ from those of fit"):
+        T.posterior(Y, pk, K, fit=r_plain, weights=W)
+    with pytest.raises(ValueError, match="fit should hold the same 3 voxels"):
+        T.posterior(Y[:3], pk[:3], K[:3], fit=r_w)
+    # equal weights given twice (a shared vector against its rows) pass the check and reach the device: the stand-in says so
+    Wrow = np.ones(66)
+    Wrow[::7] = 0.0
+    with pytest.raises(AssertionError, match="device handle"):
+        T.posterior(Y, pk, K, sigma=1.0, fit=r_w, weights=Wrow)
+    # mf_utils.fit_2Dprotocol takes the keyword
+    import inspect
+    assert inspect.signature(U.fit_2Dprotocol).parameters["weights"].kind is inspect.Parameter.KEYWORD_ONLY
+    for f in (U.RotateAtom2DTables.fit, U.RotateAtom2DTables.posterior, U.RotateAtom2DTables.profile, U.RotateAtom2DTables.interval,
+              U.RotateAtom2DTables.posterior_moments):
+        p = inspect.signature(f).parameters["weights"]
+        assert p.kind is inspect.Parameter.KEYWORD_ONLY and p.default is None
+
+
+def test_golden_conditions():
+    gold, base = np.load(os.path.join(G, "wfit2d_cases.npz")), np.load(os.path.join(G, "fit2d_cases.npz"))
+    assert os.path.getsize(os.path.join(G, "wfit2d_cases.npz")) < os.path.getsize(os.path.join(G, "rot2d_cases.npz"))
+    gap = float(gold["gap"])
+    assert gap == 1e-8
+    for name in ("syn2", "fix"):
+        V, M = base[name + "_Y"].shape
+        assert gold[name + "_W_mask"].shape == (V, M) and gold[name + "_W_smooth"].shape == (V, M) and gold[name + "_W_shared"].shape == (M,)
+        dropped = 1.0 - gold[name + "_W_mask"].mean(axis=1)
+        assert np.all((dropped > 0.05) & (dropped < 0.15))                           # about a tenth of the rows
+        assert gold[name + "_W_smooth"].min() >= 0.25 and gold[name + "_W_smooth"].max() <= 4.0
+        for kind in ("mask", "smooth", "shared"):
+            o, ysq, rows = gold["%s_obj2_%s" % (name, kind)], gold["%s_ysq_%s" % (name, kind)], gold["%s_params_%s" % (name, kind)]
+            assert o.shape == (V, 2) and rows.shape == base[name + "_params"].shape   # every voxel of fit2d_cases.npz
+            rel = (o[:, 1] - o[:, 0]) / ysq
+            print("%s %s: smallest top-2 gap %.2e |y'|^2" % (name, kind, rel.min()))
+            assert np.all(rel > gap)
+            W = gold["%s_W_%s" % (name, kind)].astype(np.float64)
+            sw = np.sum(W, axis=-1)
+            assert np.allclose(rows[:, -2] * sw, o[:, 0], rtol=0, atol=1e-9 * ysq.max())
+            # the weights matter: other parameters than the unweighted golden's
+            fitted = (base[name + "_K"] + base[name + "_csf"]) > 0
+            assert not np.allclose(rows[fitted], base[name + "_params"][fitted], rtol=1e-3)
+    n2 = gold["syn2_vox2"].size
+    for kind in ("mask", "smooth", "shared"):
+        F, c2 = gold["syn2_FW_" + kind], gold["syn2_c2_" + kind]
+        assert F.shape == (n2, 24, 24) and gold["syn2_dFW_" + kind].shape == F.shape
+        assert not np.any((c2 >= 1e-8 / 4) & (c2 <= 4e-8))
+        rows = gold["syn2_params_" + kind][gold["syn2_vox2"]]
+        im = np.array([np.unravel_index(np.argmin(f), f.shape) for f in F])
+        assert np.array_equal(im, rows[:, 3:5].astype(int))                          # F_W's arg-min is the weighted fit's pair
+
+
+def test_weighted_r2_restatement():
+    rng = np.random.default_rng(5)
+    y, yrec = rng.normal(size=66), rng.normal(size=66)
+    keep = rng.uniform(size=66) > 0.2
+    assert abs(WR.weighted_r2(y, yrec, keep.astype(float)) - np.corrcoef(y[keep], yrec[keep])[0, 1] ** 2) <= 1e-14
+    assert abs(WR.weighted_r2(y, yrec, np.ones(66)) - np.corrcoef(y, yrec)[0, 1] ** 2) <= 1e-14
+    w = rng.uniform(0.25, 4.0, 66)
+    assert abs(WR.weighted_r2(y, yrec, w) - WR.weighted_r2(y, yrec, 1e6 * w)) <= 1e-14
+    # integer weights: repeated rows
+    wi = rng.integers(0, 4, 66)
+    assert abs(WR.weighted_r2(y, yrec, wi.astype(float)) - np.corrcoef(np.repeat(y, wi), np.repeat(yrec, wi))[0, 1] ** 2) <= 1e-13
+    one = np.zeros(66)
+    one[3] = 2.0
+    assert WR.weighted_r2(y, yrec, one) == 0.0 and WR.weighted_r2(np.ones(66), yrec, np.ones(66)) == 0.0
+
+
+def test_default_sigma_and_evidence_count_follow_n_pos(monkeypatch):
+    """RotateAtom2DTables.posterior with fit=: sigma^2 = MSE sum W / (n_pos - K), the shift MSE sum W, and a Posterior
+    built with W (log_evidence counts the measurements kept).  engine.posterior2d is replaced: no device."""
+    V, M, N = 3, 66, 14
+    T = _Tables()
+    rng = np.random.default_rng(9)
+    W = rng.uniform(0.5, 2.0, (V, M))
+    W[0, :10], W[1, ::3] = 0.0, 0.0
+    K = np.array([2, 1, 2])
+    params = np.zeros((V, engine.num_params(2, False, False)))
+    params[:, -2] = [0.01, 0.02, 0.03]
+    r = U.Fit2DResult(params, np.zeros((V, 5), dtype=np.int32), 2, False, W)
+    seen = {}
+
+    def fake(tables, data, numfasc, peaks, maxfasc, sig, shift=None, W=None):
+        seen.update(sig=np.array(sig), shift=np.array(shift), W=W)
+        return np.full((V, 2, N), 0.5 / N), np.zeros(V), np.zeros(V, dtype=np.int32), np.zeros((V, 5), dtype=np.int32), 0
+
+    monkeypatch.setattr(engine, "posterior2d", fake)
+    post = T.posterior(np.ones((V, M)), np.zeros((V, 6)), K, fit=r)
+    n_pos = np.count_nonzero(W > 0, axis=1)
+    assert list(n_pos) == [56, 44, 66]
+    sse = params[:, -2] * W.sum(axis=1)
+    assert np.array_equal(seen["shift"], sse) and seen["W"] is W
+    assert np.allclose(seen["sig"] ** 2, sse / (n_pos - K), rtol=1e-15)
+    Tv = 2.0 * seen["sig"] ** 2
+    want = 0.0 - K * np.log(N) - 0.5 * n_pos * np.log(np.pi * Tv) + 0.5 * np.sum(np.log(np.where(W > 0, W, 1.0)), axis=1)
+    assert np.allclose(post.log_evidence(), want, rtol=1e-14)
+    # without weights: today's rule, M - K, and no W
+    post0 = T.posterior(np.ones((V, M)), np.zeros((V, 6)), K, fit=U.Fit2DResult(params, np.zeros((V, 5), dtype=np.int32), 2, False))
+    assert seen["W"] is None and np.allclose(seen["sig"] ** 2, params[:, -2] * M / (M - K), rtol=1e-15)
+    assert np.allclose(post0.log_evidence(), -K * np.log(N) - 0.5 * M * np.log(np.pi * 2.0 * seen["sig"] ** 2), rtol=1e-14)
+    # fewer positive weights than unknowns: no noise level
+    W1 = np.zeros((V, M))
+    W1[:, 0] = 1.0
+    T.posterior(np.ones((V, M)), np.zeros((V, 6)), K, fit=U.Fit2DResult(params, np.zeros((V, 5), dtype=np.int32), 2, False, W1))
+    assert np.all(np.isnan(seen["sig"]))
