@@ -206,7 +206,8 @@ int mfx_debug_last_guard_count(void);
  * two-fascicle + CSF/EAR kernel 2 short-listed pairs, 3 family items (one-atom / no-atom supports and ambiguous slots
  * evaluated exactly), 4 voxels of the [N, N, 1] screening pipeline handed to the FP64 kernel of the class (ring overflow,
  * an atom inside the span of the CSF column, list overflow, bound check), 5 of them by the bound check (a listed pair
- * whose exact score exceeds its screening bound by more than the margin), summed over the batch; and the screening
+ * whose exact score exceeds its screening bound by more than the margin), 6 voxels of the batched three-fascicle path
+ * whose candidate list overflowed and which the gated voxel-by-voxel path redid, summed over the batch; and the screening
  * kernels' population audit (every two-fascicle voxel compares the split-FP16 cross product of ONE pseudo-random atom pair
  * with its FP64 value, listed or not): 8 audited pairs whose error exceeds a quarter of the screening margin, 9 the largest
  * error in units of 1e-11 (cosine units), 10 audited pairs; which = 0..11. */

@@ -22,6 +22,16 @@
 //     lets 6e-3 .. 0.2 of all triples through at the best two-atom score, 3e-5 .. 1e-3 at the greedy one, 2e-7 at the end;
 //   * everything is batched over voxels (grid z / y): rotation, Gram cross blocks (only the three N x N blocks the triples
 //     need, not the 3N x 3N matrix), statistics, seed, screen, finalize, packing - no per-voxel launch chain.
+// The FP32 / FP16 quantities of the screen are formed in PER-VOXEL UNITS (mfx_k3b_scale_kernel): a power of two sd that
+// brings the largest column norm into [16, 32) and a power of two sy that brings |y| into [1, 2).  The split-FP16 operands,
+// the "always pass" slots (60000^2) and the accumulator markers (3e9, 1e8, -1e30) are absolute numbers: un-normalised,
+// column norms above ~6e4 overflowed the hi halves (NaN test values, triples dropped silently) and norms below ~0.3 put
+// the lo halves into FP16's subnormals, below what MFX_K3M_C covers.  Powers of two scale every FP32 / FP16 value exactly
+// (rsq and sqrt see even powers), so the margins MFX_K3M_D / MFX_K3M_C and every FP64 score are untouched.  For a dictionary
+// with S0 ~ 1 on a few hundred measurements (norms of 3 .. 17) sd is 1, 2 or 4: every FP32 value and every FP16 hi half is
+// the old one times sd, and a lo half differs from that only where the old one was subnormal - now it is rounded with MORE
+// bits, so the test value is closer to the exact one and the margins hold a fortiori; a triple can change sides only
+// inside the margin, where either answer is valid (a passing triple is only a candidate for the FP64 score).
 // A candidate list that overflows (more than MFX_K3B_CAP triples within 1e-9 |y|^2 of the optimum: a one-atom signal
 // fitted with three fascicles ties N^2 triples) flags the voxel; the launcher then runs solve_k3.hip's path for it, gated
 // on the device by that flag (no host read).
@@ -76,11 +86,13 @@ struct K3BArgs {
   double* nrm2;                    // [B][LD] |d|^2
   double* aty;                     // [B][LD] d.y
   double* ysq;                     // [B][2] sequential, pairwise
+  double* scl;                     // [B][4] the voxel's units of the screen's FP32 / FP16 quantities: sd, sd^2, sy, sy^2 (powers of two)
   double2* st3;                    // [B][N] 1/|d3|, y.d3/|d3|
   struct K3Item* items;            // [B][2][ceil(N / KB)][N][KB]: the threshold-independent part of every (atom, third atom) item
   unsigned long long* thr;         // [B] bits of the best score so far
   unsigned long long* seed;        // [B][3] best pair of each dictionary pair: (float score bits << 32) | (p N + q)
   int* ncand;                      // [B][2] candidates appended, overflow flag
+  int* fb;                         // the call's count of voxels whose list overflowed (mfx_debug_last_counter(6)), or null
   unsigned long long* dbg;         // diagnostics (MFX_K3_DEBUG=1), or null: [B][4] triples scored, of them on the spot, pushed, threshold at screen start
   double* cand_score;              // [B][MFX_K3B_CAP]
   long* cand_tuple;                // [B][MFX_K3B_CAP]
@@ -113,6 +125,31 @@ __global__ __launch_bounds__(256) void mfx_k3b_stats_kernel(K3BArgs k) {
     k.thr[b] = 0ull;
     k.seed[3 * b] = k.seed[3 * b + 1] = k.seed[3 * b + 2] = 0ull;
     k.ncand[2 * b] = k.ncand[2 * b + 1] = 0;
+  }
+}
+
+// ---- the voxel's units for the screen (see the head of the file): grid B.  sd 2^k with max|d| sd in [16, 32), sy 2^k with
+// |y| sy in [1, 2); 1 where the norm is zero or not finite (nothing to screen: every test then fails or passes as before)
+__device__ __forceinline__ double k3b_pow2_for(double nrm2, int target_exp) {
+  if (!(nrm2 > 0.0) || !(nrm2 < INFINITY)) return 1.0;
+  int e;
+  (void)frexp(sqrt(nrm2), &e);     // |x| = m 2^e, m in [0.5, 1)
+  return ldexp(1.0, max(-480, min(480, target_exp - e)));   // (the square must stay finite)
+}
+__global__ __launch_bounds__(256) void mfx_k3b_scale_kernel(K3BArgs k) {
+  __shared__ double s_mx[4];
+  const int b = blockIdx.x;
+  double mx = 0.0;
+  for (int c = threadIdx.x; c < k.LD; c += 256) mx = fmax(mx, k.nrm2[(size_t)b * k.LD + c]);   // (fmax drops a NaN)
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
+  if ((threadIdx.x & 63) == 0) s_mx[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    mx = fmax(fmax(s_mx[0], s_mx[1]), fmax(s_mx[2], s_mx[3]));
+    const double sd = k3b_pow2_for(mx, 5), sy = k3b_pow2_for(k.ysq[2 * b], 1);
+    double* o = k.scl + 4 * (size_t)b;
+    o[0] = sd; o[1] = sd * sd; o[2] = sy; o[3] = sy * sy;
   }
 }
 
@@ -202,6 +239,7 @@ __global__ __launch_bounds__(256) void mfx_k3b_pairs_kernel(K3BArgs k) {   // gr
   const double* __restrict__ n2 = k.nrm2 + (size_t)b * k.LD;
   const double* __restrict__ ay = k.aty + (size_t)b * k.LD;
   const long nn = (long)N * N;
+  const double sy2 = k.scl[4 * b + 3];      // (the FP32 key ranks |y|^2-sized scores: in the voxel's units)
   const int p = blockIdx.x * 8 + (threadIdx.x >> 5);
   unsigned long long best = 0ull;
   if (p < N) {
@@ -210,7 +248,7 @@ __global__ __launch_bounds__(256) void mfx_k3b_pairs_kernel(K3BArgs k) {   // gr
     const double* __restrict__ Gp = k.G + ((size_t)b * 3 + which) * nn + (size_t)p * N;
     for (int q = threadIdx.x & 31; q < N; q += 32) {
       const double s = score2(a11, Gp[q], n2[cq0 + q], y1, ay[cq0 + q]);
-      const unsigned long long key = ((unsigned long long)__float_as_uint(fmaxf((float)s, 0.0f)) << 32) | (unsigned long long)((long)p * N + q);
+      const unsigned long long key = ((unsigned long long)__float_as_uint(fmaxf((float)(s * sy2), 0.0f)) << 32) | (unsigned long long)((long)p * N + q);
       if (key > best) best = key;
     }
   }
@@ -252,20 +290,21 @@ __global__ __launch_bounds__(256) void mfx_k3b_items_kernel(K3BArgs k) {
   const double* __restrict__ G3 = k.G + ((size_t)b * 3 + 1 + side) * nn;     // G13 / G23
   const double2 s3 = k.st3[(size_t)b * N + k3];
   const double aa = k.nrm2[(size_t)b * k.LD + side * N + a], ya = k.aty[(size_t)b * k.LD + side * N + a];
+  const double sd = k.scl[4 * b], sd2 = k.scl[4 * b + 1], sy = k.scl[4 * b + 2];   // the voxel's units (head of the file)
   const double u = G3[(size_t)a * N + k3] * s3.x;
   const double np2 = aa - u * u;                            // |d'|^2
   const double zn = ya - u * s3.y;                          // d'.y'
   K3Item it;
   it.z = 0.0f; it.n = 0.0f; it.mg = (_Float16)0.0f;
   if (np2 > 1e-10 * aa) {
-    const float n2f = (float)np2, rs = __builtin_amdgcn_rsqf(n2f);
-    it.n = n2f * rs;
-    it.z = (float)zn * rs;
+    const float n2f = (float)(np2 * sd2), rs = __builtin_amdgcn_rsqf(n2f);
+    it.n = n2f * rs;                                        // |d'| sd
+    it.z = (float)(zn * (sd * sy)) * rs;                    // d'.y'/|d'| sy
     it.mg = (_Float16)(__builtin_amdgcn_sqrtf(MFX_K3M_D) * it.n * 1.002f);
   }
   {   // u in THREE halves (u = uh + um + ul to 2^-32: the products uh uh, uh um, um uh, um um, uh ul, ul uh leave ~1e-9 |u1 u2|);
       // u1 u2 nearly cancels a12, so its error is what the accumulator margin is made of
-    float f = (float)u;
+    float f = (float)(u * sd);
     asm("" : "+v"(f));
     const float h1 = __uint_as_float(__float_as_uint(f) & 0xffffe000u);
     const float r1 = f - h1;
@@ -303,6 +342,7 @@ __global__ __launch_bounds__(MFX_K3M_TI * 64) __attribute__((amdgpu_waves_per_eu
   unsigned long long* thrp = k.thr + b;
   const double y_sq = k.ysq[2 * b];
   const double eps_abs = 1e-9 * y_sq;
+  const double sd2 = k.scl[4 * b + 1], sy = k.scl[4 * b + 2], sy2 = k.scl[4 * b + 3];   // the voxel's units (head of the file)
   for (int q = tid; q < (TI + TJ) * 32; q += WGS) {
     const bool side = q >= TI * 32;
     const int a = side ? j0 + q - TI * 32 : i0 + q;
@@ -333,7 +373,7 @@ __global__ __launch_bounds__(MFX_K3M_TI * 64) __attribute__((amdgpu_waves_per_eu
         float c = -1e30f;
         if (i < N && j < N) {
           const double a11 = s_aa[il], a22 = s_aa[TI * 32 + jl], a12 = G12[(size_t)i * N + j], y1 = s_ay[il], y2 = s_ay[TI * 32 + jl];
-          const double v = fma(MFX_K3M_C, sqrt(a11 * a22), -a12);
+          const double v = fma(MFX_K3M_C, sqrt(a11 * a22), -a12) * sd2;
           c = (float)(v + fabs(v) * 1.3e-7);
           if (score2(a11, a12, a22, y1, y2) >= T0) c = 3e9f;
         }
@@ -452,9 +492,9 @@ __global__ __launch_bounds__(MFX_K3M_TI * 64) __attribute__((amdgpu_waves_per_eu
       const int k3 = k0 + kk;
       float Tp = 1e30f, rth = 0.0f, z3f = 0.0f;
       if (k3 < N) {
-        Tp = (float)(T - z3 * z3) * (1.0f - 2e-7f);         // what the two projected atoms must reach
+        Tp = (float)((T - z3 * z3) * sy2) * (1.0f - 2e-7f);   // what the two projected atoms must reach
         rth = __builtin_amdgcn_rsqf(fmaxf(Tp, 1e-30f)) * (1.0f + 1e-6f);
-        z3f = (float)z3;
+        z3f = (float)(z3 * sy);
       }
       // Straight-line code, selects instead of branches (the branchy form spent a third of its vector instructions
       // re-initialising defaults on every path); which operand an item belongs to is known at compile time: a thread's
@@ -567,7 +607,7 @@ __global__ __launch_bounds__(MFX_K3M_TI * 64) __attribute__((amdgpu_waves_per_eu
                   // E_i = e_i N12, DEN = (1 - c'^2) N12^2, NUM = num N12
                   // (a12 itself comes from the Gram in memory: this path is rare, and a register copy of the tile per column
                   // tile is what kept the workgroup at 128 x 64 pairs)
-                  const float a12f = (float)G12[(size_t)(i0 + ilr) * N + (j0 + t * 32 + lr)];
+                  const float a12f = (float)(G12[(size_t)(i0 + ilr) * N + (j0 + t * 32 + lr)] * sd2);
                   const float n12 = it1.y * it2.y, av = fmaf(-u1f, u2f, a12f);
                   const float E1 = fmaf(it1.x, n12, -av * it2.x), E2 = fmaf(it2.x, n12, -av * it1.x);
                   const float DEN = fmaf(n12, n12, -av * av), NUM = fmaf(it2.x, E2, it1.x * E1);
@@ -703,6 +743,7 @@ __global__ __launch_bounds__(256) void mfx_k3b_finish_kernel(K3BArgs k, PackArgs
     k.w[8 * b] = w[0]; k.w[8 * b + 1] = w[1]; k.w[8 * b + 2] = w[2];
     k.sub[8 * b] = i1; k.sub[8 * b + 1] = i2; k.sub[8 * b + 2] = i3;
     k.minobj[b] = br;
+    if (k.fb && k.ncand[2 * b + 1]) atomicAdd(k.fb, 1);
     s_w3[0] = w[0]; s_w3[1] = w[1]; s_w3[2] = w[2];
     s_col[0] = i1; s_col[1] = N + i2; s_col[2] = 2 * N + i3;
   }

@@ -765,7 +765,7 @@ static int fit_k3_batched(const mfx_plan* p, const double* d_Y, const double* d_
   StreamMem dA(st), dG(st), dcol(st), dst3(st), dsm(st), dcs(st), dct(st), dpart(st), dout(st), dvox(st);
   HIPCHK(dA.alloc(sizeof(double) * (size_t)BT * M * LD));
   HIPCHK(dG.alloc(sizeof(double) * (size_t)BT * 3 * nn));
-  HIPCHK(dcol.alloc(sizeof(double) * ((size_t)BT * LD * 2 + (size_t)BT * 2)));
+  HIPCHK(dcol.alloc(sizeof(double) * ((size_t)BT * LD * 2 + (size_t)BT * 2 + (size_t)BT * 4)));
   HIPCHK(dst3.alloc(sizeof(double2) * (size_t)BT * N));
   const int nblk3 = (N + MFX_K3M_KB - 1) / MFX_K3M_KB;
   StreamMem ditm(st);
@@ -787,11 +787,12 @@ static int fit_k3_batched(const mfx_plan* p, const double* d_Y, const double* d_
   k.M = M; k.N = N; k.LD = LD;
   k.cap = (mfx_thread().k3_cap > 0 && mfx_thread().k3_cap < MFX_K3B_CAP) ? mfx_thread().k3_cap : MFX_K3B_CAP;
   k.A = dA.as<double>(); k.Y = d_Y; k.G = dG.as<double>();
-  k.nrm2 = dcol.as<double>(); k.aty = k.nrm2 + (size_t)BT * LD; k.ysq = k.aty + (size_t)BT * LD;
+  k.nrm2 = dcol.as<double>(); k.aty = k.nrm2 + (size_t)BT * LD; k.ysq = k.aty + (size_t)BT * LD; k.scl = k.ysq + (size_t)BT * 2;
   k.st3 = dst3.as<double2>();
   k.items = ditm.as<K3Item>();
   k.thr = dsm.as<unsigned long long>(); k.seed = k.thr + BT; k.ncand = (int*)(k.seed + 7 * (size_t)BT);
   k.dbg = k3dbg ? k.seed + 3 * (size_t)BT : nullptr;
+  k.fb = (mfx_thread().fb_dev && mfx_thread().fb_device == p->t->device) ? mfx_thread().fb_dev + 6 : nullptr;
   k.cand_score = dcs.as<double>(); k.cand_tuple = dct.as<long>();
   k.part = dpart.as<double>();
   k.w = dout.as<double>(); k.sub = (long*)(k.w + (size_t)BT * 8); k.minobj = (double*)(k.sub + (size_t)BT * 8); k.yrec = k.minobj + BT;
@@ -843,6 +844,7 @@ static int fit_k3_batched(const mfx_plan* p, const double* d_Y, const double* d_
     hipLaunchKernelGGL(mfx_rotate_voxels_kernel, dim3((M + MFX_ROT_ROWS - 1) / MFX_ROT_ROWS, 3, B), dim3(MFX_ROT_WG), 0, st, p->t->d, p->d,
                        d_peaks, peaks_ld, k.vox, dA.as<double>());
     hipLaunchKernelGGL(mfx_k3b_stats_kernel, dim3((LD + 255) / 256, B), dim3(256), 0, st, k);
+    hipLaunchKernelGGL(mfx_k3b_scale_kernel, dim3(B), dim3(256), 0, st, k);
     hipLaunchKernelGGL(mfx_k3b_gram_kernel, dim3((N + 63) / 64, (N + 127) / 128, 3 * B), dim3(256), 0, st, k);
     hipLaunchKernelGGL(mfx_k3b_items_kernel, dim3((unsigned)(((size_t)N * nblk3 * MFX_K3M_KB + 255) / 256), 2, B), dim3(256), 0, st, k);
     hipLaunchKernelGGL(mfx_k3b_pairs_kernel, dim3((N + 7) / 8, 3, B), dim3(256), 0, st, k);

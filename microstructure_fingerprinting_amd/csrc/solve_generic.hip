@@ -317,7 +317,23 @@ __global__ __launch_bounds__(256) void mfx_tuple_finalize(SolveArgs a) {
                    G[(long)col[1] * N + col[1]], G[(long)col[1] * N + col[2]], G[(long)col[2] * N + col[2]], a.Aty[col[0]],
                    a.Aty[col[1]], a.Aty[col[2]], explicit_res, w, res);
     } else {
-      // _4up: NNLS optimum from the Gram (feasible-support enumeration), residual explicitly
+      // _4up: NNLS optimum from the Gram (feasible-support enumeration), residual explicitly.
+      // The columns are taken in a canonical order - by |d|^2, then d.y, then position - for the elimination and for the
+      // residual's sum: two tuples that hold the SAME columns in another order (identical peak directions make two
+      // sub-dictionaries bit-identical: (i, j, ..) and (j, i, ..)) then go through the same operations and tie exactly,
+      // as they do in the reference's Lawson-Hanson solve, and the first of them in scan order wins below.  In tuple order
+      // their residuals differed in the last bits and rounding picked the winner.
+      // (every K' >= 4 result's last bits follow this order, not only a mirrored tuple's)
+      int ord[MFX_GK], tcol[MFX_GK];
+      double dd[MFX_GK], dy[MFX_GK];
+      for (int p = 0; p < n; ++p) { ord[p] = p; tcol[p] = col[p]; dd[p] = G[(long)col[p] * N + col[p]]; dy[p] = a.Aty[col[p]]; }
+      for (int p = 1; p < n; ++p)
+        for (int q = p; q > 0; --q) {
+          const int u = ord[q - 1], v = ord[q];
+          if (dd[u] < dd[v] || (dd[u] == dd[v] && dy[u] <= dy[v])) break;
+          ord[q] = u; ord[q - 1] = v;
+        }
+      for (int p = 0; p < n; ++p) col[p] = tcol[ord[p]];      // canonical order from here to the residual
       double g[MFX_GK * MFX_GK], yy[MFX_GK];
       for (int p = 0; p < n; ++p) {
         yy[p] = a.Aty[col[p]];
@@ -363,6 +379,9 @@ __global__ __launch_bounds__(256) void mfx_tuple_finalize(SolveArgs a) {
         rr += tt * tt;
       }
       res = rr;
+      double wt[MFX_GK];
+      for (int p = 0; p < n; ++p) wt[p] = w[p];
+      for (int p = 0; p < n; ++p) w[ord[p]] = wt[p];          // back to tuple order
     }
     const long key = mfx_order_key(a, t);
     if (res < bres || (res == bres && key < bkey)) {

@@ -41,6 +41,36 @@ def symmetric_reference(sizes, M):
     return _cache[key]
 
 
+FOUR = [((12, 12, 1, 2), 16)]     # _4up: K' = 4 goes through the active-set optimum of the finalize stage
+
+
+def symmetric_problem_four(sizes, M, seed):
+    """(A, y, dicsizes) with K' = 4: two identical sub-dictionaries D, a CSF-like column and sizes[3] EAR-like columns; the
+    signal of two different atoms of D, the CSF column and the first EAR column plus noise (every compartment active).
+    The reference's Lawson-Hanson solve ties the mirrored tuples (i, j, ..) and (j, i, ..) exactly: its first hit,
+    the one with the smaller tuple number, is the answer."""
+    rng = np.random.default_rng(seed)
+    N = sizes[0]
+    D = np.abs(rng.standard_normal((M, N))) + 0.2
+    i, j = rng.choice(N, 2, replace=False)
+    csf = np.exp(-np.linspace(0, 3, M))
+    ear = np.stack([np.exp(-np.linspace(0, 1.0 + k, M)) for k in range(sizes[3])], axis=1)
+    y = 0.5 * D[:, i] + 0.25 * D[:, j] + 0.1 * csf + 0.15 * ear[:, 0] + 0.02 * rng.standard_normal(M)
+    return np.ascontiguousarray(np.hstack([D, D, csf[:, None], ear])), y, np.array(sizes)
+
+
+def symmetric_reference_four(sizes, M):
+    """[(A, y, dicsizes, oracle result)] over SEEDS."""
+    key = ("sym4", tuple(sizes), M)
+    if key not in _cache:
+        out = []
+        for seed in SEEDS:
+            A, y, ds = symmetric_problem_four(sizes, M, seed)
+            out.append((A, y, ds, orc.solve_exhaustive_posweights(A, y, ds)))
+        _cache[key] = out
+    return _cache[key]
+
+
 def swapped(cases):
     """Number of problems in which the oracle returns sub[0] > sub[1]: the pair in the other order than the first of
     the two in tuple-number order."""

@@ -36,6 +36,26 @@ def test_symmetric_subdictionaries(sizes, M):
     assert not bad
 
 
+@pytest.mark.parametrize("sizes,M", C.FOUR, ids=C.shape_id)
+def test_symmetric_subdictionaries_four(sizes, M):
+    """K' = 4 (the finalize stage's active-set optimum): the mirrored tuples tie exactly in the reference's solve, so the
+    first of them must win here too - whatever the units, in which the last bits of an order-dependent evaluation
+    differ (x 1e4: the units at which a fit of [N, N, N, 1] returned the mirror).  Indices exact, weights and objective
+    to 1e-9 (third-party NNLS arithmetic in the reference)."""
+    bad = []
+    for unit in (1.0, 1e4, 1.0 / 3.0):
+        for seed, (A, y, ds, _) in zip(C.SEEDS, C.symmetric_reference_four(sizes, M)):
+            ref = orc.solve_exhaustive_posweights(A * unit, y, ds)
+            got = mfu.solve_exhaustive_posweights(A * unit, y, ds)
+            act = np.array([True, True, True, ref[0][3] > 1e-9])      # (an inactive EAR compartment's index is not defined)
+            if not np.array_equal(got[1][act], ref[1][act]):
+                bad.append((unit, seed, tuple(got[1]), tuple(ref[1])))
+                continue
+            assert np.allclose(got[0], ref[0], rtol=1e-9, atol=1e-12 / unit) and np.isclose(got[3], ref[3], rtol=1e-9, atol=0), (unit, seed)
+    print("%s: %d of %d problems differ from the oracle (unit, seed, got, oracle): %s" % (sizes, len(bad), 3 * len(C.SEEDS), bad[:6]))
+    assert not bad
+
+
 # ---- b. the same through the fit paths: both fascicles along one direction
 @pytest.mark.parametrize("csf_on", [False, True])
 def test_identical_peaks_forced_generic_fit_batch(csf_on):

@@ -16,6 +16,20 @@ def test_symmetric_problems_keep_their_power(sizes, M):
     assert n >= 5
 
 
+@pytest.mark.parametrize("sizes,M", C.FOUR, ids=C.shape_id)
+def test_four_dictionary_mirrors_tie_exactly_in_the_oracle(sizes, M):
+    """K' = 4 with two identical sub-dictionaries: in every problem the two atoms differ and carry weight, the
+    mirrored tuple's objective equals the winner's bit for bit, and the oracle returns the first of the two
+    (sub[0] < sub[1]) - so the GPU test may ask for the oracle's fascicle indices exactly (the EAR index where the EAR
+    compartment is active, as everywhere for K' >= 4)."""
+    N = sizes[0]
+    for A, y, ds, (w, sub, tot, obj, yrec) in C.symmetric_reference_four(sizes, M):
+        assert sub[0] < sub[1] and w[0] > 0.1 and w[1] > 0.1
+        pick = lambda s0, s1: np.ascontiguousarray(A[:, [s0, N + s1, 2 * N, 2 * N + 1 + sub[3]]])
+        one = np.ones(4, dtype=np.int64)
+        assert orc.solve_exhaustive_posweights(pick(sub[1], sub[0]), y, one)[3] == orc.solve_exhaustive_posweights(pick(sub[0], sub[1]), y, one)[3] == obj
+
+
 def test_fit_path_voxels_keep_their_power():
     """The identical-peak voxels of the fit-path tests: the two atoms differ in every voxel, and in at least 5 of 24
     the oracle returns them as (larger, smaller) (measured: 8 without and 13 with the CSF column)."""
