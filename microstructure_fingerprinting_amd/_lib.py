@@ -61,6 +61,9 @@ SOFT2D_EXPORTS = ["mfx_soft2d_abi_version", "mfx_soft2d_max_atoms", "mfx_post2d_
 W2D_EXPORTS = ["mfx_w2d_abi_version", "mfx_w2d_max_atoms", "mfx_wfit2d_batch_dev", "mfx_wfit2d_batch", "mfx_wpost2d_dev",
                "mfx_wpost2d", "mfx_wprofile2d_dev", "mfx_wprofile2d", "mfx_w2d_debug_set_force_explicit"]
 
+# every symbol include/mfx_robust.h declares (robust fits: residual-driven reweighting on the device; versioned on its own)
+ROBUST_EXPORTS = ["mfx_robust_abi_version", "mfx_robust_weights_dev", "mfx_rfit_batch_dev", "mfx_rfit_batch"]
+
 
 class MfxError(RuntimeError):
     pass
@@ -204,6 +207,12 @@ def lib():
     L.mfx_wprofile2d.argtypes = [vp, dp, dp, C.c_int64, dp, C.c_int, C.c_int64, dp, ip, ip]
     L.mfx_w2d_debug_set_force_explicit.argtypes = [C.c_int]
     L.mfx_w2d_debug_set_force_explicit.restype = None
+    L.mfx_robust_abi_version.restype = C.c_int
+    L.mfx_robust_weights_dev.argtypes = [C.c_int, vp, vp, vp, C.c_int64, C.c_int, C.c_double, C.c_int64, vp, vp, vp, vp, vp, vp]
+    L.mfx_rfit_batch_dev.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int64, vp, vp, vp, vp,
+                                     vp, vp, vp]
+    L.mfx_rfit_batch.argtypes = [vp, dp, dp, C.c_int64, ip, bp, dp, C.c_int, C.c_int, dp, C.c_int, C.c_double, C.c_int, C.c_int64,
+                                 dp, dp, dp, ip, ip, lp, ip]
     _lib = L
     return L
 

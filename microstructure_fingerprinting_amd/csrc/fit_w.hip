@@ -780,6 +780,11 @@ int w_class_dev(const mfx_plan* p, const double* d_Y, const double* d_W, int64_t
 
 }  // namespace
 
+int mfx_wfit_class_dev(const mfx_plan* p, const double* d_Y, const double* d_W, int64_t wstride, const double* d_peaks, int K,
+                       const double* d_xc, int maxfasc, int csf_on, int64_t V, double* d_params, int32_t* d_vstat, hipStream_t st) {
+  return w_class_dev(p, d_Y, d_W, wstride, d_peaks, K, d_xc, maxfasc, csf_on, V, d_params, d_vstat, st);
+}
+
 extern "C" int mfx_wfit_abi_version(void) { return 1; }
 
 extern "C" void mfx_wfit_debug_set_force_explicit(int enabled) { g_force_explicit = enabled ? 1 : 0; }

@@ -1079,6 +1079,20 @@ extern "C" int mfx_fit_batch_dev(const mfx_plan* p, const double* d_Y, const dou
   return rc_end;
 }
 
+// one class of the voxel loop for robust.hip (mfx_host.h): what fit_batch_host enqueues for the class
+int mfx_fit_class_plain_dev(const mfx_plan* p, const double* d_Y, const double* d_peaks, int K, const double* d_xc, int maxfasc,
+                            int csf_on, int64_t V, double* d_params, hipStream_t st) {
+  if (V == 0) return MFX_OK;
+  if (V > 0x7fffffff) return fail(MFX_ERR_ARG, "V too large for one launch");
+  const int has_csf = d_xc != nullptr;
+  if (int rc = mfx_fb_begin(st)) return rc;
+  ExtrasHost X;
+  if (int rc = X.build(p->d.M, has_csf, 0, d_xc, nullptr, st)) return rc;
+  if (int rc = fit_class_dev(p, d_Y, d_peaks, 3 * K, nullptr, nullptr, (int)V, K, has_csf, 0, X, maxfasc, csf_on ? 1 : 0, 0, d_params, st))
+    return rc;
+  return mfx_fb_end(st);
+}
+
 // ---- host-buffer voxel loop: pinned staging + chunked H2D on a copy stream overlapped with the kernels on a compute
 // stream (reference loop: mf.py:976-1032).  `rows` (optional) fuses the reference's mask gather `data[mask > 0]`
 // (mf.py:644, 1020-1022) into the staging copy: voxel v's signal is the M doubles at Y + rows[v] * M.

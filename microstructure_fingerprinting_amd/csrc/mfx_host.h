@@ -137,6 +137,15 @@ int mfx_solve_dense_scratch_bytes(int M, int K, int N, int has_csf, size_t* byte
 int mfx_solve_dense_dev(const double* d_A, int M, int K, int N, int has_csf, const double* d_y, int maxfasc, int csf_on,
                         double* d_row, const int* run_if, void* d_scratch, hipStream_t st);
 
+// class launchers for robust.hip: one homogeneous class (every voxel K fascicles, d_peaks [V x 3 K] contiguous, the CSF
+// column d_xc or null) into rows of the (maxfasc, csf_on) layout; they only enqueue.
+// mfx_api.hip: the unweighted class fit, the launch sequence mfx_fit_batch* runs for the class; rows must be zero before
+int mfx_fit_class_plain_dev(const mfx_plan* p, const double* d_Y, const double* d_peaks, int K, const double* d_xc, int maxfasc,
+                            int csf_on, int64_t V, double* d_params, hipStream_t st);
+// fit_w.hip: the weighted class fit behind mfx_wfit_batch* (w_class_dev)
+int mfx_wfit_class_dev(const mfx_plan* p, const double* d_Y, const double* d_W, int64_t wstride, const double* d_peaks, int K,
+                       const double* d_xc, int maxfasc, int csf_on, int64_t V, double* d_params, int32_t* d_vstat, hipStream_t st);
+
 // ---- kernel launchers, one translation unit each
 // FP64 two-fascicle kernel (tu_k2.hip).  With a.list_count set, a.vox_list is a device-side list whose length only the
 // device knows: the launch covers nvox blocks and those beyond *a.list_count exit at once.

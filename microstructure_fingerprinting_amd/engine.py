@@ -1125,6 +1125,197 @@ def fit_weighted(plan, Y, W, K, csf, peaks, maxfasc, csf_on, sig_csf=None, ear=N
     return params, status
 
 
+ROBUST_LOSSES = {'cutoff': 0, 'huber': 1, 'tukey': 2}   # include/mfx_robust.h
+ROBUST_DEFAULTS = {'loss': 'cutoff', 'c': 4.45, 'n_iter': 3}
+
+
+def _robust_rule(loss, c, n_iter=0):
+    """The robust rule's parameters checked (before any device call); returns (loss code, c, n_iter)."""
+    if not isinstance(loss, str) or loss not in ROBUST_LOSSES:
+        raise ValueError("robust loss should be one of %s, got %r" % (", ".join(repr(k) for k in ROBUST_LOSSES), loss))
+    try:
+        cf = float(c)
+    except (TypeError, ValueError):
+        raise ValueError("robust c should be a finite number >= 1, got %r" % (c,))
+    if not (cf >= 1.0) or not np.isfinite(cf):
+        raise ValueError("robust c should be a finite number >= 1, got %r" % (c,))
+    if isinstance(n_iter, bool) or not isinstance(n_iter, (int, np.integer)) or n_iter < 0:
+        raise ValueError("robust n_iter should be a non-negative integer, got %r" % (n_iter,))
+    return ROBUST_LOSSES[loss], cf, int(n_iter)
+
+
+def robust_options(robust):
+    """MFModel.fit's ``robust`` argument -> None (the plain path) or the dict {'loss', 'c', 'n_iter'}, checked."""
+    if robust is None or robust is False:
+        return None
+    opts = dict(ROBUST_DEFAULTS)
+    if robust is not True:
+        if not isinstance(robust, dict):
+            raise ValueError("robust should be None, a bool or a dict with keys among 'loss', 'c', 'n_iter', got %r" % (robust,))
+        unknown = sorted(set(robust) - set(opts), key=str)
+        if unknown:
+            raise ValueError("robust has unknown key(s) %s: it takes 'loss', 'c', 'n_iter'" % ", ".join(repr(k) for k in unknown))
+        opts.update(robust)
+    _robust_rule(opts['loss'], opts['c'], opts['n_iter'])
+    return opts
+
+
+def _robust_w_shapes(M, y_shape, p_shape, w0_shape, wprev_shape=None):
+    """Argument checks of the weight rule's entry points (before any device call); returns (V, w0_stride)."""
+    if len(y_shape) != 2 or y_shape[1] < 1:
+        raise ValueError("data should have shape (voxels, measurements), got %s" % (tuple(y_shape),))
+    V = y_shape[0]
+    if M is not None and y_shape[1] != M:
+        raise ValueError("data has shape %s, protocol has %d measurements" % (tuple(y_shape), M))
+    M = y_shape[1]
+    if p_shape is not None and tuple(p_shape) != (V, M):
+        raise ValueError("prediction should have the data's shape (%d, %d), got %s" % (V, M, tuple(p_shape)))
+    w0_stride = 0
+    if w0_shape is not None:
+        if tuple(w0_shape) == (M,):
+            w0_stride = 0
+        elif tuple(w0_shape) == (V, M):
+            w0_stride = M
+        else:
+            raise ValueError("base weights should have shape (%d, %d) or (%d,), got %s (%d voxels)"
+                             % (V, M, M, tuple(w0_shape), V))
+    if wprev_shape is not None and tuple(wprev_shape) != (V, M):
+        raise ValueError("previous weights should have shape (%d, %d), got %s" % (V, M, tuple(wprev_shape)))
+    return V, w0_stride
+
+
+def robust_weights_dev(d_Y, d_P, d_W0=None, loss='cutoff', c=4.45, d_Wprev=None, out=None):
+    """The robust weight rule on the device (mfx_robust_weights_dev; include/mfx_robust.h states it operation by
+    operation): torch CUDA float64 tensors d_Y, d_P [V, M] (data and prediction), optional base weights d_W0 [V, M] or
+    [M], optional previous weights d_Wprev [V, M] -> (W [V, M], scale [V], state [V] int32, changed [V] int32 or None
+    without d_Wprev).  ``loss`` 'cutoff' | 'huber' | 'tukey', ``c`` >= 1 in units of the median absolute residual.
+    ``out`` may be d_Wprev itself.  Enqueues on torch's current stream and returns without waiting."""
+    import torch
+    code, cf, _ = _robust_rule(loss, c)
+    for t in (d_Y, d_P, d_W0, d_Wprev, out):
+        assert t is None or (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous())
+    V, w0_stride = _robust_w_shapes(None, d_Y.shape, d_P.shape, d_W0.shape if d_W0 is not None else None,
+                                    d_Wprev.shape if d_Wprev is not None else None)
+    M = d_Y.shape[1]
+    if out is None:
+        out = torch.empty((V, M), dtype=torch.float64, device=d_Y.device)
+    assert tuple(out.shape) == (V, M)
+    scale = torch.empty((V,), dtype=torch.float64, device=d_Y.device)
+    state = torch.empty((V,), dtype=torch.int32, device=d_Y.device)
+    changed = torch.empty((V,), dtype=torch.int32, device=d_Y.device) if d_Wprev is not None else None
+    st = torch.cuda.current_stream(d_Y.device).cuda_stream
+    with torch.cuda.device(d_Y.device):
+        L.check(L.lib().mfx_robust_weights_dev(M, d_Y.data_ptr(), d_P.data_ptr(), d_W0.data_ptr() if d_W0 is not None else None,
+                                               w0_stride, code, cf, V, d_Wprev.data_ptr() if d_Wprev is not None else None,
+                                               out.data_ptr(), scale.data_ptr(), state.data_ptr(),
+                                               changed.data_ptr() if changed is not None else None, st))
+    return out, scale, state, changed
+
+
+def robust_weights(Y, P, W0=None, loss='cutoff', c=4.45, Wprev=None, device=0):
+    """robust_weights_dev on NumPy arrays: Y, P [V, M], W0 [V, M] | [M] | None, Wprev [V, M] | None ->
+    (W [V, M], scale [V], state [V] int32, changed [V] int32 or None)."""
+    _robust_rule(loss, c)
+    Y, P = L.f64c(Y), L.f64c(P)
+    W0 = L.f64c(W0) if W0 is not None else None
+    Wprev = L.f64c(Wprev) if Wprev is not None else None
+    _robust_w_shapes(None, Y.shape, P.shape, W0.shape if W0 is not None else None, Wprev.shape if Wprev is not None else None)
+    if L.lib().mfx_device_count() <= 0:
+        raise L.MfxError("no HIP device available (this library has no CPU path)")
+    import torch
+    dev = torch.device("cuda", int(device))
+
+    def t(x):
+        return torch.from_numpy(x).to(dev) if x is not None else None
+    W, scale, state, changed = robust_weights_dev(t(Y), t(P), t(W0), loss, c, t(Wprev))
+    return (W.cpu().numpy(), scale.cpu().numpy(), state.cpu().numpy(), changed.cpu().numpy() if changed is not None else None)
+
+
+def fit_robust_dev(plan, d_Y, d_peaks, maxfasc, d_W0=None, loss='cutoff', c=4.45, n_iter=3):
+    """Device-resident robust fit (mfx_rfit_batch_dev) of ONE voxel class: every voxel has ``maxfasc`` fascicles and no
+    CSF column.  The plain fit (the weighted fit on the base weights d_W0 [V, M] or [M], if given), then ``n_iter``
+    times: predict, reweight by the rule of ``robust_weights_dev``, weighted fit.  torch CUDA float64 tensors ->
+    (params [V, num_params(maxfasc, False, False)], W [V, M], info) with info = {'scale' [V], 'state' [V] int32,
+    'status' [V] int32 (the last weighted fit's), 'n_changed' [n_iter] int32}, all tensors.  Always runs all
+    iterations; enqueues on torch's current stream and returns without waiting."""
+    import torch
+    maxfasc = int(maxfasc)
+    code, cf, n_iter = _robust_rule(loss, c, n_iter)
+    for t in (d_Y, d_peaks if maxfasc > 0 else None, d_W0):
+        assert t is None or (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous())
+    V, w0_stride = _wfit_shapes(plan, d_Y.shape, d_W0.shape if d_W0 is not None else (plan.M,),
+                                d_peaks.shape if maxfasc > 0 else (d_Y.shape[0], 0), maxfasc)
+    dev = d_Y.device
+    params = torch.empty((V, num_params(maxfasc, False, False)), dtype=torch.float64, device=dev)
+    W = torch.empty((V, plan.M), dtype=torch.float64, device=dev)
+    scale = torch.empty((V,), dtype=torch.float64, device=dev)
+    state = torch.empty((V,), dtype=torch.int32, device=dev)
+    status = torch.empty((V,), dtype=torch.int32, device=dev)
+    nch = torch.zeros((n_iter,), dtype=torch.int32, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        L.check(L.lib().mfx_rfit_batch_dev(plan.handle(), d_Y.data_ptr(), d_W0.data_ptr() if d_W0 is not None else None,
+                                           w0_stride, d_peaks.data_ptr() if maxfasc > 0 else None, maxfasc, code, cf, n_iter, V,
+                                           params.data_ptr(), W.data_ptr(), scale.data_ptr(), state.data_ptr(),
+                                           status.data_ptr(), nch.data_ptr() if n_iter > 0 else None, st))
+    return params, W, {'scale': scale, 'state': state, 'status': status, 'n_changed': nch}
+
+
+def fit_robust(plan, Y, K, csf, peaks, maxfasc, csf_on, sig_csf=None, W0=None, loss='cutoff', c=4.45, n_iter=3, ear=None):
+    """Robust fit of a mixed set of voxels on NumPy arrays (mfx_rfit_batch): Y [V, M], fascicle counts K [V] in
+    0..maxfasc, CSF flags csf [V] (or None), peaks [V, 3 maxfasc], optional base weights W0 [V, M] or [M] (rows excluded
+    for good, noise levels) -> (params [V, num_params(maxfasc, csf_on, False)], W [V, M], info).  The plain fit (the
+    weighted fit on W0, if given), then up to ``n_iter`` times: predict, weights from the residuals by the rule of
+    ``robust_weights_dev`` (``loss``, ``c``), weighted fit - with the data resident on the device throughout.  info:
+    'scale' [V] the median absolute residual the last weights were made with, 'state' [V] int32 (0 reweighted, 1 no
+    finite prediction, 2 scale 0, 3 unusable base weights), 'status' [V] int32 of the last weighted fit, 'n_changed'
+    [n_iter] int64 voxels whose weights each iteration changed, 'n_iter_used'.  The loop may stop early once an
+    iteration changed nothing; the results are those of all n_iter iterations.  EAR compartments are not served."""
+    if ear is not None and np.any(ear):
+        raise ValueError("the robust fit is not served for voxels with an EAR compartment (%d flagged)"
+                         % int(np.count_nonzero(ear)))
+    code, cf, n_iter = _robust_rule(loss, c, n_iter)
+    Y = L.f64c(Y)
+    W0 = L.f64c(W0) if W0 is not None else None
+    maxfasc = int(maxfasc)
+    pk = L.f64c(peaks).reshape(Y.shape[0], -1) if (maxfasc > 0 and Y.ndim == 2) else np.zeros((Y.shape[0], 0))
+    V, w0_stride = _wfit_shapes(plan, Y.shape, W0.shape if W0 is not None else (plan.M,), pk.shape, maxfasc)
+    K = np.ascontiguousarray(np.asarray(K).reshape(-1), dtype=np.int32)
+    if K.shape != (V,):
+        raise ValueError("K should have one entry per voxel")
+    if V and (K.min() < 0 or K.max() > maxfasc):
+        raise ValueError("K should lie in 0..maxfasc = %d" % maxfasc)
+    cs = None
+    if csf is not None:
+        cs = np.ascontiguousarray(np.asarray(csf).reshape(-1).astype(bool), dtype=np.uint8)
+        if cs.shape != (V,):
+            raise ValueError("csf should have one entry per voxel")
+    sc = L.f64c(sig_csf).reshape(-1) if sig_csf is not None else None
+    if cs is not None and np.any(cs) and (not csf_on or sc is None):
+        raise ValueError("voxels flagged CSF need csf_on and sig_csf")
+    if csf_on and sc is None:
+        raise ValueError("csf_on needs sig_csf")
+    if sc is not None and sc.shape[0] != plan.M:
+        raise ValueError("sig_csf has %d entries, protocol has %d" % (sc.shape[0], plan.M))
+    M = plan.M
+    params = np.zeros((V, num_params(maxfasc, bool(csf_on), False)))
+    W = np.zeros((V, M))
+    scale = np.zeros(V)
+    state = np.zeros(V, dtype=np.int32)
+    status = np.zeros(V, dtype=np.int32)
+    nch = np.zeros(max(n_iter, 1), dtype=np.int64)
+    used = np.zeros(1, dtype=np.int32)
+    L.check(L.lib().mfx_rfit_batch(plan.handle(), L.dptr(Y), L.dptr(W0) if W0 is not None else None, w0_stride, L.iptr(K),
+                                   L.bptr(cs) if cs is not None else None, L.dptr(pk) if maxfasc > 0 else None, maxfasc,
+                                   int(bool(csf_on)), L.dptr(sc) if sc is not None else None, code, cf, n_iter, V,
+                                   L.dptr(params), L.dptr(W), L.dptr(scale), L.iptr(state), L.iptr(status), L.lptr(nch),
+                                   L.iptr(used)))
+    if V:
+        L.check(L.lib().mfx_plan_status(plan.handle(), None))   # a direction that is not a unit vector: ValueError
+    return params, W, {'scale': scale, 'state': state, 'status': status, 'n_changed': nch[:n_iter].copy(),
+                       'n_iter_used': int(used[0])}
+
+
 def cleanup_select(f1, f2, p1, p2, cos_min, ratio, w_keep, w_small, device=0):
     """Voxel loop of cleanup_2fascicles (mfx_cleanup_2fascicles; ref mf.py:170-335): weights f1, f2 [n] and directions p1, p2
     [n x 3] of the ROI voxels -> (peaks [n x 6], count [n])."""

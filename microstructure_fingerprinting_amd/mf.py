@@ -128,7 +128,7 @@ class MFModel():
 
     # ------------------------------------------------------------------------------------------
     def fit(self, data, mask, numfasc, *, peaks=None, colat_longit=None, tensors=None, pgse_scheme=None,
-            bvals=None, bvecs=None, csf_mask=None, ear_mask=None, verbose=1, parallel=False, weights=None):
+            bvals=None, bvecs=None, csf_mask=None, ear_mask=None, verbose=1, parallel=False, weights=None, robust=None):
         r"""Fingerprinting on the pre-computed dictionary (ref:516-1051; same arguments).
 
         ``weights`` (keyword only, default None: the plain sum of squares, exactly the code path without it):
@@ -138,8 +138,19 @@ class MFModel():
         mask: False drops the measurement) or any numeric type.  Negative or non-finite weights, a voxel without a
         positive weight and weights together with ``ear_mask`` raise ValueError before anything is launched.  MSE is
         ``min_obj / sum W`` and R2 the weighted correlation; ``param_names`` and the maps are unchanged, and the fit
-        keeps ``weights_roi`` in its fitinfo.  With ``parallel=True`` a weighted fit still runs on one device."""
+        keeps ``weights_roi`` in its fitinfo.  With ``parallel=True`` a weighted fit still runs on one device.
+
+        ``robust`` (keyword only, default None; None and False are exactly the code path without it): a robust fit,
+        ``engine.fit_robust`` - the fit, then ``n_iter`` times weights derived from the residuals (per voxel, in units
+        of the median absolute residual) and a weighted refit, iterated on the device.  True stands for
+        ``{'loss': 'cutoff', 'c': 4.45, 'n_iter': 3}`` (drop what lies beyond 4.45 median absolute residuals); a dict
+        overrides any of the three (``loss`` 'cutoff' | 'huber' | 'tukey', ``c`` >= 1).  ``weights`` then are the base
+        weights: a row of weight 0 stays out for good and does not enter the median.  Not served together with
+        ``ear_mask`` (the ValueError of ``weights``); runs on one device.  The fit keeps the final weights as
+        ``weights_roi`` - profiles, intervals and posteriors answer for the final weighted objective - and gains
+        ``robust_info``, ``robust_scale``, ``n_rejected`` and ``outlier_mask()``."""
         VRB = verbose
+        ropts = engine.robust_options(robust)
         nii_affine = None
         t0 = time.time()
         if isinstance(data, str) and VRB >= 2:
@@ -285,6 +296,7 @@ class MFModel():
         weights_roi = None
         if weights is not None:
             weights_roi = self._roi_weights(weights, roi_index, img_shape, num_seq, ROI_size)
+        if weights is not None or ropts is not None:
             if ear_on:
                 raise ValueError("weights are not served together with ear_mask: %d of %d voxel(s) in mask have an EAR "
                                  "compartment." % (int(np.count_nonzero(ear_mask)), ROI_size))
@@ -310,7 +322,19 @@ class MFModel():
             print("Starting estimation in %d voxel(s) on the GPU%s." % (ROI_size, "s (sharded)" if parallel else ""))
         args = (numfasc_roi, csf_mask, ear_mask, peaks_roi, maxfasc, csf_on, ear_on, sig_csf, sig_ear, num_ear)
         devs = list(range(L.lib().mfx_device_count())) if self.SHARD_DEVICES is None else list(self.SHARD_DEVICES)
-        if weights_roi is not None:   # one device: the ROI's rows on the host, then the weighted kernels
+        robust_fit = None
+        if ropts is not None:   # one device: the ROI's rows stay there through the fits and the reweighting between them
+            plan = self.ms_interpolator.plan_for(pgse_scheme)
+            Y_roi = (engine.volume_rows(vol, rows, device=self.ms_interpolator.device) if vol is not None
+                     else (Y[rows] if rows is not None else Y))
+            params_in_mask, w_final, rinfo = engine.fit_robust(plan, Y_roi, numfasc_roi, csf_mask, peaks_roi, maxfasc, csf_on,
+                                                               sig_csf, W0=weights_roi, **ropts)
+            if np.any(rinfo['status']):
+                raise ValueError("robust fit: %d of %d voxel(s) have unusable weights."
+                                 % (int(np.count_nonzero(rinfo['status'])), ROI_size))
+            robust_fit = (rinfo, weights_roi, dict(ropts))
+            weights_roi = w_final
+        elif weights_roi is not None:   # one device: the ROI's rows on the host, then the weighted kernels
             plan = self.ms_interpolator.plan_for(pgse_scheme)
             Y_roi = (engine.volume_rows(vol, rows, device=self.ms_interpolator.device) if vol is not None
                      else (Y[rows] if rows is not None else Y))
@@ -333,6 +357,8 @@ class MFModel():
                    'ear_roi': np.asarray(ear_mask, dtype=bool)}
         if weights_roi is not None:
             fitinfo['weights_roi'] = weights_roi
+        if robust_fit is not None:
+            fitinfo['robust_info'], fitinfo['robust_base'], fitinfo['robust_options'] = robust_fit
         for n in fitinfo['fasc_propnames']:
             fitinfo['_dict_' + n] = self.dic[n]
         if ear_on:
@@ -523,6 +549,9 @@ class MFModelFit():
         self._numfasc_roi, self._csf_roi, self._ear_roi = (fitinfo.get(k) for k in ('numfasc_roi', 'csf_roi', 'ear_roi'))
         self._props = {n: np.asarray(fitinfo['_dict_' + n], dtype=np.float64).reshape(-1) for n in fitinfo['fasc_propnames']}
         self.weights_roi = fitinfo.get('weights_roi')   # float64 [ROI x M] or [M] of a weighted fit, else None (not a map)
+        # of a robust fit (else None): the per-voxel diagnostics of engine.fit_robust, the base weights and the options
+        self.robust_info, self._robust_base = fitinfo.get('robust_info'), fitinfo.get('robust_base')
+        self.robust_options = fitinfo.get('robust_options')
         whole = ROI_size == int(np.prod(mask.shape))
 
         def to_map(vals, extra=()):
@@ -562,8 +591,26 @@ class MFModelFit():
         self.R2 = to_map(model_params[:, -1])
         names += ['MSE', 'R2']
         self.param_names = names
+        if self.robust_info is not None:   # maps of a robust fit (not in param_names: write_nifti leaves them out)
+            self.robust_scale = to_map(self.robust_info['scale'])
+            self.n_rejected = to_map(np.count_nonzero(self._rejected_roi(), axis=1))
         if verbose >= 2:
             print("Microstructure Fingerprinting fit object constructed; maps: %s" % ", ".join(names))
+
+    def _rejected_roi(self):
+        """bool [ROI x M]: the base rows (positive base weight; every row without base weights) whose final weight is 0."""
+        if self.robust_info is None:
+            raise RuntimeError("this fit is not a robust fit (MFModel.fit(..., robust=...)): it has rejected nothing")
+        base = np.ones(self.weights_roi.shape[1], dtype=bool) if self._robust_base is None else np.asarray(self._robust_base) > 0
+        return base & (self.weights_roi == 0)
+
+    def outlier_mask(self):
+        """The measurements a robust fit rejected, bool of shape ``mask.shape + (M,)``: True where a row the base weights
+        admit ended with weight 0 (False outside the ROI)."""
+        rej = self._rejected_roi()
+        out = np.zeros((int(np.prod(self._grid)), rej.shape[1]), dtype=bool)
+        out[self._roi_flat] = rej
+        return out.reshape(self._grid + (rej.shape[1],))
 
     PREDICT_CHUNK = 1 << 16   # ROI voxels per device call of predict() / residuals()
 
