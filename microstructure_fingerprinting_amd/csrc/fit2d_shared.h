@@ -1,6 +1,8 @@
-// fit2d_shared.h -- what fit2d.hip (the fit of 2-D protocols) and soft2d.hip (their soft fits and objective profiles) share:
+// fit2d_shared.h -- what fit2d.hip (the fit of 2-D protocols), soft2d.hip (their soft fits and objective profiles) and
+// w2d.hip (both with measurement weights) share beside the kernel texts of fit2d_kernels.h and soft2d_kernels.h:
 // the 32-byte record of a (direction, row), the kernel that derives the records from the plan records of rotate2d.hip, the
-// expression that turns a record into a dictionary entry, and the geometry of the blocked cross-Gram (128 x 128 atoms per
+// expression that turns a record into a dictionary entry, the kernel that folds the directions' status into the voxel's,
+// the weighted kernels' arguments, and the geometry of the blocked cross-Gram (128 x 128 atoms per
 // workgroup, rows accumulated in chunks of 8).  Every translation unit gets its own copy (anonymous namespace).
 #pragma once
 #include "rot2d_shared.h"
@@ -50,5 +52,48 @@ __global__ void fit2d_rec_kernel(Rot2dDev D, Rot2dPlan pl, int64_t n, F2Rec* __r
   }
   rec[i] = r;
 }
+
+// voxel record from the directions' records: the lowest failing fascicle (the record of mfx_fit2d.h).  ok (may be null):
+// 1 where no direction fails; params (may be null): the NaN row of a voxel with a failing direction
+__global__ void fit2d_status_kernel(const int* __restrict__ pstat, int K, int64_t V, int* __restrict__ vstat, int* __restrict__ ok,
+                                    double* __restrict__ params, int np) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= V) return;
+  int rec[5] = {0, 0, 0, 0, 0};
+  for (int k = 0; k < K; ++k) {
+    const int* s = pstat + 4 * (v * K + k);
+    if (s[0] != MFX_ROT2D_OK) { rec[0] = s[0]; rec[1] = s[1]; rec[2] = s[2]; rec[3] = s[3]; rec[4] = k; break; }
+  }
+  for (int q = 0; q < 5; ++q) vstat[5 * v + q] = rec[q];
+  if (ok) ok[v] = rec[0] == 0;
+  if (params && rec[0] != 0)
+    for (int q = 0; q < np; ++q) params[v * np + q] = __builtin_nan("");
+}
+
+// The arguments of the weighted (WGT) kernels of fit2d_kernels.h and soft2d_kernels.h: those of the unweighted ones and what
+// w2d_prep_kernel (w2d.hip) prepared of the weights.
+struct W2Args {
+  int M, N;
+  const double* base;
+  const F2Rec* rec;      // [V K x M]
+  const double* Y;       // [V x M]
+  const double* W;       // [V x M] or [M]
+  int64_t wstride;       // M or 0
+  const double* S;       // [V x M] sqrt(W)               (w2d_prep_kernel)
+  const double* Ys;      // [V x M] y' = sqrt(W) y        (w2d_prep_kernel)
+  const double* sumw;    // [V] sum_m W                   (w2d_prep_kernel)
+  const int* wstat;      // [V] 0 usable, 1 a negative or non-finite weight, 2 no positive weight
+  const int* vstat;      // [V x 5]
+  // fit
+  double* params;        // [V x num_params]
+  int num_params, maxfasc;
+  // posterior / profile
+  const double* temp;    // [V] (posterior)
+  const double* shift;   // [V] (posterior)
+  double* out;           // [V x K x N]: w or obj
+  double* log_sum;       // [V] (posterior)
+  int* status;           // [V] (posterior)
+  int* partner;          // [V x K x N] or null (profile)
+};
 
 }  // namespace

@@ -2,28 +2,10 @@
 // (include/mfx_soft2d.h): per atom of each fascicle the sum over every partner atom of exp(-(F - shift) / T), normalised
 // per voxel, or the smallest F any partner reaches, on the rotated dictionaries of rotate2d.hip, never written to memory.
 //
-// mfx_soft2d_k2_kernel<MODE>   K = 2: one 4-wave workgroup per voxel on the skeleton of mfx_fit2d_k2_kernel (fit2d.hip).
-//   phase 1  ||y||^2 and the column statistics |d|^2, d.y of both dictionaries: one thread per atom, serial over the rows.
-//   phase 2  the cross-Gram D_0^T D_1 in 128 x 128 blocks on v_mfma_f64_16x16x4_f64, accumulated over the rows in chunks
-//            of 8: the 16 accumulator tiles of a wave (64 x 64 atoms) persist across the chunks, both operands of a chunk
-//            are generated into double-buffered LDS tiles from the staged 32-byte records.  The loop is the fit's, word
-//            for word; nothing depends on M beyond R2_MAX_ROWS.
-//            What happens to a finished block is new.  Every pair is scored through post_pair_frac (posterior.hip's,
-//            restated: F is the profile's value by definition) and one division:
-//              posterior  t = exp((score - (||y||^2 - shift)) / T), one FP64 exp per pair.  A row's partial sum runs over
-//                         the lane's four columns (ascending), then over the 16 lanes of the row; a column's over the
-//                         lane's 16 rows (ascending), then over the four lane groups.  Each wave leaves its 64 row and
-//                         64 column partials in an LDS slab; behind a barrier one thread per atom adds the block's two
-//                         halves, in order, to R0[N] / R1[N] in LDS.  Blocks are walked in order, so every sum has one
-//                         fixed order.  Then Z (the row sums in index order), the division and log_sum.
-//              profile    the same walk with running maxima of the score and their partner indices; strict comparisons
-//                         in ascending index order, and the lower index on equality wherever two lanes meet: a tie goes
-//                         to the lowest index.
-//            Both modes are ONE kernel template with a compile-time mode.  Register budget: 256 per lane
-//            (__launch_bounds__(256, 2)), accumulators in architectural VGPRs, no spill.
-// mfx_soft2d_k1_kernel<MODE>   K = 1: one workgroup per voxel, one thread per atom, serial statistics.
-// A voxel with a failing direction (soft2d_status_kernel wrote its record) gets NaN rows from the kernel itself.
-#include "fit2d_shared.h"
+// The kernels are mfx_soft2d_k2_kernel<MODE, WGT> and mfx_soft2d_k1_kernel<MODE, WGT> of soft2d_kernels.h (described
+// there), instantiated here without measurement weights (WGT = false) and by w2d.hip with them.  This file holds the
+// checks, the launcher and the entry points.
+#include "soft2d_kernels.h"
 #include "../../include/mfx_soft2d.h"
 #include "../../include/mfx_profile.h"   // mfx_profile_cut
 
@@ -31,439 +13,7 @@
 #include <cstring>
 #include <vector>
 
-// profile.hip's MFX_PROFILE_CUT restated as a compile-time constant; the entry points refuse to launch unless it equals
-// mfx_profile_cut()
-#define MFX_SOFT2D_CUT 1e-8
-
 namespace {
-
-constexpr int S2_POST = 0, S2_PROF = 1;
-constexpr size_t S2_LDS_MAX = 160 * 1024;
-constexpr int S2_K1_WG = 256;
-constexpr double S2_EXP_MAX = 700.0;   // exponents above this make the shift unusable (status 2)
-constexpr int S2_NO_PARTNER = 0x7fffffff;
-
-struct S2Args {
-  int M, N;
-  const double* base;
-  const F2Rec* rec;     // [V K x M]
-  const double* Y;      // [V x M]
-  const int* vstat;     // [V x 5]
-  const double* temp;   // [V] (posterior)
-  const double* shift;  // [V] (posterior)
-  double* out;          // [V x K x N]: w or obj
-  double* log_sum;      // [V] (posterior)
-  int* status;          // [V] (posterior)
-  int* partner;         // [V x K x N] or null (profile)
-};
-
-// score s = ||y||^2 - F of one atom pair as the fraction p / q (posterior.hip: post_pair_frac; profile.hip: prof_pair_frac)
-__device__ __forceinline__ void s2_pair_frac(double A11, double A22, double A12, double Y1, double Y2, double p1, double p2,
-                                             double& p, double& q) {
-  const double d1 = fma(-A12, Y2, A22 * Y1);
-  const double d2 = fma(-A12, Y1, A11 * Y2);
-  const double pd = A11 * A22;
-  const double Det = fma(-A12, A12, pd);
-  const double num = fma(Y2, d2, Y1 * d1);
-  const bool both = (d1 > 0.0) & (d2 > 0.0) & (Det > MFX_SOFT2D_CUT * pd);
-  const bool first = p1 * A22 >= p2 * A11;
-  p = both ? num : (first ? p1 : p2);
-  q = both ? Det : (first ? A11 : A22);
-}
-
-__device__ __forceinline__ bool s2_finite(double x) { return fabs(x) <= 1.79769313486231570815e308; }   // false for NaN
-
-// a voxel without a result: NaN rows (partner -1), NaN log_sum and the status code (every thread of the workgroup takes part)
-template <int MODE>
-__device__ __forceinline__ void s2_nan_rows(const S2Args& a, size_t vox, int K, int code, int tid, int wg) {
-  const double nan = __builtin_nan("");
-  const size_t n_out = (size_t)K * a.N;
-  for (size_t n = tid; n < n_out; n += wg) {
-    a.out[vox * n_out + n] = nan;
-    if (MODE == S2_PROF && a.partner) a.partner[vox * n_out + n] = -1;
-  }
-  if (MODE == S2_POST && tid == 0) { a.log_sum[vox] = nan; a.status[vox] = code; }
-}
-
-// voxel record from the directions' records: the lowest failing fascicle (the record of mfx_fit2d.h)
-__global__ void soft2d_status_kernel(const int* __restrict__ pstat, int K, int64_t V, int* __restrict__ vstat) {
-  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= V) return;
-  int rec[5] = {0, 0, 0, 0, 0};
-  for (int k = 0; k < K; ++k) {
-    const int* s = pstat + 4 * (v * K + k);
-    if (s[0] != MFX_ROT2D_OK) { rec[0] = s[0]; rec[1] = s[1]; rec[2] = s[2]; rec[3] = s[3]; rec[4] = k; break; }
-  }
-  for (int q = 0; q < 5; ++q) vstat[5 * v + q] = rec[q];
-}
-
-size_t s2_lds_bytes(int mode, int NP) {
-  const size_t dbl = (size_t)2 * F2_NT * F2_TS + 4 * (size_t)NP + 2 * (size_t)NP + 4 * F2_BLK + 8;
-  const size_t ints = (mode == S2_PROF ? 2 * (size_t)NP + 4 * F2_BLK : 0) + 4;
-  return dbl * sizeof(double) + F2_REC * sizeof(F2Rec) + ints * sizeof(int);
-}
-
-template <int MODE>
-__global__ __launch_bounds__(F2_WG, 2) void mfx_soft2d_k2_kernel(S2Args a) {
-  constexpr bool POST = MODE == S2_POST;
-  extern __shared__ double smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int lg = lane >> 4, lc = lane & 15;
-  const int wr = wave >> 1, wc = wave & 1;
-  const int M = a.M, N = a.N;
-  const int NP = (N + 15) & ~15;   // atoms padded to a multiple of 16 (padded atoms are zero columns)
-  const int ntiles = NP >> 4;
-  const size_t vox = blockIdx.x;
-  if (a.vstat[5 * vox] != 0) {     // a failing direction (workgroup-uniform)
-    s2_nan_rows<MODE>(a, vox, 2, 5, tid, F2_WG);
-    return;
-  }
-  if constexpr (POST) {
-    const double Tv = a.temp[vox], shift = a.shift[vox];
-    if (!(Tv > 0.0) || !s2_finite(Tv) || !s2_finite(shift)) {
-      s2_nan_rows<MODE>(a, vox, 2, 1, tid, F2_WG);
-      return;
-    }
-  }
-
-  // ---- LDS carve-up (s2_lds_bytes mirrors it)
-  double* sT = smem;                                    // [2][F2_NT][F2_TS]: tiles 0..7 the D_0 block, 8..15 the D_1 block
-  double2* s_st = (double2*)(sT + 2 * F2_NT * F2_TS);   // [2][NP] column statistics {|d|^2, d.y} of D_0, then of D_1
-  double* s_R = (double*)(s_st + 2 * NP);               // [2][NP] running row (R0) and column (R1) sums / best scores
-  double* s_sl = s_R + 2 * NP;                          // [4][F2_BLK] the waves' partials of one block: rows by wc, columns by wr
-  double* s_red = s_sl + 4 * F2_BLK;                    // [8]: [0] ||y||^2, [1] ||y||^2 - shift, [2] 1 / T
-  F2Rec* s_rec = (F2Rec*)(s_red + 8);                   // [F2_REC] staged records of two chunks
-  int* s_Ri = (int*)(s_rec + F2_REC);                   // [2][NP] partners of the running bests (profile)
-  int* s_sli = s_Ri + (POST ? 0 : 2 * NP);              // [4][F2_BLK] (profile)
-  int* s_flag = s_sli + (POST ? 0 : 4 * F2_BLK);        // [4]: [0] an exponent above S2_EXP_MAX was met
-
-  const double* __restrict__ yv = a.Y + vox * M;
-  const size_t rec0 = 2 * vox * M;                      // records of direction k: + k M
-
-  // ---- phase 1: ||y||^2 and the column statistics, sequential over the measurements
-  if (tid == 0) {
-    s_flag[0] = 0;
-    double s = 0.0;
-    for (int m = 0; m < M; ++m) s += yv[m] * yv[m];
-    s_red[0] = s;
-    if constexpr (POST) {   // exponent of a pair: (score - c0) / T = -(F - shift) / T; the scan reads both from LDS (no register lives
-      s_red[1] = s - a.shift[vox];   // through the chunk loop for them)
-      s_red[2] = 1.0 / a.temp[vox];
-    }
-  }
-  for (int col = tid; col < 2 * NP; col += F2_WG) {
-    const int k = col >= NP, n = col - k * NP;
-    double a2 = 0.0, ay = 0.0;
-    if (n < N) {
-#pragma unroll 4
-      for (int m = 0; m < M; ++m) {
-        const F2Rec r = a.rec[rec0 + (size_t)k * M + m];
-        const double d = f2_value(a.base, r, n);
-        a2 += d * d;
-        ay += yv[m] * d;
-      }
-    }
-    s_st[col] = double2{a2, ay};
-    s_R[col] = POST ? 0.0 : -1.0;          // a score is never negative: the first real pair wins
-    if constexpr (!POST) s_Ri[col] = S2_NO_PARTNER;
-  }
-  __syncthreads();
-  bool over = false;                       // this lane met an exponent above S2_EXP_MAX on a pair of two real atoms
-
-  // ---- phase 2: cross-Gram blocks accumulated over the rows in chunks (fit2d.hip's loop), then the block's pairs
-  const int nblk = (NP + F2_BLK - 1) / F2_BLK;
-  const int nchunks = (M + F2_MC - 1) / F2_MC;
-  const int gk = wave >> 1;
-  const int gc = tid & (F2_BLK - 1);
-  double* const gdst0 = sT + (gk * 8 + (gc >> 4)) * F2_TS + (gc & 15);
-  auto stage_rec = [&](int ch) {
-    if (tid < 2 * F2_MC) {
-      const int side = tid / F2_MC, r = tid % F2_MC, m = ch * F2_MC + r;
-      const int q = ((ch & 1) * 2 + side) * F2_MC + r;
-      const bool in = m < M;                      // rows beyond the protocol: S_par = 0 on the reference's zero -> entry 0
-      F2Rec rc = a.rec[rec0 + (size_t)side * M + (in ? m : 0)];
-      if (!in) { rc.s = 0.0; rc.dx = 0.0; rc.o = R2_OP_ZERO; rc.a = 0; rc.b = 0; }
-      s_rec[q] = rc;
-    }
-  };
-
-  for (int rb = 0; rb < nblk; ++rb) {
-    const int nta = min(max(ntiles - (rb * 8 + wr * 4), 0), 4);   // valid row tiles of this wave (wave-uniform)
-    for (int cb = 0; cb < nblk; ++cb) {
-      const int ntb = min(max(ntiles - (cb * 8 + wc * 4), 0), 4);
-      const int gn = (gk ? cb : rb) * F2_BLK + gc;   // this thread's atom
-      const double* gbase = a.base + (gn < N ? gn : 0);
-      double va[F2_MC], vb[F2_MC];
-      auto load_chunk = [&](int ch) {
-        const int q0 = ((ch & 1) * 2 + gk) * F2_MC;
-#pragma unroll
-        for (int r = 0; r < F2_MC; ++r) {
-          va[r] = gbase[s_rec[q0 + r].a];
-          vb[r] = gbase[s_rec[q0 + r].b];
-        }
-      };
-      auto store_chunk = [&](int ch, int buf) {
-        const int q0 = ((ch & 1) * 2 + gk) * F2_MC;
-        double* dst = gdst0 + (size_t)buf * (F2_NT * F2_TS);
-#pragma unroll
-        for (int r = 0; r < F2_MC; ++r) {
-          const double v = r2_value(s_rec[q0 + r].o, s_rec[q0 + r].s, va[r], s_rec[q0 + r].dx, vb[r]);
-          dst[r * 16] = gn < N ? v : 0.0;   // atoms beyond the dictionary: zero columns
-        }
-      };
-      d4 acc[4][4];
-#pragma unroll
-      for (int ti = 0; ti < 4; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 4; ++tj) acc[ti][tj] = d4{0, 0, 0, 0};
-
-      stage_rec(0);
-      stage_rec(1);
-      __syncthreads();
-      load_chunk(0);
-      store_chunk(0, 0);
-      __syncthreads();
-      for (int ch = 0; ch < nchunks; ++ch) {
-        const int buf = ch & 1;
-        const bool more = ch + 1 < nchunks;
-        if (ch + 2 < nchunks) stage_rec(ch + 2);   // into the parity of chunk ch, whose records nobody reads any more
-        if (more) load_chunk(ch + 1);
-        if (nta > 0 && ntb > 0) {
-          const double* tA = sT + (size_t)buf * (F2_NT * F2_TS) + (wr * 4) * F2_TS + lg * 16 + lc;
-          const double* tB = sT + (size_t)buf * (F2_NT * F2_TS) + (8 + wc * 4) * F2_TS + lg * 16 + lc;
-#pragma unroll
-          for (int kk = 0; kk < F2_MC / 4; ++kk) {
-            double av[4], bv[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) { av[t] = tA[t * F2_TS + kk * 64]; bv[t] = tB[t * F2_TS + kk * 64]; }
-#pragma unroll
-            for (int ti = 0; ti < 4; ++ti)
-#pragma unroll
-              for (int tj = 0; tj < 4; ++tj)
-                acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[ti], bv[tj], acc[ti][tj], 0, 0, 0);
-          }
-        }
-        if (more) store_chunk(ch + 1, buf ^ 1);
-        __syncthreads();
-      }
-
-      // ---- the block's pairs.  C/D layout of a tile: column lc, rows lg + 4 r.  Row i of the lane: its columns
-      // j = lc (mod 16) of this wave's half of the block, ascending; column j: the lane's 16 rows, ascending.
-      double cs[4];   // per column tile: the lane's column sum / best score
-      int ci[4];      // (profile) and its row
-#pragma unroll
-      for (int t = 0; t < 4; ++t) { cs[t] = POST ? 0.0 : -1.0; ci[t] = S2_NO_PARTNER; }
-      mfx_static_for<0, 4>([&](auto tic) {
-        constexpr int ti = decltype(tic)::value;
-#pragma unroll 1
-        for (int r = 0; r < 4; ++r) {
-          const int il = wr * 64 + ti * 16 + lg + 4 * r;   // row within the block
-          const int i = rb * F2_BLK + il;
-          double rv = POST ? 0.0 : -1.0;
-          int rj = S2_NO_PARTNER;
-          if (ti < nta) {   // wave-uniform; i < NP
-            const double A11 = s_st[i].x, Y1 = s_st[i].y;
-            const double yp1 = fmax(Y1, 0.0), p1 = yp1 * yp1;
-            mfx_static_for<0, 4>([&](auto tjc) {
-              constexpr int tj = decltype(tjc)::value;
-              if (tj < ntb) {   // wave-uniform; j < NP
-                const int j = cb * F2_BLK + wc * 64 + tj * 16 + lc;
-                const double A22 = s_st[NP + j].x, Y2 = s_st[NP + j].y;
-                const double yp2 = fmax(Y2, 0.0), p2 = yp2 * yp2;
-                const d4& v = acc[ti][tj];
-                const double A12 = r == 0 ? v[0] : (r == 1 ? v[1] : (r == 2 ? v[2] : v[3]));
-                double p, q;
-                s2_pair_frac(A11, A22, A12, Y1, Y2, p1, p2, p, q);
-                const double s = q > 0.0 ? p / q : 0.0;
-                const bool ok = (i < N) & (j < N);   // padded atoms contribute nothing
-                if constexpr (POST) {
-                  const double e = (s - s_red[1]) * s_red[2];
-                  over |= ok & (e > S2_EXP_MAX);
-                  const double tv = ok ? exp(e) : 0.0;
-                  rv += tv;
-                  cs[tj] += tv;
-                  __builtin_amdgcn_sched_barrier(0);   // one pair's exp at a time: four interleaved ones do not fit the register budget
-                } else {
-                  const double sv = ok ? s : -1.0;
-                  const bool brow = sv > rv;        // ascending j: the first best stays
-                  rv = brow ? sv : rv;
-                  rj = brow ? j : rj;
-                  const bool bcol = sv > cs[tj];    // ascending i
-                  cs[tj] = bcol ? sv : cs[tj];
-                  ci[tj] = bcol ? i : ci[tj];
-                }
-              }
-            });
-          }
-          // over the 16 lanes of the row (a butterfly: every lane ends with the same value)
-#pragma unroll
-          for (int o = 1; o < 16; o <<= 1) {
-            const double v2 = __shfl_xor(rv, o);
-            if constexpr (POST) {
-              rv += v2;
-            } else {
-              const int j2 = __shfl_xor(rj, o);
-              const bool take = (v2 > rv) || (v2 == rv && j2 < rj);
-              rv = take ? v2 : rv;
-              rj = take ? j2 : rj;
-            }
-          }
-          if (lc == 0) {
-            s_sl[wc * F2_BLK + il] = rv;
-            if constexpr (!POST) s_sli[wc * F2_BLK + il] = rj;
-          }
-        }
-      });
-      // columns: over the four lane groups (rows lg + 4 r), then one slab entry per wave and column
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-#pragma unroll
-        for (int o = 16; o <= 32; o <<= 1) {
-          const double v2 = __shfl_xor(cs[t], o);
-          if constexpr (POST) {
-            cs[t] += v2;
-          } else {
-            const int i2 = __shfl_xor(ci[t], o);
-            const bool take = (v2 > cs[t]) || (v2 == cs[t] && i2 < ci[t]);
-            cs[t] = take ? v2 : cs[t];
-            ci[t] = take ? i2 : ci[t];
-          }
-        }
-        if (lg == 0) {
-          const int jl = wc * 64 + t * 16 + lc;
-          s_sl[(2 + wr) * F2_BLK + jl] = cs[t];
-          if constexpr (!POST) s_sli[(2 + wr) * F2_BLK + jl] = ci[t];
-        }
-      }
-      __syncthreads();
-      // the block's two halves, in order, into the running results: threads 0..127 the rows, 128..255 the columns (an
-      // entry of s_R belongs to one thread for the whole kernel; the slab is rewritten behind the next block's barriers)
-      {
-        const int side = tid >> 7, l = tid & (F2_BLK - 1);
-        const int n = (side ? cb : rb) * F2_BLK + l;
-        if (n < NP) {
-          const double h0 = s_sl[(2 * side) * F2_BLK + l], h1 = s_sl[(2 * side + 1) * F2_BLK + l];
-          double cur = s_R[side * NP + n];
-          if constexpr (POST) {
-            cur += h0;
-            cur += h1;
-          } else {
-            int ix = s_Ri[side * NP + n];
-            if (h0 > cur) { cur = h0; ix = s_sli[(2 * side) * F2_BLK + l]; }       // ascending partner index: the first best stays
-            if (h1 > cur) { cur = h1; ix = s_sli[(2 * side + 1) * F2_BLK + l]; }
-            s_Ri[side * NP + n] = ix;
-          }
-          s_R[side * NP + n] = cur;
-        }
-      }
-    }
-  }
-  if constexpr (POST) {
-    if (over) s_flag[0] = 1;
-  }
-  __syncthreads();
-
-  // ---- last phase
-  if constexpr (POST) {
-    // Z in index order (every thread, the same value), status, normalisation, log_sum
-    double Z = 0.0;
-    for (int i = 0; i < N; ++i) Z += s_R[i];
-    if (s_flag[0] != 0 || !(Z > 0.0) || !s2_finite(Z)) {
-      s2_nan_rows<MODE>(a, vox, 2, 2, tid, F2_WG);
-      return;
-    }
-    for (int n = tid; n < N; n += F2_WG) {
-      a.out[(vox * 2 + 0) * N + n] = s_R[n] / Z;
-      a.out[(vox * 2 + 1) * N + n] = s_R[NP + n] / Z;
-    }
-    if (tid == 0) {
-      a.log_sum[vox] = log(Z) - a.shift[vox] / a.temp[vox];
-      a.status[vox] = 0;
-    }
-  } else {
-    const double y_sq = s_red[0];
-    for (int n = tid; n < N; n += F2_WG) {
-      a.out[(vox * 2 + 0) * N + n] = y_sq - s_R[n];
-      a.out[(vox * 2 + 1) * N + n] = y_sq - s_R[NP + n];
-      if (a.partner) {
-        a.partner[(vox * 2 + 0) * N + n] = s_Ri[n];
-        a.partner[(vox * 2 + 1) * N + n] = s_Ri[NP + n];
-      }
-    }
-  }
-}
-
-// K = 1: one workgroup per voxel, one thread per atom; the unnormalised t(i) wait in the output row for Z
-template <int MODE>
-__global__ __launch_bounds__(S2_K1_WG) void mfx_soft2d_k1_kernel(S2Args a) {
-  constexpr bool POST = MODE == S2_POST;
-  __shared__ double s_ysq;
-  __shared__ int s_over;
-  const int tid = threadIdx.x;
-  const int M = a.M, N = a.N;
-  const size_t vox = blockIdx.x;
-  if (a.vstat[5 * vox] != 0) {
-    s2_nan_rows<MODE>(a, vox, 1, 5, tid, S2_K1_WG);
-    return;
-  }
-  double Tv = 1.0, shift = 0.0;
-  if constexpr (POST) {
-    Tv = a.temp[vox];
-    shift = a.shift[vox];
-    if (!(Tv > 0.0) || !s2_finite(Tv) || !s2_finite(shift)) {
-      s2_nan_rows<MODE>(a, vox, 1, 1, tid, S2_K1_WG);
-      return;
-    }
-  }
-  const double* __restrict__ yv = a.Y + vox * M;
-  if (tid == 0) {
-    s_over = 0;
-    double s = 0.0;
-    for (int m = 0; m < M; ++m) s += yv[m] * yv[m];
-    s_ysq = s;
-  }
-  __syncthreads();
-  const double y_sq = s_ysq, c0 = y_sq - shift, iT = 1.0 / Tv;
-  double* row = a.out + vox * N;
-  bool over = false;
-  for (int n = tid; n < N; n += S2_K1_WG) {
-    double a2 = 0.0, ay = 0.0;
-#pragma unroll 4
-    for (int m = 0; m < M; ++m) {
-      const F2Rec r = a.rec[vox * M + m];
-      const double d = f2_value(a.base, r, n);
-      a2 += d * d;
-      ay += yv[m] * d;
-    }
-    const double yp = fmax(ay, 0.0);
-    const double s = a2 > 0.0 ? yp * yp / a2 : 0.0;
-    if constexpr (POST) {
-      const double e = (s - c0) * iT;
-      over |= e > S2_EXP_MAX;
-      row[n] = exp(e);
-    } else {
-      row[n] = y_sq - s;
-      if (a.partner) a.partner[vox * N + n] = -1;
-    }
-  }
-  if constexpr (POST) {
-    if (over) s_over = 1;
-    __syncthreads();   // the row is written and visible to the workgroup
-    double Z = 0.0;
-    for (int i = 0; i < N; ++i) Z += row[i];   // index order, every thread the same value
-    __syncthreads();   // every thread has read the unnormalised row before it is overwritten
-    if (s_over != 0 || !(Z > 0.0) || !s2_finite(Z)) {
-      s2_nan_rows<MODE>(a, vox, 1, 2, tid, S2_K1_WG);
-      return;
-    }
-    for (int n = tid; n < N; n += S2_K1_WG) row[n] = row[n] / Z;
-    if (tid == 0) {
-      a.log_sum[vox] = log(Z) - shift / Tv;
-      a.status[vox] = 0;
-    }
-  }
-}
 
 const char* S2_NO_DEVICE = "no HIP device available (this library has no CPU path)";
 
@@ -475,20 +25,14 @@ int s2_require_device(int device) {
   return MFX_OK;
 }
 
-int s2_max_atoms(int mode) {
-  int n = 0;
-  while (n < (1 << 20) && s2_lds_bytes(mode, n + 16) <= S2_LDS_MAX) n += 16;
-  return n;
-}
-
 template <int MODE>
 int s2_launch(const S2Args& a, int K, int64_t V, hipStream_t st) {
   if (K == 2) {
-    const size_t lds = s2_lds_bytes(MODE, (a.N + 15) & ~15);
-    HIPCHK(hipFuncSetAttribute((const void*)mfx_soft2d_k2_kernel<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(mfx_soft2d_k2_kernel<MODE>, dim3((unsigned)V), dim3(F2_WG), lds, st, a);
+    const size_t lds = s2_lds_bytes(MODE, (a.N + 15) & ~15, false);
+    HIPCHK(hipFuncSetAttribute((const void*)mfx_soft2d_k2_kernel<MODE, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((mfx_soft2d_k2_kernel<MODE, false>), dim3((unsigned)V), dim3(F2_WG), lds, st, a);
   } else {
-    hipLaunchKernelGGL(mfx_soft2d_k1_kernel<MODE>, dim3((unsigned)V), dim3(S2_K1_WG), 0, st, a);
+    hipLaunchKernelGGL((mfx_soft2d_k1_kernel<MODE, false>), dim3((unsigned)V), dim3(S2_K1_WG), 0, st, a);
   }
   HIPCHK(hipGetLastError());
   return MFX_OK;
@@ -505,8 +49,8 @@ int s2_check(const char* fn, int mode, const mfx_rot2d* h, const void* Y, const 
   if (V > 0x3fffffff / K) return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: more than 2^30 directions in one call", fn);
   if (((size_t)2 * h->d.K + h->d.C + 2) * (size_t)h->d.N > 0x7fffffff)
     return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: tables of more than 2^31 doubles", fn);
-  if (K == 2 && s2_lds_bytes(mode, (h->d.N + 15) & ~15) > S2_LDS_MAX)
-    return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: N = %d atoms exceed the %d that fit in LDS", fn, h->d.N, s2_max_atoms(mode));
+  if (K == 2 && s2_lds_bytes(mode, (h->d.N + 15) & ~15, false) > S2_LDS_MAX)
+    return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: N = %d atoms exceed the %d that fit in LDS", fn, h->d.N, s2_max_atoms(mode, false));
   if (mfx_profile_cut() != MFX_SOFT2D_CUT) return mfx_fail(MFX_ERR_HIP, "%s: built with a cut other than the profile's", fn);
   return MFX_OK;
 }
@@ -525,7 +69,8 @@ int s2_enqueue(const char* fn, int mode, const mfx_rot2d* h, const double* d_Y, 
   HIPCHK(pstat.alloc(sizeof(int) * 4 * (size_t)V * K));
   if (int rc = pm.alloc(V * K, M, pstat.as<int>())) return rc;
   if (int rc = mfx_rot2d_plan_enqueue(h, d_peaks, V * K, pm.pl, st)) return rc;
-  hipLaunchKernelGGL(soft2d_status_kernel, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, pstat.as<int>(), K, V, d_dir_status);
+  hipLaunchKernelGGL(fit2d_status_kernel, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, pstat.as<int>(), K, V, d_dir_status,
+                     (int*)nullptr, (double*)nullptr, 0);
   HIPCHK(hipGetLastError());
   const size_t nrec = (size_t)V * K * M;
   HIPCHK(rec.alloc(nrec * sizeof(F2Rec) + 64));
@@ -583,7 +128,7 @@ extern "C" int mfx_soft2d_abi_version(void) { return 1; }
 
 extern "C" int mfx_soft2d_max_atoms(void* hv, int what) {
   if (!hv || (what != S2_POST && what != S2_PROF)) return 0;
-  return s2_max_atoms(what);
+  return s2_max_atoms(what, false);
 }
 
 extern "C" int mfx_post2d_dev(void* hv, const double* d_Y, const double* d_peaks, int K, const double* d_T, const double* d_shift,

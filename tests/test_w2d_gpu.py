@@ -159,7 +159,7 @@ def test_profile_and_posterior_referee(shape, kind):
 
 
 # ---- 3. W = 1 is the unweighted entry point, bit for bit
-@pytest.mark.parametrize("shape", [W2.SHAPES[0], W2.SHAPES[2]], ids=[W2.IDS[0], W2.IDS[2]])
+@pytest.mark.parametrize("shape", W2.SHAPES, ids=W2.IDS)
 def test_unit_weights_bit_for_bit(shape):
     c = case(shape)
     T, V, Y, peaks = c["T"], c["V"], c["Y"], c["peaks"]
