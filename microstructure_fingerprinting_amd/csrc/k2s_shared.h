@@ -124,9 +124,13 @@ __device__ __forceinline__ void k2s_push(const LDS& L, int scap, double S, int i
   L.s_cand[idx].j = j;
 }
 
-// ---- phases 0 and 1 of a voxel: signal and knot-interval descriptors -> LDS, column statistics, margins, starting threshold
-template <int KS, int NB, bool BR, bool XC, int PQF, int WG>
-__device__ __forceinline__ K2sVoxel k2s_prologue(const FitK2Args& a, const K2sLds<KS, NB, BR, XC, PQF>& L, const int vox, const int tid) {
+// ---- phases 0 and 1 of a voxel: signal and knot-interval descriptors -> LDS, column statistics, margins, starting threshold.
+// DEFER (fit_k2s.hip, !XC) with defer_d2 (workgroup-uniform): the caller makes D2's statistics itself - the sweep of a shared
+// last row tile reads the same bytes - and runs k2s_best_single_late after them; phase 1 then leaves the margins only (they
+// do not depend on the statistics) and the threshold at 0.  Without DEFER the two conditions below are compile-time true.
+template <int KS, int NB, bool BR, bool XC, int PQF, int WG, bool DEFER = false>
+__device__ __forceinline__ K2sVoxel k2s_prologue(const FitK2Args& a, const K2sLds<KS, NB, BR, XC, PQF>& L, const int vox, const int tid,
+                                                 [[maybe_unused]] const bool defer_d2 = false) {
   constexpr int MP = KS * 16, NW = WG / 64;
   const int lane = tid & 63, wave = tid >> 6;
   const int M = a.P.M, N = a.T.N, ldn = a.T.ldn;
@@ -199,7 +203,7 @@ __device__ __forceinline__ K2sVoxel k2s_prologue(const FitK2Args& a, const K2sLd
   const double y_sq_p = XC ? fmax(y_sq - yx * yx, 0.0) : y_sq;   // |y'|^2
   double my_s[2] = {0.0, 0.0};
   int my_n[2] = {0, 0};
-  {
+  if (!(DEFER && defer_d2)) {
     // The vector-memory pipe of a CU retires roughly one wave load per 20 cycles whatever its width (<= 16 B per
     // lane), and this kernel issues ~1e4 of them per voxel: table entries are therefore fetched two atoms at a
     // time (16 B: {ylo, slope} of atoms n, n+1).  A thread accumulates the column pairs v = tid + 512 p (atoms 2v,
@@ -328,7 +332,7 @@ __device__ __forceinline__ K2sVoxel k2s_prologue(const FitK2Args& a, const K2sLd
   // best single atom of each dictionary (first index on ties): they stand for every pair whose optimum
   // has one active atom (mf_utils.py:357-379); the exact stage expands the winner's family.  D2's here, D1's
   // after the rounds (its statistics come with the A operands); the threshold starts from what is known.
-  {
+  if (!(DEFER && defer_d2)) {
     double* s_bs = s_red;            // [2][8]
     int* s_bn = (int*)(s_red + 16);  // [2][8]
 #pragma unroll
@@ -362,7 +366,7 @@ __device__ __forceinline__ K2sVoxel k2s_prologue(const FitK2Args& a, const K2sLd
   // treat as a tie must reach its list.
   const double mrg = mfx_readlane_f64(XC ? fmax(dc_eff * y_sq_p + 2e-6 * ramp * sqrt(y_sq * y_sq_p), 1e-9 * y_sq) : dc_eff * y_sq_p, 0);   // |S(c~) - S(c)| <= mrg
   const double etol = mfx_readlane_f64(XC ? dc_eff * sqrt(y_sq_p) + 2e-6 * ramp * sqrt(y_sq) : dc_eff * sqrt(y_sq_p), 0);   // |e(c~) - e(c)| <= etol
-  {
+  if (!(DEFER && defer_d2)) {
     double* s_bs = s_red;            // [2][8]
     int* s_bn = (int*)(s_red + 16);  // [2][8]
     if (tid == 0) {
@@ -395,6 +399,37 @@ __device__ __forceinline__ K2sVoxel k2s_prologue(const FitK2Args& a, const K2sLd
   }
   __syncthreads();
   return K2sVoxel{y_sq, yx, ramp, dc_eff, mrg, etol};
+}
+
+// ---- phase 1's "best single atom of D2" step for a caller that deferred D2's statistics (!XC): every wave hands in the best
+// single atom of the columns it made (first index on ties; score 0 when none is positive) in its slot of s_red - D2's half
+// of the prologue's [2][8] - and a workgroup barrier has passed since.  The sweep has begun: the ring may hold entries - the
+// winner is appended by the ring's own rule - and the threshold is only raised.  Ends with a workgroup barrier, like the
+// prologue.
+template <int NW, class LDS>
+__device__ __forceinline__ void k2s_best_single_late(const FitK2Args& a, const LDS& L, const int tid, const double mrg) {
+  const double* s_bs = L.s_red + 8;            // [8]
+  const int* s_bn = (const int*)(L.s_red + 16) + 8;  // [8]
+  if (tid == 0) {
+    double s = s_bs[0];
+    int n = s_bn[0];
+    for (int w = 1; w < NW; ++w) {
+      const double s2 = s_bs[w];
+      const int n2 = s_bn[w];
+      if (s2 > s || (s2 == s && n2 < n)) { s = s2; n = n2; }
+    }
+    if (s > 0.0) k2s_push(L, a.scap, s + mrg, 0, n | MFX_S_BOUND);   // exact single-atom score up to the statistics' rounding
+    // single-atom scores are exact: a pair matters only if S(c) >= s, i.e. S(c~) >= s - mrg
+    unsigned long long tb = mfx_nonneg_bits(s - mrg);
+#ifdef MFX_STAMPS_RND   // experiment: a starting threshold handed in by the tool (slot 15), as in the prologue
+    if (a.stamps) {
+      const double t0 = __longlong_as_double((long long)a.stamps[(size_t)blockIdx.x * 16 + 15]);
+      if (t0 > s - mrg) tb = mfx_nonneg_bits(t0);
+    }
+#endif
+    if (tb > L.s_thr[0]) L.s_thr[0] = tb;
+  }
+  __syncthreads();
 }
 
 // ---- everything after the sweep: D1's best single atom joins the candidates; hand-back decisions; XC: the voxel's short list;

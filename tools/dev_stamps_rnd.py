@@ -5,7 +5,7 @@ import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from microstructure_fingerprinting_amd import _lib as L
-L.LIB_PATH = os.path.join(ROOT, "microstructure_fingerprinting_amd", "libmfx_stamps_rnd.so")
+L.LIB_PATH = os.path.abspath(sys.argv[2]) if len(sys.argv) > 2 else os.path.join(ROOT, "microstructure_fingerprinting_amd", "libmfx_stamps_rnd.so")
 from microstructure_fingerprinting_amd import engine, synth
 import bench
 V = int(sys.argv[1]) if len(sys.argv) > 1 else 8192
@@ -14,6 +14,10 @@ dev = torch.device("cuda", 0)
 ms.device = 0
 plan = engine.Plan(ms.device_tables(), scheme=sch)
 M, N = sch.shape[0], ms.num_subs
+# order of the phases: the kernel sweeps a shared last row tile first (ntiles > 1 and ntiles % 8 == 1: fit_k2s.hip); a third
+# argument "plain" is for a library from before that (the shared tile last), e.g. to measure a parent commit's build
+NTILES = (N + 31) // 32
+FUSED = NTILES > 1 and NTILES % 8 == 1 and not (len(sys.argv) > 3 and sys.argv[3] == "plain")
 rng = np.random.default_rng(1000)
 peaks_h = np.concatenate([synth.unit_vectors(rng, V), synth.unit_vectors(rng, V)], axis=1)
 atoms_h = rng.integers(0, N, (V, 2)).astype(np.int32)
@@ -37,8 +41,14 @@ def run(thr0=None):
     torch.cuda.synchronize()
     raw = st.cpu().numpy().astype(np.float64)[V // 4: 3 * V // 4]
     x = raw[(raw[:, :9] > 0).all(axis=1)]
-    d = np.diff(x[:, :9], axis=1)
-    for k, nm in enumerate(names):
+    # the shared last row tile (slots 7, 8) runs FIRST when the kernel fuses D2's statistics into it: FUSED below
+    order = [0, 7, 8, 1, 2, 3, 4, 5, 6] if FUSED else list(range(9))
+    nms = [names[6], names[7] + " + D2 statistics"] + names[:6] if FUSED else names
+    d = np.diff(x[:, order], axis=1)
+    print("  whole kernel up to the end of the last phase: median %7.0f cycles" % np.median(x[:, order[-1]] - x[:, 0]))
+    sh = st.cpu().numpy()[V // 4: 3 * V // 4, 12]
+    print("  shared last tile: accumulator tiles sent to the FP64 criteria: mean %.1f; register groups evaluated: mean %.1f" % ((sh & 0xffffffff).mean(), (sh >> 32).mean()))
+    for k, nm in enumerate(nms):
         print("  %-26s median %7.0f  mean %7.0f  p90 %7.0f cycles" % (nm, np.median(d[:, k]), d[:, k].mean(), np.percentile(d[:, k], 90)))
     cnt = st.cpu().numpy()[V // 4: 3 * V // 4, 9:12]
     for r in range(3):
