@@ -64,6 +64,13 @@ W2D_EXPORTS = ["mfx_w2d_abi_version", "mfx_w2d_max_atoms", "mfx_wfit2d_batch_dev
 # every symbol include/mfx_robust.h declares (robust fits: residual-driven reweighting on the device; versioned on its own)
 ROBUST_EXPORTS = ["mfx_robust_abi_version", "mfx_robust_weights_dev", "mfx_rfit_batch_dev", "mfx_rfit_batch"]
 
+# every symbol include/mfx_predict2d.h declares (forward model of 2-D protocols; versioned on its own)
+PREDICT2D_EXPORTS = ["mfx_predict2d_abi_version", "mfx_predict2d_dev", "mfx_predict2d"]
+
+# every symbol include/mfx_robust2d.h declares (robust fits of 2-D protocols; versioned on its own)
+ROBUST2D_EXPORTS = ["mfx_robust2d_abi_version", "mfx_rfit2d_batch_dev", "mfx_rfit2d_batch",
+                    "mfx_robust2d_debug_last_plan_directions"]
+
 
 class MfxError(RuntimeError):
     pass
@@ -213,6 +220,17 @@ def lib():
                                      vp, vp, vp]
     L.mfx_rfit_batch.argtypes = [vp, dp, dp, C.c_int64, ip, bp, dp, C.c_int, C.c_int, dp, C.c_int, C.c_double, C.c_int, C.c_int64,
                                  dp, dp, dp, ip, ip, lp, ip]
+    L.mfx_predict2d_abi_version.restype = C.c_int
+    L.mfx_predict2d_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int64, vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint64,
+                                    vp, vp, vp, vp, vp]
+    L.mfx_predict2d.argtypes = [vp, dp, dp, C.c_int, C.c_int, dp, C.c_int64, dp, dp, C.c_int, C.c_int, C.c_uint64, C.c_uint64,
+                                dp, dp, ip]
+    L.mfx_robust2d_abi_version.restype = C.c_int
+    L.mfx_rfit2d_batch_dev.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int64, vp, vp, vp, vp,
+                                       vp, vp, vp, vp]
+    L.mfx_rfit2d_batch.argtypes = [vp, dp, dp, C.c_int64, ip, bp, dp, C.c_int, C.c_int, dp, C.c_int, C.c_double, C.c_int, C.c_int64,
+                                   dp, dp, dp, ip, ip, ip, lp, ip]
+    L.mfx_robust2d_debug_last_plan_directions.restype = C.c_int64
     _lib = L
     return L
 

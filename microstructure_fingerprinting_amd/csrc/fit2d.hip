@@ -33,39 +33,37 @@ int f2_require_device(int device) {
 }
 
 // One class on device buffers: V voxels of K fascicles each (d_peaks [V x 3 K], contiguous), with the CSF column d_xc
-// or without (null) -> d_params [V x np] (np = 1 + 2 maxfasc + csf_on + 2), d_vstat [V x 5].  Only enqueues.
+// or without (null) -> d_params [V x np] (np = 1 + 2 maxfasc + csf_on + 2), d_vstat [V x 5].  Only enqueues: the
+// directions' plan and records (F2Dirs), then the fit on them.
 int f2_class_dev(const mfx_rot2d* h, const double* d_Y, const double* d_peaks, int K, const double* d_xc, int maxfasc,
                  int csf_on, int64_t V, double* d_params, int32_t* d_vstat, hipStream_t st) {
+  if (int rc = f2_limits("mfx_fit2d", h, K, V)) return rc;
+  if (K == 0 && !d_xc) return mfx_fit2d_class_prepared(h, d_Y, nullptr, nullptr, K, d_xc, maxfasc, csf_on, V, d_params, d_vstat, st);
+  F2Dirs dirs(st);
+  if (int rc = dirs.enqueue(h, d_peaks, V * K, st)) return rc;
+  return mfx_fit2d_class_prepared(h, d_Y, dirs.rec.p, dirs.pstat.as<int>(), K, d_xc, maxfasc, csf_on, V, d_params, d_vstat, st);
+}
+
+}  // namespace
+
+// the fit of one class on prepared directions (rot2d_shared.h)
+int mfx_fit2d_class_prepared(const mfx_rot2d* h, const double* d_Y, const void* d_rec, const int* d_pstat, int K, const double* d_xc,
+                             int maxfasc, int csf_on, int64_t V, double* d_params, int32_t* d_vstat, hipStream_t st) {
   const int M = h->d.M, N = h->d.N, has_csf = d_xc != nullptr;
   const int np = 1 + 2 * maxfasc + csf_on + 2;
-  if (V > 0x3fffffff / std::max(K, 1)) return mfx_fail(MFX_ERR_UNSUPPORTED, "mfx_fit2d: more than 2^30 directions in one call");
-  if (((size_t)2 * h->d.K + h->d.C + 2) * (size_t)N > 0x7fffffff)
-    return mfx_fail(MFX_ERR_UNSUPPORTED, "mfx_fit2d: tables of more than 2^31 doubles");
+  if (int rc = f2_limits("mfx_fit2d", h, K, V)) return rc;
   HIPCHK(hipMemsetAsync(d_params, 0, sizeof(double) * (size_t)V * np, st));
   if (K == 0 && !has_csf) {   // mf.py:387: nothing to fit, a zero row
     HIPCHK(hipMemsetAsync(d_vstat, 0, sizeof(int32_t) * 5 * (size_t)V, st));
     return MFX_OK;
   }
-  PlanMem pm(st);
-  StreamMem pstat(st), ok(st);
-  HIPCHK(pstat.alloc(sizeof(int) * 4 * (size_t)V * std::max(K, 1)));
+  StreamMem ok(st);
   HIPCHK(ok.alloc(sizeof(int) * (size_t)V));
-  if (int rc = pm.alloc(V * K, M, pstat.as<int>())) return rc;
-  if (K > 0)
-    if (int rc = mfx_rot2d_plan_enqueue(h, d_peaks, V * K, pm.pl, st)) return rc;
-  hipLaunchKernelGGL(fit2d_status_kernel, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, pstat.as<int>(), K, V, d_vstat,
+  hipLaunchKernelGGL(fit2d_status_kernel, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, d_pstat, K, V, d_vstat,
                      ok.as<int>(), d_params, np);
   HIPCHK(hipGetLastError());
-  // the kernels' records of the directions (F2Args), derived once from the plan records
-  const size_t nrec = (size_t)V * K * M;
-  StreamMem rec(st);
-  HIPCHK(rec.alloc(nrec * sizeof(F2Rec) + 64));
-  if (nrec > 0) {
-    hipLaunchKernelGGL(fit2d_rec_kernel, dim3((unsigned)((nrec + 255) / 256)), dim3(256), 0, st, h->d, pm.pl, (int64_t)nrec, rec.as<F2Rec>());
-    HIPCHK(hipGetLastError());
-  }
   F2Args a{};
-  a.M = M; a.N = N; a.base = h->d.ky; a.rec = rec.as<F2Rec>();
+  a.M = M; a.N = N; a.base = h->d.ky; a.rec = (const F2Rec*)d_rec;
   a.Y = d_Y; a.vstat = d_vstat; a.params = d_params; a.num_params = np; a.maxfasc = maxfasc;
   if (!g_force_explicit && !has_csf && K == 2 && f2_lds_bytes((N + 15) & ~15, false) <= F2_LDS_MAX) {
     const size_t lds = f2_lds_bytes((N + 15) & ~15, false);
@@ -103,8 +101,6 @@ int f2_class_dev(const mfx_rot2d* h, const double* d_Y, const double* d_peaks, i
   }
   return MFX_OK;
 }
-
-}  // namespace
 
 extern "C" int mfx_fit2d_abi_version(void) { return 1; }
 

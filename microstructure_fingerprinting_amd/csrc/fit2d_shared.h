@@ -1,11 +1,14 @@
 // fit2d_shared.h -- what fit2d.hip (the fit of 2-D protocols), soft2d.hip (their soft fits and objective profiles) and
 // w2d.hip (both with measurement weights) share beside the kernel texts of fit2d_kernels.h and soft2d_kernels.h:
 // the 32-byte record of a (direction, row), the kernel that derives the records from the plan records of rotate2d.hip, the
-// expression that turns a record into a dictionary entry, the kernel that folds the directions' status into the voxel's,
+// prepared directions of a call (F2Dirs; predict2d.hip and robust2d.hip use them too), the expression that turns a record
+// into a dictionary entry, the kernel that folds the directions' status into the voxel's,
 // the weighted kernels' arguments, and the geometry of the blocked cross-Gram (128 x 128 atoms per
 // workgroup, rows accumulated in chunks of 8).  Every translation unit gets its own copy (anonymous namespace).
 #pragma once
 #include "rot2d_shared.h"
+
+#include <algorithm>
 
 namespace {
 
@@ -52,6 +55,37 @@ __global__ void fit2d_rec_kernel(Rot2dDev D, Rot2dPlan pl, int64_t n, F2Rec* __r
   }
   rec[i] = r;
 }
+
+// what a call of B = V K directions may hold: the records are indexed with ints, the tables' offsets too
+inline int f2_limits(const char* fn, const mfx_rot2d* h, int K, int64_t V) {
+  if (V > 0x3fffffff / std::max(K, 1)) return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: more than 2^30 directions in one call", fn);
+  if (((size_t)2 * h->d.K + h->d.C + 2) * (size_t)h->d.N > 0x7fffffff)
+    return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: tables of more than 2^31 doubles", fn);
+  return MFX_OK;
+}
+
+// The prepared directions of a call: the plan of B directions, their status records [B x 4] and the kernels' records
+// [B x M], scratch of the stream's arena released with the object.  Made once, they serve every fit and every prediction
+// on these directions (the class launchers of rot2d_shared.h take them).
+struct F2Dirs {
+  PlanMem pm;
+  StreamMem pstat, rec;
+  explicit F2Dirs(hipStream_t st) : pm(st), pstat(st), rec(st) {}
+  int enqueue(const mfx_rot2d* h, const double* d_dirs, int64_t B, hipStream_t st) {
+    const int M = h->d.M;
+    HIPCHK(pstat.alloc(sizeof(int) * 4 * (size_t)std::max<int64_t>(B, 1)));
+    if (int rc = pm.alloc(B, M, pstat.as<int>())) return rc;
+    if (B > 0)
+      if (int rc = mfx_rot2d_plan_enqueue(h, d_dirs, B, pm.pl, st)) return rc;
+    const size_t nrec = (size_t)B * M;
+    HIPCHK(rec.alloc(nrec * sizeof(F2Rec) + 64));
+    if (nrec > 0) {
+      hipLaunchKernelGGL(fit2d_rec_kernel, dim3((unsigned)((nrec + 255) / 256)), dim3(256), 0, st, h->d, pm.pl, (int64_t)nrec, rec.as<F2Rec>());
+      HIPCHK(hipGetLastError());
+    }
+    return MFX_OK;
+  }
+};
 
 // voxel record from the directions' records: the lowest failing fascicle (the record of mfx_fit2d.h).  ok (may be null):
 // 1 where no direction fails; params (may be null): the NaN row of a voxel with a failing direction

@@ -123,6 +123,25 @@ void mfx_scratch_free(void* p, hipStream_t s) {
     }
 }
 
+namespace {
+MfxThread::Arena* arena_find(hipStream_t s) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  for (auto& a : mfx_thread().arenas) if (a.device == dev && a.stream == s) return &a;
+  return nullptr;
+}
+}  // namespace
+bool mfx_scratch_mark(hipStream_t s, ScratchMark* m) {
+  MfxThread::Arena* A = arena_find(s);
+  if (!A || A->live == 0) return false;
+  m->cur = A->cur; m->off = A->off; m->live = A->live;
+  return true;
+}
+void mfx_scratch_rewind(hipStream_t s, const ScratchMark& m) {
+  MfxThread::Arena* A = arena_find(s);
+  if (A && A->live == m.live) { A->cur = m.cur; A->off = m.off; }
+}
+
 int mfx_prof_begin(hipStream_t st) {
   MfxThread& T = mfx_thread();
   if (!T.profiling) return MFX_OK;

@@ -107,6 +107,13 @@ struct DevMem {
 // uninitialised scratch memory).
 hipError_t mfx_scratch_alloc(void** p, size_t bytes, hipStream_t s);
 void mfx_scratch_free(void* p, hipStream_t s);
+// A call that keeps scratch alive over a loop of steps (robust2d.hip: the directions' records over the iterations) marks the
+// arena's position behind what it keeps and rewinds to it after every step, once the step's own allocations are released
+// (the rewind does nothing otherwise): the steps follow each other on the stream like separate calls, and the arena
+// does not grow with their number.  mark: false when the stream has no live allocation.
+struct ScratchMark { size_t cur = 0, off = 0; int live = 0; };
+bool mfx_scratch_mark(hipStream_t s, ScratchMark* m);
+void mfx_scratch_rewind(hipStream_t s, const ScratchMark& m);
 // scratch allocation released on every exit path
 struct StreamMem {
   void* p = nullptr;
@@ -145,6 +152,15 @@ int mfx_fit_class_plain_dev(const mfx_plan* p, const double* d_Y, const double* 
 // fit_w.hip: the weighted class fit behind mfx_wfit_batch* (w_class_dev)
 int mfx_wfit_class_dev(const mfx_plan* p, const double* d_Y, const double* d_W, int64_t wstride, const double* d_peaks, int K,
                        const double* d_xc, int maxfasc, int csf_on, int64_t V, double* d_params, int32_t* d_vstat, hipStream_t st);
+
+// robust.hip, for robust2d.hip: the check of the rule's parameters, the reweighting kernel (mfx_robust_weights_dev without its
+// argument checks), W = W0 spread to [V x M] (ones without W0), and *d_out = the number of non-zero flags; they only enqueue
+int mfx_rob_check_rule(const char* fn, int loss, double c, int M);
+int mfx_rob_launch_weights(int M, const double* d_Y, const double* d_P, const double* d_W0, int64_t w0_stride, int loss, double c,
+                           int64_t V, const double* d_Wprev, double* d_W, double* d_scale, int32_t* d_state, int32_t* d_changed,
+                           hipStream_t st);
+int mfx_rob_spread(const double* d_W0, int64_t w0_stride, int M, int64_t V, double* d_W, hipStream_t st);
+int mfx_rob_count(const int* d_flags, int64_t V, int* d_out, hipStream_t st);
 
 // ---- kernel launchers, one translation unit each
 // FP64 two-fascicle kernel (tu_k2.hip).  With a.list_count set, a.vox_list is a device-side list whose length only the

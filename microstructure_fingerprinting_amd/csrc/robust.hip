@@ -240,8 +240,7 @@ int rob_first_fit(const RobClass& r) {
   int device = 0;
   mfx_plan_view(r.p, &T, &P, &device);
   const int M = P.M, np = 1 + 2 * r.maxfasc + r.csf_on + 2;
-  hipLaunchKernelGGL(rob_spread_kernel, dim3(rob_grid(r.V * M)), dim3(256), 0, r.st, r.W0, r.w0_stride, M, r.V, r.W);
-  HIPCHK(hipGetLastError());
+  if (int rc = mfx_rob_spread(r.W0, r.w0_stride, M, r.V, r.W, r.st)) return rc;
   HIPCHK(hipMemsetAsync(r.scale, 0, sizeof(double) * (size_t)r.V, r.st));
   HIPCHK(hipMemsetAsync(r.state, 0, sizeof(int32_t) * (size_t)r.V, r.st));
   if (r.W0) return mfx_wfit_class_dev(r.p, r.Y, r.W0, r.w0_stride, r.peaksK, r.K, r.xc, r.maxfasc, r.csf_on, r.V, r.params, r.status, r.st);
@@ -268,9 +267,7 @@ int rob_reweight(const RobClass& r, int it) {
                                nullptr, 0, r.V, nullptr, nullptr, 0, 0, 0, 0, pred.as<double>(), nullptr, pst.as<int32_t>(), r.st)) return rc;
   if (int rc = rob_launch_weights(M, r.Y, pred.as<double>(), r.W0, r.w0_stride, r.loss, r.c, r.V, r.W, r.W, r.scale, r.state, chg.as<int>(),
                                   r.st)) return rc;
-  hipLaunchKernelGGL(rob_count_kernel, dim3(1), dim3(256), 0, r.st, chg.as<int>(), r.V, r.nchanged + it);
-  HIPCHK(hipGetLastError());
-  return MFX_OK;
+  return mfx_rob_count(chg.as<int>(), r.V, r.nchanged + it, r.st);
 }
 
 // the weighted fit on the current W
@@ -283,6 +280,27 @@ int rob_refit(const RobClass& r) {
 }
 
 }  // namespace
+
+// what robust2d.hip shares of this file (mfx_host.h)
+int mfx_rob_check_rule(const char* fn, int loss, double c, int M) { return rob_check_rule(fn, loss, c, M); }
+
+int mfx_rob_launch_weights(int M, const double* d_Y, const double* d_P, const double* d_W0, int64_t w0_stride, int loss, double c,
+                           int64_t V, const double* d_Wprev, double* d_W, double* d_scale, int32_t* d_state, int32_t* d_changed,
+                           hipStream_t st) {
+  return rob_launch_weights(M, d_Y, d_P, d_W0, w0_stride, loss, c, V, d_Wprev, d_W, d_scale, d_state, d_changed, st);
+}
+
+int mfx_rob_spread(const double* d_W0, int64_t w0_stride, int M, int64_t V, double* d_W, hipStream_t st) {
+  hipLaunchKernelGGL(rob_spread_kernel, dim3(rob_grid(V * M)), dim3(256), 0, st, d_W0, w0_stride, M, V, d_W);
+  HIPCHK(hipGetLastError());
+  return MFX_OK;
+}
+
+int mfx_rob_count(const int* d_flags, int64_t V, int* d_out, hipStream_t st) {
+  hipLaunchKernelGGL(rob_count_kernel, dim3(1), dim3(256), 0, st, d_flags, V, d_out);
+  HIPCHK(hipGetLastError());
+  return MFX_OK;
+}
 
 extern "C" int mfx_robust_abi_version(void) { return 1; }
 

@@ -77,3 +77,21 @@ struct PlanMem {
 
 // rotate2d.hip: enqueue mfx_rot2d_plan_kernel over B directions (records and status into pl)
 int mfx_rot2d_plan_enqueue(const mfx_rot2d* h, const double* d_dirs, int64_t B, const Rot2dPlan& pl, hipStream_t st);
+// directions handed to mfx_rot2d_plan_kernel by the calling thread since the last reset (robust2d.hip's diagnostic)
+void mfx_rot2d_plan_count_reset();
+int64_t mfx_rot2d_plan_count();
+
+// ---- on prepared directions (F2Dirs of fit2d_shared.h): d_rec the F2Rec records [V KR x M] (void*: the type lives in every
+// translation unit's own namespace), d_pstat [V KR x 4] the directions' status records.  They only enqueue.
+// predict2d.hip: the prediction kernel; fascicle k of a parameter row (maxfasc layout) reads slot k of the voxel's KR
+int mfx_predict2d_launch(const mfx_rot2d* h, const void* d_rec, const int* d_pstat, int KR, const double* d_params, int maxfasc,
+                         int csf_on, const double* d_sig_csf, int64_t V, const double* d_Y, const double* d_sigma, int sigma_mode,
+                         int ncoils, uint64_t seed, uint64_t offset, double* d_out, double* d_stats, int32_t* d_status,
+                         int32_t* d_dir_status, hipStream_t st);
+// fit2d.hip / w2d.hip: one fit class (every voxel K fascicles, the CSF column d_xc or null) into rows of the (maxfasc, csf_on)
+// layout, as mfx_fit2d_batch* / mfx_wfit2d_batch* run it for the class
+int mfx_fit2d_class_prepared(const mfx_rot2d* h, const double* d_Y, const void* d_rec, const int* d_pstat, int K, const double* d_xc,
+                             int maxfasc, int csf_on, int64_t V, double* d_params, int32_t* d_vstat, hipStream_t st);
+int mfx_wfit2d_class_prepared(const mfx_rot2d* h, const double* d_Y, const double* d_W, int64_t wstride, const void* d_rec,
+                              const int* d_pstat, int K, const double* d_xc, int maxfasc, int csf_on, int64_t V, double* d_params,
+                              int32_t* d_vstat, int32_t* d_wstat, hipStream_t st);

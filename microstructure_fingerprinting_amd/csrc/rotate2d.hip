@@ -338,7 +338,12 @@ int r2_host(const mfx_rot2d* h, const double* dirs, const int32_t* cols, int64_t
 
 }  // namespace
 
+static thread_local int64_t g_plan_dirs = 0;
+void mfx_rot2d_plan_count_reset() { g_plan_dirs = 0; }
+int64_t mfx_rot2d_plan_count() { return g_plan_dirs; }
+
 int mfx_rot2d_plan_enqueue(const mfx_rot2d* h, const double* d_dirs, int64_t B, const Rot2dPlan& pl, hipStream_t st) {
+  g_plan_dirs += B;
   hipLaunchKernelGGL(mfx_rot2d_plan_kernel, dim3((unsigned)B), dim3(R2_PLAN_WG), 0, st, h->d, d_dirs, pl);
   HIPCHK(hipGetLastError());
   return MFX_OK;

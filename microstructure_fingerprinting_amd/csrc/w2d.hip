@@ -104,29 +104,18 @@ int w2_require_device(int device) {
   return MFX_OK;
 }
 
-// what every class launch shares: the plan of the V K directions, the voxels' direction records, the kernels' records and
-// the prepared weights.  Scratch of the stream's arena, released with the object.
-struct W2Scratch {
-  PlanMem pm;
-  StreamMem pstat, rec, prep, ok;
-  explicit W2Scratch(hipStream_t st) : pm(st), pstat(st), rec(st), prep(st), ok(st) {}
+// what every class launch shares beside the prepared directions (F2Dirs: the plan of the V K directions and the kernels'
+// records): the voxels' direction records and the prepared weights.  Scratch of the stream's arena, released with the object.
+struct W2Weights {
+  StreamMem prep, ok;
+  explicit W2Weights(hipStream_t st) : prep(st), ok(st) {}
   // fills a.M .. a.vstat; d_params non-null: the fit (NaN rows are written, wstat is the caller's d_wstat)
-  int enqueue(const mfx_rot2d* h, const double* d_Y, const double* d_W, int64_t wstride, const double* d_peaks, int K, int64_t V,
-              int32_t* d_vstat, int32_t* d_wstat, double* d_params, int np, W2Args& a, hipStream_t st) {
+  int enqueue(const mfx_rot2d* h, const double* d_Y, const double* d_W, int64_t wstride, const void* d_rec, const int* d_pstat, int K,
+              int64_t V, int32_t* d_vstat, int32_t* d_wstat, double* d_params, int np, W2Args& a, hipStream_t st) {
     const int M = h->d.M;
-    HIPCHK(pstat.alloc(sizeof(int) * 4 * (size_t)V * std::max(K, 1)));
-    if (int rc = pm.alloc(V * K, M, pstat.as<int>())) return rc;
-    if (K > 0)
-      if (int rc = mfx_rot2d_plan_enqueue(h, d_peaks, V * K, pm.pl, st)) return rc;
-    hipLaunchKernelGGL(fit2d_status_kernel, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, pstat.as<int>(), K, V, d_vstat,
+    hipLaunchKernelGGL(fit2d_status_kernel, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, d_pstat, K, V, d_vstat,
                        (int*)nullptr, d_params, np);
     HIPCHK(hipGetLastError());
-    const size_t nrec = (size_t)V * K * M;
-    HIPCHK(rec.alloc(nrec * sizeof(F2Rec) + 64));
-    if (nrec > 0) {
-      hipLaunchKernelGGL(fit2d_rec_kernel, dim3((unsigned)((nrec + 255) / 256)), dim3(256), 0, st, h->d, pm.pl, (int64_t)nrec, rec.as<F2Rec>());
-      HIPCHK(hipGetLastError());
-    }
     // s [V x M], y' [V x M], sum W [V], and the weights' status where the caller has no array for it
     const size_t vm = (size_t)V * M;
     HIPCHK(prep.alloc(sizeof(double) * (2 * vm + (size_t)V) + sizeof(int) * (size_t)V + 64));
@@ -138,9 +127,22 @@ struct W2Scratch {
     hipLaunchKernelGGL(w2d_prep_kernel, dim3((unsigned)V), dim3(64), 0, st, d_Y, d_W, wstride, M, d_vstat, S, Ys, sumw, wstat, ok.as<int>(),
                        d_params, np);
     HIPCHK(hipGetLastError());
-    a.M = M; a.N = h->d.N; a.base = h->d.ky; a.rec = rec.as<F2Rec>();
+    a.M = M; a.N = h->d.N; a.base = h->d.ky; a.rec = (const F2Rec*)d_rec;
     a.Y = d_Y; a.W = d_W; a.wstride = wstride; a.S = S; a.Ys = Ys; a.sumw = sumw; a.wstat = wstat; a.vstat = d_vstat;
     return MFX_OK;
+  }
+};
+
+// directions, then weights: what the entry points that get directions run
+struct W2Scratch {
+  F2Dirs dirs;
+  W2Weights w;
+  StreamMem& ok;
+  explicit W2Scratch(hipStream_t st) : dirs(st), w(st), ok(w.ok) {}
+  int enqueue(const mfx_rot2d* h, const double* d_Y, const double* d_W, int64_t wstride, const double* d_peaks, int K, int64_t V,
+              int32_t* d_vstat, int32_t* d_wstat, double* d_params, int np, W2Args& a, hipStream_t st) {
+    if (int rc = dirs.enqueue(h, d_peaks, V * K, st)) return rc;
+    return w.enqueue(h, d_Y, d_W, wstride, dirs.rec.p, dirs.pstat.as<int>(), K, V, d_vstat, d_wstat, d_params, np, a, st);
   }
 };
 
@@ -151,18 +153,28 @@ int w2_limits(const char* fn, const mfx_rot2d* h, int K, int64_t V) {
   return MFX_OK;
 }
 
+int w2_class_fit(const mfx_rot2d* h, W2Args& a, const int* ok, int K, const double* d_xc, int maxfasc, int csf_on, int64_t V,
+                 double* d_params, hipStream_t st);
+
 // One fit class on device buffers: V voxels of K fascicles each (d_peaks [V x 3 K], contiguous), with the CSF column d_xc
 // or without (null) -> d_params [V x np] (np = 1 + 2 maxfasc + csf_on + 2), d_vstat [V x 5], d_wstat [V].  Only enqueues.
 int w2_class_dev(const mfx_rot2d* h, const double* d_Y, const double* d_W, int64_t wstride, const double* d_peaks, int K,
                  const double* d_xc, int maxfasc, int csf_on, int64_t V, double* d_params, int32_t* d_vstat, int32_t* d_wstat,
                  hipStream_t st) {
-  const int M = h->d.M, N = h->d.N, has_csf = d_xc != nullptr;
   const int np = 1 + 2 * maxfasc + csf_on + 2;
   if (int rc = w2_limits("mfx_wfit2d", h, K, V)) return rc;
   HIPCHK(hipMemsetAsync(d_params, 0, sizeof(double) * (size_t)V * np, st));
   W2Scratch sc(st);
   W2Args a{};
   if (int rc = sc.enqueue(h, d_Y, d_W, wstride, d_peaks, K, V, d_vstat, d_wstat, d_params, np, a, st)) return rc;
+  return w2_class_fit(h, a, sc.ok.as<int>(), K, d_xc, maxfasc, csf_on, V, d_params, st);
+}
+
+// the fit of a class behind the prepared weights
+int w2_class_fit(const mfx_rot2d* h, W2Args& a, const int* ok, int K, const double* d_xc, int maxfasc, int csf_on, int64_t V,
+                 double* d_params, hipStream_t st) {
+  const int M = h->d.M, N = h->d.N, has_csf = d_xc != nullptr;
+  const int np = 1 + 2 * maxfasc + csf_on + 2;
   if (K == 0 && !has_csf) return MFX_OK;   // mf.py:387: nothing to fit, a zero row (NaN where the weights are unusable)
   a.params = d_params; a.num_params = np; a.maxfasc = maxfasc;
   if (!g_force_explicit && !has_csf && K == 2 && f2_lds_bytes((N + 15) & ~15, true) <= F2_LDS_MAX) {
@@ -188,7 +200,6 @@ int w2_class_dev(const mfx_rot2d* h, const double* d_Y, const double* d_W, int64
   StreamMem dA(st), dS(st);
   HIPCHK(dA.alloc(per_vox * nvc));
   HIPCHK(dS.alloc(scratch_b));
-  const int* ok = sc.ok.as<int>();
   for (int64_t v0 = 0; v0 < V; v0 += nvc) {
     const int64_t nv = std::min(nvc, V - v0);
     hipLaunchKernelGGL(fit2d_mat_kernel<true>, dim3((unsigned)nv, (unsigned)((M + 7) / 8)), dim3(256), 0, st, a, ok, v0, K, has_csf, d_xc,
@@ -299,6 +310,19 @@ int w2_soft_host(const char* fn, int mode, const mfx_rot2d* h, const double* Y, 
 }
 
 }  // namespace
+
+// the weighted fit of one class on prepared directions (rot2d_shared.h)
+int mfx_wfit2d_class_prepared(const mfx_rot2d* h, const double* d_Y, const double* d_W, int64_t wstride, const void* d_rec,
+                              const int* d_pstat, int K, const double* d_xc, int maxfasc, int csf_on, int64_t V, double* d_params,
+                              int32_t* d_vstat, int32_t* d_wstat, hipStream_t st) {
+  const int np = 1 + 2 * maxfasc + csf_on + 2;
+  if (int rc = w2_limits("mfx_wfit2d", h, K, V)) return rc;
+  HIPCHK(hipMemsetAsync(d_params, 0, sizeof(double) * (size_t)V * np, st));
+  W2Weights w(st);
+  W2Args a{};
+  if (int rc = w.enqueue(h, d_Y, d_W, wstride, d_rec, d_pstat, K, V, d_vstat, d_wstat, d_params, np, a, st)) return rc;
+  return w2_class_fit(h, a, w.ok.as<int>(), K, d_xc, maxfasc, csf_on, V, d_params, st);
+}
 
 extern "C" int mfx_w2d_abi_version(void) { return 1; }
 

@@ -858,6 +858,98 @@ def fit2d_weighted(tables, Y, W, K, csf, peaks, maxfasc, csf_on, sig_csf=None):
     return params, status, wstatus
 
 
+def _predict2d_shapes(tables, p_shape, pk_shape, maxfasc, csf_on, y_shape, M_csf):
+    """Argument checks shared by predict2d and predict2d_dev (before any device call); returns V."""
+    maxfasc = int(maxfasc)
+    if maxfasc < 0 or maxfasc > 3:
+        raise NotImplementedError("the 2-D protocol prediction serves 0 to 3 fascicles per voxel (maxfasc = %d)" % maxfasc)
+    npar = num_params(maxfasc, csf_on, False)
+    if len(p_shape) != 2 or p_shape[1] != npar:
+        raise ValueError("params should have %d columns (maxfasc = %d, csf_on = %s), got shape %s"
+                         % (npar, maxfasc, bool(csf_on), tuple(p_shape)))
+    V = p_shape[0]
+    if maxfasc > 0 and (pk_shape is None or tuple(pk_shape) != (V, 3 * maxfasc)):
+        raise ValueError("peaks should have shape (%d, %d)" % (V, 3 * maxfasc))
+    if csf_on and M_csf != tables.M:
+        raise ValueError("sig_csf has %s entries, protocol has %d" % (M_csf, tables.M))
+    if y_shape is not None and tuple(y_shape) != (V, tables.M):
+        raise ValueError("data has shape %s, protocol has %d measurements for %d voxels" % (tuple(y_shape), tables.M, V))
+    return V
+
+
+def predict2d_dev(tables, d_params, d_peaks, maxfasc, csf_on=False, d_sig_csf=None, d_Y=None, sigma_g=None, ncoils=0, seed=0,
+                  offset=0, out=None):
+    """Forward model of a 2-D (AxCaliber-like) protocol on the device (mfx_predict2d_dev, include/mfx_predict2d.h) for a
+    mf_utils.RotateAtom2DTables: parameter rows [V, num_params(maxfasc, csf_on, False)] in the layout ``fit2d_dev``
+    returns and peaks [V, 3 maxfasc] (torch CUDA float64 tensors) -> the signal [V, M] they stand for: per present
+    fascicle the column ``rotate_cols`` returns, bit for bit, times M0 nu, summed in the order f0, f1, f2, csf.  With
+    ``ncoils`` > 0 the magnitude noise of ``sos_noise_dev`` is applied in the same pass (``sigma_g`` a number or a tensor
+    with one value, one per voxel or one per element; element (v, m) draws with index ``offset + v M + m``); with ``d_Y``
+    [V, M] the per-voxel residual sum of squares and R2 come back too.  Returns (out, stats [V, 2] or None, status [2]
+    int32, dir_status [V, 5] int32): a row with a bad atom index or weight is NaN and flags ``status`` (bits 1 / 2); a
+    present fascicle with a failing direction gives a NaN row and its record in ``dir_status``.  Enqueues on torch's
+    current stream and returns without waiting."""
+    import torch
+    maxfasc = int(maxfasc)
+    assert d_params.is_cuda and d_params.dtype == torch.float64 and d_params.is_contiguous()
+    dev = d_params.device
+    for t in (d_peaks if maxfasc > 0 else None, d_sig_csf if csf_on else None, d_Y):
+        assert t is None or (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous())
+    V = _predict2d_shapes(tables, d_params.shape, d_peaks.shape if maxfasc > 0 else None, maxfasc, csf_on,
+                          d_Y.shape if d_Y is not None else None, d_sig_csf.numel() if csf_on else None)
+    M = tables.M
+    mode, d_sigma = SIGMA_SCALAR, None
+    if ncoils:
+        if sigma_g is None:
+            raise ValueError("noise (ncoils > 0) needs sigma_g")
+        d_sigma = (sigma_g.to(device=dev, dtype=torch.float64).contiguous() if torch.is_tensor(sigma_g)
+                   else torch.full((1,), float(sigma_g), dtype=torch.float64, device=dev))
+        mode = _sigma_mode(d_sigma.shape, d_sigma.numel(), V, M)
+    if out is None:
+        out = torch.empty((V, M), dtype=torch.float64, device=dev)
+    assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (V, M)
+    stats = torch.empty((V, 2), dtype=torch.float64, device=dev) if d_Y is not None else None
+    status = torch.zeros(2, dtype=torch.int32, device=dev)
+    dstat = torch.empty((V, 5), dtype=torch.int32, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    L.check(L.lib().mfx_predict2d_dev(tables.handle(), d_params.data_ptr(), d_peaks.data_ptr() if maxfasc > 0 else None,
+                                      maxfasc, int(bool(csf_on)), d_sig_csf.data_ptr() if csf_on else None, V,
+                                      d_Y.data_ptr() if d_Y is not None else None,
+                                      d_sigma.data_ptr() if d_sigma is not None else None, mode, int(ncoils),
+                                      int(seed) & _U64, int(offset) & _U64, out.data_ptr(),
+                                      stats.data_ptr() if stats is not None else None, status.data_ptr(), dstat.data_ptr(), st))
+    return out, stats, status, dstat
+
+
+def predict2d(tables, params, peaks, maxfasc, csf_on=False, sig_csf=None, Y=None, sigma_g=None, ncoils=0, seed=0, offset=0):
+    """predict2d_dev on NumPy buffers (mfx_predict2d): returns (out [V, M], dir_status [V, 5] int32), or (out, stats
+    [V, 2], dir_status) when Y is given.  Bad atom indices and weights raise ValueError before anything is launched; a
+    present fascicle with a failing direction gives a NaN row and its record in ``dir_status``."""
+    maxfasc = int(maxfasc)
+    params = L.f64c(params)
+    pk = L.f64c(peaks) if maxfasc > 0 else None
+    sc = L.f64c(sig_csf).reshape(-1) if csf_on else None
+    Yc = L.f64c(Y) if Y is not None else None
+    V = _predict2d_shapes(tables, params.shape, pk.shape if pk is not None else None, maxfasc, csf_on,
+                          Yc.shape if Yc is not None else None, sc.shape[0] if sc is not None else None)
+    M = tables.M
+    mode, sg = SIGMA_SCALAR, None
+    if ncoils:
+        if sigma_g is None:
+            raise ValueError("noise (ncoils > 0) needs sigma_g")
+        sg = np.atleast_1d(L.f64c(sigma_g))
+        mode = _sigma_mode(sg.shape, sg.size, V, M)
+    out = np.zeros((V, M))
+    stats = np.zeros((V, 2)) if Yc is not None else None
+    dstat = np.zeros((V, 5), dtype=np.int32)
+    L.check(L.lib().mfx_predict2d(tables.handle(), L.dptr(params), L.dptr(pk) if pk is not None else None, maxfasc,
+                                  int(bool(csf_on)), L.dptr(sc) if sc is not None else None, V,
+                                  L.dptr(Yc) if Yc is not None else None, L.dptr(sg) if sg is not None else None, mode,
+                                  int(ncoils), int(seed) & _U64, int(offset) & _U64, L.dptr(out),
+                                  L.dptr(stats) if stats is not None else None, L.iptr(dstat)))
+    return (out, dstat) if stats is None else (out, stats, dstat)
+
+
 def _soft2d_shapes(tables, y_shape, pk_shape, K):
     """Argument checks shared by the device entry points of the 2-D protocols' soft fits and profiles (before any device
     call); returns V."""
@@ -1314,6 +1406,88 @@ def fit_robust(plan, Y, K, csf, peaks, maxfasc, csf_on, sig_csf=None, W0=None, l
         L.check(L.lib().mfx_plan_status(plan.handle(), None))   # a direction that is not a unit vector: ValueError
     return params, W, {'scale': scale, 'state': state, 'status': status, 'n_changed': nch[:n_iter].copy(),
                        'n_iter_used': int(used[0])}
+
+
+def fit2d_robust_dev(tables, d_Y, d_peaks, maxfasc, d_W0=None, loss='cutoff', c=4.45, n_iter=3):
+    """Device-resident robust fit of voxels of a 2-D protocol (mfx_rfit2d_batch_dev, include/mfx_robust2d.h) for a
+    mf_utils.RotateAtom2DTables and ONE voxel class: every voxel has ``maxfasc`` fascicles and no CSF column.  The loop of
+    ``fit_robust_dev`` on ``fit2d_dev``, ``predict2d_dev`` and ``fit2d_weighted_dev``, with the directions' plan made
+    once.  torch CUDA float64 tensors -> (params [V, num_params(maxfasc, False, False)], W [V, M], info) with info =
+    {'scale' [V], 'state' [V] int32, 'dir_status' [V, 5] int32, 'status' [V] int32 (the last weighted fit's weight
+    status), 'n_changed' [n_iter] int32}, all tensors.  Always runs all iterations; enqueues on torch's current stream
+    and returns without waiting."""
+    import torch
+    maxfasc = int(maxfasc)
+    code, cf, n_iter = _robust_rule(loss, c, n_iter)
+    for t in (d_Y, d_peaks if maxfasc > 0 else None, d_W0):
+        assert t is None or (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous())
+    V = _fit2d_shapes(tables, d_Y.shape, d_peaks.shape if maxfasc > 0 else (d_Y.shape[0], 0), maxfasc)
+    w0_stride = _w2d_stride(tables, V, d_W0.shape) if d_W0 is not None else 0
+    dev = d_Y.device
+    params = torch.empty((V, num_params(maxfasc, False, False)), dtype=torch.float64, device=dev)
+    W = torch.empty((V, tables.M), dtype=torch.float64, device=dev)
+    scale = torch.empty((V,), dtype=torch.float64, device=dev)
+    state = torch.empty((V,), dtype=torch.int32, device=dev)
+    dstat = torch.empty((V, 5), dtype=torch.int32, device=dev)
+    wstat = torch.empty((V,), dtype=torch.int32, device=dev)
+    nch = torch.zeros((n_iter,), dtype=torch.int32, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    L.check(L.lib().mfx_rfit2d_batch_dev(tables.handle(), d_Y.data_ptr(), d_W0.data_ptr() if d_W0 is not None else None,
+                                         w0_stride, d_peaks.data_ptr() if maxfasc > 0 else None, maxfasc, code, cf, n_iter, V,
+                                         params.data_ptr(), W.data_ptr(), scale.data_ptr(), state.data_ptr(), dstat.data_ptr(),
+                                         wstat.data_ptr(), nch.data_ptr() if n_iter > 0 else None, st))
+    return params, W, {'scale': scale, 'state': state, 'dir_status': dstat, 'status': wstat, 'n_changed': nch}
+
+
+def fit2d_robust(tables, Y, K, csf, peaks, maxfasc, csf_on, sig_csf=None, W0=None, loss='cutoff', c=4.45, n_iter=3):
+    """Robust fit of a mixed set of voxels of a 2-D protocol on NumPy arrays (mfx_rfit2d_batch): arguments as ``fit2d``,
+    optional base weights W0 [V, M] or [M] -> (params, W [V, M], info).  The plain fit (the weighted fit on W0, if given),
+    then up to ``n_iter`` times: predict, weights from the residuals by the rule of ``robust_weights_dev`` (``loss``,
+    ``c``), weighted fit - with the data resident on the device throughout and the directions' plan made once per class.
+    info is ``fit_robust``'s dict - 'scale', 'state', 'status' [V] int32 (the last weighted fit's weight status),
+    'n_changed' [n_iter] int64, 'n_iter_used' - plus 'dir_status' [V, 5] int32: a voxel with a failing direction has a NaN
+    row, state 1, its base weights and its record there.  The loop may stop early once an iteration changed nothing; the
+    results are those of all n_iter iterations."""
+    code, cf, n_iter = _robust_rule(loss, c, n_iter)
+    Y = L.f64c(Y)
+    W0 = L.f64c(W0) if W0 is not None else None
+    maxfasc = int(maxfasc)
+    pk = L.f64c(peaks).reshape(Y.shape[0], -1) if (maxfasc > 0 and Y.ndim == 2) else np.zeros((Y.shape[0], 0))
+    V = _fit2d_shapes(tables, Y.shape, pk.shape, maxfasc)
+    w0_stride = _w2d_stride(tables, V, W0.shape) if W0 is not None else 0
+    K = np.ascontiguousarray(np.asarray(K).reshape(-1), dtype=np.int32)
+    if K.shape != (V,):
+        raise ValueError("K should have one entry per voxel")
+    if V and (K.min() < 0 or K.max() > maxfasc):
+        raise ValueError("K should lie in 0..maxfasc = %d" % maxfasc)
+    cs = None
+    if csf is not None:
+        cs = np.ascontiguousarray(np.asarray(csf).reshape(-1).astype(bool), dtype=np.uint8)
+        if cs.shape != (V,):
+            raise ValueError("csf should have one entry per voxel")
+    sc = L.f64c(sig_csf).reshape(-1) if sig_csf is not None else None
+    if cs is not None and np.any(cs) and (not csf_on or sc is None):
+        raise ValueError("voxels flagged CSF need csf_on and sig_csf")
+    if csf_on and sc is None:
+        raise ValueError("csf_on needs sig_csf")
+    if sc is not None and sc.shape[0] != tables.M:
+        raise ValueError("sig_csf has %d entries, protocol has %d" % (sc.shape[0], tables.M))
+    M = tables.M
+    params = np.zeros((V, num_params(maxfasc, bool(csf_on), False)))
+    W = np.zeros((V, M))
+    scale = np.zeros(V)
+    state = np.zeros(V, dtype=np.int32)
+    dstat = np.zeros((V, 5), dtype=np.int32)
+    wstat = np.zeros(V, dtype=np.int32)
+    nch = np.zeros(max(n_iter, 1), dtype=np.int64)
+    used = np.zeros(1, dtype=np.int32)
+    L.check(L.lib().mfx_rfit2d_batch(tables.handle(), L.dptr(Y), L.dptr(W0) if W0 is not None else None, w0_stride, L.iptr(K),
+                                     L.bptr(cs) if cs is not None else None, L.dptr(pk) if maxfasc > 0 else None, maxfasc,
+                                     int(bool(csf_on)), L.dptr(sc) if sc is not None else None, code, cf, n_iter, V,
+                                     L.dptr(params), L.dptr(W), L.dptr(scale), L.iptr(state), L.iptr(dstat), L.iptr(wstat),
+                                     L.lptr(nch), L.iptr(used)))
+    return params, W, {'scale': scale, 'state': state, 'status': wstat, 'dir_status': dstat,
+                       'n_changed': nch[:n_iter].copy(), 'n_iter_used': int(used[0])}
 
 
 def cleanup_select(f1, f2, p1, p2, cos_min, ratio, w_keep, w_small, device=0):

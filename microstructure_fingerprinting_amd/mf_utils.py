@@ -603,7 +603,7 @@ class RotateAtom2DTables:
         self.raise_for_status(status)
         return out
 
-    def fit(self, data, peaks, numfasc, csf_mask=None, sig_csf=None, on_error='raise', *, weights=None):
+    def fit(self, data, peaks, numfasc, csf_mask=None, sig_csf=None, on_error='raise', *, weights=None, robust=None):
         """Fit ``data`` [V, M]: voxel v has ``numfasc[v]`` fascicles along ``peaks[v, 3k:3k+3]`` (unit vectors,
         peaks [V, 3 maxfasc]) and, where ``csf_mask[v]``, a CSF column ``sig_csf`` [M].  Per voxel the dictionaries
         ``rotate(peaks[v, 3k:3k+3])`` side by side go through ``solve_exhaustive_posweights`` on the device; returns
@@ -613,8 +613,90 @@ class RotateAtom2DTables:
         mask, inverse noise variances): the fit minimises sum_m W[v, m] (y_m - model_m)^2 (``engine.fit2d_weighted``,
         include/mfx_w2d.h), MSE = min_obj / sum_m W and R2 the squared weighted correlation; the result keeps them in
         ``weights``.  Negative or non-finite weights, or a voxel without a positive weight, raise ValueError before any
-        device call; ``on_error`` is about directions only."""
-        return _fit2d(self, data, peaks, numfasc, csf_mask, sig_csf, on_error, weights)
+        device call; ``on_error`` is about directions only.  ``robust``: None / False (the fit above), True or a dict with
+        keys among 'loss' ('cutoff' | 'huber' | 'tukey'), 'c' (>= 1, in units of the median absolute residual) and 'n_iter'
+        (True = {'loss': 'cutoff', 'c': 4.45, 'n_iter': 3}): the fit, then n_iter times predict -> weights from the
+        residuals -> weighted fit, on the device (``engine.fit2d_robust``, include/mfx_robust2d.h); ``weights`` are then the
+        base weights.  The result keeps the final weights in ``weights`` - ``posterior(fit=r)``, ``profile``, ``interval``
+        and ``posterior_moments`` on them answer for the final weighted objective - and has ``robust_info``,
+        ``robust_scale``, ``n_rejected`` and ``outlier_mask()``."""
+        return _fit2d(self, data, peaks, numfasc, csf_mask, sig_csf, on_error, weights, robust)
+
+    def _predict_args(self, fit_or_params, peaks, sig_csf):
+        """Argument checks of predict / residuals / simulate (before any device call): (params, peaks, maxfasc, csf_on, sig_csf)."""
+        params = fit_or_params.params if isinstance(fit_or_params, Fit2DResult) else fit_or_params
+        params = np.asarray(params, dtype=np.float64)
+        if params.ndim != 2:
+            raise ValueError("params should be a 2-D array [voxels x parameters], got shape %s" % (params.shape,))
+        V = params.shape[0]
+        peaks = np.asarray(peaks, dtype=np.float64)
+        if peaks.ndim != 2 or peaks.shape[0] != V or peaks.shape[1] % 3 != 0:
+            raise ValueError("peaks should have shape (%d, 3 maxfasc)" % V)
+        maxfasc = peaks.shape[1] // 3
+        if maxfasc > 3:
+            raise NotImplementedError("the 2-D protocol prediction serves at most 3 fascicles per voxel (peaks holds %d)" % maxfasc)
+        extra = params.shape[1] - 3 - 2 * maxfasc
+        if extra not in (0, 1):
+            raise ValueError("params should have 1 + 2 maxfasc + csf + 2 columns for the %d fascicle(s) of peaks, got shape %s"
+                             % (maxfasc, params.shape))
+        csf_on = bool(extra)
+        if csf_on:
+            if sig_csf is None:
+                raise ValueError("params hold a CSF fraction: sig_csf is needed")
+            sig_csf = np.asarray(sig_csf, dtype=np.float64).reshape(-1)
+            if sig_csf.size != self.M:
+                raise ValueError("sig_csf has %d entries, protocol has %d" % (sig_csf.size, self.M))
+        return params, peaks, maxfasc, csf_on, (sig_csf if csf_on else None)
+
+    def _predict(self, fit_or_params, peaks, sig_csf, on_error, data=None, **noise):
+        if on_error not in ("raise", "nan"):
+            raise ValueError("on_error should be 'raise' or 'nan'")
+        params, peaks, maxfasc, csf_on, sig_csf = self._predict_args(fit_or_params, peaks, sig_csf)
+        if data is not None:
+            data = np.asarray(data, dtype=np.float64)
+            if data.shape != (params.shape[0], self.M):
+                raise ValueError("data has shape %s, protocol has %d measurements for %d voxels" % (data.shape, self.M, params.shape[0]))
+        unserved = np.isnan(params[:, 0])           # the NaN rows of voxels a fit could not serve
+        if unserved.any():
+            params = np.where(unserved[:, None], 0.0, params)
+        out, dstat = engine.predict2d(self, params, peaks, maxfasc, csf_on, sig_csf, **noise)
+        if on_error == "raise":
+            bad = np.flatnonzero(dstat[:, 0])
+            if bad.size:
+                raise self.error_for(dstat[bad[0], :4])
+        out[unserved] = np.nan
+        return out if data is None else data - out
+
+    def predict(self, fit_or_params, peaks, sig_csf=None, on_error='raise'):
+        """The signal [V, M] that parameter rows stand for (``engine.predict2d``, include/mfx_predict2d.h): per present
+        fascicle the column ``rotate_cols`` returns, times M0 nu, summed in the order f0, f1, f2, csf - the ``y_rec`` the
+        reference's solver computes.  ``fit_or_params``: a :class:`Fit2DResult` or rows in its layout [V, 1 + 2 maxfasc +
+        csf + 2] (the column count says whether there is a CSF fraction, which needs ``sig_csf`` [M]); ``peaks``
+        [V, 3 maxfasc] as for ``fit``.  A voxel the fit could not serve (a NaN row) is NaN.  A present fascicle (M0 nu > 0)
+        with a failing direction: ``on_error='raise'`` raises the reference's exception for the lowest such voxel,
+        ``'nan'`` returns NaN rows.  Atom indices outside the dictionary and negative or non-finite weights raise
+        ValueError before anything is launched."""
+        return self._predict(fit_or_params, peaks, sig_csf, on_error)
+
+    def residuals(self, data, fit_or_params, peaks, sig_csf=None):
+        """``data - predict(fit_or_params, peaks, sig_csf)`` [V, M]."""
+        return self._predict(fit_or_params, peaks, sig_csf, 'raise', data=data)
+
+    def simulate(self, params, peaks, sig_csf=None, *, SNR=None, sigma_g=None, N=1, seed=None, offset=0):
+        """``predict`` with the sum-of-squares magnitude noise of ``N`` coils (Rician for N = 1) applied in the same pass:
+        give either ``sigma_g`` (a scalar, one value per voxel or one per element) or ``SNR``, which sets ``sigma_g = M0 /
+        SNR`` in every voxel.  ``seed=None`` draws a seed from NumPy's global generator; an int makes the call reproducible
+        by itself.  Element (v, m) draws with index ``offset + v M + m``."""
+        if (SNR is None) == (sigma_g is None):
+            raise ValueError("simulate needs exactly one of SNR and sigma_g")
+        if isinstance(N, bool) or int(N) != N or N < 1:
+            raise ValueError("N should be a positive integer, got %r" % (N,))
+        prm = params.params if isinstance(params, Fit2DResult) else np.asarray(params, dtype=np.float64)
+        if SNR is not None:
+            if prm.ndim != 2:
+                raise ValueError("params should be a 2-D array [voxels x parameters], got shape %s" % (prm.shape,))
+            sigma_g = prm[:, 0] / SNR
+        return self._predict(prm, peaks, sig_csf, 'raise', sigma_g=sigma_g, ncoils=int(N), seed=_sos_seed(seed), offset=offset)
 
     def posterior(self, data, peaks, numfasc, sigma=None, fit=None, props=None, on_error='raise', *, weights=None):
         """The soft answer beside ``fit``'s arg-min (``engine.posterior2d``, include/mfx_soft2d.h): for every atom of each
@@ -722,7 +804,11 @@ class Fit2DResult:
     fascicle or a voxel that was not fitted), ``frac_csf`` [V] (None without a CSF column), ``MSE``, ``R2`` [V];
     ``status`` [V, 5] int32: {code, pair, value, value2, fascicle} of the voxel's lowest failing fascicle
     direction, zeros for a fitted voxel (such a voxel's row is NaN).  ``weights``: the measurement weights [V, M] or [M]
-    (float64) of a weighted fit, None for an unweighted one."""
+    (float64) of a weighted fit, None for an unweighted one.  A robust fit (``fit(..., robust=...)``) keeps its final
+    weights [V, M] there and has ``robust_info`` (``engine.fit2d_robust``'s dict; None otherwise), ``robust_scale`` [V]
+    (the median absolute residual the last weights were made with), ``n_rejected`` [V] and ``outlier_mask()``."""
+
+    robust_info = robust_scale = n_rejected = _robust_base = None
 
     def __init__(self, params, status, maxfasc, csf_on, weights=None):
         params = np.asarray(params, dtype=np.float64)
@@ -743,6 +829,18 @@ class Fit2DResult:
     def failed(self):
         """Indices of the voxels that were not fitted."""
         return np.flatnonzero(self.status[:, 0])
+
+    def _set_robust(self, info, base):
+        self.robust_info, self._robust_base = info, base
+        self.robust_scale = info['scale']
+        self.n_rejected = np.count_nonzero(self.outlier_mask(), axis=1)
+
+    def outlier_mask(self):
+        """The measurements a robust fit rejected, bool [V, M]: True where a row the base weights admit ended with weight 0."""
+        if self.robust_info is None:
+            raise RuntimeError("this fit is not a robust fit (fit(..., robust=...)): it has rejected nothing")
+        base = np.ones(self.weights.shape[1], dtype=bool) if self._robust_base is None else np.asarray(self._robust_base) > 0
+        return base & (self.weights == 0)
 
 
 def _w2d_weights(T, weights, V):
@@ -766,9 +864,10 @@ def _w2d_weights(T, weights, V):
     return w
 
 
-def _fit2d(T, data, peaks, numfasc, csf_mask, sig_csf, on_error, weights=None):
+def _fit2d(T, data, peaks, numfasc, csf_mask, sig_csf, on_error, weights=None, robust=None):
     if on_error not in ("raise", "nan"):
         raise ValueError("on_error should be 'raise' or 'nan'")
+    opts = engine.robust_options(robust)
     data = np.asarray(data, dtype=np.float64)
     if data.ndim != 2 or data.shape[1] != T.M:
         raise ValueError("data has shape %s, protocol has %d measurements" % (data.shape, T.M))
@@ -796,6 +895,16 @@ def _fit2d(T, data, peaks, numfasc, csf_mask, sig_csf, on_error, weights=None):
     if sig_csf is not None and np.asarray(sig_csf).size != T.M:
         raise ValueError("sig_csf has %d entries, protocol has %d" % (np.asarray(sig_csf).size, T.M))
     W = _w2d_weights(T, weights, V) if weights is not None else None
+    if opts is not None:
+        sc = sig_csf if (sig_csf is not None or not csf_on) else np.zeros(T.M)   # (no voxel is flagged: never read)
+        params, Wf, info = engine.fit2d_robust(T, data, numfasc, csf, peaks, maxfasc, csf_on, sc, W0=W, **opts)
+        if on_error == "raise":
+            bad = np.flatnonzero(info['dir_status'][:, 0])
+            if bad.size:
+                raise T.error_for(info['dir_status'][bad[0], :4])
+        r = Fit2DResult(params, info['dir_status'], maxfasc, csf_on, Wf)
+        r._set_robust(info, W)
+        return r
     if W is None:
         params, status = engine.fit2d(T, data, numfasc, csf, peaks, maxfasc, csf_on, sig_csf)
     else:
@@ -845,11 +954,11 @@ def _soft2d_raise(T, dir_status, on_error):
 
 
 def fit_2Dprotocol(sig, sch_mat, refdir, DIFF, data, peaks, numfasc, csf_mask=None, sig_csf=None, on_error='raise',
-                   device=0, *, weights=None):
+                   device=0, *, weights=None, robust=None):
     """Fit voxels of a 2-D protocol: :class:`RotateAtom2DTables` of (sig, sch_mat, refdir, DIFF), then its ``fit``
-    (``weights``: its measurement weights)."""
+    (``weights``: its measurement weights; ``robust``: its robust options)."""
     return RotateAtom2DTables(sig, sch_mat, refdir, DIFF, device=device).fit(data, peaks, numfasc, csf_mask, sig_csf,
-                                                                            on_error, weights=weights)
+                                                                            on_error, weights=weights, robust=robust)
 
 
 def rotate_atom_2Dprotocol(sig, sch_mat, refdir, newdir, DIFF):
