@@ -92,3 +92,43 @@ def test_rotate_vs_oracle_random_and_single_columns(rot):
     oc = np.zeros((B, sch.shape[0]))
     L.check(L.lib().mfx_rotate_cols(plan.handle(), L.dptr(d), L.iptr(cols), B, 0, L.dptr(oc)))
     assert np.array_equal(oc, ref[np.arange(B), :, cols])
+
+
+def test_rotate_vs_oracle_on_knots_and_table_ends(rot):
+    """The same comparison where u = |g . d| sits on a knot or at an end of the table, which random directions never
+    reach: d along +-g_m (u = 1 or a hair off it, the end knot), d orthogonal to g_m (u = 0 or rounding noise) and the
+    dictionary's own orientation on the dense scheme (every u is a stored knot)."""
+    from microstructure_fingerprinting_amd import _lib as L
+    from microstructure_fingerprinting_amd import mf_utils as mfu
+    from oracle import oracle as orc
+    ms = mfu.init_PGSE_multishell_interp(rot["uk_dic"], rot["uk_sch_ms"], rot["uk_ordir"])
+    T = orc.init_tables(rot["uk_dic"], rot["uk_sch_ms"], rot["uk_ordir"])
+    sch = rot["uk_sch_subj"]
+    dw = np.where(sch[:, 3] > 0)[0]
+    rows = dw[[0, 1, dw.size // 3, dw.size // 2, dw.size - 1]]
+    d = []
+    for m in rows:
+        g = sch[m, :3] / np.sqrt(np.sum(sch[m, :3] ** 2))
+        p = np.cross(g, [0.0, 0.0, 1.0] if abs(g[2]) < 0.9 else [1.0, 0.0, 0.0])
+        # the scheme's g_m is unit to about 5e-7 only: +-g_m / |g_m| gives u = |g_m|, a hair inside or beyond the end knot,
+        # g_m / |g_m|^2 (accepted unnormalised) gives u = 1 up to the last bit
+        d += [g, -g, sch[m, :3] / np.sum(sch[m, :3] ** 2), p / np.sqrt(np.sum(p ** 2))]
+    d = np.ascontiguousarray(d)
+    dot = lambda k: np.abs(sch[rows, 0] * d[k::4, 0] + sch[rows, 1] * d[k::4, 1] + sch[rows, 2] * d[k::4, 2])   # noqa: E731
+    assert np.all(np.abs(dot(0) - 1.0) <= 1e-6) and np.any(dot(0) > 1.0) and np.any(dot(0) < 1.0)
+    assert np.any(dot(2) == 1.0) and np.all(np.abs(dot(2) - 1.0) <= 3e-16)
+    assert np.all(dot(3) <= 1e-15) and np.any(dot(3) == 0.0) and np.any(dot(3) > 0.0)
+    ordir = np.squeeze(rot["uk_ordir"]).astype(np.float64)
+    dense = rot["uk_sch_ms"]
+    for s, dirs in ((sch, d), (dense, np.ascontiguousarray([ordir, -ordir]))):
+        plan = ms.plan_for(s)
+        B = dirs.shape[0]
+        out = np.zeros((B, s.shape[0], ms.num_subs))
+        L.check(L.lib().mfx_rotate(plan.handle(), L.dptr(dirs), B, 0, L.dptr(out)))
+        ref = np.stack([orc.interp(s, x, T) for x in dirs])
+        assert np.array_equal(out, ref)
+        cols = (np.arange(B) * 7 % ms.num_subs).astype(np.int32)
+        cols[0], cols[-1] = 0, ms.num_subs - 1
+        oc = np.zeros((B, s.shape[0]))
+        L.check(L.lib().mfx_rotate_cols(plan.handle(), L.dptr(dirs), L.iptr(cols), B, 0, L.dptr(oc)))
+        assert np.array_equal(oc, ref[np.arange(B), :, cols])
