@@ -10,7 +10,9 @@
 // The kernels are those of fit2d_kernels.h (described there), instantiated here without measurement weights (WGT = false)
 // and by w2d.hip with them: mfx_fit2d_k2_kernel (K = 2, no extra column), mfx_fit2d_k1_kernel (K = 1, no extra column) and,
 // for every other class, fit2d_mat_kernel, which materialises the dictionaries (the same expression) in voxel chunks for
-// the explicit solver of mfx_api.hip per voxel on the device.  This file holds the class launcher and the entry points.
+// the explicit solver of mfx_api.hip per voxel on the device (the chunk loop is mfx_solve_dense_chunks of mfx_host.h).  This
+// file holds the class launcher and the entry points; the host side of a mixed batch - binning by class, the rows' gather,
+// upload, download and scatter - is class_batch.h and DevBuf (mfx_host.h).
 #include "fit2d_kernels.h"
 #include "../../include/mfx_fit2d.h"
 
@@ -21,16 +23,6 @@
 namespace {
 
 thread_local int g_force_explicit = 0;
-
-const char* NO_DEVICE = "no HIP device available (this library has no CPU path)";
-
-int f2_require_device(int device) {
-  const int n = mfx_device_count();
-  if (n <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
-  if (device < 0 || device >= n) return mfx_fail(MFX_ERR_ARG, "device %d out of range (have %d)", device, n);
-  HIPCHK(hipSetDevice(device));
-  return MFX_OK;
-}
 
 // One class on device buffers: V voxels of K fascicles each (d_peaks [V x 3 K], contiguous), with the CSF column d_xc
 // or without (null) -> d_params [V x np] (np = 1 + 2 maxfasc + csf_on + 2), d_vstat [V x 5].  Only enqueues: the
@@ -78,28 +70,18 @@ int mfx_fit2d_class_prepared(const mfx_rot2d* h, const double* d_Y, const void* 
     HIPCHK(hipGetLastError());
     return MFX_OK;
   }
-  // every other class: materialise the dictionaries in voxel chunks within a byte budget, explicit solver per voxel
-  const size_t Ntot = (size_t)K * N + has_csf, per_vox = sizeof(double) * M * Ntot;
-  size_t free_b = 0, total_b = 0, scratch_b = 0;
-  HIPCHK(hipMemGetInfo(&free_b, &total_b));
-  if (int rc = mfx_solve_dense_scratch_bytes(M, K, N, has_csf, &scratch_b)) return rc;
-  const size_t budget = std::min<size_t>(free_b / 4, (size_t)1 << 30);
-  const int64_t nvc = std::max<int64_t>(1, std::min<int64_t>(V, (int64_t)(budget / per_vox)));
-  StreamMem dA(st), dS(st);
-  HIPCHK(dA.alloc(per_vox * nvc));
-  HIPCHK(dS.alloc(scratch_b));
-  for (int64_t v0 = 0; v0 < V; v0 += nvc) {
-    const int64_t nv = std::min(nvc, V - v0);
-    hipLaunchKernelGGL(fit2d_mat_kernel<false>, dim3((unsigned)nv, (unsigned)((M + 7) / 8)), dim3(256), 0, st, a, ok.as<int>(), v0, K, has_csf, d_xc,
-                       dA.as<double>());
-    HIPCHK(hipGetLastError());
-    for (int64_t q = 0; q < nv; ++q) {
-      const int64_t v = v0 + q;
-      if (int rc = mfx_solve_dense_dev(dA.as<double>() + (size_t)q * M * Ntot, M, K, N, has_csf, d_Y + (size_t)v * M, maxfasc, csf_on,
-                                       d_params + (size_t)v * np, ok.as<int>() + v, dS.p, st)) return rc;
-    }
-  }
-  return MFX_OK;
+  // every other class: the dictionaries in voxel chunks, explicit solver per voxel (mfx_solve_dense_chunks, mfx_host.h)
+  const int* okp = ok.as<int>();
+  return mfx_solve_dense_chunks(
+      M, K, N, has_csf, sizeof(double) * M * ((size_t)K * N + has_csf), V, maxfasc, csf_on, d_params, okp, st,
+      [&](int64_t v0, int64_t nv, int64_t, double* dA, const double** y) -> int {
+        hipLaunchKernelGGL(fit2d_mat_kernel<false>, dim3((unsigned)nv, (unsigned)((M + 7) / 8)), dim3(256), 0, st, a, okp, v0, K, has_csf, d_xc,
+                           dA);
+        HIPCHK(hipGetLastError());
+        *y = d_Y + (size_t)v0 * M;
+        return MFX_OK;
+      },
+      [](int64_t, int64_t) -> int { return MFX_OK; });
 }
 
 extern "C" int mfx_fit2d_abi_version(void) { return 1; }
@@ -115,20 +97,20 @@ extern "C" int mfx_fit2d_max_atoms(void* hv, int K) {
 
 extern "C" int mfx_fit2d_batch_dev(void* hv, const double* d_Y, const double* d_peaks, int maxfasc, int64_t V, double* d_params,
                                    int32_t* d_status, void* stream) {
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
+  if (mfx_device_count() <= 0) return mfx_no_device();
   const mfx_rot2d* h = (const mfx_rot2d*)hv;
   if (!h || V < 0 || maxfasc < 0 || (V > 0 && (!d_Y || !d_params || !d_status || (maxfasc > 0 && !d_peaks))))
     return mfx_fail(MFX_ERR_ARG, "mfx_fit2d_batch_dev: bad argument");
   if (maxfasc > 3) return mfx_fail(MFX_ERR_UNSUPPORTED, "mfx_fit2d_batch_dev: at most 3 fascicles (got %d)", maxfasc);
   if (V == 0) return MFX_OK;
-  if (int rc = f2_require_device(h->device)) return rc;
+  if (int rc = mfx_require_device(h->device)) return rc;
   return f2_class_dev(h, d_Y, d_peaks, maxfasc, nullptr, maxfasc, 0, V, d_params, d_status, (hipStream_t)stream);
 }
 
 extern "C" int mfx_fit2d_batch(void* hv, const double* Y, const int32_t* K, const uint8_t* csf, const double* peaks, int maxfasc,
                                int csf_on, const double* sig_csf, int64_t V, double* params, int32_t* status) {
   const char* fn = "mfx_fit2d_batch";
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
+  if (mfx_device_count() <= 0) return mfx_no_device();
   const mfx_rot2d* h = (const mfx_rot2d*)hv;
   if (!h || V < 0 || maxfasc < 0 || (V > 0 && (!Y || !K || !params || !status || (maxfasc > 0 && !peaks))))
     return mfx_fail(MFX_ERR_ARG, "%s: bad argument", fn);
@@ -136,47 +118,24 @@ extern "C" int mfx_fit2d_batch(void* hv, const double* Y, const int32_t* K, cons
   csf_on = csf_on != 0;
   const int M = h->d.M, np = 1 + 2 * maxfasc + csf_on + 2;
   // bin by class (K, CSF flag) before any device call
-  std::vector<std::vector<int64_t>> bins((size_t)2 * (maxfasc + 1));
-  for (int64_t v = 0; v < V; ++v) {
-    const int c = csf && csf[v];
-    if (K[v] < 0 || K[v] > maxfasc) return mfx_fail(MFX_ERR_ARG, "%s: K[%lld] = %d outside 0..%d", fn, (long long)v, K[v], maxfasc);
-    if (c && (!csf_on || !sig_csf)) return mfx_fail(MFX_ERR_ARG, "%s: voxels flagged CSF need csf_on and sig_csf", fn);
-    bins[(size_t)2 * K[v] + c].push_back(v);
-  }
+  MfxClassBins bins;
+  if (int rc = mfx_class_bins(fn, K, csf, maxfasc, csf_on && sig_csf, V, &bins)) return rc;
   if (V == 0) return MFX_OK;
-  if (int rc = f2_require_device(h->device)) return rc;
-  DevMem dxc;
-  if (sig_csf) {
-    HIPCHK(dxc.alloc(sizeof(double) * M));
-    HIPCHK(hipMemcpy(dxc.p, sig_csf, sizeof(double) * M, hipMemcpyHostToDevice));
-  }
-  for (size_t b = 0; b < bins.size(); ++b) {
-    const std::vector<int64_t>& ix = bins[b];
-    if (ix.empty()) continue;
-    const int k = (int)(b >> 1), c = (int)(b & 1);
-    const size_t nv = ix.size();
-    std::vector<double> Yc(nv * M), pc(nv * 3 * (size_t)std::max(k, 1)), prm(nv * np);
-    std::vector<int32_t> stc(nv * 5);
-    for (size_t q = 0; q < nv; ++q) {
-      std::memcpy(&Yc[q * M], Y + (size_t)ix[q] * M, sizeof(double) * M);
-      if (k > 0) std::memcpy(&pc[q * 3 * k], peaks + (size_t)ix[q] * 3 * maxfasc, sizeof(double) * 3 * k);
-    }
-    DevMem dY, dpk, dpr, dst;
-    HIPCHK(dY.alloc(sizeof(double) * Yc.size()));
-    HIPCHK(dpk.alloc(sizeof(double) * pc.size()));
-    HIPCHK(dpr.alloc(sizeof(double) * prm.size()));
-    HIPCHK(dst.alloc(sizeof(int32_t) * stc.size()));
-    HIPCHK(hipMemcpy(dY.p, Yc.data(), sizeof(double) * Yc.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dpk.p, pc.data(), sizeof(double) * pc.size(), hipMemcpyHostToDevice));
-    if (int rc = f2_class_dev(h, dY.as<double>(), dpk.as<double>(), k, c ? dxc.as<double>() : nullptr, maxfasc, csf_on, (int64_t)nv,
-                              dpr.as<double>(), dst.as<int32_t>(), nullptr)) return rc;
+  if (int rc = mfx_require_device(h->device)) return rc;
+  DevBuf<double> dxc;
+  if (sig_csf) HIPCHK(dxc.upload(sig_csf, M));
+  return mfx_class_walk(bins, SIZE_MAX, [&](int k, int c, const int64_t* ix, size_t nv) -> int {   // a bin at a time
+    DevBuf<double> dY, dpk, dpr;
+    DevBuf<int32_t> dst;
+    HIPCHK(dY.upload_rows(Y, ix, nv, M, M));
+    HIPCHK(mfx_upload_peaks(dpk, peaks, ix, nv, maxfasc, k));
+    HIPCHK(dpr.alloc_n(nv * np));
+    HIPCHK(dst.alloc_n(nv * 5));
+    if (int rc = f2_class_dev(h, dY.get(), dpk.get(), k, c ? dxc.get() : nullptr, maxfasc, csf_on, (int64_t)nv, dpr.get(), dst.get(), nullptr))
+      return rc;
     HIPCHK(hipStreamSynchronize(nullptr));
-    HIPCHK(hipMemcpy(prm.data(), dpr.p, sizeof(double) * prm.size(), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(stc.data(), dst.p, sizeof(int32_t) * stc.size(), hipMemcpyDeviceToHost));
-    for (size_t q = 0; q < nv; ++q) {
-      std::memcpy(params + (size_t)ix[q] * np, &prm[q * np], sizeof(double) * np);
-      std::memcpy(status + (size_t)ix[q] * 5, &stc[q * 5], sizeof(int32_t) * 5);
-    }
-  }
-  return MFX_OK;
+    HIPCHK(dpr.download_rows(params, ix, nv, np));
+    HIPCHK(dst.download_rows(status, ix, nv, 5));
+    return MFX_OK;
+  });
 }

@@ -22,7 +22,8 @@
 // mfx_wfit_k1_kernel   K = 1, no extra column: one thread per atom, serial statistics, the reference's _1 rule.
 // every other class    scaled dictionaries and y' materialised by wfit_mat_kernel in voxel chunks, the explicit solver
 //                      of mfx_api.hip per voxel on (s A, s y), then wfit_repack_kernel puts the weighted MSE and R2
-//                      into the row.
+//                      into the row (the chunk loop is mfx_solve_dense_chunks of mfx_host.h).
+// The host side of a mixed batch (mfx_wfit_batch) is class_batch.h and DevBuf (mfx_host.h).
 // A voxel whose weights are unusable is skipped by every kernel (wfit_status_kernel wrote its NaN row and code).
 #include "mfx_host.h"
 #include "../../include/mfx_wfit.h"
@@ -687,16 +688,6 @@ __global__ __launch_bounds__(64) void wfit_repack_kernel(WArgs a, int64_t v0, in
   }
 }
 
-const char* NO_DEVICE = "no HIP device available (this library has no CPU path)";
-
-int w_require_device(int device) {
-  const int n = mfx_device_count();
-  if (n <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
-  if (device < 0 || device >= n) return mfx_fail(MFX_ERR_ARG, "device %d out of range (have %d)", device, n);
-  HIPCHK(hipSetDevice(device));
-  return MFX_OK;
-}
-
 int w_max_atoms_k2(int M, bool br) {
   if (M > W_MAX_ROWS) return 0;
   const int MP = (M + W_MC - 1) & ~(W_MC - 1);
@@ -750,32 +741,25 @@ int w_class_dev(const mfx_plan* p, const double* d_Y, const double* d_W, int64_t
     HIPCHK(hipGetLastError());
     return MFX_OK;
   }
-  // every other class: materialise the scaled dictionaries in voxel chunks within a byte budget, explicit solver per voxel
+  // every other class: the scaled dictionaries in voxel chunks, explicit solver per voxel (mfx_solve_dense_chunks,
+  // mfx_host.h).  A chunk's block holds the dictionaries [nvc x M x Ntot] and behind them the scaled signals s y
+  // [nvc x M], both written by wfit_mat_kernel; wfit_repack_kernel follows every chunk.
   if ((size_t)M * sizeof(double) > 64 * 1024) return mfx_fail(MFX_ERR_UNSUPPORTED, "mfx_wfit: more than 8192 measurements");
-  const size_t Ntot = (size_t)K * N + has_csf, per_vox = sizeof(double) * M * (Ntot + 1);
-  size_t free_b = 0, total_b = 0, scratch_b = 0;
-  HIPCHK(hipMemGetInfo(&free_b, &total_b));
-  if (int rc = mfx_solve_dense_scratch_bytes(M, K, N, has_csf, &scratch_b)) return rc;
-  const size_t budget = std::min<size_t>(free_b / 4, (size_t)1 << 30);
-  const int64_t nvc = std::max<int64_t>(1, std::min<int64_t>(V, (int64_t)(budget / per_vox)));
-  StreamMem dA(st), dYs(st), dS(st);
-  HIPCHK(dA.alloc(sizeof(double) * M * Ntot * nvc));
-  HIPCHK(dYs.alloc(sizeof(double) * M * nvc));
-  HIPCHK(dS.alloc(scratch_b));
-  for (int64_t v0 = 0; v0 < V; v0 += nvc) {
-    const int64_t nv = std::min(nvc, V - v0);
-    hipLaunchKernelGGL(wfit_mat_kernel, dim3((unsigned)nv, (unsigned)((M + 7) / 8)), dim3(256), 0, st, a, v0, K, has_csf, d_xc,
-                       dA.as<double>(), dYs.as<double>());
-    HIPCHK(hipGetLastError());
-    for (int64_t q = 0; q < nv; ++q) {
-      const int64_t v = v0 + q;
-      if (int rc = mfx_solve_dense_dev(dA.as<double>() + (size_t)q * M * Ntot, M, K, N, has_csf, dYs.as<double>() + (size_t)q * M, maxfasc,
-                                       csf_on, d_params + (size_t)v * np, ok.as<int>() + v, dS.p, st)) return rc;
-    }
-    hipLaunchKernelGGL(wfit_repack_kernel, dim3((unsigned)nv), dim3(64), sizeof(double) * M, st, a, v0, K, has_csf, d_xc);
-    HIPCHK(hipGetLastError());
-  }
-  return MFX_OK;
+  const size_t Ntot = (size_t)K * N + has_csf;
+  return mfx_solve_dense_chunks(
+      M, K, N, has_csf, sizeof(double) * M * (Ntot + 1), V, maxfasc, csf_on, d_params, ok.as<int>(), st,
+      [&](int64_t v0, int64_t nv, int64_t nvc, double* dA, const double** y) -> int {
+        double* dYs = dA + (size_t)nvc * M * Ntot;
+        hipLaunchKernelGGL(wfit_mat_kernel, dim3((unsigned)nv, (unsigned)((M + 7) / 8)), dim3(256), 0, st, a, v0, K, has_csf, d_xc, dA, dYs);
+        HIPCHK(hipGetLastError());
+        *y = dYs;
+        return MFX_OK;
+      },
+      [&](int64_t v0, int64_t nv) -> int {
+        hipLaunchKernelGGL(wfit_repack_kernel, dim3((unsigned)nv), dim3(64), sizeof(double) * M, st, a, v0, K, has_csf, d_xc);
+        HIPCHK(hipGetLastError());
+        return MFX_OK;
+      });
 }
 
 }  // namespace
@@ -803,7 +787,7 @@ extern "C" int mfx_wfit_max_atoms(const void* pv, int K) {
 
 extern "C" int mfx_wfit_batch_dev(const void* pv, const double* d_Y, const double* d_W, int64_t w_stride, const double* d_peaks,
                                   int maxfasc, int64_t V, double* d_params, int32_t* d_status, void* stream) {
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
+  if (mfx_device_count() <= 0) return mfx_no_device();
   const mfx_plan* p = (const mfx_plan*)pv;
   if (!p || V < 0 || maxfasc < 0 || (V > 0 && (!d_Y || !d_W || !d_params || !d_status || (maxfasc > 0 && !d_peaks))))
     return mfx_fail(MFX_ERR_ARG, "mfx_wfit_batch_dev: bad argument");
@@ -814,7 +798,7 @@ extern "C" int mfx_wfit_batch_dev(const void* pv, const double* d_Y, const doubl
   if (w_stride != 0 && w_stride != a.P.M)
     return mfx_fail(MFX_ERR_ARG, "mfx_wfit_batch_dev: w_stride should be M = %d or 0 (got %lld)", a.P.M, (long long)w_stride);
   if (V == 0) return MFX_OK;
-  if (int rc = w_require_device(device)) return rc;
+  if (int rc = mfx_require_device(device)) return rc;
   return w_class_dev(p, d_Y, d_W, w_stride, d_peaks, maxfasc, nullptr, maxfasc, 0, V, d_params, d_status, (hipStream_t)stream);
 }
 
@@ -822,7 +806,7 @@ extern "C" int mfx_wfit_batch(const void* pv, const double* Y, const double* W, 
                               const uint8_t* csf, const double* peaks, int maxfasc, int csf_on, const double* sig_csf, int64_t V,
                               double* params, int32_t* status) {
   const char* fn = "mfx_wfit_batch";
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
+  if (mfx_device_count() <= 0) return mfx_no_device();
   const mfx_plan* p = (const mfx_plan*)pv;
   if (!p || V < 0 || maxfasc < 0 || (V > 0 && (!Y || !W || !K || !params || !status || (maxfasc > 0 && !peaks))))
     return mfx_fail(MFX_ERR_ARG, "%s: bad argument", fn);
@@ -835,58 +819,27 @@ extern "C" int mfx_wfit_batch(const void* pv, const double* Y, const double* W, 
   if (w_stride != 0 && w_stride != M)
     return mfx_fail(MFX_ERR_ARG, "%s: w_stride should be M = %d or 0 (got %lld)", fn, M, (long long)w_stride);
   // bin by class (K, CSF flag) before any device call
-  std::vector<std::vector<int64_t>> bins((size_t)2 * (maxfasc + 1));
-  for (int64_t v = 0; v < V; ++v) {
-    const int c = csf && csf[v];
-    if (K[v] < 0 || K[v] > maxfasc) return mfx_fail(MFX_ERR_ARG, "%s: K[%lld] = %d outside 0..%d", fn, (long long)v, K[v], maxfasc);
-    if (c && (!csf_on || !sig_csf)) return mfx_fail(MFX_ERR_ARG, "%s: voxels flagged CSF need csf_on and sig_csf", fn);
-    bins[(size_t)2 * K[v] + c].push_back(v);
-  }
+  MfxClassBins bins;
+  if (int rc = mfx_class_bins(fn, K, csf, maxfasc, csf_on && sig_csf, V, &bins)) return rc;
   if (V == 0) return MFX_OK;
-  if (int rc = w_require_device(device)) return rc;
-  DevMem dxc, dWs;
-  if (sig_csf) {
-    HIPCHK(dxc.alloc(sizeof(double) * M));
-    HIPCHK(hipMemcpy(dxc.p, sig_csf, sizeof(double) * M, hipMemcpyHostToDevice));
-  }
-  if (w_stride == 0) {   // the shared vector is uploaded once
-    HIPCHK(dWs.alloc(sizeof(double) * M));
-    HIPCHK(hipMemcpy(dWs.p, W, sizeof(double) * M, hipMemcpyHostToDevice));
-  }
+  if (int rc = mfx_require_device(device)) return rc;
+  DevBuf<double> dxc, dWs;
+  if (sig_csf) HIPCHK(dxc.upload(sig_csf, M));
+  if (w_stride == 0) HIPCHK(dWs.upload(W, M));   // the shared vector is uploaded once
   const size_t chunk = std::max<size_t>(1, ((size_t)256 << 20) / (sizeof(double) * 2 * (size_t)M));   // voxels per upload
-  for (size_t b = 0; b < bins.size(); ++b) {
-    const std::vector<int64_t>& all = bins[b];
-    const int k = (int)(b >> 1), c = (int)(b & 1);
-    for (size_t c0 = 0; c0 < all.size(); c0 += chunk) {
-      const size_t nv = std::min(chunk, all.size() - c0);
-      const int64_t* ix = all.data() + c0;
-      std::vector<double> Yc(nv * M), Wc(w_stride ? nv * M : 0), pc(nv * 3 * (size_t)std::max(k, 1)), prm(nv * np);
-      std::vector<int32_t> stc(nv);
-      for (size_t q = 0; q < nv; ++q) {
-        std::memcpy(&Yc[q * M], Y + (size_t)ix[q] * M, sizeof(double) * M);
-        if (w_stride) std::memcpy(&Wc[q * M], W + (size_t)ix[q] * M, sizeof(double) * M);
-        if (k > 0) std::memcpy(&pc[q * 3 * k], peaks + (size_t)ix[q] * 3 * maxfasc, sizeof(double) * 3 * k);
-      }
-      DevMem dY, dW, dpk, dpr, dst;
-      HIPCHK(dY.alloc(sizeof(double) * Yc.size()));
-      HIPCHK(dW.alloc(sizeof(double) * Wc.size()));
-      HIPCHK(dpk.alloc(sizeof(double) * pc.size()));
-      HIPCHK(dpr.alloc(sizeof(double) * prm.size()));
-      HIPCHK(dst.alloc(sizeof(int32_t) * stc.size()));
-      HIPCHK(hipMemcpy(dY.p, Yc.data(), sizeof(double) * Yc.size(), hipMemcpyHostToDevice));
-      if (w_stride) HIPCHK(hipMemcpy(dW.p, Wc.data(), sizeof(double) * Wc.size(), hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(dpk.p, pc.data(), sizeof(double) * pc.size(), hipMemcpyHostToDevice));
-      if (int rc = w_class_dev(p, dY.as<double>(), w_stride ? dW.as<double>() : dWs.as<double>(), w_stride, dpk.as<double>(), k,
-                               c ? dxc.as<double>() : nullptr, maxfasc, csf_on, (int64_t)nv, dpr.as<double>(), dst.as<int32_t>(), nullptr))
-        return rc;
-      HIPCHK(hipStreamSynchronize(nullptr));
-      HIPCHK(hipMemcpy(prm.data(), dpr.p, sizeof(double) * prm.size(), hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(stc.data(), dst.p, sizeof(int32_t) * stc.size(), hipMemcpyDeviceToHost));
-      for (size_t q = 0; q < nv; ++q) {
-        std::memcpy(params + (size_t)ix[q] * np, &prm[q * np], sizeof(double) * np);
-        status[ix[q]] = stc[q];
-      }
-    }
-  }
-  return MFX_OK;
+  return mfx_class_walk(bins, chunk, [&](int k, int c, const int64_t* ix, size_t nv) -> int {
+    DevBuf<double> dY, dW, dpk, dpr;
+    DevBuf<int32_t> dst;
+    HIPCHK(dY.upload_rows(Y, ix, nv, M, M));
+    if (w_stride) HIPCHK(dW.upload_rows(W, ix, nv, M, M));
+    HIPCHK(mfx_upload_peaks(dpk, peaks, ix, nv, maxfasc, k));
+    HIPCHK(dpr.alloc_n(nv * np));
+    HIPCHK(dst.alloc_n(nv));
+    if (int rc = w_class_dev(p, dY.get(), w_stride ? dW.get() : dWs.get(), w_stride, dpk.get(), k, c ? dxc.get() : nullptr, maxfasc, csf_on,
+                             (int64_t)nv, dpr.get(), dst.get(), nullptr)) return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    HIPCHK(dpr.download_rows(params, ix, nv, np));
+    HIPCHK(dst.download_rows(status, ix, nv, 1));
+    return MFX_OK;
+  });
 }

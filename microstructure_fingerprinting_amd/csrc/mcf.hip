@@ -397,7 +397,7 @@ int mcf_run(const double* lam, const double* B, int M, const double* seq, int64_
   if (n_seq == 0 || n_atoms == 0) return MFX_OK;
   {
     int dev = 0;
-    if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)");
+    if (mfx_device_count() <= 0) return mfx_no_device();
     HIPCHK(hipGetDevice(&dev));
     HIPCHK(hipSetDevice(dev));
   }

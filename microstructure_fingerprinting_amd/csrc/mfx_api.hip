@@ -290,9 +290,9 @@ void mfx_plan_view(const mfx_plan* p, TablesDev* T, PlanDev* P, int* device) {
   *T = p->t->d; *P = p->d; *device = p->t->device;
 }
 
-static int require_device(int device) {
+int mfx_require_device(int device) {
   int n = mfx_device_count();
-  if (n <= 0) return fail(MFX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)");
+  if (n <= 0) return mfx_no_device();
   if (device < 0 || device >= n) return fail(MFX_ERR_ARG, "device %d out of range (have %d)", device, n);
   HIPCHK(hipSetDevice(device));
   return MFX_OK;
@@ -302,7 +302,7 @@ extern "C" int mfx_tables_create(const double* knots_x, const int32_t* shell_off
                                  const double* G_un, int S, int N, int device, mfx_tables** out) {
   if (!knots_x || !shell_off || !knots_Y || !G_un || !out || S < 1 || N < 1)
     return fail(MFX_ERR_ARG, "mfx_tables_create: null or empty argument");
-  if (int rc = require_device(device)) return rc;
+  if (int rc = mfx_require_device(device)) return rc;
   const int P = shell_off[S];
   for (int s = 0; s < S; ++s)
     if (shell_off[s + 1] - shell_off[s] < 2) return fail(MFX_ERR_ARG, "shell %d has fewer than 2 knots", s);
@@ -527,7 +527,7 @@ extern "C" void mfx_plan_destroy(mfx_plan* p) {
 // unit-norm check (mf_utils.py:1798-1802; the reference raises ValueError from inside the voxel loop).
 extern "C" int mfx_plan_status(const mfx_plan* p, void* stream) {
   if (!p) return fail(MFX_ERR_ARG, "mfx_plan_status: null plan");
-  if (int rc = require_device(p->t->device)) return rc;
+  if (int rc = mfx_require_device(p->t->device)) return rc;
   int st[4] = {0, 0, 0, 0};
   HIPCHK(hipMemcpyAsync(st, p->dstatus, sizeof(st), hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));
@@ -1082,7 +1082,7 @@ extern "C" int mfx_fit_batch_dev(const mfx_plan* p, const double* d_Y, const dou
   if (maxfasc > 0 && !d_peaks) return fail(MFX_ERR_ARG, "mfx_fit_batch_dev: d_peaks is null but maxfasc = %d", maxfasc);
   if (V == 0) return MFX_OK;
   if (V > 0x7fffffff) return fail(MFX_ERR_ARG, "V too large for one launch");
-  if (int rc = require_device(p->t->device)) return rc;
+  if (int rc = mfx_require_device(p->t->device)) return rc;
   hipStream_t st = (hipStream_t)stream;
   HostTrace tr;
   if (int rc = mfx_fb_begin(st)) return rc;
@@ -1264,7 +1264,7 @@ static int fit_batch_host(const mfx_plan* p, const HostSource& src, const int32_
   if (maxfasc < 0 || maxfasc > 3) return fail(MFX_ERR_ARG, "maxfasc must be 0..3 (MFModel.fit itself allows 2: MAX_FASC, mf.py:467)");
   if (maxfasc > 0 && !peaks) return fail(MFX_ERR_ARG, "mfx_fit_batch: peaks is null but maxfasc = %d", maxfasc);
   if (V > 0x7fffffff) return fail(MFX_ERR_ARG, "V too large");
-  if (int rc = require_device(p->t->device)) return rc;
+  if (int rc = mfx_require_device(p->t->device)) return rc;
   csf_on = csf_on ? 1 : 0;
   ear_on = ear_on ? 1 : 0;
   const int M = p->d.M;
@@ -1441,7 +1441,7 @@ extern "C" int mfx_volume_rows(const void* vol, int vol_dtype, double scl_slope,
   if (V > 0x7fffffff) return fail(MFX_ERR_ARG, "V too large");
   for (int64_t v = 0; v < V; ++v)
     if (vox[v] < 0 || vox[v] >= nvox) return fail(MFX_ERR_ARG, "mfx_volume_rows: voxel %lld: index %lld outside the volume", (long long)v, (long long)vox[v]);
-  if (int rc = require_device(device)) return rc;
+  if (int rc = mfx_require_device(device)) return rc;
   const size_t vol_bytes = es * (size_t)nvox * (size_t)ncomp;
   if (int rc = pipe_setup(device, std::min<size_t>(vol_bytes, (size_t)64 << 20))) return rc;
   MfxThread& T = mfx_thread();
@@ -1487,7 +1487,7 @@ extern "C" int mfx_rotate_dev(const mfx_plan* p, const double* d_dirs, int64_t B
                               void* stream) {
   if (!p || !d_dirs || !d_out || B < 0) return fail(MFX_ERR_ARG, "mfx_rotate_dev: bad argument");
   if (B == 0) return MFX_OK;
-  if (int rc = require_device(p->t->device)) return rc;
+  if (int rc = mfx_require_device(p->t->device)) return rc;
   const int M = p->d.M;
   for (int64_t b0 = 0; b0 < B; b0 += 32768) {  // gridDim.y limit
     const int nb = (int)std::min<int64_t>(32768, B - b0);
@@ -1502,7 +1502,7 @@ extern "C" int mfx_rotate_dev(const mfx_plan* p, const double* d_dirs, int64_t B
 extern "C" int mfx_rotate(const mfx_plan* p, const double* dirs, int64_t B, int normalise_dirs, double* out) {
   if (!p || !dirs || !out || B < 0) return fail(MFX_ERR_ARG, "mfx_rotate: bad argument");
   if (B == 0) return MFX_OK;
-  if (int rc = require_device(p->t->device)) return rc;
+  if (int rc = mfx_require_device(p->t->device)) return rc;
   const size_t n_out = (size_t)B * p->d.M * p->t->d.N;
   double *dd = nullptr, *dout = nullptr;
   HIPCHK(hipMalloc(&dd, sizeof(double) * 3 * B));
@@ -1521,7 +1521,7 @@ extern "C" int mfx_rotate_cols_dev(const mfx_plan* p, const double* d_dirs, cons
                                    int normalise_dirs, double* d_out, void* stream) {
   if (!p || !d_dirs || !d_cols || !d_out || B < 0) return fail(MFX_ERR_ARG, "mfx_rotate_cols_dev: bad argument");
   if (B == 0) return MFX_OK;
-  if (int rc = require_device(p->t->device)) return rc;
+  if (int rc = mfx_require_device(p->t->device)) return rc;
   const int64_t total = B * p->d.M;
   const int64_t blocks = (total + 255) / 256;
   if (blocks > 0x7fffffff) return fail(MFX_ERR_ARG, "batch too large");
@@ -1535,7 +1535,7 @@ extern "C" int mfx_rotate_cols(const mfx_plan* p, const double* dirs, const int3
                                int normalise_dirs, double* out) {
   if (!p || !dirs || !cols || !out || B < 0) return fail(MFX_ERR_ARG, "mfx_rotate_cols: bad argument");
   if (B == 0) return MFX_OK;
-  if (int rc = require_device(p->t->device)) return rc;
+  if (int rc = mfx_require_device(p->t->device)) return rc;
   for (int64_t b = 0; b < B; ++b)
     if (cols[b] < 0 || cols[b] >= p->t->d.N) return fail(MFX_ERR_ARG, "atom index %d out of range", cols[b]);
   double *dd = nullptr, *dout = nullptr;
@@ -1576,7 +1576,7 @@ extern "C" int mfx_cleanup_2fascicles(const double* f1, const double* f2, const 
   if (n < 0 || (n > 0 && (!f1 || !f2 || !p1 || !p2 || !peaks_out || !count_out)))
     return fail(MFX_ERR_ARG, "mfx_cleanup_2fascicles: bad argument");
   if (n == 0) return MFX_OK;
-  if (int rc = require_device(device)) return rc;
+  if (int rc = mfx_require_device(device)) return rc;
   DevMem din, dout;
   HIPCHK(din.alloc(sizeof(double) * 8 * (size_t)n));
   HIPCHK(dout.alloc(sizeof(double) * 7 * (size_t)n));
@@ -1601,9 +1601,9 @@ extern "C" int mfx_solve_exhaustive(const double* A, int64_t lda, int M, const i
   if (Kp > MFX_GK) return fail(MFX_ERR_UNSUPPORTED, "at most %d sub-dictionaries are supported (got %d)", MFX_GK, Kp);
   {   // runs on the calling thread's current device
     int dev = 0;
-    if (mfx_device_count() <= 0) return fail(MFX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)");
+    if (mfx_device_count() <= 0) return mfx_no_device();
     HIPCHK(hipGetDevice(&dev));
-    if (int rc = require_device(dev)) return rc;
+    if (int rc = mfx_require_device(dev)) return rc;
   }
   SolveArgs a{};
   long Ntot = 0, ntup = 1;
@@ -1738,7 +1738,7 @@ extern "C" int mfx_monte_carlo_average(const double* sim_phases, int64_t n_entri
     return fail(MFX_ERR_ARG, "mfx_monte_carlo_average: need n_seq >= 0, 1 <= dim <= 3, num_spins >= 1");
   if (n_seq == 0) return MFX_OK;
   if (!sim_phases) return fail(MFX_ERR_ARG, "mfx_monte_carlo_average: null argument");
-  if (int rc = require_device(device)) return rc;
+  if (int rc = mfx_require_device(device)) return rc;
   DevMem dph;
   HIPCHK(dph.alloc(sizeof(double) * (size_t)n_entries * dim));
   HIPCHK(hipMemcpy(dph.p, sim_phases, sizeof(double) * (size_t)n_entries * dim, hipMemcpyHostToDevice));

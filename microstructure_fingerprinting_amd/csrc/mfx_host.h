@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "class_batch.h"
 #include "fit_k2.hip"
 #include "fit_k2x.hip"
 
@@ -78,6 +79,10 @@ struct MfxThread {
 
 MfxThread& mfx_thread();
 int mfx_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+// what every compute entry point answers first where mfx_device_count() <= 0
+inline int mfx_no_device() { return mfx_fail(MFX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)"); }
+// mfx_api.hip: the device count, then the range of `device`, then hipSetDevice
+int mfx_require_device(int device);
 
 #define HIPCHK(x)                                                                                   \
   do {                                                                                              \
@@ -96,6 +101,37 @@ struct DevMem {
   void* release() { void* q = p; p = nullptr; return q; }
   template <class T> T* as() const { return (T*)p; }
 };
+// a device array of n elements of T and its copies from and to host memory, each one checked call (HIPCHK).  The row
+// forms move the rows ix[0 .. nv) of a host array through a contiguous [nv x width] copy (class_batch.h).
+template <class T>
+struct DevBuf : DevMem {
+  size_t n = 0;
+  T* get() const { return (T*)p; }
+  hipError_t alloc_n(size_t n_) { n = n_; return alloc(sizeof(T) * n); }
+  hipError_t upload(const T* src, size_t n_) {
+    const hipError_t e = alloc_n(n_);
+    return e != hipSuccess ? e : hipMemcpy(p, src, sizeof(T) * n, hipMemcpyHostToDevice);
+  }
+  hipError_t download(T* dst) const { return hipMemcpy(dst, p, sizeof(T) * n, hipMemcpyDeviceToHost); }
+  hipError_t upload_rows(const T* src, const int64_t* ix, size_t nv, size_t src_ld, size_t width) {
+    std::vector<T> rows(nv * width);
+    gather_rows(rows.data(), src, ix, nv, src_ld, width);
+    return upload(rows.data(), rows.size());
+  }
+  hipError_t download_rows(T* dst, const int64_t* ix, size_t nv, size_t width) const {
+    std::vector<T> rows(nv * width);
+    const hipError_t e = download(rows.data());
+    if (e == hipSuccess) scatter_rows(dst, rows.data(), ix, nv, width);
+    return e;
+  }
+};
+// the directions of a class chunk: the first 3 k of every [3 maxfasc] row of peaks -> [nv x 3 k]; for k = 0 three zeros
+// per voxel, which nobody reads, so that no upload is empty
+inline hipError_t mfx_upload_peaks(DevBuf<double>& d, const double* peaks, const int64_t* ix, size_t nv, int maxfasc, int k) {
+  if (k > 0) return d.upload_rows(peaks, ix, nv, 3 * (size_t)maxfasc, 3 * (size_t)k);
+  const std::vector<double> zeros(nv * 3, 0.0);
+  return d.upload(zeros.data(), zeros.size());
+}
 // Scratch memory of a call (per-workgroup slabs, short lists, extra columns, Gram / candidate buffers) comes from an ARENA
 // per (host thread, stream): a few device blocks (a new one whenever a request does not fit: hipMalloc, once), handed out
 // by bumping an offset through them in order, and taken back when the call's last StreamMem dies.  Calls on one stream execute in order, so the next call may reuse the
@@ -143,6 +179,35 @@ void mfx_plan_view(const mfx_plan* p, TablesDev* T, PlanDev* P, int* device);
 int mfx_solve_dense_scratch_bytes(int M, int K, int N, int has_csf, size_t* bytes);
 int mfx_solve_dense_dev(const double* d_A, int M, int K, int N, int has_csf, const double* d_y, int maxfasc, int csf_on,
                         double* d_row, const int* run_if, void* d_scratch, hipStream_t st);
+// The explicit fallback of a class launcher (fit2d.hip, w2d.hip, fit_w.hip): the V voxels in chunks of nvc within a byte
+// budget of min(free / 4, 1 GiB) at per_vox bytes a voxel, one scratch block of per_vox * nvc bytes for all chunks.  Per
+// chunk: materialise(v0, nv, nvc, block, &y) enqueues the dictionaries [nv x M x (K N + has_csf)] at the front of the
+// block and sets y to the signal of voxel v0 (stride M); the solver runs voxel by voxel where ok[v]; after(v0, nv)
+// enqueues what follows a chunk.  Only enqueues, in that order.
+template <class Materialise, class After>
+int mfx_solve_dense_chunks(int M, int K, int N, int has_csf, size_t per_vox, int64_t V, int maxfasc, int csf_on, double* d_params,
+                           const int* ok, hipStream_t st, Materialise materialise, After after) {
+  const size_t Ntot = (size_t)K * N + has_csf;
+  const int np = 1 + 2 * maxfasc + csf_on + 2;
+  size_t free_b = 0, total_b = 0, scratch_b = 0;
+  HIPCHK(hipMemGetInfo(&free_b, &total_b));
+  if (int rc = mfx_solve_dense_scratch_bytes(M, K, N, has_csf, &scratch_b)) return rc;
+  const size_t budget = std::min<size_t>(free_b / 4, (size_t)1 << 30);
+  const int64_t nvc = std::max<int64_t>(1, std::min<int64_t>(V, (int64_t)(budget / per_vox)));
+  StreamMem dA(st), dS(st);
+  HIPCHK(dA.alloc(per_vox * nvc));
+  HIPCHK(dS.alloc(scratch_b));
+  for (int64_t v0 = 0; v0 < V; v0 += nvc) {
+    const int64_t nv = std::min(nvc, V - v0);
+    const double* y = nullptr;
+    if (int rc = materialise(v0, nv, nvc, dA.as<double>(), &y)) return rc;
+    for (int64_t q = 0; q < nv; ++q)
+      if (int rc = mfx_solve_dense_dev(dA.as<double>() + (size_t)q * M * Ntot, M, K, N, has_csf, y + (size_t)q * M, maxfasc, csf_on,
+                                       d_params + (size_t)(v0 + q) * np, ok + v0 + q, dS.p, st)) return rc;
+    if (int rc = after(v0, nv)) return rc;
+  }
+  return MFX_OK;
+}
 
 // class launchers for robust.hip: one homogeneous class (every voxel K fascicles, d_peaks [V x 3 K] contiguous, the CSF
 // column d_xc or null) into rows of the (maxfasc, csf_on) layout; they only enqueue.
@@ -161,6 +226,37 @@ int mfx_rob_launch_weights(int M, const double* d_Y, const double* d_P, const do
                            hipStream_t st);
 int mfx_rob_spread(const double* d_W0, int64_t w0_stride, int M, int64_t V, double* d_W, hipStream_t st);
 int mfx_rob_count(const int* d_flags, int64_t V, int* d_out, hipStream_t st);
+// The robust loop of robust.hip and robust2d.hip: the first fit, then per iteration the reweighting and the weighted fit.
+// steps: first_fit(), reweight(it), refit() (they only enqueue) and step_done(), which follows each of them.  The device
+// entry points pass host = null and enqueue every iteration.  The host entry points go one iteration at a time: they read
+// nchanged[it] (the copy waits for the default stream), add it to n_changed[it], and an iteration that changed nothing
+// leaves its fit out when the parameters already are those of a weighted fit on these weights (any iteration but the
+// first one after an unweighted fit): every later iteration would repeat it bit for bit.
+struct MfxRobHostCount {
+  const int32_t* d_nchanged;
+  bool has_w0;
+  int64_t* n_changed;
+  int32_t* n_iter_used;   // raised to the iterations this chunk took
+};
+template <class Steps>
+int mfx_rob_iterate(const Steps& s, int n_iter, const MfxRobHostCount* host) {
+  if (int rc = s.first_fit()) return rc;
+  s.step_done();
+  for (int it = 0; it < n_iter; ++it) {
+    if (int rc = s.reweight(it)) return rc;
+    s.step_done();
+    if (host) {
+      int32_t nc = 0;
+      HIPCHK(hipMemcpy(&nc, host->d_nchanged + it, sizeof(int32_t), hipMemcpyDeviceToHost));
+      host->n_changed[it] += nc;
+      *host->n_iter_used = std::max<int32_t>(*host->n_iter_used, it + 1);
+      if (nc == 0 && (it > 0 || host->has_w0)) break;
+    }
+    if (int rc = s.refit()) return rc;
+    s.step_done();
+  }
+  return MFX_OK;
+}
 
 // ---- kernel launchers, one translation unit each
 // FP64 two-fascicle kernel (tu_k2.hip).  With a.list_count set, a.vox_list is a device-side list whose length only the

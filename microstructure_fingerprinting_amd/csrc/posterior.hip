@@ -592,16 +592,6 @@ int post_launch_k1(const PostArgsW& a, int nvox, bool csf, hipStream_t st) {
   return MFX_OK;
 }
 
-const char* POST_NO_DEVICE = "no HIP device available (this library has no CPU path)";
-
-int post_require_device(int device) {
-  const int n = mfx_device_count();
-  if (n <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", POST_NO_DEVICE);
-  if (device < 0 || device >= n) return mfx_fail(MFX_ERR_ARG, "device %d out of range (have %d)", device, n);
-  HIPCHK(hipSetDevice(device));
-  return MFX_OK;
-}
-
 int post_check_args(const char* fn, const mfx_plan* p, const void* Y, const void* peaks, int K, int csf_on, const void* sig_csf,
                     const void* T, const void* shift, int64_t V, const void* w, const void* log_sum, const void* status) {
   if (!p || V < 0 || (V > 0 && (!Y || !peaks || !T || !shift || !w || !log_sum || !status)))
@@ -617,7 +607,7 @@ int post_check_args(const char* fn, const mfx_plan* p, const void* Y, const void
 int post_enqueue(const char* fn, const mfx_plan* p, const double* d_Y, const double* d_peaks, int K, int csf_on,
                  const double* d_sig_csf, const double* d_T, const double* d_shift, int64_t V, double* d_w, double* d_log_sum,
                  int32_t* d_status, void* stream, bool wgt = false, const double* d_W = nullptr, int64_t w_stride = 0) {
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", POST_NO_DEVICE);
+  if (mfx_device_count() <= 0) return mfx_no_device();
   if (int rc = post_check_args(fn, p, d_Y, d_peaks, K, csf_on, d_sig_csf, d_T, d_shift, V, d_w, d_log_sum, d_status)) return rc;
   PostArgsW a{};
   int device = 0;
@@ -628,7 +618,7 @@ int post_enqueue(const char* fn, const mfx_plan* p, const double* d_Y, const dou
     return mfx_fail(MFX_ERR_ARG, "%s: w_stride should be M = %d or 0 (got %lld)", fn, a.P.M, (long long)w_stride);
   if (mfx_profile_cut() != MFX_POST_CUT) return mfx_fail(MFX_ERR_HIP, "%s: built with a cut other than the profile's", fn);
   if (V == 0) return MFX_OK;
-  if (int rc = post_require_device(device)) return rc;
+  if (int rc = mfx_require_device(device)) return rc;
   a.Y = d_Y; a.peaks = d_peaks; a.xc = csf_on ? d_sig_csf : nullptr; a.temp = d_T; a.shift = d_shift;
   a.w = d_w; a.log_sum = d_log_sum; a.status = d_status;
   a.W = d_W; a.wstride = w_stride;
@@ -641,7 +631,7 @@ int post_enqueue(const char* fn, const mfx_plan* p, const double* d_Y, const dou
 int post_host(const char* fn, const mfx_plan* p, const double* Y, const double* peaks, int K, int csf_on, const double* sig_csf,
               const double* T, const double* shift, int64_t V, double* w, double* log_sum, int32_t* status, bool wgt = false,
               const double* W = nullptr, int64_t w_stride = 0) {
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", POST_NO_DEVICE);   // before the plan is looked at
+  if (mfx_device_count() <= 0) return mfx_no_device();   // before the plan is looked at
   if (int rc = post_check_args(fn, p, Y, peaks, K, csf_on, sig_csf, T, shift, V, w, log_sum, status)) return rc;
   if (V == 0) return MFX_OK;
   TablesDev Td;
@@ -650,7 +640,7 @@ int post_host(const char* fn, const mfx_plan* p, const double* Y, const double* 
   mfx_plan_view(p, &Td, &P, &device);
   if (wgt && (!W || (w_stride != 0 && w_stride != P.M)))
     return mfx_fail(MFX_ERR_ARG, "%s: W should be given with w_stride M = %d or 0 (got %lld)", fn, P.M, (long long)w_stride);
-  if (int rc = post_require_device(device)) return rc;
+  if (int rc = mfx_require_device(device)) return rc;
   const size_t M = P.M, N = Td.N, nout = (size_t)V * K * N;
   const size_t nW = wgt ? (w_stride ? (size_t)V * M : M) : 0;
   DevMem dY, dpk, dx, dT, dsh, dw, dls, dst, dW;

@@ -189,16 +189,6 @@ __global__ __launch_bounds__(256) void mfx_sos_noise_kernel(const double* S0, in
     out[i] = sos_value(S0[i], sigma[sigma_mode == MFX_SIGMA_ELEMENT ? i : 0], ncoils, seed, offset + (unsigned long long)i);
 }
 
-const char* NO_DEVICE = "no HIP device available (this library has no CPU path)";
-
-int pred_require_device(int device) {
-  const int n = mfx_device_count();
-  if (n <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
-  if (device < 0 || device >= n) return mfx_fail(MFX_ERR_ARG, "device %d out of range (have %d)", device, n);
-  HIPCHK(hipSetDevice(device));
-  return MFX_OK;
-}
-
 int pred_num_params(int maxfasc, int csf_on, int ear_on) { return 1 + 2 * maxfasc + (csf_on ? 1 : 0) + (ear_on ? 2 : 0) + 2; }
 
 // what both prediction entry points check before anything else
@@ -238,7 +228,7 @@ extern "C" int mfx_predict_dev(const mfx_plan* p, const double* d_params, const 
                                int ear_on, const double* d_sig_csf, const double* d_sig_ear, int E, int64_t V,
                                const double* d_Y, const double* d_sigma, int sigma_mode, int ncoils, uint64_t seed,
                                uint64_t offset, double* d_out, double* d_stats, int32_t* d_status, void* stream) {
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
+  if (mfx_device_count() <= 0) return mfx_no_device();
   if (int rc = pred_check_args("mfx_predict_dev", p, d_params, d_peaks, maxfasc, csf_on, ear_on, d_sig_csf, d_sig_ear, E, V, d_Y,
                                d_sigma, sigma_mode, ncoils, d_out, d_stats)) return rc;
   if (V > 0 && !d_status) return mfx_fail(MFX_ERR_ARG, "mfx_predict_dev: d_status is null");
@@ -248,7 +238,7 @@ extern "C" int mfx_predict_dev(const mfx_plan* p, const double* d_params, const 
   PlanDev P;
   int device = 0;
   mfx_plan_view(p, &T, &P, &device);
-  if (int rc = pred_require_device(device)) return rc;
+  if (int rc = mfx_require_device(device)) return rc;
   PredArgs a{};
   a.params = d_params; a.peaks = d_peaks; a.sig_csf = d_sig_csf; a.sig_ear = d_sig_ear; a.Y = d_Y; a.sigma = d_sigma;
   a.out = d_out; a.stats = d_stats; a.status = d_status; a.V = V; a.seed = seed; a.offset = offset;
@@ -299,7 +289,7 @@ extern "C" int mfx_predict(const mfx_plan* p, const double* params, const double
       }
     }
   }
-  if (int rc = pred_require_device(device)) return rc;
+  if (int rc = mfx_require_device(device)) return rc;
   const size_t VM = (size_t)V * M;
   const size_t n_sigma = ncoils > 0 ? (sigma_mode == MFX_SIGMA_SCALAR ? 1 : (sigma_mode == MFX_SIGMA_VOXEL ? (size_t)V : VM)) : 0;
   DevMem dpar, dpk, dcsf, dear, dY, dsig, dout, dstats, dst;
@@ -334,10 +324,10 @@ extern "C" int mfx_predict(const mfx_plan* p, const double* params, const double
 
 extern "C" int mfx_sos_noise_dev(const double* d_S0, int64_t n, const double* d_sigma, int sigma_mode, int ncoils, uint64_t seed,
                                  uint64_t offset, double* d_out, int device, void* stream) {
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
+  if (mfx_device_count() <= 0) return mfx_no_device();
   if (int rc = sos_check_args("mfx_sos_noise_dev", d_S0, n, d_sigma, sigma_mode, ncoils, d_out)) return rc;
   if (n == 0) return MFX_OK;
-  if (int rc = pred_require_device(device)) return rc;
+  if (int rc = mfx_require_device(device)) return rc;
   hipLaunchKernelGGL(mfx_sos_noise_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, d_S0, n, d_sigma,
                      sigma_mode, ncoils, (unsigned long long)seed, (unsigned long long)offset, d_out);
   HIPCHK(hipGetLastError());
@@ -348,7 +338,7 @@ extern "C" int mfx_sos_noise(const double* S0, int64_t n, const double* sigma, i
                              uint64_t offset, double* out, int device) {
   if (int rc = sos_check_args("mfx_sos_noise", S0, n, sigma, sigma_mode, ncoils, out)) return rc;
   if (n == 0) return MFX_OK;
-  if (int rc = pred_require_device(device)) return rc;
+  if (int rc = mfx_require_device(device)) return rc;
   const size_t ns = sigma_mode == MFX_SIGMA_ELEMENT ? (size_t)n : 1;
   DevMem dS, dsig;
   HIPCHK(dS.alloc(sizeof(double) * n));

@@ -142,16 +142,6 @@ __global__ __launch_bounds__(P2_WG) void mfx_predict2d_kernel(P2Args a) {
   }
 }
 
-const char* NO_DEVICE = "no HIP device available (this library has no CPU path)";
-
-int p2_require_device(int device) {
-  const int n = mfx_device_count();
-  if (n <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
-  if (device < 0 || device >= n) return mfx_fail(MFX_ERR_ARG, "device %d out of range (have %d)", device, n);
-  HIPCHK(hipSetDevice(device));
-  return MFX_OK;
-}
-
 // what both entry points check before anything else
 int p2_check_args(const char* fn, const mfx_rot2d* h, const void* params, const void* peaks, int maxfasc, int csf_on,
                   const void* sig_csf, int64_t V, const void* Y, const void* sigma, int sigma_mode, int ncoils, const void* out,
@@ -203,14 +193,14 @@ extern "C" int mfx_predict2d_dev(void* hv, const double* d_params, const double*
                                  int ncoils, uint64_t seed, uint64_t offset, double* d_out, double* d_stats, int32_t* d_status,
                                  int32_t* d_dir_status, void* stream) {
   const char* fn = "mfx_predict2d_dev";
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
+  if (mfx_device_count() <= 0) return mfx_no_device();
   const mfx_rot2d* h = (const mfx_rot2d*)hv;
   if (int rc = p2_check_args(fn, h, d_params, d_peaks, maxfasc, csf_on, d_sig_csf, V, d_Y, d_sigma, sigma_mode, ncoils, d_out,
                              d_stats, d_dir_status)) return rc;
   if (V > 0 && !d_status) return mfx_fail(MFX_ERR_ARG, "%s: d_status is null", fn);
   if (V == 0) return MFX_OK;
   if (int rc = f2_limits(fn, h, maxfasc, V)) return rc;
-  if (int rc = p2_require_device(h->device)) return rc;
+  if (int rc = mfx_require_device(h->device)) return rc;
   hipStream_t st = (hipStream_t)stream;
   F2Dirs dirs(st);
   if (int rc = dirs.enqueue(h, d_peaks, V * maxfasc, st)) return rc;
@@ -222,7 +212,7 @@ extern "C" int mfx_predict2d(void* hv, const double* params, const double* peaks
                              int64_t V, const double* Y, const double* sigma, int sigma_mode, int ncoils, uint64_t seed,
                              uint64_t offset, double* out, double* stats, int32_t* dir_status) {
   const char* fn = "mfx_predict2d";
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
+  if (mfx_device_count() <= 0) return mfx_no_device();
   const mfx_rot2d* h = (const mfx_rot2d*)hv;
   if (int rc = p2_check_args(fn, h, params, peaks, maxfasc, csf_on, sig_csf, V, Y, sigma, sigma_mode, ncoils, out, stats,
                              dir_status)) return rc;
@@ -245,7 +235,7 @@ extern "C" int mfx_predict2d(void* hv, const double* params, const double* peaks
       }
     }
   }
-  if (int rc = p2_require_device(h->device)) return rc;
+  if (int rc = mfx_require_device(h->device)) return rc;
   const size_t VM = (size_t)V * M;
   const size_t n_sigma = ncoils > 0 ? (sigma_mode == MFX_SIGMA_SCALAR ? 1 : (sigma_mode == MFX_SIGMA_VOXEL ? (size_t)V : VM)) : 0;
   DevMem dpar, dpk, dcsf, dY, dsig, dout, dstats, dst, dds;

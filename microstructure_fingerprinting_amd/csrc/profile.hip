@@ -598,16 +598,6 @@ int prof_launch_k1(const ProfArgsW& a, int nvox, bool csf, hipStream_t st) {
   return MFX_OK;
 }
 
-const char* NO_DEVICE = "no HIP device available (this library has no CPU path)";
-
-int prof_require_device(int device) {
-  const int n = mfx_device_count();
-  if (n <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
-  if (device < 0 || device >= n) return mfx_fail(MFX_ERR_ARG, "device %d out of range (have %d)", device, n);
-  HIPCHK(hipSetDevice(device));
-  return MFX_OK;
-}
-
 int prof_check_args(const char* fn, const mfx_plan* p, const void* Y, const void* peaks, int K, int csf_on, const void* sig_csf,
                     int64_t V, const void* out) {
   if (!p || V < 0 || (V > 0 && (!Y || !peaks || !out))) return mfx_fail(MFX_ERR_ARG, "%s: bad argument", fn);
@@ -622,7 +612,7 @@ int prof_check_args(const char* fn, const mfx_plan* p, const void* Y, const void
 int prof_enqueue(const char* fn, const mfx_plan* p, const double* d_Y, const double* d_peaks, int K, int csf_on,
                  const double* d_sig_csf, int64_t V, double* d_obj, int32_t* d_partner, bool land, void* stream, bool wgt = false,
                  const double* d_W = nullptr, int64_t w_stride = 0) {
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
+  if (mfx_device_count() <= 0) return mfx_no_device();
   if (int rc = prof_check_args(fn, p, d_Y, d_peaks, K, csf_on, d_sig_csf, V, d_obj)) return rc;
   ProfArgsW a{};
   int device = 0;
@@ -632,7 +622,7 @@ int prof_enqueue(const char* fn, const mfx_plan* p, const double* d_Y, const dou
   if (wgt && w_stride != 0 && w_stride != a.P.M)
     return mfx_fail(MFX_ERR_ARG, "%s: w_stride should be M = %d or 0 (got %lld)", fn, a.P.M, (long long)w_stride);
   if (V == 0) return MFX_OK;
-  if (int rc = prof_require_device(device)) return rc;
+  if (int rc = mfx_require_device(device)) return rc;
   a.Y = d_Y; a.peaks = d_peaks; a.xc = csf_on ? d_sig_csf : nullptr; a.obj = d_obj; a.partner = d_partner;
   a.W = d_W; a.wstride = w_stride;
   hipStream_t st = (hipStream_t)stream;
@@ -644,7 +634,7 @@ int prof_enqueue(const char* fn, const mfx_plan* p, const double* d_Y, const dou
 // shared body of the host entry points: out [V x rows x N] with rows = K (profile) or N (landscape)
 int prof_host(const char* fn, const mfx_plan* p, const double* Y, const double* peaks, int K, int csf_on, const double* sig_csf,
               int64_t V, double* obj, int32_t* partner, bool land, bool wgt = false, const double* W = nullptr, int64_t w_stride = 0) {
-  if (wgt && mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);   // before the plan is looked at
+  if (wgt && mfx_device_count() <= 0) return mfx_no_device();   // before the plan is looked at
   if (int rc = prof_check_args(fn, p, Y, peaks, K, csf_on, sig_csf, V, obj)) return rc;
   if (V == 0) return MFX_OK;
   TablesDev T;
@@ -653,7 +643,7 @@ int prof_host(const char* fn, const mfx_plan* p, const double* Y, const double* 
   mfx_plan_view(p, &T, &P, &device);
   if (wgt && (!W || (w_stride != 0 && w_stride != P.M)))
     return mfx_fail(MFX_ERR_ARG, "%s: W should be given with w_stride M = %d or 0 (got %lld)", fn, P.M, (long long)w_stride);
-  if (int rc = prof_require_device(device)) return rc;
+  if (int rc = mfx_require_device(device)) return rc;
   const size_t M = P.M, N = T.N, nout = (size_t)V * (land ? N : (size_t)K) * N;
   const size_t nW = wgt ? (w_stride ? (size_t)V * M : M) : 0;
   DevMem dY, dpk, dx, dobj, dpar, dW;

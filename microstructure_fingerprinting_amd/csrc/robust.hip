@@ -1,6 +1,7 @@
 // robust.hip -- robust fits (include/mfx_robust.h): measurement weights from the residuals of a fit, and the loop
 // fit -> predict -> reweight -> weighted fit on device-resident data.  The fits and the prediction are the class
-// launchers of mfx_api.hip (unweighted), fit_w.hip (weighted) and predict.hip; what is new here is one kernel.
+// launchers of mfx_api.hip (unweighted), fit_w.hip (weighted) and predict.hip; what is new here is one kernel.  The loop
+// itself is mfx_rob_iterate (mfx_host.h) over the three steps below; the host side of a mixed batch is class_batch.h.
 //
 // mfx_robust_weights_kernel   One wave per voxel, ROB_WAVES(M) voxels per workgroup (a wave beyond the batch idles
 //                        through the barriers).  Lane l owns the rows l, l + 64, ...
@@ -178,16 +179,6 @@ __global__ __launch_bounds__(256) void rob_count_kernel(const int* __restrict__ 
   if (threadIdx.x == 0) *out = s_n[0];
 }
 
-const char* NO_DEVICE = "no HIP device available (this library has no CPU path)";
-
-int rob_require_device(int device) {
-  const int n = mfx_device_count();
-  if (n <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
-  if (device < 0 || device >= n) return mfx_fail(MFX_ERR_ARG, "device %d out of range (have %d)", device, n);
-  HIPCHK(hipSetDevice(device));
-  return MFX_OK;
-}
-
 int rob_check_rule(const char* fn, int loss, double c, int M) {
   if (loss != MFX_ROBUST_CUTOFF && loss != MFX_ROBUST_HUBER && loss != MFX_ROBUST_TUKEY)
     return mfx_fail(MFX_ERR_ARG, "%s: loss should be 0 (cutoff), 1 (huber) or 2 (tukey), got %d", fn, loss);
@@ -279,6 +270,15 @@ int rob_refit(const RobClass& r) {
   return mfx_wfit_class_dev(r.p, r.Y, r.W, P.M, r.peaksK, r.K, r.xc, r.maxfasc, r.csf_on, r.V, r.params, r.status, r.st);
 }
 
+// the loop's steps for mfx_rob_iterate (mfx_host.h); the steps give their scratch back themselves
+struct RobSteps {
+  const RobClass& r;
+  int first_fit() const { return rob_first_fit(r); }
+  int reweight(int it) const { return rob_reweight(r, it); }
+  int refit() const { return rob_refit(r); }
+  void step_done() const {}
+};
+
 }  // namespace
 
 // what robust2d.hip shares of this file (mfx_host.h)
@@ -308,7 +308,7 @@ extern "C" int mfx_robust_weights_dev(int M, const double* d_Y, const double* d_
                                       double c, int64_t V, const double* d_Wprev, double* d_W, double* d_scale, int32_t* d_state,
                                       int32_t* d_changed, void* stream) {
   const char* fn = "mfx_robust_weights_dev";
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
+  if (mfx_device_count() <= 0) return mfx_no_device();
   if (V < 0 || (V > 0 && (!d_Y || !d_P || !d_W || !d_scale || !d_state))) return mfx_fail(MFX_ERR_ARG, "%s: bad argument", fn);
   if (int rc = rob_check_rule(fn, loss, c, M)) return rc;
   if (d_W0 && w0_stride != 0 && w0_stride != M)
@@ -321,7 +321,7 @@ extern "C" int mfx_rfit_batch_dev(const void* pv, const double* d_Y, const doubl
                                   int maxfasc, int loss, double c, int n_iter, int64_t V, double* d_params, double* d_W,
                                   double* d_scale, int32_t* d_state, int32_t* d_status, int32_t* d_nchanged, void* stream) {
   const char* fn = "mfx_rfit_batch_dev";
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
+  if (mfx_device_count() <= 0) return mfx_no_device();
   const mfx_plan* p = (const mfx_plan*)pv;
   if (!p || V < 0 || maxfasc < 0 || n_iter < 0 ||
       (V > 0 && (!d_Y || !d_params || !d_W || !d_scale || !d_state || !d_status || (maxfasc > 0 && !d_peaks) || (n_iter > 0 && !d_nchanged))))
@@ -335,7 +335,7 @@ extern "C" int mfx_rfit_batch_dev(const void* pv, const double* d_Y, const doubl
   if (d_W0 && w0_stride != 0 && w0_stride != P.M)
     return mfx_fail(MFX_ERR_ARG, "%s: w0_stride should be M = %d or 0 (got %lld)", fn, P.M, (long long)w0_stride);
   if (V > 0x7fffffff) return mfx_fail(MFX_ERR_ARG, "%s: V too large for one launch", fn);
-  if (int rc = rob_require_device(device)) return rc;
+  if (int rc = mfx_require_device(device)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (V == 0) {
     if (n_iter > 0) HIPCHK(hipMemsetAsync(d_nchanged, 0, sizeof(int32_t) * (size_t)n_iter, st));
@@ -343,12 +343,7 @@ extern "C" int mfx_rfit_batch_dev(const void* pv, const double* d_Y, const doubl
   }
   const RobClass r{p, d_Y, d_W0, d_W0 ? w0_stride : 0, d_peaks, d_peaks, maxfasc, nullptr, nullptr, maxfasc, 0, loss, c, V,
                    d_params, d_W, d_scale, d_state, d_status, d_nchanged, st};
-  if (int rc = rob_first_fit(r)) return rc;
-  for (int it = 0; it < n_iter; ++it) {
-    if (int rc = rob_reweight(r, it)) return rc;
-    if (int rc = rob_refit(r)) return rc;
-  }
-  return MFX_OK;
+  return mfx_rob_iterate(RobSteps{r}, n_iter, nullptr);
 }
 
 extern "C" int mfx_rfit_batch(const void* pv, const double* Y, const double* W0, int64_t w0_stride, const int32_t* K,
@@ -356,7 +351,7 @@ extern "C" int mfx_rfit_batch(const void* pv, const double* Y, const double* W0,
                               double c, int n_iter, int64_t V, double* params, double* W_out, double* scale, int32_t* state,
                               int32_t* status, int64_t* n_changed, int32_t* n_iter_used) {
   const char* fn = "mfx_rfit_batch";
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
+  if (mfx_device_count() <= 0) return mfx_no_device();
   const mfx_plan* p = (const mfx_plan*)pv;
   if (!p || V < 0 || maxfasc < 0 || n_iter < 0 || !n_iter_used || (n_iter > 0 && !n_changed) ||
       (V > 0 && (!Y || !K || !params || !W_out || !scale || !state || !status || (maxfasc > 0 && !peaks))))
@@ -374,90 +369,41 @@ extern "C" int mfx_rfit_batch(const void* pv, const double* Y, const double* W0,
   if (!W0) w0_stride = 0;
   if (csf_on && !sig_csf) return mfx_fail(MFX_ERR_ARG, "%s: csf_on without sig_csf", fn);   // (the prediction of every class needs it)
   // bin by class (K, CSF flag) before any device call
-  std::vector<std::vector<int64_t>> bins((size_t)2 * (maxfasc + 1));
-  for (int64_t v = 0; v < V; ++v) {
-    const int cf = csf && csf[v];
-    if (K[v] < 0 || K[v] > maxfasc) return mfx_fail(MFX_ERR_ARG, "%s: K[%lld] = %d outside 0..%d", fn, (long long)v, K[v], maxfasc);
-    if (cf && (!csf_on || !sig_csf)) return mfx_fail(MFX_ERR_ARG, "%s: voxels flagged CSF need csf_on and sig_csf", fn);
-    bins[(size_t)2 * K[v] + cf].push_back(v);
-  }
+  MfxClassBins bins;
+  if (int rc = mfx_class_bins(fn, K, csf, maxfasc, csf_on && sig_csf, V, &bins)) return rc;
   *n_iter_used = 0;
   for (int it = 0; it < n_iter; ++it) n_changed[it] = 0;
   if (V == 0) return MFX_OK;
-  if (int rc = rob_require_device(device)) return rc;
-  DevMem dxc, dW0s, dnc;
-  if (sig_csf) {
-    HIPCHK(dxc.alloc(sizeof(double) * M));
-    HIPCHK(hipMemcpy(dxc.p, sig_csf, sizeof(double) * M, hipMemcpyHostToDevice));
-  }
-  if (W0 && w0_stride == 0) {   // the shared vector is uploaded once
-    HIPCHK(dW0s.alloc(sizeof(double) * M));
-    HIPCHK(hipMemcpy(dW0s.p, W0, sizeof(double) * M, hipMemcpyHostToDevice));
-  }
-  HIPCHK(dnc.alloc(sizeof(int32_t) * (size_t)std::max(n_iter, 1)));
+  if (int rc = mfx_require_device(device)) return rc;
+  DevBuf<double> dxc, dW0s;
+  DevBuf<int32_t> dnc;
+  if (sig_csf) HIPCHK(dxc.upload(sig_csf, M));
+  if (W0 && w0_stride == 0) HIPCHK(dW0s.upload(W0, M));   // the shared vector is uploaded once
+  HIPCHK(dnc.alloc_n((size_t)std::max(n_iter, 1)));
   const size_t chunk = std::max<size_t>(1, ((size_t)256 << 20) / (sizeof(double) * 4 * (size_t)M));   // voxels per upload: Y, W0, W, prediction
-  for (size_t b = 0; b < bins.size(); ++b) {
-    const std::vector<int64_t>& all = bins[b];
-    const int k = (int)(b >> 1), cf = (int)(b & 1);
-    for (size_t c0 = 0; c0 < all.size(); c0 += chunk) {
-      const size_t nv = std::min(chunk, all.size() - c0);
-      const int64_t* ix = all.data() + c0;
-      const size_t F = (size_t)std::max(maxfasc, 1), kk = (size_t)std::max(k, 1);
-      std::vector<double> Yc(nv * M), Wc(nv * M), pcK(nv * 3 * kk), pcF(nv * 3 * F), prm(nv * np), scc(nv);
-      std::vector<int32_t> stc(nv), stt(nv);
-      for (size_t q = 0; q < nv; ++q) {
-        std::memcpy(&Yc[q * M], Y + (size_t)ix[q] * M, sizeof(double) * M);
-        if (w0_stride) std::memcpy(&Wc[q * M], W0 + (size_t)ix[q] * M, sizeof(double) * M);
-        if (k > 0) std::memcpy(&pcK[q * 3 * k], peaks + (size_t)ix[q] * 3 * maxfasc, sizeof(double) * 3 * k);
-        if (maxfasc > 0) std::memcpy(&pcF[q * 3 * maxfasc], peaks + (size_t)ix[q] * 3 * maxfasc, sizeof(double) * 3 * maxfasc);
-      }
-      DevMem dY, dW0, dW, dpK, dpF, dpr, dsc, dstt, dst;
-      HIPCHK(dY.alloc(sizeof(double) * Yc.size()));
-      HIPCHK(dW0.alloc(w0_stride ? sizeof(double) * Wc.size() : 0));
-      HIPCHK(dW.alloc(sizeof(double) * Wc.size()));
-      HIPCHK(dpK.alloc(sizeof(double) * pcK.size()));
-      HIPCHK(dpF.alloc(sizeof(double) * pcF.size()));
-      HIPCHK(dpr.alloc(sizeof(double) * prm.size()));
-      HIPCHK(dsc.alloc(sizeof(double) * nv));
-      HIPCHK(dstt.alloc(sizeof(int32_t) * nv));
-      HIPCHK(dst.alloc(sizeof(int32_t) * nv));
-      HIPCHK(hipMemcpy(dY.p, Yc.data(), sizeof(double) * Yc.size(), hipMemcpyHostToDevice));
-      if (w0_stride) HIPCHK(hipMemcpy(dW0.p, Wc.data(), sizeof(double) * Wc.size(), hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(dpK.p, pcK.data(), sizeof(double) * pcK.size(), hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(dpF.p, pcF.data(), sizeof(double) * pcF.size(), hipMemcpyHostToDevice));
-      const double* w0d = !W0 ? nullptr : (w0_stride ? dW0.as<double>() : dW0s.as<double>());
-      // one iteration at a time: the count of changed voxels decides whether the chunk goes on.  An iteration that
-      // changed nothing leaves its fit out when the parameters already are those of a weighted fit on these weights
-      // (any iteration but the first one after an unweighted fit); every later iteration would repeat it bit for bit.
-      int used = 0;
-      const RobClass r{p, dY.as<double>(), w0d, w0_stride, dpK.as<double>(), dpF.as<double>(), k, cf ? dxc.as<double>() : nullptr,
-                       dxc.as<double>(), maxfasc, csf_on, loss, c, (int64_t)nv, dpr.as<double>(), dW.as<double>(), dsc.as<double>(),
-                       dstt.as<int32_t>(), dst.as<int32_t>(), dnc.as<int32_t>(), nullptr};
-      if (int rc = rob_first_fit(r)) return rc;
-      for (int it = 0; it < n_iter; ++it) {
-        if (int rc = rob_reweight(r, it)) return rc;
-        int32_t nc = 0;
-        HIPCHK(hipMemcpy(&nc, dnc.as<int32_t>() + it, sizeof(int32_t), hipMemcpyDeviceToHost));   // (waits for the default stream)
-        n_changed[it] += nc;
-        used = it + 1;
-        if (nc == 0 && (it > 0 || W0)) break;
-        if (int rc = rob_refit(r)) return rc;
-      }
-      *n_iter_used = std::max<int32_t>(*n_iter_used, used);
-      HIPCHK(hipStreamSynchronize(nullptr));
-      HIPCHK(hipMemcpy(prm.data(), dpr.p, sizeof(double) * prm.size(), hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(Wc.data(), dW.p, sizeof(double) * Wc.size(), hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(scc.data(), dsc.p, sizeof(double) * nv, hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(stt.data(), dstt.p, sizeof(int32_t) * nv, hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(stc.data(), dst.p, sizeof(int32_t) * nv, hipMemcpyDeviceToHost));
-      for (size_t q = 0; q < nv; ++q) {
-        std::memcpy(params + (size_t)ix[q] * np, &prm[q * np], sizeof(double) * np);
-        std::memcpy(W_out + (size_t)ix[q] * M, &Wc[q * M], sizeof(double) * M);
-        scale[ix[q]] = scc[q];
-        state[ix[q]] = stt[q];
-        status[ix[q]] = stc[q];
-      }
-    }
-  }
-  return MFX_OK;
+  return mfx_class_walk(bins, chunk, [&](int k, int cf, const int64_t* ix, size_t nv) -> int {
+    DevBuf<double> dY, dW0, dW, dpK, dpF, dpr, dsc;
+    DevBuf<int32_t> dstt, dst;
+    HIPCHK(dY.upload_rows(Y, ix, nv, M, M));
+    if (w0_stride) HIPCHK(dW0.upload_rows(W0, ix, nv, M, M));
+    HIPCHK(mfx_upload_peaks(dpK, peaks, ix, nv, maxfasc, k));
+    HIPCHK(mfx_upload_peaks(dpF, peaks, ix, nv, maxfasc, maxfasc));   // whole rows, the layout of the parameter rows
+    HIPCHK(dW.alloc_n(nv * M));
+    HIPCHK(dpr.alloc_n(nv * np));
+    HIPCHK(dsc.alloc_n(nv));
+    HIPCHK(dstt.alloc_n(nv));
+    HIPCHK(dst.alloc_n(nv));
+    const double* w0d = !W0 ? nullptr : (w0_stride ? dW0.get() : dW0s.get());
+    const RobClass r{p, dY.get(), w0d, w0_stride, dpK.get(), dpF.get(), k, cf ? dxc.get() : nullptr, dxc.get(), maxfasc, csf_on, loss, c,
+                     (int64_t)nv, dpr.get(), dW.get(), dsc.get(), dstt.get(), dst.get(), dnc.get(), nullptr};
+    const MfxRobHostCount host{dnc.get(), W0 != nullptr, n_changed, n_iter_used};
+    if (int rc = mfx_rob_iterate(RobSteps{r}, n_iter, &host)) return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    HIPCHK(dpr.download_rows(params, ix, nv, np));
+    HIPCHK(dW.download_rows(W_out, ix, nv, M));
+    HIPCHK(dsc.download_rows(scale, ix, nv, 1));
+    HIPCHK(dstt.download_rows(state, ix, nv, 1));
+    HIPCHK(dst.download_rows(status, ix, nv, 1));
+    return MFX_OK;
+  });
 }

@@ -3,7 +3,8 @@
 // Nothing here computes: the fits are the class launchers of fit2d.hip (unweighted) and w2d.hip (weighted) on prepared
 // directions, the prediction is the kernel of predict2d.hip on the same records, the rule is mfx_robust_weights_kernel
 // of robust.hip.  What this file adds is the order of the launches - and that the plan of the class's directions and
-// the kernels' 32-byte records (F2Dirs) are made once per class chunk, not once per fit and prediction.
+// the kernels' 32-byte records (F2Dirs) are made once per class chunk, not once per fit and prediction.  The loop itself is
+// mfx_rob_iterate (mfx_host.h) over the three steps below; the host side of a mixed batch is class_batch.h.
 #include "fit2d_shared.h"
 #include "../../include/mfx_robust.h"
 #include "../../include/mfx_robust2d.h"
@@ -15,16 +16,6 @@
 namespace {
 
 thread_local int64_t g_last_plan_dirs = 0;
-
-const char* NO_DEVICE = "no HIP device available (this library has no CPU path)";
-
-int r2d_require_device(int device) {
-  const int n = mfx_device_count();
-  if (n <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
-  if (device < 0 || device >= n) return mfx_fail(MFX_ERR_ARG, "device %d out of range (have %d)", device, n);
-  HIPCHK(hipSetDevice(device));
-  return MFX_OK;
-}
 
 // One class on device buffers: V voxels of K fascicles (d_peaksK [V x 3 K]), with the CSF column d_xc or without
 // (null); d_params [V x np] (np = 1 + 2 maxfasc + csf_on + 2); d_sig_csf [M] is the CSF signal of the batch (csf_on),
@@ -91,6 +82,16 @@ struct StepScratch {
   void done() const { if (marked) mfx_scratch_rewind(st, mk); }
 };
 
+// the loop's steps for mfx_rob_iterate (mfx_host.h)
+struct Rob2Steps {
+  const Rob2Class& r;
+  const StepScratch& step;
+  int first_fit() const { return r2d_first_fit(r); }
+  int reweight(int it) const { return r2d_reweight(r, it); }
+  int refit() const { return r2d_refit(r); }
+  void step_done() const { step.done(); }
+};
+
 struct PlanCount {   // the diagnostic of mfx_robust2d_debug_last_plan_directions, kept on every exit path
   PlanCount() { mfx_rot2d_plan_count_reset(); g_last_plan_dirs = 0; }
   ~PlanCount() { g_last_plan_dirs = mfx_rot2d_plan_count(); }
@@ -107,7 +108,7 @@ extern "C" int mfx_rfit2d_batch_dev(void* hv, const double* d_Y, const double* d
                                     double* d_scale, int32_t* d_state, int32_t* d_dir_status, int32_t* d_wstatus,
                                     int32_t* d_nchanged, void* stream) {
   const char* fn = "mfx_rfit2d_batch_dev";
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
+  if (mfx_device_count() <= 0) return mfx_no_device();
   const mfx_rot2d* h = (const mfx_rot2d*)hv;
   if (!h || V < 0 || maxfasc < 0 || n_iter < 0 ||
       (V > 0 && (!d_Y || !d_params || !d_W || !d_scale || !d_state || !d_dir_status || !d_wstatus || (maxfasc > 0 && !d_peaks) ||
@@ -119,7 +120,7 @@ extern "C" int mfx_rfit2d_batch_dev(void* hv, const double* d_Y, const double* d
   if (d_W0 && w0_stride != 0 && w0_stride != M)
     return mfx_fail(MFX_ERR_ARG, "%s: w0_stride should be M = %d or 0 (got %lld)", fn, M, (long long)w0_stride);
   if (int rc = f2_limits(fn, h, maxfasc, V)) return rc;
-  if (int rc = r2d_require_device(h->device)) return rc;
+  if (int rc = mfx_require_device(h->device)) return rc;
   PlanCount count;
   hipStream_t st = (hipStream_t)stream;
   if (V == 0) {
@@ -131,15 +132,7 @@ extern "C" int mfx_rfit2d_batch_dev(void* hv, const double* d_Y, const double* d
   const StepScratch step(st);
   const Rob2Class r{h, dirs.rec.p, dirs.pstat.as<int>(), d_Y, d_W0, d_W0 ? w0_stride : 0, maxfasc, nullptr, nullptr, maxfasc, 0, loss, c,
                     V, d_params, d_W, d_scale, d_state, d_dir_status, d_wstatus, d_nchanged, st};
-  if (int rc = r2d_first_fit(r)) return rc;
-  step.done();
-  for (int it = 0; it < n_iter; ++it) {
-    if (int rc = r2d_reweight(r, it)) return rc;
-    step.done();
-    if (int rc = r2d_refit(r)) return rc;
-    step.done();
-  }
-  return MFX_OK;
+  return mfx_rob_iterate(Rob2Steps{r, step}, n_iter, nullptr);
 }
 
 extern "C" int mfx_rfit2d_batch(void* hv, const double* Y, const double* W0, int64_t w0_stride, const int32_t* K, const uint8_t* csf,
@@ -147,7 +140,7 @@ extern "C" int mfx_rfit2d_batch(void* hv, const double* Y, const double* W0, int
                                 int64_t V, double* params, double* W_out, double* scale, int32_t* state, int32_t* dir_status,
                                 int32_t* wstatus, int64_t* n_changed, int32_t* n_iter_used) {
   const char* fn = "mfx_rfit2d_batch";
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
+  if (mfx_device_count() <= 0) return mfx_no_device();
   const mfx_rot2d* h = (const mfx_rot2d*)hv;
   if (!h || V < 0 || maxfasc < 0 || n_iter < 0 || !n_iter_used || (n_iter > 0 && !n_changed) ||
       (V > 0 && (!Y || !K || !params || !W_out || !scale || !state || !dir_status || !wstatus || (maxfasc > 0 && !peaks))))
@@ -161,102 +154,52 @@ extern "C" int mfx_rfit2d_batch(void* hv, const double* Y, const double* W0, int
   if (!W0) w0_stride = 0;
   if (csf_on && !sig_csf) return mfx_fail(MFX_ERR_ARG, "%s: csf_on without sig_csf", fn);   // (the prediction of every class needs it)
   // bin by class (K, CSF flag) before any device call
-  std::vector<std::vector<int64_t>> bins((size_t)2 * (maxfasc + 1));
-  for (int64_t v = 0; v < V; ++v) {
-    const int cf = csf && csf[v];
-    if (K[v] < 0 || K[v] > maxfasc) return mfx_fail(MFX_ERR_ARG, "%s: K[%lld] = %d outside 0..%d", fn, (long long)v, K[v], maxfasc);
-    if (cf && (!csf_on || !sig_csf)) return mfx_fail(MFX_ERR_ARG, "%s: voxels flagged CSF need csf_on and sig_csf", fn);
-    bins[(size_t)2 * K[v] + cf].push_back(v);
-  }
+  MfxClassBins bins;
+  if (int rc = mfx_class_bins(fn, K, csf, maxfasc, csf_on && sig_csf, V, &bins)) return rc;
   *n_iter_used = 0;
   for (int it = 0; it < n_iter; ++it) n_changed[it] = 0;
   if (int rc = f2_limits(fn, h, maxfasc, V)) return rc;
-  if (int rc = r2d_require_device(h->device)) return rc;
+  if (int rc = mfx_require_device(h->device)) return rc;
   PlanCount count;
   if (V == 0) return MFX_OK;
-  DevMem dxc, dW0s, dnc;
-  if (sig_csf) {
-    HIPCHK(dxc.alloc(sizeof(double) * M));
-    HIPCHK(hipMemcpy(dxc.p, sig_csf, sizeof(double) * M, hipMemcpyHostToDevice));
-  }
-  if (W0 && w0_stride == 0) {   // the shared vector is uploaded once
-    HIPCHK(dW0s.alloc(sizeof(double) * M));
-    HIPCHK(hipMemcpy(dW0s.p, W0, sizeof(double) * M, hipMemcpyHostToDevice));
-  }
-  HIPCHK(dnc.alloc(sizeof(int32_t) * (size_t)std::max(n_iter, 1)));
-  for (size_t b = 0; b < bins.size(); ++b) {
-    const std::vector<int64_t>& all = bins[b];
-    const int k = (int)(b >> 1), cf = (int)(b & 1);
-    // voxels per upload from a byte budget: Y, W0, W, the prediction and the weighted fit's s and y' (8 M bytes each), the
-    // plan's records (28 K M) and the kernels' records (32 K M)
-    const size_t per_vox = (size_t)M * (sizeof(double) * 6 + (size_t)k * (28 + sizeof(F2Rec)));
-    const size_t chunk = std::max<size_t>(1, ((size_t)256 << 20) / per_vox);
-    for (size_t c0 = 0; c0 < all.size(); c0 += chunk) {
-      const size_t nv = std::min(chunk, all.size() - c0);
-      const int64_t* ix = all.data() + c0;
-      const size_t kk = (size_t)std::max(k, 1);
-      std::vector<double> Yc(nv * M), Wc(nv * M), pcK(nv * 3 * kk), prm(nv * np), scc(nv);
-      std::vector<int32_t> vsc(nv * 5), wsc(nv), stt(nv);
-      for (size_t q = 0; q < nv; ++q) {
-        std::memcpy(&Yc[q * M], Y + (size_t)ix[q] * M, sizeof(double) * M);
-        if (w0_stride) std::memcpy(&Wc[q * M], W0 + (size_t)ix[q] * M, sizeof(double) * M);
-        if (k > 0) std::memcpy(&pcK[q * 3 * k], peaks + (size_t)ix[q] * 3 * maxfasc, sizeof(double) * 3 * k);
-      }
-      DevMem dY, dW0, dW, dpK, dpr, dsc, dstt, dvs, dws;
-      HIPCHK(dY.alloc(sizeof(double) * Yc.size()));
-      HIPCHK(dW0.alloc(w0_stride ? sizeof(double) * Wc.size() : 0));
-      HIPCHK(dW.alloc(sizeof(double) * Wc.size()));
-      HIPCHK(dpK.alloc(sizeof(double) * pcK.size()));
-      HIPCHK(dpr.alloc(sizeof(double) * prm.size()));
-      HIPCHK(dsc.alloc(sizeof(double) * nv));
-      HIPCHK(dstt.alloc(sizeof(int32_t) * nv));
-      HIPCHK(dvs.alloc(sizeof(int32_t) * 5 * nv));
-      HIPCHK(dws.alloc(sizeof(int32_t) * nv));
-      HIPCHK(hipMemcpy(dY.p, Yc.data(), sizeof(double) * Yc.size(), hipMemcpyHostToDevice));
-      if (w0_stride) HIPCHK(hipMemcpy(dW0.p, Wc.data(), sizeof(double) * Wc.size(), hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(dpK.p, pcK.data(), sizeof(double) * pcK.size(), hipMemcpyHostToDevice));
-      const double* w0d = !W0 ? nullptr : (w0_stride ? dW0.as<double>() : dW0s.as<double>());
-      // the chunk's directions, once: every fit and every prediction below reads these records
-      F2Dirs dirs(nullptr);
-      if (int rc = dirs.enqueue(h, dpK.as<double>(), (int64_t)nv * k, nullptr)) return rc;
-      // one iteration at a time: the count of changed voxels decides whether the chunk goes on.  An iteration that
-      // changed nothing leaves its fit out when the parameters already are those of a weighted fit on these weights
-      // (any iteration but the first one after an unweighted fit); every later iteration would repeat it bit for bit.
-      int used = 0;
-      const StepScratch step(nullptr);
-      const Rob2Class r{h, dirs.rec.p, dirs.pstat.as<int>(), dY.as<double>(), w0d, w0_stride, k, cf ? dxc.as<double>() : nullptr,
-                        dxc.as<double>(), maxfasc, csf_on, loss, c, (int64_t)nv, dpr.as<double>(), dW.as<double>(), dsc.as<double>(),
-                        dstt.as<int32_t>(), dvs.as<int32_t>(), dws.as<int32_t>(), dnc.as<int32_t>(), nullptr};
-      if (int rc = r2d_first_fit(r)) return rc;
-      step.done();
-      for (int it = 0; it < n_iter; ++it) {
-        if (int rc = r2d_reweight(r, it)) return rc;
-        step.done();
-        int32_t nc = 0;
-        HIPCHK(hipMemcpy(&nc, dnc.as<int32_t>() + it, sizeof(int32_t), hipMemcpyDeviceToHost));   // (waits for the default stream)
-        n_changed[it] += nc;
-        used = it + 1;
-        if (nc == 0 && (it > 0 || W0)) break;
-        if (int rc = r2d_refit(r)) return rc;
-        step.done();
-      }
-      *n_iter_used = std::max<int32_t>(*n_iter_used, used);
-      HIPCHK(hipStreamSynchronize(nullptr));
-      HIPCHK(hipMemcpy(prm.data(), dpr.p, sizeof(double) * prm.size(), hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(Wc.data(), dW.p, sizeof(double) * Wc.size(), hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(scc.data(), dsc.p, sizeof(double) * nv, hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(stt.data(), dstt.p, sizeof(int32_t) * nv, hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(vsc.data(), dvs.p, sizeof(int32_t) * 5 * nv, hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(wsc.data(), dws.p, sizeof(int32_t) * nv, hipMemcpyDeviceToHost));
-      for (size_t q = 0; q < nv; ++q) {
-        std::memcpy(params + (size_t)ix[q] * np, &prm[q * np], sizeof(double) * np);
-        std::memcpy(W_out + (size_t)ix[q] * M, &Wc[q * M], sizeof(double) * M);
-        std::memcpy(dir_status + (size_t)ix[q] * 5, &vsc[q * 5], sizeof(int32_t) * 5);
-        scale[ix[q]] = scc[q];
-        state[ix[q]] = stt[q];
-        wstatus[ix[q]] = wsc[q];
-      }
-    }
-  }
-  return MFX_OK;
+  DevBuf<double> dxc, dW0s;
+  DevBuf<int32_t> dnc;
+  if (sig_csf) HIPCHK(dxc.upload(sig_csf, M));
+  if (W0 && w0_stride == 0) HIPCHK(dW0s.upload(W0, M));   // the shared vector is uploaded once
+  HIPCHK(dnc.alloc_n((size_t)std::max(n_iter, 1)));
+  // voxels per upload from a byte budget: Y, W0, W, the prediction and the weighted fit's s and y' (8 M bytes each), the
+  // plan's records (28 K M) and the kernels' records (32 K M)
+  const auto chunk_of = [M](int k) {
+    return ((size_t)256 << 20) / ((size_t)M * (sizeof(double) * 6 + (size_t)k * (28 + sizeof(F2Rec))));
+  };
+  return mfx_class_walk(bins, chunk_of, [&](int k, int cf, const int64_t* ix, size_t nv) -> int {
+    DevBuf<double> dY, dW0, dW, dpK, dpr, dsc;
+    DevBuf<int32_t> dstt, dvs, dws;
+    HIPCHK(dY.upload_rows(Y, ix, nv, M, M));
+    if (w0_stride) HIPCHK(dW0.upload_rows(W0, ix, nv, M, M));
+    HIPCHK(mfx_upload_peaks(dpK, peaks, ix, nv, maxfasc, k));
+    HIPCHK(dW.alloc_n(nv * M));
+    HIPCHK(dpr.alloc_n(nv * np));
+    HIPCHK(dsc.alloc_n(nv));
+    HIPCHK(dstt.alloc_n(nv));
+    HIPCHK(dvs.alloc_n(nv * 5));
+    HIPCHK(dws.alloc_n(nv));
+    const double* w0d = !W0 ? nullptr : (w0_stride ? dW0.get() : dW0s.get());
+    // the chunk's directions, once: every fit and every prediction below reads these records
+    F2Dirs dirs(nullptr);
+    if (int rc = dirs.enqueue(h, dpK.get(), (int64_t)nv * k, nullptr)) return rc;
+    const StepScratch step(nullptr);
+    const Rob2Class r{h, dirs.rec.p, dirs.pstat.as<int>(), dY.get(), w0d, w0_stride, k, cf ? dxc.get() : nullptr, dxc.get(), maxfasc, csf_on,
+                      loss, c, (int64_t)nv, dpr.get(), dW.get(), dsc.get(), dstt.get(), dvs.get(), dws.get(), dnc.get(), nullptr};
+    const MfxRobHostCount host{dnc.get(), W0 != nullptr, n_changed, n_iter_used};
+    if (int rc = mfx_rob_iterate(Rob2Steps{r, step}, n_iter, &host)) return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    HIPCHK(dpr.download_rows(params, ix, nv, np));
+    HIPCHK(dW.download_rows(W_out, ix, nv, M));
+    HIPCHK(dvs.download_rows(dir_status, ix, nv, 5));
+    HIPCHK(dsc.download_rows(scale, ix, nv, 1));
+    HIPCHK(dstt.download_rows(state, ix, nv, 1));
+    HIPCHK(dws.download_rows(wstatus, ix, nv, 1));
+    return MFX_OK;
+  });
 }

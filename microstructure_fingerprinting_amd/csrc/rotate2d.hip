@@ -290,14 +290,6 @@ __global__ __launch_bounds__(256) void mfx_rot2d_cols_kernel(Rot2dDev D, Rot2dPl
   out[i] = r2_elem(D, o, x, s, n);
 }
 
-int r2_require_device(int device) {
-  const int n = mfx_device_count();
-  if (n <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)");
-  if (device < 0 || device >= n) return mfx_fail(MFX_ERR_ARG, "device %d out of range (have %d)", device, n);
-  HIPCHK(hipSetDevice(device));
-  return MFX_OK;
-}
-
 int r2_launch(const mfx_rot2d* h, const double* d_dirs, const int* d_cols, int64_t B, double* d_out, int* d_status,
               hipStream_t st) {
   if (B > 0x7fffffff) return mfx_fail(MFX_ERR_UNSUPPORTED, "mfx_rot2d: more than 2^31 - 1 directions");
@@ -385,7 +377,7 @@ extern "C" int mfx_rot2d_create(const double* sch, int M, const int32_t* pair_of
   for (int t = 0; t < T; ++t)
     if (tab_off[t + 1] - tab_off[t] < 2) return mfx_fail(MFX_ERR_ARG, "%s: table %d has fewer than 2 knots", fn, t);
   const int K = tab_off[T];
-  if (int rc = r2_require_device(device)) return rc;
+  if (int rc = mfx_require_device(device)) return rc;
   // slopes of SciPy's _call_linear, per interval: (y_hi - y_lo) / (x_hi - x_lo)
   std::vector<double> slope((size_t)K * N, 0.0);
   for (int t = 0; t < T; ++t)
@@ -452,43 +444,43 @@ extern "C" void mfx_rot2d_destroy(void* hv) {
 
 extern "C" int mfx_rot2d_rotate_dev(void* hv, const double* d_dirs, int64_t B, double* d_out, int32_t* d_status,
                                     void* stream) {
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)");
+  if (mfx_device_count() <= 0) return mfx_no_device();
   const mfx_rot2d* h = (const mfx_rot2d*)hv;
   if (!h || B < 0 || (B > 0 && (!d_dirs || !d_out || !d_status))) return mfx_fail(MFX_ERR_ARG, "mfx_rot2d_rotate_dev: bad argument");
   if (B == 0) return MFX_OK;
-  if (int rc = r2_require_device(h->device)) return rc;
+  if (int rc = mfx_require_device(h->device)) return rc;
   return r2_launch(h, d_dirs, nullptr, B, d_out, d_status, (hipStream_t)stream);
 }
 
 extern "C" int mfx_rot2d_rotate(void* hv, const double* dirs, int64_t B, double* out, int32_t* status) {
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)");
+  if (mfx_device_count() <= 0) return mfx_no_device();
   const mfx_rot2d* h = (const mfx_rot2d*)hv;
   if (!h || B < 0 || (B > 0 && (!dirs || !out || !status))) return mfx_fail(MFX_ERR_ARG, "mfx_rot2d_rotate: bad argument");
   if (B == 0) return MFX_OK;
-  if (int rc = r2_require_device(h->device)) return rc;
+  if (int rc = mfx_require_device(h->device)) return rc;
   return r2_host(h, dirs, nullptr, B, out, status, "mfx_rot2d_rotate");
 }
 
 extern "C" int mfx_rot2d_rotate_cols_dev(void* hv, const double* d_dirs, const int32_t* d_cols, int64_t B, double* d_out,
                                          int32_t* d_status, void* stream) {
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)");
+  if (mfx_device_count() <= 0) return mfx_no_device();
   const mfx_rot2d* h = (const mfx_rot2d*)hv;
   if (!h || B < 0 || (B > 0 && (!d_dirs || !d_cols || !d_out || !d_status)))
     return mfx_fail(MFX_ERR_ARG, "mfx_rot2d_rotate_cols_dev: bad argument");
   if (B == 0) return MFX_OK;
-  if (int rc = r2_require_device(h->device)) return rc;
+  if (int rc = mfx_require_device(h->device)) return rc;
   return r2_launch(h, d_dirs, d_cols, B, d_out, d_status, (hipStream_t)stream);
 }
 
 extern "C" int mfx_rot2d_rotate_cols(void* hv, const double* dirs, const int32_t* cols, int64_t B, double* out,
                                      int32_t* status) {
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "no HIP device available (this library has no CPU path)");
+  if (mfx_device_count() <= 0) return mfx_no_device();
   const mfx_rot2d* h = (const mfx_rot2d*)hv;
   if (!h || B < 0 || (B > 0 && (!dirs || !cols || !out || !status)))
     return mfx_fail(MFX_ERR_ARG, "mfx_rot2d_rotate_cols: bad argument");
   if (B == 0) return MFX_OK;
   for (int64_t b = 0; b < B; ++b)
     if (cols[b] < 0 || cols[b] >= h->d.N) return mfx_fail(MFX_ERR_ARG, "mfx_rot2d_rotate_cols: atom index %d out of range", cols[b]);
-  if (int rc = r2_require_device(h->device)) return rc;
+  if (int rc = mfx_require_device(h->device)) return rc;
   return r2_host(h, dirs, cols, B, out, status, "mfx_rot2d_rotate_cols");
 }

@@ -15,16 +15,6 @@
 
 namespace {
 
-const char* S2_NO_DEVICE = "no HIP device available (this library has no CPU path)";
-
-int s2_require_device(int device) {
-  const int n = mfx_device_count();
-  if (n <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", S2_NO_DEVICE);
-  if (device < 0 || device >= n) return mfx_fail(MFX_ERR_ARG, "device %d out of range (have %d)", device, n);
-  HIPCHK(hipSetDevice(device));
-  return MFX_OK;
-}
-
 template <int MODE>
 int s2_launch(const S2Args& a, int K, int64_t V, hipStream_t st) {
   if (K == 2) {
@@ -59,10 +49,10 @@ int s2_check(const char* fn, int mode, const mfx_rot2d* h, const void* Y, const 
 int s2_enqueue(const char* fn, int mode, const mfx_rot2d* h, const double* d_Y, const double* d_peaks, int K, const double* d_T,
                const double* d_shift, int64_t V, double* d_out, double* d_log_sum, int32_t* d_status, int32_t* d_partner,
                int32_t* d_dir_status, hipStream_t st) {
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", S2_NO_DEVICE);
+  if (mfx_device_count() <= 0) return mfx_no_device();
   if (int rc = s2_check(fn, mode, h, d_Y, d_peaks, K, d_T, d_shift, V, d_out, d_log_sum, d_status, d_dir_status)) return rc;
   if (V == 0) return MFX_OK;
-  if (int rc = s2_require_device(h->device)) return rc;
+  if (int rc = mfx_require_device(h->device)) return rc;
   const int M = h->d.M;
   PlanMem pm(st);
   StreamMem pstat(st), rec(st);
@@ -86,10 +76,10 @@ int s2_enqueue(const char* fn, int mode, const mfx_rot2d* h, const double* d_Y, 
 // shared body of the host entry points
 int s2_host(const char* fn, int mode, const mfx_rot2d* h, const double* Y, const double* peaks, int K, const double* T,
             const double* shift, int64_t V, double* out, double* log_sum, int32_t* status, int32_t* partner, int32_t* dir_status) {
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", S2_NO_DEVICE);
+  if (mfx_device_count() <= 0) return mfx_no_device();
   if (int rc = s2_check(fn, mode, h, Y, peaks, K, T, shift, V, out, log_sum, status, dir_status)) return rc;
   if (V == 0) return MFX_OK;
-  if (int rc = s2_require_device(h->device)) return rc;
+  if (int rc = mfx_require_device(h->device)) return rc;
   const bool post = mode == S2_POST;
   const size_t M = h->d.M, nout = (size_t)V * K * h->d.N;
   DevMem dY, dpk, dT, dsh, dout, dls, dst, dpar, dds;

@@ -15,6 +15,8 @@
 //                        and y' live in memory, not LDS: the kernels' LDS footprint stays independent of M.
 // w2d_repack_kernel      behind the explicit solver of mfx_api.hip, which ran per voxel on the materialised (s A, y'): puts
 //                        the weighted MSE and R2 into the row.
+// The explicit fallback's chunk loop is mfx_solve_dense_chunks (mfx_host.h); the host side of a mixed batch is class_batch.h
+// and DevBuf (mfx_host.h).
 #include "fit2d_kernels.h"
 #include "soft2d_kernels.h"
 #include "../../include/mfx_w2d.h"
@@ -92,16 +94,6 @@ __global__ __launch_bounds__(64) void w2d_repack_kernel(W2Args a, const int* __r
     row[a.num_params - 2] = row[a.num_params - 2] * ((double)M / a.sumw[v]);
     row[a.num_params - 1] = r2;
   }
-}
-
-const char* NO_DEVICE = "no HIP device available (this library has no CPU path)";
-
-int w2_require_device(int device) {
-  const int n = mfx_device_count();
-  if (n <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
-  if (device < 0 || device >= n) return mfx_fail(MFX_ERR_ARG, "device %d out of range (have %d)", device, n);
-  HIPCHK(hipSetDevice(device));
-  return MFX_OK;
 }
 
 // what every class launch shares beside the prepared directions (F2Dirs: the plan of the V K directions and the kernels'
@@ -190,30 +182,21 @@ int w2_class_fit(const mfx_rot2d* h, W2Args& a, const int* ok, int K, const doub
     HIPCHK(hipGetLastError());
     return MFX_OK;
   }
-  // every other class: materialise the scaled dictionaries in voxel chunks within a byte budget, explicit solver per voxel
-  const size_t Ntot = (size_t)K * N + has_csf, per_vox = sizeof(double) * M * Ntot;
-  size_t free_b = 0, total_b = 0, scratch_b = 0;
-  HIPCHK(hipMemGetInfo(&free_b, &total_b));
-  if (int rc = mfx_solve_dense_scratch_bytes(M, K, N, has_csf, &scratch_b)) return rc;
-  const size_t budget = std::min<size_t>(free_b / 4, (size_t)1 << 30);
-  const int64_t nvc = std::max<int64_t>(1, std::min<int64_t>(V, (int64_t)(budget / per_vox)));
-  StreamMem dA(st), dS(st);
-  HIPCHK(dA.alloc(per_vox * nvc));
-  HIPCHK(dS.alloc(scratch_b));
-  for (int64_t v0 = 0; v0 < V; v0 += nvc) {
-    const int64_t nv = std::min(nvc, V - v0);
-    hipLaunchKernelGGL(fit2d_mat_kernel<true>, dim3((unsigned)nv, (unsigned)((M + 7) / 8)), dim3(256), 0, st, a, ok, v0, K, has_csf, d_xc,
-                       dA.as<double>());
-    HIPCHK(hipGetLastError());
-    for (int64_t q = 0; q < nv; ++q) {
-      const int64_t v = v0 + q;
-      if (int rc = mfx_solve_dense_dev(dA.as<double>() + (size_t)q * M * Ntot, M, K, N, has_csf, a.Ys + (size_t)v * M, maxfasc, csf_on,
-                                       d_params + (size_t)v * np, ok + v, dS.p, st)) return rc;
-    }
-    hipLaunchKernelGGL(w2d_repack_kernel, dim3((unsigned)nv), dim3(64), sizeof(double) * M, st, a, ok, v0, K, has_csf, d_xc);
-    HIPCHK(hipGetLastError());
-  }
-  return MFX_OK;
+  // every other class: the scaled dictionaries in voxel chunks, explicit solver per voxel on (s A, y'), then the weighted
+  // figures into the chunk's rows (mfx_solve_dense_chunks, mfx_host.h)
+  return mfx_solve_dense_chunks(
+      M, K, N, has_csf, sizeof(double) * M * ((size_t)K * N + has_csf), V, maxfasc, csf_on, d_params, ok, st,
+      [&](int64_t v0, int64_t nv, int64_t, double* dA, const double** y) -> int {
+        hipLaunchKernelGGL(fit2d_mat_kernel<true>, dim3((unsigned)nv, (unsigned)((M + 7) / 8)), dim3(256), 0, st, a, ok, v0, K, has_csf, d_xc, dA);
+        HIPCHK(hipGetLastError());
+        *y = a.Ys + (size_t)v0 * M;
+        return MFX_OK;
+      },
+      [&](int64_t v0, int64_t nv) -> int {
+        hipLaunchKernelGGL(w2d_repack_kernel, dim3((unsigned)nv), dim3(64), sizeof(double) * M, st, a, ok, v0, K, has_csf, d_xc);
+        HIPCHK(hipGetLastError());
+        return MFX_OK;
+      });
 }
 
 template <int MODE>
@@ -255,10 +238,10 @@ int w2_soft_check(const char* fn, int mode, const mfx_rot2d* h, const void* Y, c
 int w2_soft_enqueue(const char* fn, int mode, const mfx_rot2d* h, const double* d_Y, const double* d_W, int64_t w_stride,
                     const double* d_peaks, int K, const double* d_T, const double* d_shift, int64_t V, double* d_out, double* d_log_sum,
                     int32_t* d_status, int32_t* d_partner, int32_t* d_dir_status, hipStream_t st) {
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
+  if (mfx_device_count() <= 0) return mfx_no_device();
   if (int rc = w2_soft_check(fn, mode, h, d_Y, d_W, w_stride, d_peaks, K, d_T, d_shift, V, d_out, d_log_sum, d_status, d_dir_status)) return rc;
   if (V == 0) return MFX_OK;
-  if (int rc = w2_require_device(h->device)) return rc;
+  if (int rc = mfx_require_device(h->device)) return rc;
   W2Scratch sc(st);
   W2Args a{};
   if (int rc = sc.enqueue(h, d_Y, d_W, w_stride, d_peaks, K, V, d_dir_status, nullptr, nullptr, 0, a, st)) return rc;
@@ -270,10 +253,10 @@ int w2_soft_enqueue(const char* fn, int mode, const mfx_rot2d* h, const double* 
 int w2_soft_host(const char* fn, int mode, const mfx_rot2d* h, const double* Y, const double* W, int64_t w_stride, const double* peaks,
                  int K, const double* T, const double* shift, int64_t V, double* out, double* log_sum, int32_t* status, int32_t* partner,
                  int32_t* dir_status) {
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
+  if (mfx_device_count() <= 0) return mfx_no_device();
   if (int rc = w2_soft_check(fn, mode, h, Y, W, w_stride, peaks, K, T, shift, V, out, log_sum, status, dir_status)) return rc;
   if (V == 0) return MFX_OK;
-  if (int rc = w2_require_device(h->device)) return rc;
+  if (int rc = mfx_require_device(h->device)) return rc;
   const bool post = mode == S2_POST;
   const size_t M = h->d.M, nout = (size_t)V * K * h->d.N, nw = w_stride ? (size_t)V * M : M;
   DevMem dY, dW, dpk, dT, dsh, dout, dls, dst, dpar, dds;
@@ -339,14 +322,14 @@ extern "C" int mfx_w2d_max_atoms(void* hv, int what) {
 extern "C" int mfx_wfit2d_batch_dev(void* hv, const double* d_Y, const double* d_W, int64_t w_stride, const double* d_peaks, int maxfasc,
                                     int64_t V, double* d_params, int32_t* d_status, int32_t* d_wstatus, void* stream) {
   const char* fn = "mfx_wfit2d_batch_dev";
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
+  if (mfx_device_count() <= 0) return mfx_no_device();
   const mfx_rot2d* h = (const mfx_rot2d*)hv;
   if (!h || V < 0 || maxfasc < 0 || (V > 0 && (!d_Y || !d_W || !d_params || !d_status || !d_wstatus || (maxfasc > 0 && !d_peaks))))
     return mfx_fail(MFX_ERR_ARG, "%s: bad argument", fn);
   if (maxfasc > 3) return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: at most 3 fascicles (got %d)", fn, maxfasc);
   if (int rc = w2_stride_check(fn, h, w_stride)) return rc;
   if (V == 0) return MFX_OK;
-  if (int rc = w2_require_device(h->device)) return rc;
+  if (int rc = mfx_require_device(h->device)) return rc;
   return w2_class_dev(h, d_Y, d_W, w_stride, d_peaks, maxfasc, nullptr, maxfasc, 0, V, d_params, d_status, d_wstatus, (hipStream_t)stream);
 }
 
@@ -354,7 +337,7 @@ extern "C" int mfx_wfit2d_batch(void* hv, const double* Y, const double* W, int6
                                 const double* peaks, int maxfasc, int csf_on, const double* sig_csf, int64_t V, double* params,
                                 int32_t* status, int32_t* wstatus) {
   const char* fn = "mfx_wfit2d_batch";
-  if (mfx_device_count() <= 0) return mfx_fail(MFX_ERR_NO_DEVICE, "%s", NO_DEVICE);
+  if (mfx_device_count() <= 0) return mfx_no_device();
   const mfx_rot2d* h = (const mfx_rot2d*)hv;
   if (!h || V < 0 || maxfasc < 0 || (V > 0 && (!Y || !W || !K || !params || !status || !wstatus || (maxfasc > 0 && !peaks))))
     return mfx_fail(MFX_ERR_ARG, "%s: bad argument", fn);
@@ -363,60 +346,30 @@ extern "C" int mfx_wfit2d_batch(void* hv, const double* Y, const double* W, int6
   csf_on = csf_on != 0;
   const int M = h->d.M, np = 1 + 2 * maxfasc + csf_on + 2;
   // bin by class (K, CSF flag) before any device call
-  std::vector<std::vector<int64_t>> bins((size_t)2 * (maxfasc + 1));
-  for (int64_t v = 0; v < V; ++v) {
-    const int c = csf && csf[v];
-    if (K[v] < 0 || K[v] > maxfasc) return mfx_fail(MFX_ERR_ARG, "%s: K[%lld] = %d outside 0..%d", fn, (long long)v, K[v], maxfasc);
-    if (c && (!csf_on || !sig_csf)) return mfx_fail(MFX_ERR_ARG, "%s: voxels flagged CSF need csf_on and sig_csf", fn);
-    bins[(size_t)2 * K[v] + c].push_back(v);
-  }
+  MfxClassBins bins;
+  if (int rc = mfx_class_bins(fn, K, csf, maxfasc, csf_on && sig_csf, V, &bins)) return rc;
   if (V == 0) return MFX_OK;
-  if (int rc = w2_require_device(h->device)) return rc;
-  DevMem dxc, dWs;
-  if (sig_csf) {
-    HIPCHK(dxc.alloc(sizeof(double) * M));
-    HIPCHK(hipMemcpy(dxc.p, sig_csf, sizeof(double) * M, hipMemcpyHostToDevice));
-  }
-  if (w_stride == 0) {   // the shared vector is uploaded once and read with stride 0
-    HIPCHK(dWs.alloc(sizeof(double) * M));
-    HIPCHK(hipMemcpy(dWs.p, W, sizeof(double) * M, hipMemcpyHostToDevice));
-  }
-  for (size_t b = 0; b < bins.size(); ++b) {
-    const std::vector<int64_t>& ix = bins[b];
-    if (ix.empty()) continue;
-    const int k = (int)(b >> 1), c = (int)(b & 1);
-    const size_t nv = ix.size();
-    std::vector<double> Yc(nv * M), Wc(w_stride ? nv * M : 0), pc(nv * 3 * (size_t)std::max(k, 1)), prm(nv * np);
-    std::vector<int32_t> stc(nv * 5), wsc(nv);
-    for (size_t q = 0; q < nv; ++q) {
-      std::memcpy(&Yc[q * M], Y + (size_t)ix[q] * M, sizeof(double) * M);
-      if (w_stride) std::memcpy(&Wc[q * M], W + (size_t)ix[q] * M, sizeof(double) * M);
-      if (k > 0) std::memcpy(&pc[q * 3 * k], peaks + (size_t)ix[q] * 3 * maxfasc, sizeof(double) * 3 * k);
-    }
-    DevMem dY, dW, dpk, dpr, dst, dws;
-    HIPCHK(dY.alloc(sizeof(double) * Yc.size()));
-    HIPCHK(dW.alloc(sizeof(double) * Wc.size()));
-    HIPCHK(dpk.alloc(sizeof(double) * pc.size()));
-    HIPCHK(dpr.alloc(sizeof(double) * prm.size()));
-    HIPCHK(dst.alloc(sizeof(int32_t) * stc.size()));
-    HIPCHK(dws.alloc(sizeof(int32_t) * wsc.size()));
-    HIPCHK(hipMemcpy(dY.p, Yc.data(), sizeof(double) * Yc.size(), hipMemcpyHostToDevice));
-    if (w_stride) HIPCHK(hipMemcpy(dW.p, Wc.data(), sizeof(double) * Wc.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dpk.p, pc.data(), sizeof(double) * pc.size(), hipMemcpyHostToDevice));
-    if (int rc = w2_class_dev(h, dY.as<double>(), w_stride ? dW.as<double>() : dWs.as<double>(), w_stride, dpk.as<double>(), k,
-                              c ? dxc.as<double>() : nullptr, maxfasc, csf_on, (int64_t)nv, dpr.as<double>(), dst.as<int32_t>(),
-                              dws.as<int32_t>(), nullptr)) return rc;
+  if (int rc = mfx_require_device(h->device)) return rc;
+  DevBuf<double> dxc, dWs;
+  if (sig_csf) HIPCHK(dxc.upload(sig_csf, M));
+  if (w_stride == 0) HIPCHK(dWs.upload(W, M));   // the shared vector is uploaded once and read with stride 0
+  return mfx_class_walk(bins, SIZE_MAX, [&](int k, int c, const int64_t* ix, size_t nv) -> int {   // a bin at a time
+    DevBuf<double> dY, dW, dpk, dpr;
+    DevBuf<int32_t> dst, dws;
+    HIPCHK(dY.upload_rows(Y, ix, nv, M, M));
+    if (w_stride) HIPCHK(dW.upload_rows(W, ix, nv, M, M));
+    HIPCHK(mfx_upload_peaks(dpk, peaks, ix, nv, maxfasc, k));
+    HIPCHK(dpr.alloc_n(nv * np));
+    HIPCHK(dst.alloc_n(nv * 5));
+    HIPCHK(dws.alloc_n(nv));
+    if (int rc = w2_class_dev(h, dY.get(), w_stride ? dW.get() : dWs.get(), w_stride, dpk.get(), k, c ? dxc.get() : nullptr, maxfasc, csf_on,
+                              (int64_t)nv, dpr.get(), dst.get(), dws.get(), nullptr)) return rc;
     HIPCHK(hipStreamSynchronize(nullptr));
-    HIPCHK(hipMemcpy(prm.data(), dpr.p, sizeof(double) * prm.size(), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(stc.data(), dst.p, sizeof(int32_t) * stc.size(), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(wsc.data(), dws.p, sizeof(int32_t) * wsc.size(), hipMemcpyDeviceToHost));
-    for (size_t q = 0; q < nv; ++q) {
-      std::memcpy(params + (size_t)ix[q] * np, &prm[q * np], sizeof(double) * np);
-      std::memcpy(status + (size_t)ix[q] * 5, &stc[q * 5], sizeof(int32_t) * 5);
-      wstatus[ix[q]] = wsc[q];
-    }
-  }
-  return MFX_OK;
+    HIPCHK(dpr.download_rows(params, ix, nv, np));
+    HIPCHK(dst.download_rows(status, ix, nv, 5));
+    HIPCHK(dws.download_rows(wstatus, ix, nv, 1));
+    return MFX_OK;
+  });
 }
 
 extern "C" int mfx_wpost2d_dev(void* hv, const double* d_Y, const double* d_W, int64_t w_stride, const double* d_peaks, int K,
