@@ -170,8 +170,6 @@ __global__ __launch_bounds__(512, 2) void mfx_fit_k2s_kernel(FitK2Args a) {
 #ifdef MFX_STAMPS_RND
   if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 16] = __builtin_amdgcn_s_memtime();
 #endif
-  double bs1 = 0.0;   // best single atom of D1 among the row tiles this wave has generated
-  int bn1 = 0;
   const int nrounds = (ntiles + NW - 1) / NW;
   // the voxel's audited pair (k2s_shared.h): its row tile and column chunk; the shared last row tile is not audited
 #ifdef MFX_EXP_NOAUDIT   // timing experiment
@@ -204,5 +202,5 @@ __global__ __launch_bounds__(512, 2) void mfx_fit_k2s_kernel(FitK2Args a) {
 #undef K2S_ROUND_MODE
     }
   }
-  k2s_finish<KS, NB, BR, XC, NW * 64, WG>(a, L, VX, vox, wave, lane, bs1, bn1);
+  k2s_finish<KS, NB, BR, XC, NW * 64, WG>(a, L, VX, vox, wave, lane);
 }

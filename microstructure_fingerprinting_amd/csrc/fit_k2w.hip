@@ -47,8 +47,6 @@ __global__ __launch_bounds__(256, 1) void mfx_fit_k2w_kernel(FitK2Args a) {
   auto push = [&](double S, int i, int j) { k2s_push(L, a.scap, S, i, j); };
 
   MFX_STAMP(2);
-  double bs1 = 0.0;   // best single atom of D1 among the row tiles this wave has generated
-  int bn1 = 0;
   constexpr int TPR = NW * TL;   // row tiles per round
   const int nrounds = (ntiles + TPR - 1) / TPR;
   // the voxel's audited pair: the key k2s_finish evaluates (its rule for the shared last tile: workgroup waves, not TPR)
@@ -115,19 +113,11 @@ __global__ __launch_bounds__(256, 1) void mfx_fit_k2w_kernel(FitK2Args a) {
         s_Zf[n] = act ? (float)z : -1e30f;
         s_cs[n] = (act && a2 > 0.0) ? (float)nrm : 0.0f;
       }
+      // best single-atom score of this row tile (the atoms themselves join the candidates in k2s_finish, from s_Zf)
       double sb = (act && z > 0.0) ? z * z : 0.0;
-      int nb = n;
 #pragma unroll
-      for (int o = 16; o > 0; o >>= 1) {
-        const double s2 = __shfl_xor(sb, o);
-        const int n2 = __shfl_xor(nb, o);
-        const bool take = (s2 > sb) || (s2 == sb && n2 < nb);
-        sb = take ? s2 : sb;
-        nb = take ? n2 : nb;
-      }
+      for (int o = 16; o > 0; o >>= 1) sb = fmax(sb, __shfl_xor(sb, o));
       sb = mfx_readlane_f64(sb, 0);
-      nb = __builtin_amdgcn_readfirstlane(nb);
-      if (sb > bs1) { bs1 = sb; bn1 = nb; }
       if (lane == 0 && sb - mrg > 0.0) atomicMax(&s_thr[0], mfx_nonneg_bits(sb - mrg));
       }
     });
@@ -563,5 +553,5 @@ __global__ __launch_bounds__(256, 1) void mfx_fit_k2w_kernel(FitK2Args a) {
     }
     if (round == 0) MFX_STAMP(5);
   }
-  k2s_finish<KS, NB, BR, XC, NW * TL * 64, WG>(a, L, VX, vox, wave, lane, bs1, bn1);
+  k2s_finish<KS, NB, BR, XC, NW * TL * 64, WG>(a, L, VX, vox, wave, lane);
 }

@@ -58,20 +58,11 @@
         s_Zf[n] = act ? (float)z : -1e30f;
         s_cs[n] = (act && a2 > 0.0) ? (float)nrm : 0.0f;
       }
-      // best single atom of D1 so far (first index on ties)
+      // best single-atom score of this row tile (the atoms themselves join the candidates in k2s_finish, from s_Zf)
       double sb = (act && z > 0.0) ? z * z : 0.0;
-      int nb = n;
 #pragma unroll
-      for (int o = 16; o > 0; o >>= 1) {
-        const double s2 = __shfl_xor(sb, o);
-        const int n2 = __shfl_xor(nb, o);
-        const bool take = (s2 > sb) || (s2 == sb && n2 < nb);
-        sb = take ? s2 : sb;
-        nb = take ? n2 : nb;
-      }
+      for (int o = 16; o > 0; o >>= 1) sb = fmax(sb, __shfl_xor(sb, o));
       sb = mfx_readlane_f64(sb, 0);
-      nb = __builtin_amdgcn_readfirstlane(nb);
-      if (sb > bs1 || (sb == bs1 && sb > 0.0 && nb < bn1)) { bs1 = sb; bn1 = nb; }
       // a pair matters only if it beats every single atom
       if (lane == 0 && sb - mrg > 0.0) atomicMax(&s_thr[0], mfx_nonneg_bits(sb - mrg));
       }
@@ -384,7 +375,7 @@
 #endif
       __syncthreads();   // all appends of the round are in the ring, D2's statistics in LDS
       if constexpr (!XC) {
-        // D2's best single atom joins the candidates and the threshold, as after phase 1 (k2s_shared.h)
+        // D2's best single atom joins the threshold, as after phase 1 (k2s_shared.h)
         k2s_best_single_late<NW>(a, L, tid, mrg);
       }
 #ifdef MFX_STAMPS_RND

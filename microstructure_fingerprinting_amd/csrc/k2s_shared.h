@@ -330,8 +330,9 @@ __device__ __forceinline__ K2sVoxel k2s_prologue(const FitK2Args& a, const K2sLd
     }
   }
   // best single atom of each dictionary (first index on ties): they stand for every pair whose optimum
-  // has one active atom (mf_utils.py:357-379); the exact stage expands the winner's family.  D2's here, D1's
-  // after the rounds (its statistics come with the A operands); the threshold starts from what is known.
+  // has one active atom (mf_utils.py:357-379): no pair below the best single score minus the margin matters.  D2's here,
+  // D1's with the rounds (its statistics come with the A operands); the threshold starts from what is known.  (The single
+  // atoms that reach the final threshold join the candidates in k2s_finish.)
   if (!(DEFER && defer_d2)) {
     double* s_bs = s_red;            // [2][8]
     int* s_bn = (int*)(s_red + 16);  // [2][8]
@@ -380,14 +381,9 @@ __device__ __forceinline__ K2sVoxel k2s_prologue(const FitK2Args& a, const K2sLd
           if (s2 > s || (s2 == s && n2 < n)) { s = s2; n = n2; }
         }
         best1 = fmax(best1, s);
-        if (!XC && s > 0.0) {   // (XC: supports with fewer than two fascicle atoms belong to the exact kernel's families)
-          const int slot = s_cnt[0]++;
-          s_cand[slot].score = s + mrg;   // exact single-atom score up to the statistics' rounding: evaluated only if it can win
-          s_cand[slot].i = k ? 0 : n;
-          s_cand[slot].j = (k ? n : 0) | MFX_S_BOUND;
-        }
       }
-      // single-atom scores are exact: a pair matters only if S(c) >= best1, i.e. S(c~) >= best1 - mrg
+      // (the single atoms themselves join the candidates after the sweep: k2s_finish)
+      // single-atom scores are exact up to the statistics' rounding: a pair matters only if S(c) >= best1, i.e. S(c~) >= best1 - mrg
       s_thr[0] = mfx_nonneg_bits(best1 - mrg);
 #ifdef MFX_STAMPS_RND   // experiment: a starting threshold handed in by the tool (slot 15), to price the threshold's convergence
       if (a.stamps) {
@@ -403,9 +399,8 @@ __device__ __forceinline__ K2sVoxel k2s_prologue(const FitK2Args& a, const K2sLd
 
 // ---- phase 1's "best single atom of D2" step for a caller that deferred D2's statistics (!XC): every wave hands in the best
 // single atom of the columns it made (first index on ties; score 0 when none is positive) in its slot of s_red - D2's half
-// of the prologue's [2][8] - and a workgroup barrier has passed since.  The sweep has begun: the ring may hold entries - the
-// winner is appended by the ring's own rule - and the threshold is only raised.  Ends with a workgroup barrier, like the
-// prologue.
+// of the prologue's [2][8] - and a workgroup barrier has passed since.  The sweep has begun: the threshold is only raised.
+// Ends with a workgroup barrier, like the prologue.
 template <int NW, class LDS>
 __device__ __forceinline__ void k2s_best_single_late(const FitK2Args& a, const LDS& L, const int tid, const double mrg) {
   const double* s_bs = L.s_red + 8;            // [8]
@@ -418,8 +413,8 @@ __device__ __forceinline__ void k2s_best_single_late(const FitK2Args& a, const L
       const int n2 = s_bn[w];
       if (s2 > s || (s2 == s && n2 < n)) { s = s2; n = n2; }
     }
-    if (s > 0.0) k2s_push(L, a.scap, s + mrg, 0, n | MFX_S_BOUND);   // exact single-atom score up to the statistics' rounding
-    // single-atom scores are exact: a pair matters only if S(c) >= s, i.e. S(c~) >= s - mrg
+    // single-atom scores are exact up to the statistics' rounding: a pair matters only if S(c) >= s, i.e. S(c~) >= s - mrg
+    // (the single atoms themselves join the candidates after the sweep: k2s_finish)
     unsigned long long tb = mfx_nonneg_bits(s - mrg);
 #ifdef MFX_STAMPS_RND   // experiment: a starting threshold handed in by the tool (slot 15), as in the prologue
     if (a.stamps) {
@@ -432,12 +427,12 @@ __device__ __forceinline__ void k2s_best_single_late(const FitK2Args& a, const L
   __syncthreads();
 }
 
-// ---- everything after the sweep: D1's best single atom joins the candidates; hand-back decisions; XC: the voxel's short list;
+// ---- everything after the sweep: the single atoms that can still win join the candidates; hand-back decisions; XC: the voxel's short list;
 // otherwise the exact stage (reference arithmetic and order on the ring entries that reach the final threshold, strict-'<'
 // first hit, family expansion, run-time guard on the screening error) and the parameters (mf.py:420-450)
 template <int KS, int NB, bool BR, bool XC, int PQF, int WG>
 __device__ __forceinline__ void k2s_finish(const FitK2Args& a, const K2sLds<KS, NB, BR, XC, PQF>& L, const K2sVoxel& VX, const int vox,
-                                           const int wave, const int lane, const double bs1, const int bn1) {
+                                           const int wave, const int lane) {
   constexpr int MP = KS * 16, NW = WG / 64;
   const int M = a.P.M, N = a.T.N;
   const int NP = (N + 31) & ~31;
@@ -465,22 +460,20 @@ __device__ __forceinline__ void k2s_finish(const FitK2Args& a, const K2sLds<KS, 
 
   // (the thread index is re-derived here instead of being kept - spilled, 4 KB of scratch per voxel - across the sweep)
   tid = wave * 64 + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-  // D1's best single atom (first index on ties) joins the candidates, like D2's after phase 1
-  {
-    double* s_bs = (double*)smem + 64;            // [8]  inside the chunk images, idle from here on (a constant
-    int* s_bn = (int*)((double*)smem + 80);       // [8]  address: nothing to keep in a register across the sweep)
-    if (lane == 0) { s_bs[wave] = bs1; s_bn[wave] = bn1; }
-    __syncthreads();
-    if (tid == 0) {
-      double sb = s_bs[0];
-      int nb = s_bn[0];
-      for (int w = 1; w < NW; ++w) {
-        const double s2 = s_bs[w];
-        const int n2 = s_bn[w];
-        if (s2 > sb || (s2 == sb && n2 < nb)) { sb = s2; nb = n2; }
-      }
-      s_cnt[3] = -1;
-      if (sb > 0.0) { s_cnt[3] = s_cnt[0] & (a.scap - 1); push(sb + mrg, nb, MFX_S_BOUND); }   // [3]: its slot (diagnostics)
+  // The single atoms join the candidates: they stand for every pair whose optimum has one active atom (mf_utils.py:357-379;
+  // the exact stage expands the winner's family).  The statistics (FP32 table, FP32 signal: s_Zf) rank them to a few 1e-7 |y|^2
+  // only, well inside mrg, so the best one alone does not stand for the others: of two atoms whose scores differ by less - near-
+  // duplicate atoms of one dictionary - the reference takes the one that is better in ITS arithmetic.  EVERY atom of either
+  // dictionary whose score could reach the final threshold is listed, by the rule of every other entry (upper bound >= thr):
+  // the best ones always are (thr's single-atom part is best - mrg), and none is once a pair beats them all by more than 2 mrg.
+  // (XC: supports with fewer than two fascicle atoms belong to the exact kernel's families, see below)
+  __syncthreads();   // the sweep's last appends, statistics and threshold updates
+  if constexpr (!XC) {
+    const double thr_now = __longlong_as_double((long long)s_thr[0]);
+    for (int q = tid; q < 2 * NP; q += WG) {
+      const int k = q >= NP, n = q - k * NP;
+      const double z = (double)s_Zf[q];
+      if (n < N && z > 0.0 && z * z + mrg >= thr_now) push(z * z + mrg, k ? 0 : n, (k ? n : 0) | MFX_S_BOUND);
     }
     __syncthreads();
   }
