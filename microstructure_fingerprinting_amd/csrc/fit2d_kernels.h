@@ -42,6 +42,7 @@
 namespace {
 
 constexpr int F2_MAXC = 512;               // short-list entries
+constexpr int F2_SINGLE = 1 << 30;         // in Cand::j: a single atom's entry - the pair itself, no slot row
 constexpr size_t F2_LDS_MAX = 160 * 1024;
 constexpr int F2_K1_WG = 256;
 
@@ -232,9 +233,8 @@ __global__ __launch_bounds__(F2_WG, 2) void mfx_fit2d_k2_kernel(F2ArgsT<WGT> a) 
   // ||y||^2 stays in s_red[31] and the running best lower bound on the score in s_red[30] (one value for the workgroup):
   // they live through the whole of phase 2, whose registers belong to the accumulators
   {
-    const double eps_abs = 1e-9 * s_red[31];
-    // best single atom of each dictionary (first index on ties): they stand for every pair whose optimum has one
-    // active atom (mf_utils.py:357-379); phase 3 expands the winner's family exactly (as fit_k2.hip)
+    // best single-atom score of either dictionary: no pair below it matters (a pair whose optimum has one active atom,
+    // mf_utils.py:357-379, scores as that atom).  The single atoms themselves join the candidates behind phase 2.
     double* s_bs = s_red;            // [2][8] per-wave bests
     int* s_bn = (int*)(s_red + 16);  // [2][8]
 #pragma unroll
@@ -263,15 +263,9 @@ __global__ __launch_bounds__(F2_WG, 2) void mfx_fit2d_k2_kernel(F2ArgsT<WGT> a) 
         if (s2 > s || (s2 == s && n2 < n)) { s = s2; n = n2; }
       }
       best1 = fmax(best1, s);
-      if (tid == 0 && s > 0.0) {
-        const int slot = s_cnt[0]++;
-        s_cand[slot].score = s + eps_abs;
-        s_cand[slot].i = k ? 0 : n;
-        s_cand[slot].j = k ? n : 0;
-      }
     }
     __syncthreads();   // (s_red[0..23] read by everybody)
-    if (tid == 0) { s_red[30] = best1; s_cnt[1] = s_cnt[0]; }   // the single-atom representatives (0..2)
+    if (tid == 0) s_red[30] = best1;
   }
   __syncthreads();
 
@@ -450,6 +444,25 @@ __global__ __launch_bounds__(F2_WG, 2) void mfx_fit2d_k2_kernel(F2ArgsT<WGT> a) 
     }
   }
 
+  // The single atoms stand for every pair whose optimum has one active atom; phase 3 expands the winner's family exactly.
+  // The best one alone does not stand for the others: of two near-duplicate atoms whose scores differ by rounding the
+  // reference takes the one whose ROUNDED residual is smaller and, when those tie, the first - not the one that scores
+  // higher.  EVERY atom of either dictionary whose score reaches the final bound joins the list, by the rule of every
+  // other entry; none does once a pair beats them all by more than the window.
+  __syncthreads();
+  {
+    const double thr = s_red[30], eps_abs = 1e-9 * s_red[31];
+    for (int col = tid; col < 2 * NP; col += F2_WG) {
+      const int k = col >= NP, n = col - k * NP;
+      const double a2 = s_st[col].x, ay = s_st[col].y;
+      const double s = (n < N && ay > 0.0) ? (ay * ay) / a2 : 0.0;
+      if (s > 0.0 && s + eps_abs >= thr) {
+        const int slot = atomicAdd(&s_cnt[0], 1);
+        if (slot < F2_MAXC) { s_cand[slot].score = s + eps_abs; s_cand[slot].i = k ? 0 : n; s_cand[slot].j = (k ? n : 0) | F2_SINGLE; }
+      }
+    }
+  }
+
   // ---- phase 3: exact re-evaluation of the short list (reference arithmetic and order), as fit_k2.hip
   __syncthreads();
   const double y_sq = s_red[31], glb_run = s_red[30];
@@ -509,15 +522,15 @@ __global__ __launch_bounds__(F2_WG, 2) void mfx_fit2d_k2_kernel(F2ArgsT<WGT> a) 
       // A scan candidate is the best pair of its slot - row i, the columns j = lc (mod 16) of one wave's half of one
       // column block; a second pair of the slot within rounding distance of the optimum was never listed.  The whole
       // row i over the columns j = lc (mod 16) (a superset of the slot) is therefore evaluated exactly for every listed
-      // candidate that still reaches the final lower bound.  The first entries are the single-atom representatives of
-      // phase 1: themselves only.
-      const int NJ = (N + 15) >> 4, nsingle = s_cnt[1];
+      // candidate that still reaches the final lower bound.  A single atom's entry (F2_SINGLE) is itself only.
+      const int NJ = (N + 15) >> 4;
       for (int q = tid; q < ncand * NJ; q += F2_WG) {
         const int c = q / NJ, u = q - c * NJ;
         if (!(s_cand[c].score >= glb_run)) continue;
-        const int ci = s_cand[c].i, cj = s_cand[c].j;
-        const int jj = (c < nsingle) ? cj : (cj & 15) + 16 * u;
-        if ((c < nsingle && u > 0) || jj >= N) continue;
+        const int ci = s_cand[c].i, cj = s_cand[c].j & ~F2_SINGLE;
+        const bool single = (s_cand[c].j & F2_SINGLE) != 0;
+        const int jj = single ? cj : (cj & 15) + 16 * u;
+        if ((single && u > 0) || jj >= N) continue;
         double r, u0, u1;
         exact_pair(ci, jj, u0, u1, r);
         const long ix = (long)ci * N + jj;

@@ -6,8 +6,9 @@
 //   1. mfx_gram_kernel     G = A^T A and A^T y, every entry summed sequentially over the rows exactly as
 //                          the reference's precompute loops (mf_utils.py:307-325, 503-535)  -> HBM
 //   2. mfx_tuple_scan      all prod(sizes) index tuples, one thread per tuple (grid-stride); scores a tuple
-//                          by the NNLS optimum of its tiny Gram system; the best score of every block -> HBM,
-//                          the best score of all (atomicMax)
+//                          by the NNLS optimum of its tiny Gram system, with a bound on that score's rounding
+//                          error (mfx_tuple_score_err); the best upper bound of every block -> HBM, the best
+//                          lower bound of all (atomicMax)
 //   3. mfx_tuple_collect   the blocks whose best lies within 1e-9*||y||^2 of the best of all (the finalize
 //                          stage's tie window) score their tuples again and append EVERY tuple inside the
 //                          window to a candidate list (atomic counter); every other block exits at once.
@@ -160,30 +161,71 @@ __device__ inline double mfx_tuple_score(const SolveArgs& a, const int col[MFX_G
 // ||y||^2 as the reference's kernel for this number of sub-dictionaries sums it: np.sum(y**2) in _1/_4up, sequential in _2/_3
 __device__ __forceinline__ double mfx_ref_ysq(const SolveArgs& a) { return (a.Kp == 1 || a.Kp >= 4) ? a.ysq[1] : a.ysq[0]; }
 
-// lower edge of the tie window: what the finalize stage computes from the best listed score
+// Bound on the rounding error of mfx_tuple_score for two and three sub-dictionaries.  score2 / score3 solve the tuple's
+// Gram system by cofactors: with d = Det / prod |a_k|^2 the relative determinant of the system a branch solves, the
+// rounding of the cofactors, of Det and of the Gram's own sums moves the score by a few eps |y|^2 / d.  A CSF column
+// almost inside the span of two fascicle atoms gives d = 1e-5 .. 1e-7 on ordinary voxels: the score is then good to
+// 1e-11 .. 1e-9 |y|^2 only, and a tuple that the reference's explicit residual prefers could fall out of a fixed window
+// of 1e-9 |y|^2 under the best score.  MFX_SCORE_ERR: 16 eps (measured on the CSF fits of tests/_twin2d_cases.py: at
+// most 3.5 eps |y|^2 / d).  The smallest d over the branches the score may have taken counts (a branch below its own
+// cut - 1e-8, 1e-12 - is never taken).  Other tuple sizes: 0, as before.
+#define MFX_SCORE_ERR (16.0 * 2.220446049250313e-16)
+__device__ inline double mfx_tuple_score_err(const SolveArgs& a, const int col[MFX_GK]) {
+  const int n = a.Kp, N = a.Ntot;
+  if (n != 2 && n != 3) return 0.0;
+  const double* G = a.G;
+  auto g = [&](int p, int q) { return G[(long)col[p] * N + col[q]]; };
+  double rel = 1.0;
+  auto pair = [&](int p, int q) {
+    const double pd = g(p, p) * g(q, q), det = pd - g(p, q) * g(p, q);
+    if (det > 1e-8 * pd) rel = fmin(rel, det / pd);
+  };
+  pair(0, 1);
+  if (n == 3) {
+    pair(0, 2);
+    pair(1, 2);
+    const double a11 = g(0, 0), a12 = g(0, 1), a13 = g(0, 2), a22 = g(1, 1), a23 = g(1, 2), a33 = g(2, 2);
+    const double det = a11 * (a22 * a33 - a23 * a23) + a12 * (a13 * a23 - a12 * a33) + a13 * (a12 * a23 - a13 * a22);
+    const double pd = a11 * a22 * a33;
+    if (det > 1e-12 * pd) rel = fmin(rel, det / pd);
+  }
+  return MFX_SCORE_ERR * mfx_ref_ysq(a) / rel;
+}
+
+// lower edge of the tie window: *a.smax holds the best LOWER bound (score - error) of all tuples; a tuple is listed when
+// its upper bound (score + error) reaches this edge
 __device__ __forceinline__ double mfx_tie_threshold(const SolveArgs& a) {
   return __longlong_as_double((long long)*a.smax) - 1e-9 * mfx_ref_ysq(a);
+}
+// what the list stores for a tuple inside the window: its upper bound, not above the best lower bound - so that the
+// finalize stage, which takes its window from the largest stored value, keeps every listed tuple
+__device__ __forceinline__ double mfx_listed_score(const SolveArgs& a, double ub) {
+  return fmin(ub, __longlong_as_double((long long)*a.smax));
 }
 
 // pass 1: the best score of every block and of all tuples.  Nothing is selected here: which tuples reach the finalize
 // stage is decided against the maximum of ALL tuples, in mfx_tuple_collect.
 __global__ __launch_bounds__(256) void mfx_tuple_scan(SolveArgs a) {
-  __shared__ double s_sc[256];
+  __shared__ double s_sc[256], s_lb[256];
   if (a.run_if && !*a.run_if) return;
   if (a.scan_enable && !*a.scan_enable) return;   // (three-dictionary fast path: only after a candidate-list overflow)
-  double best = 0.0;
+  double best = 0.0, lb = 0.0;   // the block's best upper and lower bound
   for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < a.ntuples; t += (long)gridDim.x * 256) {
     int col[MFX_GK];
     mfx_decode(a, t, col);
     const double s = mfx_tuple_score(a, col);
-    if (s > best) best = s;
+    if (!(s > 0.0)) continue;
+    const double e = mfx_tuple_score_err(a, col);
+    best = fmax(best, s + e);
+    lb = fmax(lb, s - e);
   }
   s_sc[threadIdx.x] = best;
+  s_lb[threadIdx.x] = lb;
   __syncthreads();
   if (threadIdx.x == 0) {
-    for (int i = 1; i < 256; ++i) best = fmax(best, s_sc[i]);
+    for (int i = 1; i < 256; ++i) { best = fmax(best, s_sc[i]); lb = fmax(lb, s_lb[i]); }
     a.blk_max[blockIdx.x] = best;
-    if (best > 0.0) atomicMax(a.smax, (unsigned long long)__double_as_longlong(best));
+    if (lb > 0.0) atomicMax(a.smax, (unsigned long long)__double_as_longlong(lb));
   }
 }
 
@@ -208,11 +250,13 @@ __global__ __launch_bounds__(256) void mfx_tuple_collect(SolveArgs a) {
     int col[MFX_GK];
     mfx_decode(a, t, col);
     const double s = mfx_tuple_score(a, col);
-    if (!(s > 0.0) || s < thr) continue;
+    if (!(s > 0.0)) continue;
+    const double ub = s + mfx_tuple_score_err(a, col);
+    if (ub < thr) continue;
     if (*(volatile int*)a.ncand < 0) return;   // overflowed: mfx_tuple_overflow takes over
     const int slot = atomicAdd(a.ncand, 1);
     if (slot >= 0 && slot < a.list_cap) {
-      a.blk_score[slot] = s;
+      a.blk_score[slot] = mfx_listed_score(a, ub);
       a.blk_tuple[slot] = t;
     } else {
       atomicOr(a.ncand, (int)0x80000000);
@@ -239,9 +283,11 @@ __global__ __launch_bounds__(256) void mfx_tuple_overflow(SolveArgs a) {
       int col[MFX_GK];
       mfx_decode(a, t, col);
       const double s = mfx_tuple_score(a, col);
-      if (!(s > 0.0) || s < thr) continue;
+      if (!(s > 0.0)) continue;
+      const double ub = s + mfx_tuple_score_err(a, col);
+      if (ub < thr) continue;
       const long key = mfx_order_key(a, t);
-      if (bt < 0 || key < bkey) { bs = s; bkey = key; bt = t; }
+      if (bt < 0 || key < bkey) { bs = mfx_listed_score(a, ub); bkey = key; bt = t; }
     }
   }
   s_sc[threadIdx.x] = bs;
