@@ -71,6 +71,10 @@ PREDICT2D_EXPORTS = ["mfx_predict2d_abi_version", "mfx_predict2d_dev", "mfx_pred
 ROBUST2D_EXPORTS = ["mfx_robust2d_abi_version", "mfx_rfit2d_batch_dev", "mfx_rfit2d_batch",
                     "mfx_robust2d_debug_last_plan_directions"]
 
+# every symbol include/mfx_boot.h declares (bootstrap: resampled refits reduced on the device; versioned on its own)
+BOOT_EXPORTS = ["mfx_boot_abi_version", "mfx_boot_resample_dev", "mfx_boot_gather_dev", "mfx_boot_reduce_dev",
+                "mfx_boot_fit_dev", "mfx_boot_fit"]
+
 
 class MfxError(RuntimeError):
     pass
@@ -231,6 +235,15 @@ def lib():
     L.mfx_rfit2d_batch.argtypes = [vp, dp, dp, C.c_int64, ip, bp, dp, C.c_int, C.c_int, dp, C.c_int, C.c_double, C.c_int, C.c_int64,
                                    dp, dp, dp, ip, ip, ip, lp, ip]
     L.mfx_robust2d_debug_last_plan_directions.restype = C.c_int64
+    L.mfx_boot_abi_version.restype = C.c_int
+    L.mfx_boot_resample_dev.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int64, C.c_int, C.c_int,
+                                        C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp, vp]
+    L.mfx_boot_gather_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int64, C.c_int, vp, vp, vp, vp]
+    L.mfx_boot_reduce_dev.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int, vp, vp]
+    L.mfx_boot_fit_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int64, C.c_int,
+                                   C.c_int, C.c_int, C.c_uint64, C.c_uint64, vp, C.c_int, vp, C.c_int, C.c_int64, vp, vp, vp, vp, vp]
+    L.mfx_boot_fit.argtypes = [vp, dp, ip, bp, bp, dp, C.c_int, C.c_int, C.c_int, dp, dp, C.c_int, dp, ip, lp, C.c_int64, C.c_int,
+                               C.c_int, C.c_int, C.c_uint64, C.c_uint64, dp, C.c_int, dp, C.c_int, C.c_int64, dp, ip, ip, dp]
     _lib = L
     return L
 

@@ -47,12 +47,14 @@ class Plan:
 
     def __init__(self, tables, scheme=None, gdirs=None, shell_of_row=None):
         self.tables = tables
+        self.scheme = None          # the [M x 7] scheme of a multi-shell plan (boot_groups reads it)
         h = C.c_void_p()
         if scheme is not None:
             sch = L.f64c(scheme)
             if sch.ndim != 2 or sch.shape[1] != 7:
                 raise ValueError("pgse_scheme should have 7 columns")
             self.M = sch.shape[0]
+            self.scheme = sch
             L.check(L.lib().mfx_plan_create_multishell(tables.handle(), L.dptr(sch), self.M, C.byref(h)))
         else:
             g = L.f64c(gdirs)
@@ -1488,6 +1490,289 @@ def fit2d_robust(tables, Y, K, csf, peaks, maxfasc, csf_on, sig_csf=None, W0=Non
                                      L.lptr(nch), L.iptr(used)))
     return params, W, {'scale': scale, 'state': state, 'status': wstat, 'dir_status': dstat,
                        'n_changed': nch[:n_iter].copy(), 'n_iter_used': int(used[0])}
+
+
+BOOT_KINDS = {'wild': 0, 'residual': 1}   # include/mfx_boot.h
+BOOT_MAX_B, BOOT_MAX_Q, BOOT_NSTAT = 4096, 32, 5
+BOOT_DEFAULT_BYTES = 256 << 20
+
+
+def boot_columns(maxfasc, csf_on, ear_on, nprop=0):
+    """The column names of the bootstrap's value table for a parameter layout (include/mfx_boot.h): 'M0', 'nu_k',
+    'nu_csf', 'nu_ear', 'MSE', then ('prop', k, t) for fascicle k and property table t."""
+    cols = ['M0'] + ['nu_%d' % k for k in range(int(maxfasc))]
+    cols += ['nu_csf'] if csf_on else []
+    cols += ['nu_ear'] if ear_on else []
+    cols.append('MSE')
+    return cols + [('prop', k, t) for k in range(int(maxfasc)) for t in range(int(nprop))]
+
+
+def boot_groups(scheme):
+    """The default groups of the residual bootstrap: int32 [M], rows sharing (G, Delta, delta) share a group."""
+    sch = L.f64c(scheme)
+    if sch.ndim != 2 or sch.shape[1] != 7:
+        raise ValueError("pgse_scheme should have 7 columns")
+    return np.ascontiguousarray(np.unique(sch[:, 3:6], axis=0, return_inverse=True)[1].reshape(-1), dtype=np.int32)
+
+
+def _boot_rule(B, kind, q=(), seed=0, offset=0, reduce=True):
+    """The bootstrap's options checked (before any device call); returns (B, kind code, q float64 [Q])."""
+    if isinstance(B, bool) or not isinstance(B, (int, np.integer)) or B < 1:
+        raise ValueError("bootstrap B should be an integer >= 1, got %r" % (B,))
+    if not isinstance(kind, str) or kind not in BOOT_KINDS:
+        raise ValueError("bootstrap kind should be one of %s, got %r" % (", ".join(repr(k) for k in BOOT_KINDS), kind))
+    try:
+        qa = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)).reshape(-1))
+    except (TypeError, ValueError):
+        raise ValueError("bootstrap q should be numbers in [0, 1], got %r" % (q,))
+    if qa.size and not np.all((qa >= 0.0) & (qa <= 1.0)):
+        raise ValueError("bootstrap q should lie in [0, 1], got %r" % (q,))
+    for name, x in (("seed", seed), ("offset", offset)):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+            raise ValueError("bootstrap %s should be an integer, got %r" % (name, x))
+    if reduce and B > BOOT_MAX_B:
+        raise NotImplementedError("at most %d bootstrap replicates are reduced on the device (got B = %d)" % (BOOT_MAX_B, B))
+    if qa.size > BOOT_MAX_Q:
+        raise NotImplementedError("at most %d bootstrap quantiles (got %d)" % (BOOT_MAX_Q, qa.size))
+    return int(B), BOOT_KINDS[kind], qa
+
+
+def _boot_groups_arg(kind, groups, M, scheme):
+    """int32 [M] groups of the residual bootstrap (None for the wild one): given, or the default from the scheme."""
+    if kind != 1:
+        return None
+    if groups is None:
+        if scheme is None:
+            raise ValueError("the residual bootstrap needs groups (the plan knows no scheme to derive them from)")
+        groups = boot_groups(scheme)
+    g = np.asarray(groups)
+    if g.shape != (M,) or g.dtype.kind not in 'iu':
+        raise ValueError("groups should be %d integers (one per measurement), got shape %s" % (M, g.shape))
+    return np.ascontiguousarray(g, dtype=np.int32)
+
+
+def boot_resample_dev(d_Y, d_P, d_params, maxfasc, csf_on=False, ear_on=False, B=200, kind='wild', seed=0, inflate=True,
+                      offset=0, d_groups=None, d_peaks=None, d_vox=None):
+    """The bootstrap's resampling rule on the device (mfx_boot_resample_dev; include/mfx_boot.h states it operation by
+    operation): torch CUDA float64 tensors d_Y, d_P [V, M] (data and the prediction of the voxels' own fit), d_params
+    [V, num_params] (their parameter rows: the number of positive weights scales the residuals with ``inflate``),
+    optional d_peaks [V, 3 maxfasc], d_groups [M] int32 (kind 'residual'), d_vox [V] int64 (batch indices, default
+    0..V-1) -> (Ystar [V, B, M], peaks [V B, 3 maxfasc] or None, status [V] int32).  Enqueues on torch's current stream
+    and returns without waiting."""
+    import torch
+    B, code, _ = _boot_rule(B, kind, (), seed, offset, reduce=False)
+    maxfasc = int(maxfasc)
+    if maxfasc < 0 or maxfasc > 3:
+        raise ValueError("maxfasc must be 0..3")
+    for t in (d_Y, d_P, d_params, d_peaks):
+        assert t is None or (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous())
+    if d_Y.dim() != 2 or d_Y.shape[1] < 1:
+        raise ValueError("data should have shape (voxels, measurements), got %s" % (tuple(d_Y.shape),))
+    V, M = d_Y.shape
+    if tuple(d_P.shape) != (V, M):
+        raise ValueError("prediction should have the data's shape (%d, %d), got %s" % (V, M, tuple(d_P.shape)))
+    npar = num_params(maxfasc, csf_on, ear_on)
+    if tuple(d_params.shape) != (V, npar):
+        raise ValueError("params should have shape (%d, %d), got %s" % (V, npar, tuple(d_params.shape)))
+    if d_peaks is not None and (maxfasc == 0 or tuple(d_peaks.shape) != (V, 3 * maxfasc)):
+        raise ValueError("peaks should have shape (%d, %d)" % (V, 3 * maxfasc))
+    if code == 1:
+        if d_groups is None:
+            raise ValueError("the residual bootstrap needs groups")
+        assert d_groups.is_cuda and d_groups.dtype == torch.int32 and d_groups.is_contiguous()
+        if tuple(d_groups.shape) != (M,):
+            raise ValueError("groups should be %d integers (one per measurement), got shape %s" % (M, tuple(d_groups.shape)))
+    if d_vox is not None:
+        assert d_vox.is_cuda and d_vox.dtype == torch.int64 and d_vox.is_contiguous()
+        if tuple(d_vox.shape) != (V,):
+            raise ValueError("vox should have one entry per voxel")
+    dev = d_Y.device
+    Ys = torch.empty((V, B, M), dtype=torch.float64, device=dev)
+    pk = torch.empty((V * B, 3 * maxfasc), dtype=torch.float64, device=dev) if d_peaks is not None else None
+    status = torch.empty((V,), dtype=torch.int32, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        L.check(L.lib().mfx_boot_resample_dev(M, d_Y.data_ptr(), d_P.data_ptr(), d_params.data_ptr(), maxfasc, int(bool(csf_on)),
+                                              int(bool(ear_on)), d_peaks.data_ptr() if d_peaks is not None else None,
+                                              d_groups.data_ptr() if code == 1 else None,
+                                              d_vox.data_ptr() if d_vox is not None else None, V, B, code, int(bool(inflate)),
+                                              int(seed) & _U64, int(offset) & _U64, Ys.data_ptr(),
+                                              pk.data_ptr() if pk is not None else None, status.data_ptr(), st))
+    return Ys, pk, status
+
+
+def boot_reduce_dev(d_X, d_valid, q=()):
+    """The bootstrap's statistics on the device (mfx_boot_reduce_dev): torch CUDA tensors d_X [V, B, C] float64 and d_valid
+    [V, B, C] uint8 or bool -> stats [V, C, 5 + Q] float64: per voxel and column over the valid replicates the count, the
+    mean (serial sum in replicate order), the standard deviation (two-pass, ddof = 1), the smallest and largest value and
+    the quantiles ``q`` by linear interpolation.  Enqueues on torch's current stream and returns without waiting."""
+    import torch
+    if d_X.dim() != 3 or d_X.shape[1] < 1 or d_X.shape[2] < 1:
+        raise ValueError("X should have shape (voxels, replicates, columns), got %s" % (tuple(d_X.shape),))
+    V, B, Cn = d_X.shape
+    _, _, qa = _boot_rule(B, 'wild', q)
+    if tuple(d_valid.shape) != (V, B, Cn):
+        raise ValueError("valid should have the shape of X %s, got %s" % ((V, B, Cn), tuple(d_valid.shape)))
+    assert d_X.is_cuda and d_X.dtype == torch.float64 and d_X.is_contiguous()
+    assert d_valid.is_cuda and d_valid.dtype in (torch.uint8, torch.bool) and d_valid.is_contiguous()
+    dev = d_X.device
+    d_q = torch.from_numpy(qa).to(dev) if qa.size else None
+    stats = torch.empty((V, Cn, BOOT_NSTAT + qa.size), dtype=torch.float64, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        L.check(L.lib().mfx_boot_reduce_dev(d_X.data_ptr(), d_valid.data_ptr(), V, B, Cn, d_q.data_ptr() if d_q is not None else None,
+                                            int(qa.size), stats.data_ptr(), st))
+    return stats
+
+
+def fit_bootstrap_dev(plan, d_Y, d_peaks, maxfasc, csf_on=False, ear_on=False, d_sig_csf=None, d_sig_ear=None, E=0, B=200,
+                      kind='wild', seed=0, inflate=True, offset=0, q=(0.025, 0.975), d_props=None, d_groups=None, d_params=None,
+                      d_pred=None, d_vox=None, max_bytes=BOOT_DEFAULT_BYTES, keep=False):
+    """Device-resident bootstrap (mfx_boot_fit_dev) of ONE voxel class (every voxel: K == maxfasc, csf == csf_on,
+    ear == ear_on), torch CUDA tensors as ``fit_batch_dev`` takes them.  The voxels' own fit (``d_params`` [V, num_params],
+    fitted here if None) is predicted (``d_pred`` [V, M] if given), its residuals are resampled into B replicates per
+    voxel by the rule of ``boot_resample_dev``, the replicates are fitted by ``fit_batch_dev``'s kernels and reduced:
+    returns {'stats' [V, C, 5 + Q], 'agree' [V, maxfasc] int32, 'status' [V] int32, 'replicates' [V, B, num_params] or
+    None (``keep``), 'columns' (``boot_columns``)}; d_props [nprop, N] are the property tables whose values at the chosen
+    atoms become columns.  Voxel chunks keep the replicate signals within ``max_bytes``.  Enqueues on torch's current
+    stream and returns without waiting; a direction that is not a unit vector is reported by mfx_plan_status."""
+    import torch
+    B, code, qa = _boot_rule(B, kind, q, seed, offset)
+    maxfasc = int(maxfasc)
+    if maxfasc < 0 or maxfasc > 3:
+        raise ValueError("maxfasc must be 0..3")
+    for t in (d_Y, d_peaks if maxfasc > 0 else None, d_sig_csf if csf_on else None, d_sig_ear if ear_on else None, d_props,
+              d_params, d_pred):
+        assert t is None or (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous())
+    if d_Y.dim() != 2 or d_Y.shape[1] != plan.M:
+        raise ValueError("data should have shape (voxels, %d), got %s" % (plan.M, tuple(d_Y.shape)))
+    V, M = d_Y.shape
+    npar = num_params(maxfasc, csf_on, ear_on)
+    if maxfasc > 0 and (d_peaks is None or tuple(d_peaks.shape) != (V, 3 * maxfasc)):
+        raise ValueError("peaks should have shape (%d, %d)" % (V, 3 * maxfasc))
+    if csf_on and (d_sig_csf is None or d_sig_csf.numel() != M):
+        raise ValueError("csf_on needs sig_csf with %d entries" % M)
+    if ear_on and (d_sig_ear is None or tuple(d_sig_ear.shape) != (M, E) or E < 1):
+        raise ValueError("sig_ear should have shape (%d, E) with E >= 1" % M)
+    if d_params is not None and tuple(d_params.shape) != (V, npar):
+        raise ValueError("params should have shape (%d, %d), got %s" % (V, npar, tuple(d_params.shape)))
+    if d_pred is not None and (d_params is None or tuple(d_pred.shape) != (V, M)):
+        raise ValueError("a prediction needs the parameters it was made from and the data's shape (%d, %d)" % (V, M))
+    nprop = 0
+    if d_props is not None:
+        if d_props.dim() != 2 or d_props.shape[1] != plan.tables.N:
+            raise ValueError("props should have shape (nprop, %d), got %s" % (plan.tables.N, tuple(d_props.shape)))
+        nprop = int(d_props.shape[0])
+    dev = d_Y.device
+    if code == 1 and d_groups is None:
+        d_groups = torch.from_numpy(_boot_groups_arg(code, None, M, plan.scheme)).to(dev)
+    if code == 1:
+        assert d_groups.is_cuda and d_groups.dtype == torch.int32 and d_groups.is_contiguous()
+        if tuple(d_groups.shape) != (M,):
+            raise ValueError("groups should be %d integers (one per measurement), got shape %s" % (M, tuple(d_groups.shape)))
+    if d_vox is not None:
+        assert d_vox.is_cuda and d_vox.dtype == torch.int64 and d_vox.is_contiguous()
+        if tuple(d_vox.shape) != (V,):
+            raise ValueError("vox should have one entry per voxel")
+    cols = boot_columns(maxfasc, csf_on, ear_on, nprop)
+    d_q = torch.from_numpy(qa).to(dev) if qa.size else None
+    stats = torch.empty((V, len(cols), BOOT_NSTAT + qa.size), dtype=torch.float64, device=dev)
+    agree = torch.zeros((V, maxfasc), dtype=torch.int32, device=dev)
+    status = torch.zeros((V,), dtype=torch.int32, device=dev)
+    reps = torch.empty((V, B, npar), dtype=torch.float64, device=dev) if keep else None
+    st = torch.cuda.current_stream(dev).cuda_stream
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(dev):
+        L.check(L.lib().mfx_boot_fit_dev(plan.handle(), d_Y.data_ptr(), ptr(d_peaks) if maxfasc > 0 else None, maxfasc,
+                                         int(bool(csf_on)), int(bool(ear_on)), ptr(d_sig_csf) if csf_on else None,
+                                         ptr(d_sig_ear) if ear_on else None, int(E), ptr(d_params), ptr(d_pred),
+                                         ptr(d_groups) if code == 1 else None, ptr(d_vox), V, B, code, int(bool(inflate)),
+                                         int(seed) & _U64, int(offset) & _U64, ptr(d_props), nprop, ptr(d_q), int(qa.size),
+                                         int(max_bytes), stats.data_ptr(), agree.data_ptr() if maxfasc > 0 else None,
+                                         status.data_ptr(), ptr(reps), st))
+    return {'stats': stats, 'agree': agree, 'status': status, 'replicates': reps, 'columns': cols}
+
+
+def fit_bootstrap(plan, Y, K, csf, ear, peaks, maxfasc, csf_on, ear_on, sig_csf=None, sig_ear=None, E=0, B=200, kind='wild',
+                  seed=0, inflate=True, offset=0, q=(0.025, 0.975), props=None, groups=None, params=None, vox=None,
+                  max_bytes=BOOT_DEFAULT_BYTES, keep=False):
+    """Bootstrap of a mixed set of voxels on NumPy arrays (mfx_boot_fit), arguments as ``fit_batch`` takes them: every
+    voxel class of the plain fit is served (K in 0..maxfasc, CSF, EAR).  ``params`` [V, num_params]: the voxels' own fit
+    (fitted here if None); ``vox`` [V] int64: the voxels' batch indices (default 0..V-1) - the random stream is keyed by
+    them, so a subset gives the replicates the whole batch gives; ``props`` [nprop, N]: property tables; ``groups`` [M]:
+    the residual bootstrap's groups (default ``boot_groups`` of the plan's scheme).  Returns {'stats' [V, C, 5 + Q]
+    (count, mean, std, min, max, quantiles per column of ``boot_columns``), 'agree' [V, maxfasc] int32 (replicates that
+    chose the original atom with a positive weight), 'status' [V] int32 (0 fine, 1 no degree of freedom, 2 original row
+    not usable), 'replicates' [V, B, num_params] or None (``keep``), 'columns'}."""
+    B, code, qa = _boot_rule(B, kind, q, seed, offset)
+    maxfasc = int(maxfasc)
+    if maxfasc < 0 or maxfasc > 3:
+        raise ValueError("maxfasc must be 0..3")
+    Y = L.f64c(Y)
+    if Y.ndim != 2 or Y.shape[1] != plan.M:
+        raise ValueError("data should have shape (voxels, %d), got %s" % (plan.M, Y.shape))
+    V, M = Y.shape
+    csf_on, ear_on = bool(csf_on), bool(ear_on)
+    npar = num_params(maxfasc, csf_on, ear_on)
+    K = np.ascontiguousarray(np.asarray(K).reshape(-1), dtype=np.int32)
+    if K.shape != (V,):
+        raise ValueError("K should have one entry per voxel")
+    if V and (K.min() < 0 or K.max() > maxfasc):
+        raise ValueError("K should lie in 0..maxfasc = %d" % maxfasc)
+    flags = []
+    for name, f, on in (("csf", csf, csf_on), ("ear", ear, ear_on)):
+        a = None
+        if f is not None:
+            a = np.ascontiguousarray(np.asarray(f).reshape(-1).astype(bool), dtype=np.uint8)
+            if a.shape != (V,):
+                raise ValueError("%s should have one entry per voxel" % name)
+            if a.any() and not on:
+                raise ValueError("voxels flagged %s need %s_on" % (name.upper(), name))
+        flags.append(a)
+    pk = None
+    if maxfasc > 0:
+        pk = L.f64c(peaks).reshape(V, -1)
+        if pk.shape != (V, 3 * maxfasc):
+            raise ValueError("peaks should have shape (%d, %d)" % (V, 3 * maxfasc))
+    sc = L.f64c(sig_csf).reshape(-1) if sig_csf is not None else None
+    se = L.f64c(sig_ear) if sig_ear is not None else None
+    if csf_on and (sc is None or sc.shape[0] != M):
+        raise ValueError("csf_on needs sig_csf with %d entries" % M)
+    if ear_on and (se is None or se.shape != (M, E) or E < 1):
+        raise ValueError("sig_ear should have shape (%d, E) with E >= 1" % M)
+    p0 = None
+    if params is not None:
+        p0 = L.f64c(params)
+        if p0.shape != (V, npar):
+            raise ValueError("params should have shape (%d, %d), got %s" % (V, npar, p0.shape))
+    vx = None
+    if vox is not None:
+        vx = np.ascontiguousarray(np.asarray(vox).reshape(-1), dtype=np.int64)
+        if vx.shape != (V,):
+            raise ValueError("vox should have one entry per voxel")
+    pr, nprop = None, 0
+    if props is not None:
+        pr = np.atleast_2d(L.f64c(props))
+        N = getattr(getattr(plan, 'tables', None), 'N', pr.shape[1])
+        if pr.ndim != 2 or pr.shape[1] != N:
+            raise ValueError("props should have shape (nprop, %d), got %s" % (N, pr.shape))
+        nprop = pr.shape[0]
+    gr = _boot_groups_arg(code, groups, M, getattr(plan, 'scheme', None))
+    cols = boot_columns(maxfasc, csf_on, ear_on, nprop)
+    stats = np.zeros((V, len(cols), BOOT_NSTAT + qa.size))
+    agree = np.zeros((V, maxfasc), dtype=np.int32)
+    status = np.zeros(V, dtype=np.int32)
+    reps = np.zeros((V, B, npar)) if keep else None
+    opt = lambda a, f: f(a) if a is not None else None
+    L.check(L.lib().mfx_boot_fit(plan.handle(), L.dptr(Y), L.iptr(K), opt(flags[0], L.bptr), opt(flags[1], L.bptr), opt(pk, L.dptr),
+                                 maxfasc, int(csf_on), int(ear_on), opt(sc, L.dptr) if csf_on else None,
+                                 opt(se, L.dptr) if ear_on else None, int(E), opt(p0, L.dptr), opt(gr, L.iptr), opt(vx, L.lptr), V, B,
+                                 code, int(bool(inflate)), int(seed) & _U64, int(offset) & _U64, opt(pr, L.dptr), nprop,
+                                 L.dptr(qa) if qa.size else None, int(qa.size), int(max_bytes), L.dptr(stats),
+                                 L.iptr(agree) if maxfasc > 0 else None, L.iptr(status), opt(reps, L.dptr)))
+    if V:
+        L.check(L.lib().mfx_plan_status(plan.handle(), None))   # a direction that is not a unit vector: ValueError
+    return {'stats': stats, 'agree': agree, 'status': status, 'replicates': reps, 'columns': cols}
 
 
 def cleanup_select(f1, f2, p1, p2, cos_min, ratio, w_keep, w_small, device=0):

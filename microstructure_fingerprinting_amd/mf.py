@@ -838,6 +838,47 @@ class MFModelFit():
             return m.reshape(self._grid + (nf,))
         return to_map(mean), to_map(std)
 
+    def bootstrap(self, data, B=200, *, kind='wild', seed=0, inflate=True, q=(0.025, 0.975), voxels=None, keep=False,
+                  groups=None):
+        """Model-free uncertainty of every estimated parameter: the residuals of each voxel's own fit are resampled
+        into ``B`` replicate signals, every replicate is fitted by the plain fit, and the B parameter rows of a voxel
+        are reduced to statistics, all on the device (``engine.fit_bootstrap``; include/mfx_boot.h states the rule).
+        ``data`` as given to ``fit``.  ``kind`` 'wild' flips the sign of every residual at random; 'residual' draws, for
+        every measurement, a residual of its group - ``groups`` [M] integers, default: rows sharing (G, Delta, delta).
+        ``inflate`` scales the residuals by sqrt(M / (M - number of active compartments)).  ``q``: the quantiles kept.
+        ``voxels``: positions in the ROI (default: all of it); the random stream is keyed by the ROI position, so a
+        subset gives the replicates the whole ROI gives.  ``keep``: also return the replicate parameter rows.  Every
+        voxel class of the plain fit is served (CSF, EAR); a fit made with ``weights=`` or ``robust=`` is not.
+        Returns a ``BootstrapResult``."""
+        if self.weights_roi is not None or self.robust_info is not None:
+            raise NotImplementedError("bootstrap of a weighted or robust fit is not served")
+        B, _, qa = engine._boot_rule(B, kind, q, seed)
+        if self._model is None or self._pgse_scheme is None or self._numfasc_roi is None:
+            raise RuntimeError("this fit object was not made by MFModel.fit: it knows neither its model nor its protocol "
+                               "nor the voxels' classes")
+        sch = self._pgse_scheme
+        gr = engine._boot_groups_arg(engine.BOOT_KINDS[kind], groups, sch.shape[0], sch)
+        R = self._roi_flat.shape[0]
+        vox = np.arange(R) if voxels is None else np.asarray(voxels, dtype=np.int64).reshape(-1)
+        if vox.size and (vox.min() < 0 or vox.max() >= R):
+            raise ValueError("voxels should be positions in the ROI (0..%d)" % (R - 1))
+        data_arr, _ = _load_volume(data)
+        shape = self._grid + (sch.shape[0],)
+        if data_arr.shape != shape:
+            raise ValueError("data should have shape (%s), got (%s)" % (" ".join("%d" % x for x in shape),
+                                                                        " ".join("%d" % x for x in data_arr.shape)))
+        m = self._model
+        sig_csf, sig_ear, num_ear = m._extra_signals(sch, self._csf_on, self._ear_on)
+        plan = m.ms_interpolator.plan_for(sch)
+        names = list(self._props)
+        props = np.stack([self._props[n] for n in names]) if names else None
+        res = engine.fit_bootstrap(plan, self._data_rows(data_arr, self._roi_flat[vox]), self._numfasc_roi[vox],
+                                   self._csf_roi[vox], self._ear_roi[vox], self._peaks_roi[vox] if self._nf > 0 else None,
+                                   self._nf, self._csf_on, self._ear_on, sig_csf, sig_ear, num_ear, B=B, kind=kind, seed=seed,
+                                   inflate=inflate, q=qa, props=props, groups=gr,
+                                   params=np.ascontiguousarray(self.params_in_mask[vox]), vox=vox, keep=keep)
+        return BootstrapResult(res, names, qa, vox, self._roi_flat, self._grid, self._nf, self._csf_on, self._ear_on, B, seed)
+
     def write_nifti(self, output_basename, affine=None):
         """One NIfTI file per parameter map, ``<stem>_<param><ext>``; returns the file names (reference mf.py:1177-1229).
         ``output_basename`` may end in .nii.gz (kept), .nii or nothing (both give .nii); any other extension is refused."""
@@ -921,6 +962,75 @@ class Posterior(object):
             if self._n_pos is None:
                 return self.log_sum - self._K * np.log(N) - 0.5 * self._M * np.log(np.pi * self._T)
             return self.log_sum - self._K * np.log(N) - 0.5 * self._n_pos * np.log(np.pi * self._T) + 0.5 * self._sum_log_w
+
+
+class BootstrapResult(object):
+    """Result of ``MFModelFit.bootstrap``.  ``mean(name)``, ``std(name)``, ``quantile(name, q)`` and ``n_valid(name)`` give
+    volumes over the replicates of a voxel: ``name`` is a fascicle property of the dictionary (shape ``mask.shape +
+    (maxfasc,)``; a replicate counts for fascicle k only where its weight nu_k is positive - ``n_valid`` says how many
+    did), 'frac' (the fascicle weights, ``mask.shape + (maxfasc,)``), or 'M0', 'frac_csf', 'frac_ear', 'MSE'
+    (``mask.shape``); these count every replicate.  NaN (0 for ``n_valid``) outside the mask and outside ``voxels``.
+    ``agreement`` (``mask.shape + (maxfasc,)``): the share of replicates that chose the original fit's atom with a
+    positive weight; ``status`` (``mask.shape``, -1 outside): 0 fine, 1 no degree of freedom, 2 original row not
+    usable; ``B``, ``seed``, ``q``, ``voxels`` (the ROI positions bootstrapped); ``stats`` [n x C x (5 + Q)] with
+    ``columns``, the table the maps are cut from; ``replicates`` [n x B x num_params] with ``keep=True``, else None."""
+
+    def __init__(self, res, prop_names, q, voxels, roi_flat, grid, nf, csf_on, ear_on, B, seed):
+        self.stats, self.columns, self.replicates = res['stats'], res['columns'], res['replicates']
+        self.B, self.seed, self.q, self.voxels = int(B), seed, np.asarray(q, dtype=np.float64), voxels
+        self._names, self._flat, self._grid, self._nf = list(prop_names), roi_flat[voxels], tuple(grid), nf
+        self._csf_on, self._ear_on = csf_on, ear_on
+        self.agreement = self._to_map(res['agree'].astype(np.float64) / float(B), np.nan)
+        self.status = self._to_map(res['status'], -1)
+
+    def _to_map(self, vals, fill):
+        vals = np.asarray(vals)
+        m = np.full((int(np.prod(self._grid)),) + vals.shape[1:], fill, dtype=vals.dtype)
+        m[self._flat] = vals
+        return m.reshape(self._grid + vals.shape[1:])
+
+    def _cols(self, name):
+        """(column indices, per fascicle?) of a statistic's name."""
+        if name in self._names:
+            t = self._names.index(name)
+            return [self.columns.index(('prop', k, t)) for k in range(self._nf)], True
+        if name == 'frac':
+            return [self.columns.index('nu_%d' % k) for k in range(self._nf)], True
+        single = {'M0': 'M0', 'MSE': 'MSE'}
+        if self._csf_on:
+            single['frac_csf'] = 'nu_csf'
+        if self._ear_on:
+            single['frac_ear'] = 'nu_ear'
+        if name in single:
+            return [self.columns.index(single[name])], False
+        raise ValueError("unknown bootstrap statistic %s (have: %s)" % (name, ", ".join(self._names + ['frac'] + sorted(single))))
+
+    def _stat(self, name, i, fill=np.nan):
+        cols, per_fasc = self._cols(name)
+        vals = self.stats[:, cols, i] if per_fasc else self.stats[:, cols[0], i]
+        return self._to_map(vals, fill)
+
+    def n_valid(self, name):
+        return self._stat(name, 0, 0.0).astype(np.int64)
+
+    def mean(self, name):
+        return self._stat(name, 1)
+
+    def std(self, name):
+        return self._stat(name, 2)
+
+    def min(self, name):
+        return self._stat(name, 3)
+
+    def max(self, name):
+        return self._stat(name, 4)
+
+    def quantile(self, name, q):
+        """The quantile ``q`` - one of those the bootstrap was asked for (``self.q``) - by linear interpolation."""
+        hit = np.flatnonzero(self.q == float(q))
+        if hit.size == 0:
+            raise ValueError("quantile %r was not asked for (have: %s)" % (q, ", ".join("%g" % x for x in self.q)))
+        return self._stat(name, 5 + int(hit[0]))
 
 
 def _nifti_stem(output_basename):
