@@ -278,5 +278,14 @@ def bptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint8))
 
 
+def opt(a, ptr=dptr):
+    """The pointer of an optional array: ``ptr(a)``, or None (a null pointer) without one."""
+    return ptr(a) if a is not None else None
+
+
 def f64c(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def f64c_opt(a):
+    return np.ascontiguousarray(a, dtype=np.float64) if a is not None else None

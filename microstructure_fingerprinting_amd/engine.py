@@ -82,6 +82,103 @@ def num_params(maxfasc, csf_on, ear_on):
     return 1 + 2 * maxfasc + int(csf_on) + 2 * int(ear_on) + 2   # mf.py:381
 
 
+# ---- argument and marshalling plumbing shared by the entry points below (all of it runs before any device call)
+def _f64_cuda(*tensors):
+    """Asserts that every tensor given (None: an absent optional one) is a contiguous CUDA float64 tensor."""
+    import torch
+    for t in tensors:
+        assert t is None or (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous())
+
+
+def _out_like(out, shape, dev):
+    """The output tensor of a device entry point: ``out`` if the caller gave one, else a new one; asserted either way."""
+    import torch
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=dev)
+    assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == tuple(shape)
+    return out
+
+
+def _tptr(t):
+    """The device pointer of an optional tensor (None: a null pointer)."""
+    return t.data_ptr() if t is not None else None
+
+
+def _w_stride(M, V, w_shape):
+    """w_stride of measurement weights: M for [V, M], 0 for one [M] vector shared by the voxels."""
+    if tuple(w_shape) == (M,):
+        return 0
+    if tuple(w_shape) == (V, M):
+        return M
+    raise ValueError("weights should have shape (%d, %d) or (%d,), got %s (%d voxels)" % (V, M, M, tuple(w_shape), V))
+
+
+def _host_weights(M, V, W):
+    """Optional NumPy weights of a host entry point: (float64 array or None, w_stride)."""
+    if W is None:
+        return None, 0
+    W = L.f64c(W)
+    return W, _w_stride(M, V, W.shape)
+
+
+def _w_chunk(W, w_stride, ix):
+    """The weights of the voxels ``ix`` of a class: their rows of [V, M] weights, the shared [M] vector as it is."""
+    return np.ascontiguousarray(W[ix]) if W is not None and w_stride else W
+
+
+def _twin(name, h, Y, W, w_stride, *rest):
+    """One C call from one argument list: ``mfx_<name>(h, Y, *rest)``, or with weights its twin ``mfx_w<name>(h, Y, W,
+    w_stride, *rest)`` (include/mfx_wsoft.h, include/mfx_w2d.h).  Y and W are pointers, W None without weights."""
+    if W is None:
+        L.check(getattr(L.lib(), "mfx_" + name)(h, Y, *rest))
+    else:
+        L.check(getattr(L.lib(), "mfx_w" + name)(h, Y, W, w_stride, *rest))
+
+
+def _k_arg(V, maxfasc, K):
+    """Per-voxel fascicle counts as int32 [V], each in 0..maxfasc."""
+    K = np.ascontiguousarray(np.asarray(K).reshape(-1), dtype=np.int32)
+    if K.shape != (V,):
+        raise ValueError("K should have one entry per voxel")
+    if V and (K.min() < 0 or K.max() > maxfasc):
+        raise ValueError("K should lie in 0..maxfasc = %d" % maxfasc)
+    return K
+
+
+def _mixed_args(M, V, maxfasc, K, csf, csf_on, sig_csf, need_sig=False):
+    """The per-voxel arguments of a mixed-batch fit: (K int32 [V], csf uint8 [V] or None, sig_csf float64 [M] or None).
+    ``need_sig``: csf_on alone, without a flagged voxel, already asks for sig_csf (the robust fits predict with it)."""
+    K = _k_arg(V, maxfasc, K)
+    cs = None
+    if csf is not None:
+        cs = np.ascontiguousarray(np.asarray(csf).reshape(-1).astype(bool), dtype=np.uint8)
+        if cs.shape != (V,):
+            raise ValueError("csf should have one entry per voxel")
+    sc = L.f64c(sig_csf).reshape(-1) if sig_csf is not None else None
+    if cs is not None and np.any(cs) and (not csf_on or sc is None):
+        raise ValueError("voxels flagged CSF need csf_on and sig_csf")
+    if need_sig and csf_on and sc is None:
+        raise ValueError("csf_on needs sig_csf")
+    if sc is not None and sc.shape[0] != M:
+        raise ValueError("sig_csf has %d entries, protocol has %d" % (sc.shape[0], M))
+    return K, cs, sc
+
+
+def _batch_args(V, K, csf, ear, peaks, maxfasc, csf_on, ear_on, sig_csf, sig_ear):
+    """The per-voxel arguments of fit_batch and fit_batch_volume and their output: (K, csf, ear, peaks, out, sig_csf,
+    sig_ear)."""
+    K = np.ascontiguousarray(K, dtype=np.int32)
+    if K.shape[0] != V:
+        raise ValueError("K should have one entry per voxel")
+    csf_a = np.ascontiguousarray(csf, dtype=np.uint8) if csf is not None else np.zeros(V, np.uint8)
+    ear_a = np.ascontiguousarray(ear, dtype=np.uint8) if ear is not None else np.zeros(V, np.uint8)
+    pk = L.f64c(peaks).reshape(V, -1) if maxfasc > 0 else np.zeros((V, 3))
+    if maxfasc > 0 and pk.shape[1] != 3 * maxfasc:
+        raise ValueError("peaks should have %d columns" % (3 * maxfasc))
+    out = np.zeros((V, num_params(maxfasc, csf_on, ear_on)))
+    return K, csf_a, ear_a, pk, out, L.f64c_opt(sig_csf), L.f64c_opt(sig_ear)
+
+
 class FileOrderVolume(object):
     """A 4-D data volume in the layout NIfTI files (and nibabel's arrays) have: ``array`` is Fortran-contiguous with
     shape (..., M), i.e. one 3-D image per measurement, in one of the scalar types of ``NIFTI_CODES``; ``slope`` /
@@ -139,22 +236,11 @@ def fit_batch_volume(plan, vol, vox, K, csf, ear, peaks, maxfasc, csf_on, ear_on
     V = vox.shape[0]
     if V and (vox.min() < 0 or vox.max() >= nvox):
         raise ValueError("voxel indices out of range")
-    K = np.ascontiguousarray(K, dtype=np.int32)
-    if K.shape[0] != V:
-        raise ValueError("K should have one entry per voxel")
-    csf_a = np.ascontiguousarray(csf, dtype=np.uint8) if csf is not None else np.zeros(V, np.uint8)
-    ear_a = np.ascontiguousarray(ear, dtype=np.uint8) if ear is not None else np.zeros(V, np.uint8)
-    pk = L.f64c(peaks).reshape(V, -1) if maxfasc > 0 else np.zeros((V, 3))
-    if maxfasc > 0 and pk.shape[1] != 3 * maxfasc:
-        raise ValueError("peaks should have %d columns" % (3 * maxfasc))
-    out = np.zeros((V, num_params(maxfasc, csf_on, ear_on)))
-    sc = L.f64c(sig_csf) if sig_csf is not None else None
-    se = L.f64c(sig_ear) if sig_ear is not None else None
+    K, csf_a, ear_a, pk, out, sc, se = _batch_args(V, K, csf, ear, peaks, maxfasc, csf_on, ear_on, sig_csf, sig_ear)
     L.check(L.lib().mfx_fit_batch_volume(plan.handle(), a.ctypes.data, FileOrderVolume.NIFTI_CODES[a.dtype.str[1:]],
                                          vol.slope, vol.inter, nvox, L.lptr(vox), L.iptr(K), L.bptr(csf_a), L.bptr(ear_a),
-                                         L.dptr(pk), int(maxfasc), int(csf_on), int(ear_on),
-                                         L.dptr(sc) if sc is not None else None, L.dptr(se) if se is not None else None,
-                                         int(E), V, L.dptr(out)))
+                                         L.dptr(pk), int(maxfasc), int(csf_on), int(ear_on), L.opt(sc), L.opt(se), int(E), V,
+                                         L.dptr(out)))
     return out
 
 
@@ -176,21 +262,10 @@ def fit_batch(plan, Y, K, csf, ear, peaks, maxfasc, csf_on, ear_on, sig_csf=None
         V = Y.shape[0]
     if M != plan.M:
         raise ValueError("data has %d measurements, protocol has %d" % (M, plan.M))
-    K = np.ascontiguousarray(K, dtype=np.int32)
-    if K.shape[0] != V:
-        raise ValueError("K should have one entry per voxel")
-    csf_a = np.ascontiguousarray(csf, dtype=np.uint8) if csf is not None else np.zeros(V, np.uint8)
-    ear_a = np.ascontiguousarray(ear, dtype=np.uint8) if ear is not None else np.zeros(V, np.uint8)
-    pk = L.f64c(peaks).reshape(V, -1) if maxfasc > 0 else np.zeros((V, 3))
-    if maxfasc > 0 and pk.shape[1] != 3 * maxfasc:
-        raise ValueError("peaks should have %d columns" % (3 * maxfasc))
-    out = np.zeros((V, num_params(maxfasc, csf_on, ear_on)))
-    sc = L.f64c(sig_csf) if sig_csf is not None else None
-    se = L.f64c(sig_ear) if sig_ear is not None else None
-    L.check(L.lib().mfx_fit_batch_rows(plan.handle(), L.dptr(Y), L.lptr(rows) if rows is not None else None, L.iptr(K),
-                                       L.bptr(csf_a), L.bptr(ear_a), L.dptr(pk), int(maxfasc), int(csf_on), int(ear_on),
-                                       L.dptr(sc) if sc is not None else None, L.dptr(se) if se is not None else None,
-                                       int(E), V, L.dptr(out)))
+    K, csf_a, ear_a, pk, out, sc, se = _batch_args(V, K, csf, ear, peaks, maxfasc, csf_on, ear_on, sig_csf, sig_ear)
+    L.check(L.lib().mfx_fit_batch_rows(plan.handle(), L.dptr(Y), L.opt(rows, L.lptr), L.iptr(K), L.bptr(csf_a), L.bptr(ear_a),
+                                       L.dptr(pk), int(maxfasc), int(csf_on), int(ear_on), L.opt(sc), L.opt(se), int(E), V,
+                                       L.dptr(out)))
     return out
 
 
@@ -201,22 +276,20 @@ def fit_batch_dev(plan, d_Y, d_peaks, maxfasc, csf_on=False, ear_on=False, d_sig
     output tensor without waiting; ``check=True`` then waits and raises what the kernels flagged (a fascicle
     direction that is not a unit vector: the reference's per-voxel ValueError, mf_utils.py:1798-1802)."""
     import torch
-    assert d_Y.is_cuda and d_Y.dtype == torch.float64 and d_Y.is_contiguous()
+    _f64_cuda(d_Y)
     V = d_Y.shape[0]
     if d_Y.shape[1] != plan.M:
         raise ValueError("data has %d measurements, protocol has %d" % (d_Y.shape[1], plan.M))
     if maxfasc > 0:
-        assert d_peaks.is_cuda and d_peaks.dtype == torch.float64 and d_peaks.is_contiguous()
+        _f64_cuda(d_peaks)
         if tuple(d_peaks.shape) != (V, 3 * maxfasc):
             raise ValueError("peaks should have shape (%d, %d)" % (V, 3 * maxfasc))
     if out is None:
         out = torch.zeros((V, num_params(maxfasc, csf_on, ear_on)), dtype=torch.float64, device=d_Y.device)
     st = torch.cuda.current_stream(d_Y.device).cuda_stream
     L.check(L.lib().mfx_fit_batch_dev(plan.handle(), d_Y.data_ptr(), d_peaks.data_ptr() if maxfasc > 0 else None,
-                                      int(maxfasc), int(bool(csf_on)), int(bool(ear_on)),
-                                      d_sig_csf.data_ptr() if d_sig_csf is not None else None,
-                                      d_sig_ear.data_ptr() if d_sig_ear is not None else None, int(E), V,
-                                      out.data_ptr(), st))
+                                      int(maxfasc), int(bool(csf_on)), int(bool(ear_on)), _tptr(d_sig_csf), _tptr(d_sig_ear),
+                                      int(E), V, out.data_ptr(), st))
     if check:
         L.check(L.lib().mfx_plan_status(plan.handle(), st))
     return out
@@ -225,7 +298,7 @@ def fit_batch_dev(plan, d_Y, d_peaks, maxfasc, csf_on=False, ear_on=False, d_sig
 def rotate_columns_dev(plan, d_dirs, d_cols, normalise=False):
     """Device-resident single-atom rotation: torch CUDA tensors dirs [B,3] f64, cols [B] i32 -> [B,M] f64."""
     import torch
-    assert d_dirs.is_cuda and d_dirs.dtype == torch.float64 and d_dirs.is_contiguous()
+    _f64_cuda(d_dirs)
     cols = d_cols.to(torch.int32).contiguous()
     B = d_dirs.shape[0]
     out = torch.empty((B, plan.M), dtype=torch.float64, device=d_dirs.device)
@@ -303,10 +376,9 @@ def predict_dev(plan, d_params, d_peaks, maxfasc, csf_on=False, ear_on=False, d_
     Enqueues on torch's current stream; ``check=True`` then waits and raises the ValueError of a bad atom index or
     weight (that voxel's row is NaN) or of a direction that is not a unit vector."""
     import torch
-    assert d_params.is_cuda and d_params.dtype == torch.float64 and d_params.is_contiguous()
+    d_peaks, d_sig_csf, d_sig_ear = d_peaks if maxfasc > 0 else None, d_sig_csf if csf_on else None, d_sig_ear if ear_on else None
+    _f64_cuda(d_params, d_peaks, d_sig_csf, d_sig_ear, d_Y)
     dev = d_params.device
-    for t in (d_peaks if maxfasc > 0 else None, d_sig_csf if csf_on else None, d_sig_ear if ear_on else None, d_Y):
-        assert t is None or (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous())
     V = _predict_shapes(plan, d_params.shape, d_peaks.shape if maxfasc > 0 else None, maxfasc, csf_on, ear_on,
                         d_Y.shape if d_Y is not None else None, d_sig_csf.numel() if csf_on else None,
                         d_sig_ear.shape if ear_on else None, E)
@@ -318,19 +390,14 @@ def predict_dev(plan, d_params, d_peaks, maxfasc, csf_on=False, ear_on=False, d_
         d_sigma = (sigma_g.to(device=dev, dtype=torch.float64).contiguous() if torch.is_tensor(sigma_g)
                    else torch.full((1,), float(sigma_g), dtype=torch.float64, device=dev))
         mode = _sigma_mode(d_sigma.shape, d_sigma.numel(), V, M)
-    if out is None:
-        out = torch.empty((V, M), dtype=torch.float64, device=dev)
-    assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (V, M)
+    out = _out_like(out, (V, M), dev)
     stats = torch.empty((V, 2), dtype=torch.float64, device=dev) if d_Y is not None else None
     status = torch.zeros(2, dtype=torch.int32, device=dev)
     st = torch.cuda.current_stream(dev).cuda_stream
-    L.check(L.lib().mfx_predict_dev(plan.handle(), d_params.data_ptr(), d_peaks.data_ptr() if maxfasc > 0 else None,
-                                    int(maxfasc), int(bool(csf_on)), int(bool(ear_on)),
-                                    d_sig_csf.data_ptr() if csf_on else None, d_sig_ear.data_ptr() if ear_on else None,
-                                    int(E), V, d_Y.data_ptr() if d_Y is not None else None,
-                                    d_sigma.data_ptr() if d_sigma is not None else None, mode, int(ncoils),
-                                    int(seed) & _U64, int(offset) & _U64, out.data_ptr(),
-                                    stats.data_ptr() if stats is not None else None, status.data_ptr(), st))
+    L.check(L.lib().mfx_predict_dev(plan.handle(), d_params.data_ptr(), _tptr(d_peaks), int(maxfasc), int(bool(csf_on)),
+                                    int(bool(ear_on)), _tptr(d_sig_csf), _tptr(d_sig_ear), int(E), V, _tptr(d_Y),
+                                    _tptr(d_sigma), mode, int(ncoils), int(seed) & _U64, int(offset) & _U64, out.data_ptr(),
+                                    _tptr(stats), status.data_ptr(), st))
     if check:
         flag, vox = status.tolist()
         dir_err = None
@@ -355,7 +422,7 @@ def predict(plan, params, peaks, maxfasc, csf_on=False, ear_on=False, sig_csf=No
     pk = L.f64c(peaks) if maxfasc > 0 else None
     sc = L.f64c(sig_csf).reshape(-1) if csf_on else None
     se = L.f64c(sig_ear) if ear_on else None
-    Yc = L.f64c(Y) if Y is not None else None
+    Yc = L.f64c_opt(Y)
     V = _predict_shapes(plan, params.shape, pk.shape if pk is not None else None, maxfasc, csf_on, ear_on,
                         Yc.shape if Yc is not None else None, sc.shape[0] if sc is not None else None,
                         se.shape if se is not None else None, E)
@@ -368,12 +435,9 @@ def predict(plan, params, peaks, maxfasc, csf_on=False, ear_on=False, sig_csf=No
         mode = _sigma_mode(sg.shape, sg.size, V, M)
     out = np.zeros((V, M))
     stats = np.zeros((V, 2)) if Yc is not None else None
-    L.check(L.lib().mfx_predict(plan.handle(), L.dptr(params), L.dptr(pk) if pk is not None else None, int(maxfasc),
-                                int(bool(csf_on)), int(bool(ear_on)), L.dptr(sc) if sc is not None else None,
-                                L.dptr(se) if se is not None else None, int(E), V,
-                                L.dptr(Yc) if Yc is not None else None, L.dptr(sg) if sg is not None else None, mode,
-                                int(ncoils), int(seed) & _U64, int(offset) & _U64, L.dptr(out),
-                                L.dptr(stats) if stats is not None else None))
+    L.check(L.lib().mfx_predict(plan.handle(), L.dptr(params), L.opt(pk), int(maxfasc), int(bool(csf_on)), int(bool(ear_on)),
+                                L.opt(sc), L.opt(se), int(E), V, L.opt(Yc), L.opt(sg), mode, int(ncoils), int(seed) & _U64,
+                                int(offset) & _U64, L.dptr(out), L.opt(stats)))
     return out if stats is None else (out, stats)
 
 
@@ -384,7 +448,7 @@ def sos_noise_dev(d_S0, sigma_g, ncoils=1, seed=0, offset=0, out=None):
     counter ``offset + i`` of the Philox stream keyed by ``seed``: splitting an array into calls with matching
     offsets gives the same values.  Enqueues on torch's current stream; ``out`` may be ``d_S0`` itself."""
     import torch
-    assert d_S0.is_cuda and d_S0.dtype == torch.float64 and d_S0.is_contiguous()
+    _f64_cuda(d_S0)
     dev = d_S0.device
     d_sigma = (sigma_g.to(device=dev, dtype=torch.float64).contiguous() if torch.is_tensor(sigma_g)
                else torch.full((1,), float(sigma_g), dtype=torch.float64, device=dev))
@@ -393,9 +457,7 @@ def sos_noise_dev(d_S0, sigma_g, ncoils=1, seed=0, offset=0, out=None):
                          % (tuple(d_S0.shape), tuple(d_sigma.shape)))
     if int(ncoils) < 1:
         raise ValueError("ncoils should be at least 1")
-    if out is None:
-        out = torch.empty_like(d_S0)
-    assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.shape == d_S0.shape
+    out = _out_like(out, d_S0.shape, dev)
     st = torch.cuda.current_stream(dev).cuda_stream
     L.check(L.lib().mfx_sos_noise_dev(d_S0.data_ptr(), d_S0.numel(), d_sigma.data_ptr(),
                                       SIGMA_SCALAR if d_sigma.numel() == 1 else SIGMA_ELEMENT, int(ncoils),
@@ -416,31 +478,40 @@ def sos_noise(S0, sigma_g, ncoils=1, seed=0, offset=0, device=0):
     return out
 
 
-def _profile_shapes(plan, y_shape, pk_shape, K, csf_on, M_csf):
-    """Argument checks shared by the profile entry points (before any device call); returns V."""
+_PROFILE_SCOPE, _SOFT2D_SCOPE = "objective profiles", "soft fits and profiles of 2-D protocols"
+
+
+def _soft_shapes(what, M, y_shape, pk_shape, K, csf_on=False, M_csf=None):
+    """Argument checks shared by the profile, posterior and pair-objective entry points (``what`` _PROFILE_SCOPE) and their
+    2-D protocol forms (_SOFT2D_SCOPE, which have no CSF column), before any device call; returns V."""
     K = int(K)
     if K not in (1, 2):
-        raise NotImplementedError("objective profiles serve K = 1 or 2 fascicles (got %d): three fascicles and voxels "
-                                  "without one are out of scope" % K)
-    if len(y_shape) != 2 or y_shape[1] != plan.M:
-        raise ValueError("data has shape %s, protocol has %d measurements" % (tuple(y_shape), plan.M))
+        raise NotImplementedError("%s serve K = 1 or 2 fascicles (got %d): three fascicles and voxels without one are out "
+                                  "of scope" % (what, K))
+    if len(y_shape) != 2 or y_shape[1] != M:
+        raise ValueError("data has shape %s, protocol has %d measurements" % (tuple(y_shape), M))
     V = y_shape[0]
     if pk_shape is None or tuple(pk_shape) != (V, 3 * K):
         raise ValueError("peaks should have shape (%d, %d)" % (V, 3 * K))
-    if csf_on and M_csf != plan.M:
-        raise ValueError("sig_csf has %s entries, protocol has %d" % (M_csf, plan.M))
+    if csf_on and M_csf != M:
+        raise ValueError("sig_csf has %s entries, protocol has %d" % (M_csf, M))
     return V
 
 
-def _soft_weights(plan, V, w_shape):
-    """w_stride of measurement weights given to a profile or posterior entry point (before any device call): M for
-    [V x M], 0 for one [M] vector shared by the voxels."""
-    if tuple(w_shape) == (plan.M,):
-        return 0
-    if tuple(w_shape) == (V, plan.M):
-        return plan.M
-    raise ValueError("weights should have shape (%d, %d) or (%d,), got %s (%d voxels)"
-                     % (V, plan.M, plan.M, tuple(w_shape), V))
+def _soft_dev_args(what, M, d_Y, d_peaks, K, d_W, csf_on=False, d_sig_csf=None, T_shift=()):
+    """Argument checks of the device forms of those entry points, shapes first and the tensors' kind last; ``T_shift``
+    the posteriors' (T, shift).  Returns (V, w_stride, the pointer of sig_csf: None without a CSF column)."""
+    import torch
+    if csf_on and d_sig_csf is None:
+        raise ValueError("csf_on without d_sig_csf")
+    d_sig_csf = d_sig_csf if csf_on else None
+    V = _soft_shapes(what, M, d_Y.shape, d_peaks.shape, K, csf_on, d_sig_csf.numel() if csf_on else None)
+    for t, name in zip(T_shift, ("T", "shift")):
+        if not torch.is_tensor(t) or tuple(t.shape) != (V,):
+            raise ValueError("%s should be a tensor with one entry per voxel (%d)" % (name, V))
+    w_stride = _w_stride(M, V, d_W.shape) if d_W is not None else None
+    _f64_cuda(d_Y, d_peaks, *T_shift, d_sig_csf, d_W)
+    return V, w_stride, _tptr(d_sig_csf)
 
 
 def profile_dev(plan, d_Y, d_peaks, K, csf_on=False, d_sig_csf=None, partner=False, out=None, d_W=None):
@@ -453,26 +524,13 @@ def profile_dev(plan, d_Y, d_peaks, K, csf_on=False, d_sig_csf=None, partner=Fal
     sum_m W (y_m - model_m)^2; a voxel whose weights are unusable (one negative or not finite, none positive) gets NaN
     values and partner -1."""
     import torch
-    if csf_on and d_sig_csf is None:
-        raise ValueError("csf_on without d_sig_csf")
-    V = _profile_shapes(plan, d_Y.shape, d_peaks.shape, K, csf_on, d_sig_csf.numel() if csf_on else None)
-    w_stride = _soft_weights(plan, V, d_W.shape) if d_W is not None else None
-    for t in (d_Y, d_peaks) + ((d_sig_csf,) if csf_on else ()) + ((d_W,) if d_W is not None else ()):
-        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+    V, w_stride, sc = _soft_dev_args(_PROFILE_SCOPE, plan.M, d_Y, d_peaks, K, d_W, csf_on, d_sig_csf)
     N = plan.tables.N
-    if out is None:
-        out = torch.empty((V, int(K), N), dtype=torch.float64, device=d_Y.device)
-    assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (V, int(K), N)
+    out = _out_like(out, (V, int(K), N), d_Y.device)
     part = torch.empty((V, int(K), N), dtype=torch.int32, device=d_Y.device) if partner else None
     st = torch.cuda.current_stream(d_Y.device).cuda_stream
-    if d_W is None:
-        L.check(L.lib().mfx_profile_dev(plan.handle(), d_Y.data_ptr(), d_peaks.data_ptr(), int(K), int(bool(csf_on)),
-                                        d_sig_csf.data_ptr() if csf_on else None, V, out.data_ptr(),
-                                        part.data_ptr() if partner else None, st))
-    else:
-        L.check(L.lib().mfx_wprofile_dev(plan.handle(), d_Y.data_ptr(), d_W.data_ptr(), w_stride, d_peaks.data_ptr(), int(K),
-                                         int(bool(csf_on)), d_sig_csf.data_ptr() if csf_on else None, V, out.data_ptr(),
-                                         part.data_ptr() if partner else None, st))
+    _twin("profile_dev", plan.handle(), d_Y.data_ptr(), _tptr(d_W), w_stride, d_peaks.data_ptr(), int(K), int(bool(csf_on)), sc,
+          V, out.data_ptr(), _tptr(part), st)
     return (out, part) if partner else out
 
 
@@ -480,22 +538,12 @@ def pair_objectives_dev(plan, d_Y, d_peaks, csf_on=False, d_sig_csf=None, d_W=No
     """The objective of every atom pair (mfx_pair_objectives_dev): [V x N x N] torch tensor, two-fascicle voxels.
     ``d_W``: measurement weights [V x M] or [M] (mfx_wpair_objectives_dev)."""
     import torch
-    if csf_on and d_sig_csf is None:
-        raise ValueError("csf_on without d_sig_csf")
-    V = _profile_shapes(plan, d_Y.shape, d_peaks.shape, 2, csf_on, d_sig_csf.numel() if csf_on else None)
-    w_stride = _soft_weights(plan, V, d_W.shape) if d_W is not None else None
-    for t in (d_Y, d_peaks) + ((d_sig_csf,) if csf_on else ()) + ((d_W,) if d_W is not None else ()):
-        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+    V, w_stride, sc = _soft_dev_args(_PROFILE_SCOPE, plan.M, d_Y, d_peaks, 2, d_W, csf_on, d_sig_csf)
     N = plan.tables.N
     out = torch.empty((V, N, N), dtype=torch.float64, device=d_Y.device)
     st = torch.cuda.current_stream(d_Y.device).cuda_stream
-    if d_W is None:
-        L.check(L.lib().mfx_pair_objectives_dev(plan.handle(), d_Y.data_ptr(), d_peaks.data_ptr(), int(bool(csf_on)),
-                                                d_sig_csf.data_ptr() if csf_on else None, V, out.data_ptr(), st))
-    else:
-        L.check(L.lib().mfx_wpair_objectives_dev(plan.handle(), d_Y.data_ptr(), d_W.data_ptr(), w_stride, d_peaks.data_ptr(),
-                                                 int(bool(csf_on)), d_sig_csf.data_ptr() if csf_on else None, V,
-                                                 out.data_ptr(), st))
+    _twin("pair_objectives_dev", plan.handle(), d_Y.data_ptr(), _tptr(d_W), w_stride, d_peaks.data_ptr(), int(bool(csf_on)), sc,
+          V, out.data_ptr(), st)
     return out
 
 
@@ -520,14 +568,9 @@ def profile_classes(K, csf, ear, maxfasc):
     return bins, int(V - np.count_nonzero(ok))
 
 
-def profile(plan, Y, K, csf, peaks, maxfasc, csf_on, sig_csf, partner=False, ear=None, W=None):
-    """Objective profiles of a mixed set of voxels on NumPy arrays (mfx_profile, one call per voxel class): Y [V x M],
-    per-voxel K, csf (and ear) flags, peaks [V x 3 maxfasc] as for ``fit_batch``.  Returns ``(obj, partner,
-    n_unsupported)``: obj [V x maxfasc x N] float64 (rows of absent fascicles and of the voxel classes out of scope -
-    EAR, no fascicle, three fascicles - are NaN), partner [V x maxfasc x N] int32 (-1 where there is none) or None,
-    and the number of voxels out of scope.  ``W``: measurement weights [V x M] or [M] of a weighted fit (mfx_wprofile):
-    the profile of sum_m W (y_m - model_m)^2, whose minimum is ``fit_weighted``'s MSE * sum_m W; a voxel whose weights are
-    unusable (one negative or not finite, none positive) gets NaN values and partner -1."""
+def _soft_host_args(plan, Y, K, csf, peaks, maxfasc, csf_on, sig_csf, W):
+    """Argument checks of ``profile`` and ``posterior`` (before any device call): (Y, V, maxfasc, W, w_stride, peaks
+    [V x 3 maxfasc], sig_csf).  The voxel classes are binned by the caller (``profile_classes`` checks K and the flags)."""
     Y = L.f64c(Y)
     maxfasc = int(maxfasc)
     if Y.ndim != 2 or Y.shape[1] != plan.M:
@@ -535,9 +578,7 @@ def profile(plan, Y, K, csf, peaks, maxfasc, csf_on, sig_csf, partner=False, ear
     V = Y.shape[0]
     if np.asarray(K).shape != (V,):
         raise ValueError("K should have one entry per voxel")
-    if W is not None:
-        W = L.f64c(W)
-        w_stride = _soft_weights(plan, V, W.shape)
+    W, w_stride = _host_weights(plan.M, V, W)
     pk = L.f64c(peaks).reshape(V, -1) if maxfasc > 0 else np.zeros((V, 0))
     if pk.shape[1] != 3 * maxfasc:
         raise ValueError("peaks should have %d columns" % (3 * maxfasc))
@@ -546,6 +587,18 @@ def profile(plan, Y, K, csf, peaks, maxfasc, csf_on, sig_csf, partner=False, ear
         raise ValueError("voxels flagged CSF need csf_on and sig_csf")
     if sc is not None and sc.shape[0] != plan.M:
         raise ValueError("sig_csf has %d entries, protocol has %d" % (sc.shape[0], plan.M))
+    return Y, V, maxfasc, W, w_stride, pk, sc
+
+
+def profile(plan, Y, K, csf, peaks, maxfasc, csf_on, sig_csf, partner=False, ear=None, W=None):
+    """Objective profiles of a mixed set of voxels on NumPy arrays (mfx_profile, one call per voxel class): Y [V x M],
+    per-voxel K, csf (and ear) flags, peaks [V x 3 maxfasc] as for ``fit_batch``.  Returns ``(obj, partner,
+    n_unsupported)``: obj [V x maxfasc x N] float64 (rows of absent fascicles and of the voxel classes out of scope -
+    EAR, no fascicle, three fascicles - are NaN), partner [V x maxfasc x N] int32 (-1 where there is none) or None,
+    and the number of voxels out of scope.  ``W``: measurement weights [V x M] or [M] of a weighted fit (mfx_wprofile):
+    the profile of sum_m W (y_m - model_m)^2, whose minimum is ``fit_weighted``'s MSE * sum_m W; a voxel whose weights are
+    unusable (one negative or not finite, none positive) gets NaN values and partner -1."""
+    Y, V, maxfasc, W, w_stride, pk, sc = _soft_host_args(plan, Y, K, csf, peaks, maxfasc, csf_on, sig_csf, W)
     bins, n_uns = profile_classes(K, csf, ear, maxfasc)
     N = plan.tables.N
     obj = np.full((V, maxfasc, N), np.nan)
@@ -554,13 +607,9 @@ def profile(plan, Y, K, csf, peaks, maxfasc, csf_on, sig_csf, partner=False, ear
         Yc, pc = np.ascontiguousarray(Y[ix]), np.ascontiguousarray(pk[ix, :3 * k])
         o = np.zeros((ix.size, k, N))
         p = np.zeros((ix.size, k, N), dtype=np.int32) if partner else None
-        if W is None:
-            L.check(L.lib().mfx_profile(plan.handle(), L.dptr(Yc), L.dptr(pc), k, int(c), L.dptr(sc) if c else None, ix.size,
-                                        L.dptr(o), L.iptr(p) if partner else None))
-        else:
-            Wc = np.ascontiguousarray(W[ix]) if w_stride else W
-            L.check(L.lib().mfx_wprofile(plan.handle(), L.dptr(Yc), L.dptr(Wc), w_stride, L.dptr(pc), k, int(c),
-                                         L.dptr(sc) if c else None, ix.size, L.dptr(o), L.iptr(p) if partner else None))
+        Wc = _w_chunk(W, w_stride, ix)
+        _twin("profile", plan.handle(), L.dptr(Yc), L.opt(Wc), w_stride, L.dptr(pc), k, int(c), L.dptr(sc) if c else None,
+              ix.size, L.dptr(o), L.opt(p, L.iptr))
         obj[ix, :k] = o
         if partner:
             par[ix, :k] = p
@@ -576,18 +625,12 @@ def pair_objectives(plan, Y, peaks, csf_on=False, sig_csf=None, W=None):
     sc = L.f64c(sig_csf).reshape(-1) if csf_on else None
     if csf_on and sig_csf is None:
         raise ValueError("csf_on without sig_csf")
-    V = _profile_shapes(plan, Y.shape, pk.shape, 2, csf_on, sc.shape[0] if sc is not None else None)
-    if W is not None:
-        W = L.f64c(W)
-        w_stride = _soft_weights(plan, V, W.shape)
+    V = _soft_shapes(_PROFILE_SCOPE, plan.M, Y.shape, pk.shape, 2, csf_on, sc.shape[0] if sc is not None else None)
+    W, w_stride = _host_weights(plan.M, V, W)
     N = plan.tables.N
     out = np.zeros((V, N, N))
-    if W is None:
-        L.check(L.lib().mfx_pair_objectives(plan.handle(), L.dptr(Y), L.dptr(pk), int(bool(csf_on)),
-                                            L.dptr(sc) if sc is not None else None, V, L.dptr(out)))
-    else:
-        L.check(L.lib().mfx_wpair_objectives(plan.handle(), L.dptr(Y), L.dptr(W), w_stride, L.dptr(pk), int(bool(csf_on)),
-                                             L.dptr(sc) if sc is not None else None, V, L.dptr(out)))
+    _twin("pair_objectives", plan.handle(), L.dptr(Y), L.opt(W), w_stride, L.dptr(pk), int(bool(csf_on)), L.opt(sc), V,
+          L.dptr(out))
     return out
 
 
@@ -611,28 +654,14 @@ def posterior_dev(plan, d_Y, d_peaks, K, T, shift, csf_on=False, d_sig_csf=None,
     weighted fit (mfx_wpost_dev, include/mfx_wsoft.h): F is the weighted sum of squares and T = 2 sigma^2 means that
     measurement m has noise variance sigma^2 / W_m; status 3: a weight is negative or not finite, 4: none is positive."""
     import torch
-    if csf_on and d_sig_csf is None:
-        raise ValueError("csf_on without d_sig_csf")
-    V = _profile_shapes(plan, d_Y.shape, d_peaks.shape, K, csf_on, d_sig_csf.numel() if csf_on else None)
-    for t, what in ((T, "T"), (shift, "shift")):
-        if not torch.is_tensor(t) or tuple(t.shape) != (V,):
-            raise ValueError("%s should be a tensor with one entry per voxel (%d)" % (what, V))
-    w_stride = _soft_weights(plan, V, d_W.shape) if d_W is not None else None
-    for t in (d_Y, d_peaks, T, shift) + ((d_sig_csf,) if csf_on else ()) + ((d_W,) if d_W is not None else ()):
-        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+    V, w_stride, sc = _soft_dev_args(_PROFILE_SCOPE, plan.M, d_Y, d_peaks, K, d_W, csf_on, d_sig_csf, (T, shift))
     N = plan.tables.N
     w = torch.empty((V, int(K), N), dtype=torch.float64, device=d_Y.device)
     log_sum = torch.empty((V,), dtype=torch.float64, device=d_Y.device)
     status = torch.empty((V,), dtype=torch.int32, device=d_Y.device)
     st = torch.cuda.current_stream(d_Y.device).cuda_stream
-    if d_W is None:
-        L.check(L.lib().mfx_post_dev(plan.handle(), d_Y.data_ptr(), d_peaks.data_ptr(), int(K), int(bool(csf_on)),
-                                     d_sig_csf.data_ptr() if csf_on else None, T.data_ptr(), shift.data_ptr(), V, w.data_ptr(),
-                                     log_sum.data_ptr(), status.data_ptr(), st))
-    else:
-        L.check(L.lib().mfx_wpost_dev(plan.handle(), d_Y.data_ptr(), d_W.data_ptr(), w_stride, d_peaks.data_ptr(), int(K),
-                                      int(bool(csf_on)), d_sig_csf.data_ptr() if csf_on else None, T.data_ptr(),
-                                      shift.data_ptr(), V, w.data_ptr(), log_sum.data_ptr(), status.data_ptr(), st))
+    _twin("post_dev", plan.handle(), d_Y.data_ptr(), _tptr(d_W), w_stride, d_peaks.data_ptr(), int(K), int(bool(csf_on)), sc,
+          T.data_ptr(), shift.data_ptr(), V, w.data_ptr(), log_sum.data_ptr(), status.data_ptr(), st)
     return w, log_sum, status
 
 
@@ -646,24 +675,7 @@ def posterior(plan, Y, K, csf, peaks, maxfasc, csf_on, sig_csf, sigma, shift=Non
     status are NaN.  ``W``: measurement weights [V x M] or [M] of a weighted fit (mfx_wpost): F is the weighted sum of
     squares, ``sigma`` the noise of a measurement of weight 1 (measurement m has variance sigma^2 / W_m), the default
     shift ``fit_weighted``'s objective MSE * sum_m W; status 3: a weight is negative or not finite, 4: none is positive."""
-    Y = L.f64c(Y)
-    maxfasc = int(maxfasc)
-    if Y.ndim != 2 or Y.shape[1] != plan.M:
-        raise ValueError("data has shape %s, protocol has %d measurements" % (Y.shape, plan.M))
-    V = Y.shape[0]
-    if np.asarray(K).shape != (V,):
-        raise ValueError("K should have one entry per voxel")
-    if W is not None:
-        W = L.f64c(W)
-        w_stride = _soft_weights(plan, V, W.shape)
-    pk = L.f64c(peaks).reshape(V, -1) if maxfasc > 0 else np.zeros((V, 0))
-    if pk.shape[1] != 3 * maxfasc:
-        raise ValueError("peaks should have %d columns" % (3 * maxfasc))
-    sc = L.f64c(sig_csf).reshape(-1) if sig_csf is not None else None
-    if np.any(csf) and (not csf_on or sc is None):
-        raise ValueError("voxels flagged CSF need csf_on and sig_csf")
-    if sc is not None and sc.shape[0] != plan.M:
-        raise ValueError("sig_csf has %d entries, protocol has %d" % (sc.shape[0], plan.M))
+    Y, V, maxfasc, W, w_stride, pk, sc = _soft_host_args(plan, Y, K, csf, peaks, maxfasc, csf_on, sig_csf, W)
     sig = _per_voxel(sigma, V, "sigma")
     sh = _per_voxel(shift, V, "shift") if shift is not None else None
     bins, n_uns = profile_classes(K, csf, ear, maxfasc)
@@ -672,9 +684,7 @@ def posterior(plan, Y, K, csf, peaks, maxfasc, csf_on, sig_csf, sigma, shift=Non
     log_sum = np.full(V, np.nan)
     status = np.full(V, -1, dtype=np.int32)
     for k, c, ix in bins:
-        Yc, pc = np.ascontiguousarray(Y[ix]), np.ascontiguousarray(pk[ix, :3 * k])
-        if W is not None:
-            Wc = np.ascontiguousarray(W[ix]) if w_stride else W
+        Yc, pc, Wc = np.ascontiguousarray(Y[ix]), np.ascontiguousarray(pk[ix, :3 * k]), _w_chunk(W, w_stride, ix)
         if sh is not None:
             shc = np.ascontiguousarray(sh[ix])
         elif W is None:
@@ -688,13 +698,8 @@ def posterior(plan, Y, K, csf, peaks, maxfasc, csf_on, sig_csf, sigma, shift=Non
             shc[fst != 0] = 0.0
         Tc = np.ascontiguousarray(2.0 * sig[ix] ** 2)
         wc, lc, stc = np.zeros((ix.size, k, N)), np.zeros(ix.size), np.zeros(ix.size, dtype=np.int32)
-        if W is None:
-            L.check(L.lib().mfx_post(plan.handle(), L.dptr(Yc), L.dptr(pc), k, int(c), L.dptr(sc) if c else None, L.dptr(Tc),
-                                     L.dptr(shc), ix.size, L.dptr(wc), L.dptr(lc), L.iptr(stc)))
-        else:
-            L.check(L.lib().mfx_wpost(plan.handle(), L.dptr(Yc), L.dptr(Wc), w_stride, L.dptr(pc), k, int(c),
-                                      L.dptr(sc) if c else None, L.dptr(Tc), L.dptr(shc), ix.size, L.dptr(wc), L.dptr(lc),
-                                      L.iptr(stc)))
+        _twin("post", plan.handle(), L.dptr(Yc), L.opt(Wc), w_stride, L.dptr(pc), k, int(c), L.dptr(sc) if c else None,
+              L.dptr(Tc), L.dptr(shc), ix.size, L.dptr(wc), L.dptr(lc), L.iptr(stc))
         w[ix, :k], log_sum[ix], status[ix] = wc, lc, stc
     return w, log_sum, status, n_uns
 
@@ -706,7 +711,7 @@ def rotate2d_dev(tables, d_dirs, d_cols=None):
     host synchronisation.  A failing direction's output is NaN; ``tables.raise_for_status(status.cpu())``
     raises the reference's exception for the first one."""
     import torch
-    assert d_dirs.is_cuda and d_dirs.dtype == torch.float64 and d_dirs.is_contiguous()
+    _f64_cuda(d_dirs)
     B = d_dirs.shape[0]
     h = tables.handle()
     st = torch.cuda.current_stream(d_dirs.device).cuda_stream
@@ -743,13 +748,9 @@ def fit2d_dev(tables, d_Y, d_peaks, maxfasc, out=None):
     Enqueues on torch's current stream and returns without waiting; a voxel with a failing direction has a NaN row."""
     import torch
     maxfasc = int(maxfasc)
-    assert d_Y.is_cuda and d_Y.dtype == torch.float64 and d_Y.is_contiguous()
-    assert d_peaks.is_cuda and d_peaks.dtype == torch.float64 and d_peaks.is_contiguous()
+    _f64_cuda(d_Y, d_peaks)
     V = _fit2d_shapes(tables, d_Y.shape, d_peaks.shape, maxfasc)
-    npar = num_params(maxfasc, False, False)
-    if out is None:
-        out = torch.empty((V, npar), dtype=torch.float64, device=d_Y.device)
-    assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (V, npar)
+    out = _out_like(out, (V, num_params(maxfasc, False, False)), d_Y.device)
     status = torch.empty((V, 5), dtype=torch.int32, device=d_Y.device)
     st = torch.cuda.current_stream(d_Y.device).cuda_stream
     L.check(L.lib().mfx_fit2d_batch_dev(tables.handle(), d_Y.data_ptr(), d_peaks.data_ptr(), maxfasc, V, out.data_ptr(),
@@ -765,38 +766,12 @@ def fit2d(tables, Y, K, csf, peaks, maxfasc, csf_on, sig_csf=None):
     maxfasc = int(maxfasc)
     pk = L.f64c(peaks).reshape(Y.shape[0], -1) if (maxfasc > 0 and Y.ndim == 2) else np.zeros((Y.shape[0], 0))
     V = _fit2d_shapes(tables, Y.shape, pk.shape, maxfasc)
-    K = np.ascontiguousarray(np.asarray(K).reshape(-1), dtype=np.int32)
-    if K.shape != (V,):
-        raise ValueError("K should have one entry per voxel")
-    if V and (K.min() < 0 or K.max() > maxfasc):
-        raise ValueError("K should lie in 0..maxfasc = %d" % maxfasc)
-    cs = None
-    if csf is not None:
-        cs = np.ascontiguousarray(np.asarray(csf).reshape(-1).astype(bool), dtype=np.uint8)
-        if cs.shape != (V,):
-            raise ValueError("csf should have one entry per voxel")
-    sc = L.f64c(sig_csf).reshape(-1) if sig_csf is not None else None
-    if cs is not None and np.any(cs) and (not csf_on or sc is None):
-        raise ValueError("voxels flagged CSF need csf_on and sig_csf")
-    if sc is not None and sc.shape[0] != tables.M:
-        raise ValueError("sig_csf has %d entries, protocol has %d" % (sc.shape[0], tables.M))
+    K, cs, sc = _mixed_args(tables.M, V, maxfasc, K, csf, csf_on, sig_csf)
     params = np.zeros((V, num_params(maxfasc, bool(csf_on), False)))
     status = np.zeros((V, 5), dtype=np.int32)
-    L.check(L.lib().mfx_fit2d_batch(tables.handle(), L.dptr(Y), L.iptr(K), L.bptr(cs) if cs is not None else None,
-                                    L.dptr(pk) if maxfasc > 0 else None, maxfasc, int(bool(csf_on)),
-                                    L.dptr(sc) if sc is not None else None, V, L.dptr(params), L.iptr(status)))
+    L.check(L.lib().mfx_fit2d_batch(tables.handle(), L.dptr(Y), L.iptr(K), L.opt(cs, L.bptr), L.dptr(pk) if maxfasc > 0 else None,
+                                    maxfasc, int(bool(csf_on)), L.opt(sc), V, L.dptr(params), L.iptr(status)))
     return params, status
-
-
-def _w2d_stride(tables, V, w_shape):
-    """w_stride of measurement weights given to an entry point of include/mfx_w2d.h (before any device call): M for
-    [V, M], 0 for one [M] vector shared by the voxels."""
-    if tuple(w_shape) == (tables.M,):
-        return 0
-    if tuple(w_shape) == (V, tables.M):
-        return tables.M
-    raise ValueError("weights should have shape (%d, %d) or (%d,), got %s (%d voxels)"
-                     % (V, tables.M, tables.M, tuple(w_shape), V))
 
 
 def fit2d_weighted_dev(tables, d_Y, d_W, d_peaks, maxfasc, out=None):
@@ -808,13 +783,9 @@ def fit2d_weighted_dev(tables, d_Y, d_W, d_peaks, maxfasc, out=None):
     import torch
     maxfasc = int(maxfasc)
     V = _fit2d_shapes(tables, d_Y.shape, d_peaks.shape, maxfasc)
-    w_stride = _w2d_stride(tables, V, d_W.shape)
-    for t in (d_Y, d_W, d_peaks):
-        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
-    npar = num_params(maxfasc, False, False)
-    if out is None:
-        out = torch.empty((V, npar), dtype=torch.float64, device=d_Y.device)
-    assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (V, npar)
+    w_stride = _w_stride(tables.M, V, d_W.shape)
+    _f64_cuda(d_Y, d_W, d_peaks)
+    out = _out_like(out, (V, num_params(maxfasc, False, False)), d_Y.device)
     status = torch.empty((V, 5), dtype=torch.int32, device=d_Y.device)
     wstatus = torch.empty((V,), dtype=torch.int32, device=d_Y.device)
     st = torch.cuda.current_stream(d_Y.device).cuda_stream
@@ -834,29 +805,14 @@ def fit2d_weighted(tables, Y, W, K, csf, peaks, maxfasc, csf_on, sig_csf=None):
     maxfasc = int(maxfasc)
     pk = L.f64c(peaks).reshape(Y.shape[0], -1) if (maxfasc > 0 and Y.ndim == 2) else np.zeros((Y.shape[0], 0))
     V = _fit2d_shapes(tables, Y.shape, pk.shape, maxfasc)
-    w_stride = _w2d_stride(tables, V, W.shape)
-    K = np.ascontiguousarray(np.asarray(K).reshape(-1), dtype=np.int32)
-    if K.shape != (V,):
-        raise ValueError("K should have one entry per voxel")
-    if V and (K.min() < 0 or K.max() > maxfasc):
-        raise ValueError("K should lie in 0..maxfasc = %d" % maxfasc)
-    cs = None
-    if csf is not None:
-        cs = np.ascontiguousarray(np.asarray(csf).reshape(-1).astype(bool), dtype=np.uint8)
-        if cs.shape != (V,):
-            raise ValueError("csf should have one entry per voxel")
-    sc = L.f64c(sig_csf).reshape(-1) if sig_csf is not None else None
-    if cs is not None and np.any(cs) and (not csf_on or sc is None):
-        raise ValueError("voxels flagged CSF need csf_on and sig_csf")
-    if sc is not None and sc.shape[0] != tables.M:
-        raise ValueError("sig_csf has %d entries, protocol has %d" % (sc.shape[0], tables.M))
+    w_stride = _w_stride(tables.M, V, W.shape)
+    K, cs, sc = _mixed_args(tables.M, V, maxfasc, K, csf, csf_on, sig_csf)
     params = np.zeros((V, num_params(maxfasc, bool(csf_on), False)))
     status = np.zeros((V, 5), dtype=np.int32)
     wstatus = np.zeros(V, dtype=np.int32)
-    L.check(L.lib().mfx_wfit2d_batch(tables.handle(), L.dptr(Y), L.dptr(W), w_stride, L.iptr(K),
-                                     L.bptr(cs) if cs is not None else None, L.dptr(pk) if maxfasc > 0 else None, maxfasc,
-                                     int(bool(csf_on)), L.dptr(sc) if sc is not None else None, V, L.dptr(params),
-                                     L.iptr(status), L.iptr(wstatus)))
+    L.check(L.lib().mfx_wfit2d_batch(tables.handle(), L.dptr(Y), L.dptr(W), w_stride, L.iptr(K), L.opt(cs, L.bptr),
+                                     L.dptr(pk) if maxfasc > 0 else None, maxfasc, int(bool(csf_on)), L.opt(sc), V,
+                                     L.dptr(params), L.iptr(status), L.iptr(wstatus)))
     return params, status, wstatus
 
 
@@ -893,10 +849,9 @@ def predict2d_dev(tables, d_params, d_peaks, maxfasc, csf_on=False, d_sig_csf=No
     current stream and returns without waiting."""
     import torch
     maxfasc = int(maxfasc)
-    assert d_params.is_cuda and d_params.dtype == torch.float64 and d_params.is_contiguous()
+    d_peaks, d_sig_csf = d_peaks if maxfasc > 0 else None, d_sig_csf if csf_on else None
+    _f64_cuda(d_params, d_peaks, d_sig_csf, d_Y)
     dev = d_params.device
-    for t in (d_peaks if maxfasc > 0 else None, d_sig_csf if csf_on else None, d_Y):
-        assert t is None or (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous())
     V = _predict2d_shapes(tables, d_params.shape, d_peaks.shape if maxfasc > 0 else None, maxfasc, csf_on,
                           d_Y.shape if d_Y is not None else None, d_sig_csf.numel() if csf_on else None)
     M = tables.M
@@ -907,19 +862,14 @@ def predict2d_dev(tables, d_params, d_peaks, maxfasc, csf_on=False, d_sig_csf=No
         d_sigma = (sigma_g.to(device=dev, dtype=torch.float64).contiguous() if torch.is_tensor(sigma_g)
                    else torch.full((1,), float(sigma_g), dtype=torch.float64, device=dev))
         mode = _sigma_mode(d_sigma.shape, d_sigma.numel(), V, M)
-    if out is None:
-        out = torch.empty((V, M), dtype=torch.float64, device=dev)
-    assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (V, M)
+    out = _out_like(out, (V, M), dev)
     stats = torch.empty((V, 2), dtype=torch.float64, device=dev) if d_Y is not None else None
     status = torch.zeros(2, dtype=torch.int32, device=dev)
     dstat = torch.empty((V, 5), dtype=torch.int32, device=dev)
     st = torch.cuda.current_stream(dev).cuda_stream
-    L.check(L.lib().mfx_predict2d_dev(tables.handle(), d_params.data_ptr(), d_peaks.data_ptr() if maxfasc > 0 else None,
-                                      maxfasc, int(bool(csf_on)), d_sig_csf.data_ptr() if csf_on else None, V,
-                                      d_Y.data_ptr() if d_Y is not None else None,
-                                      d_sigma.data_ptr() if d_sigma is not None else None, mode, int(ncoils),
-                                      int(seed) & _U64, int(offset) & _U64, out.data_ptr(),
-                                      stats.data_ptr() if stats is not None else None, status.data_ptr(), dstat.data_ptr(), st))
+    L.check(L.lib().mfx_predict2d_dev(tables.handle(), d_params.data_ptr(), _tptr(d_peaks), maxfasc, int(bool(csf_on)),
+                                      _tptr(d_sig_csf), V, _tptr(d_Y), _tptr(d_sigma), mode, int(ncoils), int(seed) & _U64,
+                                      int(offset) & _U64, out.data_ptr(), _tptr(stats), status.data_ptr(), dstat.data_ptr(), st))
     return out, stats, status, dstat
 
 
@@ -931,7 +881,7 @@ def predict2d(tables, params, peaks, maxfasc, csf_on=False, sig_csf=None, Y=None
     params = L.f64c(params)
     pk = L.f64c(peaks) if maxfasc > 0 else None
     sc = L.f64c(sig_csf).reshape(-1) if csf_on else None
-    Yc = L.f64c(Y) if Y is not None else None
+    Yc = L.f64c_opt(Y)
     V = _predict2d_shapes(tables, params.shape, pk.shape if pk is not None else None, maxfasc, csf_on,
                           Yc.shape if Yc is not None else None, sc.shape[0] if sc is not None else None)
     M = tables.M
@@ -944,27 +894,10 @@ def predict2d(tables, params, peaks, maxfasc, csf_on=False, sig_csf=None, Y=None
     out = np.zeros((V, M))
     stats = np.zeros((V, 2)) if Yc is not None else None
     dstat = np.zeros((V, 5), dtype=np.int32)
-    L.check(L.lib().mfx_predict2d(tables.handle(), L.dptr(params), L.dptr(pk) if pk is not None else None, maxfasc,
-                                  int(bool(csf_on)), L.dptr(sc) if sc is not None else None, V,
-                                  L.dptr(Yc) if Yc is not None else None, L.dptr(sg) if sg is not None else None, mode,
-                                  int(ncoils), int(seed) & _U64, int(offset) & _U64, L.dptr(out),
-                                  L.dptr(stats) if stats is not None else None, L.iptr(dstat)))
+    L.check(L.lib().mfx_predict2d(tables.handle(), L.dptr(params), L.opt(pk), maxfasc, int(bool(csf_on)), L.opt(sc), V,
+                                  L.opt(Yc), L.opt(sg), mode, int(ncoils), int(seed) & _U64, int(offset) & _U64, L.dptr(out),
+                                  L.opt(stats), L.iptr(dstat)))
     return (out, dstat) if stats is None else (out, stats, dstat)
-
-
-def _soft2d_shapes(tables, y_shape, pk_shape, K):
-    """Argument checks shared by the device entry points of the 2-D protocols' soft fits and profiles (before any device
-    call); returns V."""
-    K = int(K)
-    if K not in (1, 2):
-        raise NotImplementedError("soft fits and profiles of 2-D protocols serve K = 1 or 2 fascicles (got %d): three "
-                                  "fascicles and voxels without one are out of scope" % K)
-    if len(y_shape) != 2 or y_shape[1] != tables.M:
-        raise ValueError("data has shape %s, protocol has %d measurements" % (tuple(y_shape), tables.M))
-    V = y_shape[0]
-    if pk_shape is None or tuple(pk_shape) != (V, 3 * K):
-        raise ValueError("peaks should have shape (%d, %d)" % (V, 3 * K))
-    return V
 
 
 def posterior2d_dev(tables, d_Y, d_peaks, K, T, shift, d_W=None):
@@ -979,26 +912,15 @@ def posterior2d_dev(tables, d_Y, d_peaks, K, T, shift, d_W=None):
     T = 2 sigma^2 means that measurement m has variance sigma^2 / W_m; status 3: a weight is negative or not finite,
     4: none is positive."""
     import torch
-    V = _soft2d_shapes(tables, d_Y.shape, d_peaks.shape, K)
-    for t, what in ((T, "T"), (shift, "shift")):
-        if not torch.is_tensor(t) or tuple(t.shape) != (V,):
-            raise ValueError("%s should be a tensor with one entry per voxel (%d)" % (what, V))
-    w_stride = _w2d_stride(tables, V, d_W.shape) if d_W is not None else None
-    for t in (d_Y, d_peaks, T, shift) + ((d_W,) if d_W is not None else ()):
-        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+    V, w_stride, _ = _soft_dev_args(_SOFT2D_SCOPE, tables.M, d_Y, d_peaks, K, d_W, T_shift=(T, shift))
     N = tables.N
     w = torch.empty((V, int(K), N), dtype=torch.float64, device=d_Y.device)
     log_sum = torch.empty((V,), dtype=torch.float64, device=d_Y.device)
     status = torch.empty((V,), dtype=torch.int32, device=d_Y.device)
     dir_status = torch.empty((V, 5), dtype=torch.int32, device=d_Y.device)
     st = torch.cuda.current_stream(d_Y.device).cuda_stream
-    if d_W is None:
-        L.check(L.lib().mfx_post2d_dev(tables.handle(), d_Y.data_ptr(), d_peaks.data_ptr(), int(K), T.data_ptr(), shift.data_ptr(), V,
-                                       w.data_ptr(), log_sum.data_ptr(), status.data_ptr(), dir_status.data_ptr(), st))
-    else:
-        L.check(L.lib().mfx_wpost2d_dev(tables.handle(), d_Y.data_ptr(), d_W.data_ptr(), w_stride, d_peaks.data_ptr(), int(K),
-                                        T.data_ptr(), shift.data_ptr(), V, w.data_ptr(), log_sum.data_ptr(), status.data_ptr(),
-                                        dir_status.data_ptr(), st))
+    _twin("post2d_dev", tables.handle(), d_Y.data_ptr(), _tptr(d_W), w_stride, d_peaks.data_ptr(), int(K), T.data_ptr(),
+          shift.data_ptr(), V, w.data_ptr(), log_sum.data_ptr(), status.data_ptr(), dir_status.data_ptr(), st)
     return w, log_sum, status, dir_status
 
 
@@ -1011,23 +933,14 @@ def profile2d_dev(tables, d_Y, d_peaks, K, partner=False, out=None, d_W=None):
     [V, M] or [M] (mfx_wprofile2d_dev): obj is the weighted sum of squares; a voxel with unusable weights has NaN values
     and partner -1."""
     import torch
-    V = _soft2d_shapes(tables, d_Y.shape, d_peaks.shape, K)
-    w_stride = _w2d_stride(tables, V, d_W.shape) if d_W is not None else None
-    for t in (d_Y, d_peaks) + ((d_W,) if d_W is not None else ()):
-        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+    V, w_stride, _ = _soft_dev_args(_SOFT2D_SCOPE, tables.M, d_Y, d_peaks, K, d_W)
     N = tables.N
-    if out is None:
-        out = torch.empty((V, int(K), N), dtype=torch.float64, device=d_Y.device)
-    assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (V, int(K), N)
+    out = _out_like(out, (V, int(K), N), d_Y.device)
     part = torch.empty((V, int(K), N), dtype=torch.int32, device=d_Y.device) if partner else None
     dir_status = torch.empty((V, 5), dtype=torch.int32, device=d_Y.device)
     st = torch.cuda.current_stream(d_Y.device).cuda_stream
-    if d_W is None:
-        L.check(L.lib().mfx_profile2d_dev(tables.handle(), d_Y.data_ptr(), d_peaks.data_ptr(), int(K), V, out.data_ptr(),
-                                          part.data_ptr() if partner else None, dir_status.data_ptr(), st))
-    else:
-        L.check(L.lib().mfx_wprofile2d_dev(tables.handle(), d_Y.data_ptr(), d_W.data_ptr(), w_stride, d_peaks.data_ptr(), int(K), V,
-                                           out.data_ptr(), part.data_ptr() if partner else None, dir_status.data_ptr(), st))
+    _twin("profile2d_dev", tables.handle(), d_Y.data_ptr(), _tptr(d_W), w_stride, d_peaks.data_ptr(), int(K), V, out.data_ptr(),
+          _tptr(part), dir_status.data_ptr(), st)
     return out, part, dir_status
 
 
@@ -1069,9 +982,7 @@ def posterior2d(tables, Y, K, peaks, maxfasc, sigma, shift=None, csf=None, W=Non
     MSE * sum_m W; status 3: a weight is negative or not finite, 4: none is positive."""
     Y, pk, maxfasc, bins, n_uns = _soft2d_host_args(tables, Y, K, peaks, maxfasc, csf)
     V, N = Y.shape[0], tables.N
-    if W is not None:
-        W = L.f64c(W)
-        w_stride = _w2d_stride(tables, V, W.shape)
+    W, w_stride = _host_weights(tables.M, V, W)
     sig = _per_voxel(sigma, V, "sigma")
     sh = _per_voxel(shift, V, "shift") if shift is not None else None
     w = np.full((V, maxfasc, N), np.nan)
@@ -1079,9 +990,7 @@ def posterior2d(tables, Y, K, peaks, maxfasc, sigma, shift=None, csf=None, W=Non
     status = np.full(V, -1, dtype=np.int32)
     dir_status = np.zeros((V, 5), dtype=np.int32)
     for k, ix in bins:
-        Yc, pc = np.ascontiguousarray(Y[ix]), np.ascontiguousarray(pk[ix, :3 * k])
-        if W is not None:
-            Wc = np.ascontiguousarray(W[ix]) if w_stride else W
+        Yc, pc, Wc = np.ascontiguousarray(Y[ix]), np.ascontiguousarray(pk[ix, :3 * k]), _w_chunk(W, w_stride, ix)
         if sh is not None:
             shc = np.ascontiguousarray(sh[ix])
         elif W is None:   # a voxel with a failing direction has a NaN row there and status 5 here
@@ -1095,12 +1004,8 @@ def posterior2d(tables, Y, K, peaks, maxfasc, sigma, shift=None, csf=None, W=Non
         Tc = np.ascontiguousarray(2.0 * sig[ix] ** 2)
         wc, lc = np.zeros((ix.size, k, N)), np.zeros(ix.size)
         stc, dsc = np.zeros(ix.size, dtype=np.int32), np.zeros((ix.size, 5), dtype=np.int32)
-        if W is None:
-            L.check(L.lib().mfx_post2d(tables.handle(), L.dptr(Yc), L.dptr(pc), k, L.dptr(Tc), L.dptr(shc), ix.size, L.dptr(wc),
-                                       L.dptr(lc), L.iptr(stc), L.iptr(dsc)))
-        else:
-            L.check(L.lib().mfx_wpost2d(tables.handle(), L.dptr(Yc), L.dptr(Wc), w_stride, L.dptr(pc), k, L.dptr(Tc), L.dptr(shc),
-                                        ix.size, L.dptr(wc), L.dptr(lc), L.iptr(stc), L.iptr(dsc)))
+        _twin("post2d", tables.handle(), L.dptr(Yc), L.opt(Wc), w_stride, L.dptr(pc), k, L.dptr(Tc), L.dptr(shc), ix.size,
+              L.dptr(wc), L.dptr(lc), L.iptr(stc), L.iptr(dsc))
         w[ix, :k], log_sum[ix], status[ix], dir_status[ix] = wc, lc, stc, dsc
     return w, log_sum, status, dir_status, n_uns
 
@@ -1113,9 +1018,7 @@ def profile2d(tables, Y, K, peaks, maxfasc, partner=False, csf=None, W=None):
     weights [V, M] or [M] (mfx_wprofile2d): obj is the weighted sum of squares; a voxel with unusable weights has NaN rows."""
     Y, pk, maxfasc, bins, n_uns = _soft2d_host_args(tables, Y, K, peaks, maxfasc, csf)
     V, N = Y.shape[0], tables.N
-    if W is not None:
-        W = L.f64c(W)
-        w_stride = _w2d_stride(tables, V, W.shape)
+    W, w_stride = _host_weights(tables.M, V, W)
     obj = np.full((V, maxfasc, N), np.nan)
     par = np.full((V, maxfasc, N), -1, dtype=np.int32) if partner else None
     dir_status = np.zeros((V, 5), dtype=np.int32)
@@ -1123,13 +1026,9 @@ def profile2d(tables, Y, K, peaks, maxfasc, partner=False, csf=None, W=None):
         Yc, pc = np.ascontiguousarray(Y[ix]), np.ascontiguousarray(pk[ix, :3 * k])
         o, dsc = np.zeros((ix.size, k, N)), np.zeros((ix.size, 5), dtype=np.int32)
         p = np.zeros((ix.size, k, N), dtype=np.int32) if partner else None
-        if W is None:
-            L.check(L.lib().mfx_profile2d(tables.handle(), L.dptr(Yc), L.dptr(pc), k, ix.size, L.dptr(o),
-                                          L.iptr(p) if partner else None, L.iptr(dsc)))
-        else:
-            Wc = np.ascontiguousarray(W[ix]) if w_stride else W
-            L.check(L.lib().mfx_wprofile2d(tables.handle(), L.dptr(Yc), L.dptr(Wc), w_stride, L.dptr(pc), k, ix.size, L.dptr(o),
-                                           L.iptr(p) if partner else None, L.iptr(dsc)))
+        Wc = _w_chunk(W, w_stride, ix)
+        _twin("profile2d", tables.handle(), L.dptr(Yc), L.opt(Wc), w_stride, L.dptr(pc), k, ix.size, L.dptr(o), L.opt(p, L.iptr),
+              L.iptr(dsc))
         obj[ix, :k], dir_status[ix] = o, dsc
         if partner:
             par[ix, :k] = p
@@ -1143,13 +1042,7 @@ def _wfit_shapes(plan, y_shape, w_shape, pk_shape, maxfasc):
     if len(y_shape) != 2 or y_shape[1] != plan.M:
         raise ValueError("data has shape %s, protocol has %d measurements" % (tuple(y_shape), plan.M))
     V = y_shape[0]
-    if tuple(w_shape) == (plan.M,):
-        w_stride = 0
-    elif tuple(w_shape) == (V, plan.M):
-        w_stride = plan.M
-    else:
-        raise ValueError("weights should have shape (%d, %d) or (%d,), got %s (%d voxels)"
-                         % (V, plan.M, plan.M, tuple(w_shape), V))
+    w_stride = _w_stride(plan.M, V, w_shape)
     if tuple(pk_shape) != (V, 3 * maxfasc):
         raise ValueError("peaks should have shape (%d, %d)" % (V, 3 * maxfasc))
     return V, w_stride
@@ -1164,13 +1057,9 @@ def fit_weighted_dev(plan, d_Y, d_W, d_peaks, maxfasc, out=None):
     mfx_plan_status as in fit_batch_dev."""
     import torch
     maxfasc = int(maxfasc)
-    for t in (d_Y, d_W, d_peaks):
-        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+    _f64_cuda(d_Y, d_W, d_peaks)
     V, w_stride = _wfit_shapes(plan, d_Y.shape, d_W.shape, d_peaks.shape, maxfasc)
-    npar = num_params(maxfasc, False, False)
-    if out is None:
-        out = torch.empty((V, npar), dtype=torch.float64, device=d_Y.device)
-    assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (V, npar)
+    out = _out_like(out, (V, num_params(maxfasc, False, False)), d_Y.device)
     status = torch.empty((V,), dtype=torch.int32, device=d_Y.device)
     st = torch.cuda.current_stream(d_Y.device).cuda_stream
     L.check(L.lib().mfx_wfit_batch_dev(plan.handle(), d_Y.data_ptr(), d_W.data_ptr(), w_stride,
@@ -1193,26 +1082,11 @@ def fit_weighted(plan, Y, W, K, csf, peaks, maxfasc, csf_on, sig_csf=None, ear=N
     maxfasc = int(maxfasc)
     pk = L.f64c(peaks).reshape(Y.shape[0], -1) if (maxfasc > 0 and Y.ndim == 2) else np.zeros((Y.shape[0], 0))
     V, w_stride = _wfit_shapes(plan, Y.shape, W.shape, pk.shape, maxfasc)
-    K = np.ascontiguousarray(np.asarray(K).reshape(-1), dtype=np.int32)
-    if K.shape != (V,):
-        raise ValueError("K should have one entry per voxel")
-    if V and (K.min() < 0 or K.max() > maxfasc):
-        raise ValueError("K should lie in 0..maxfasc = %d" % maxfasc)
-    cs = None
-    if csf is not None:
-        cs = np.ascontiguousarray(np.asarray(csf).reshape(-1).astype(bool), dtype=np.uint8)
-        if cs.shape != (V,):
-            raise ValueError("csf should have one entry per voxel")
-    sc = L.f64c(sig_csf).reshape(-1) if sig_csf is not None else None
-    if cs is not None and np.any(cs) and (not csf_on or sc is None):
-        raise ValueError("voxels flagged CSF need csf_on and sig_csf")
-    if sc is not None and sc.shape[0] != plan.M:
-        raise ValueError("sig_csf has %d entries, protocol has %d" % (sc.shape[0], plan.M))
+    K, cs, sc = _mixed_args(plan.M, V, maxfasc, K, csf, csf_on, sig_csf)
     params = np.zeros((V, num_params(maxfasc, bool(csf_on), False)))
     status = np.zeros(V, dtype=np.int32)
-    L.check(L.lib().mfx_wfit_batch(plan.handle(), L.dptr(Y), L.dptr(W), w_stride, L.iptr(K),
-                                   L.bptr(cs) if cs is not None else None, L.dptr(pk) if maxfasc > 0 else None, maxfasc,
-                                   int(bool(csf_on)), L.dptr(sc) if sc is not None else None, V, L.dptr(params),
+    L.check(L.lib().mfx_wfit_batch(plan.handle(), L.dptr(Y), L.dptr(W), w_stride, L.iptr(K), L.opt(cs, L.bptr),
+                                   L.dptr(pk) if maxfasc > 0 else None, maxfasc, int(bool(csf_on)), L.opt(sc), V, L.dptr(params),
                                    L.iptr(status)))
     if V:
         L.check(L.lib().mfx_plan_status(plan.handle(), None))   # a direction that is not a unit vector: ValueError
@@ -1286,23 +1160,19 @@ def robust_weights_dev(d_Y, d_P, d_W0=None, loss='cutoff', c=4.45, d_Wprev=None,
     ``out`` may be d_Wprev itself.  Enqueues on torch's current stream and returns without waiting."""
     import torch
     code, cf, _ = _robust_rule(loss, c)
-    for t in (d_Y, d_P, d_W0, d_Wprev, out):
-        assert t is None or (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous())
+    _f64_cuda(d_Y, d_P, d_W0, d_Wprev, out)
     V, w0_stride = _robust_w_shapes(None, d_Y.shape, d_P.shape, d_W0.shape if d_W0 is not None else None,
                                     d_Wprev.shape if d_Wprev is not None else None)
     M = d_Y.shape[1]
-    if out is None:
-        out = torch.empty((V, M), dtype=torch.float64, device=d_Y.device)
-    assert tuple(out.shape) == (V, M)
+    out = _out_like(out, (V, M), d_Y.device)
     scale = torch.empty((V,), dtype=torch.float64, device=d_Y.device)
     state = torch.empty((V,), dtype=torch.int32, device=d_Y.device)
     changed = torch.empty((V,), dtype=torch.int32, device=d_Y.device) if d_Wprev is not None else None
     st = torch.cuda.current_stream(d_Y.device).cuda_stream
     with torch.cuda.device(d_Y.device):
-        L.check(L.lib().mfx_robust_weights_dev(M, d_Y.data_ptr(), d_P.data_ptr(), d_W0.data_ptr() if d_W0 is not None else None,
-                                               w0_stride, code, cf, V, d_Wprev.data_ptr() if d_Wprev is not None else None,
-                                               out.data_ptr(), scale.data_ptr(), state.data_ptr(),
-                                               changed.data_ptr() if changed is not None else None, st))
+        L.check(L.lib().mfx_robust_weights_dev(M, d_Y.data_ptr(), d_P.data_ptr(), _tptr(d_W0), w0_stride, code, cf, V,
+                                               _tptr(d_Wprev), out.data_ptr(), scale.data_ptr(), state.data_ptr(),
+                                               _tptr(changed), st))
     return out, scale, state, changed
 
 
@@ -1311,8 +1181,7 @@ def robust_weights(Y, P, W0=None, loss='cutoff', c=4.45, Wprev=None, device=0):
     (W [V, M], scale [V], state [V] int32, changed [V] int32 or None)."""
     _robust_rule(loss, c)
     Y, P = L.f64c(Y), L.f64c(P)
-    W0 = L.f64c(W0) if W0 is not None else None
-    Wprev = L.f64c(Wprev) if Wprev is not None else None
+    W0, Wprev = L.f64c_opt(W0), L.f64c_opt(Wprev)
     _robust_w_shapes(None, Y.shape, P.shape, W0.shape if W0 is not None else None, Wprev.shape if Wprev is not None else None)
     if L.lib().mfx_device_count() <= 0:
         raise L.MfxError("no HIP device available (this library has no CPU path)")
@@ -1335,8 +1204,7 @@ def fit_robust_dev(plan, d_Y, d_peaks, maxfasc, d_W0=None, loss='cutoff', c=4.45
     import torch
     maxfasc = int(maxfasc)
     code, cf, n_iter = _robust_rule(loss, c, n_iter)
-    for t in (d_Y, d_peaks if maxfasc > 0 else None, d_W0):
-        assert t is None or (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous())
+    _f64_cuda(d_Y, d_peaks if maxfasc > 0 else None, d_W0)
     V, w0_stride = _wfit_shapes(plan, d_Y.shape, d_W0.shape if d_W0 is not None else (plan.M,),
                                 d_peaks.shape if maxfasc > 0 else (d_Y.shape[0], 0), maxfasc)
     dev = d_Y.device
@@ -1348,8 +1216,8 @@ def fit_robust_dev(plan, d_Y, d_peaks, maxfasc, d_W0=None, loss='cutoff', c=4.45
     nch = torch.zeros((n_iter,), dtype=torch.int32, device=dev)
     st = torch.cuda.current_stream(dev).cuda_stream
     with torch.cuda.device(dev):
-        L.check(L.lib().mfx_rfit_batch_dev(plan.handle(), d_Y.data_ptr(), d_W0.data_ptr() if d_W0 is not None else None,
-                                           w0_stride, d_peaks.data_ptr() if maxfasc > 0 else None, maxfasc, code, cf, n_iter, V,
+        L.check(L.lib().mfx_rfit_batch_dev(plan.handle(), d_Y.data_ptr(), _tptr(d_W0), w0_stride,
+                                           d_peaks.data_ptr() if maxfasc > 0 else None, maxfasc, code, cf, n_iter, V,
                                            params.data_ptr(), W.data_ptr(), scale.data_ptr(), state.data_ptr(),
                                            status.data_ptr(), nch.data_ptr() if n_iter > 0 else None, st))
     return params, W, {'scale': scale, 'state': state, 'status': status, 'n_changed': nch}
@@ -1370,27 +1238,11 @@ def fit_robust(plan, Y, K, csf, peaks, maxfasc, csf_on, sig_csf=None, W0=None, l
                          % int(np.count_nonzero(ear)))
     code, cf, n_iter = _robust_rule(loss, c, n_iter)
     Y = L.f64c(Y)
-    W0 = L.f64c(W0) if W0 is not None else None
+    W0 = L.f64c_opt(W0)
     maxfasc = int(maxfasc)
     pk = L.f64c(peaks).reshape(Y.shape[0], -1) if (maxfasc > 0 and Y.ndim == 2) else np.zeros((Y.shape[0], 0))
     V, w0_stride = _wfit_shapes(plan, Y.shape, W0.shape if W0 is not None else (plan.M,), pk.shape, maxfasc)
-    K = np.ascontiguousarray(np.asarray(K).reshape(-1), dtype=np.int32)
-    if K.shape != (V,):
-        raise ValueError("K should have one entry per voxel")
-    if V and (K.min() < 0 or K.max() > maxfasc):
-        raise ValueError("K should lie in 0..maxfasc = %d" % maxfasc)
-    cs = None
-    if csf is not None:
-        cs = np.ascontiguousarray(np.asarray(csf).reshape(-1).astype(bool), dtype=np.uint8)
-        if cs.shape != (V,):
-            raise ValueError("csf should have one entry per voxel")
-    sc = L.f64c(sig_csf).reshape(-1) if sig_csf is not None else None
-    if cs is not None and np.any(cs) and (not csf_on or sc is None):
-        raise ValueError("voxels flagged CSF need csf_on and sig_csf")
-    if csf_on and sc is None:
-        raise ValueError("csf_on needs sig_csf")
-    if sc is not None and sc.shape[0] != plan.M:
-        raise ValueError("sig_csf has %d entries, protocol has %d" % (sc.shape[0], plan.M))
+    K, cs, sc = _mixed_args(plan.M, V, maxfasc, K, csf, csf_on, sig_csf, need_sig=True)
     M = plan.M
     params = np.zeros((V, num_params(maxfasc, bool(csf_on), False)))
     W = np.zeros((V, M))
@@ -1399,10 +1251,9 @@ def fit_robust(plan, Y, K, csf, peaks, maxfasc, csf_on, sig_csf=None, W0=None, l
     status = np.zeros(V, dtype=np.int32)
     nch = np.zeros(max(n_iter, 1), dtype=np.int64)
     used = np.zeros(1, dtype=np.int32)
-    L.check(L.lib().mfx_rfit_batch(plan.handle(), L.dptr(Y), L.dptr(W0) if W0 is not None else None, w0_stride, L.iptr(K),
-                                   L.bptr(cs) if cs is not None else None, L.dptr(pk) if maxfasc > 0 else None, maxfasc,
-                                   int(bool(csf_on)), L.dptr(sc) if sc is not None else None, code, cf, n_iter, V,
-                                   L.dptr(params), L.dptr(W), L.dptr(scale), L.iptr(state), L.iptr(status), L.lptr(nch),
+    L.check(L.lib().mfx_rfit_batch(plan.handle(), L.dptr(Y), L.opt(W0), w0_stride, L.iptr(K), L.opt(cs, L.bptr),
+                                   L.dptr(pk) if maxfasc > 0 else None, maxfasc, int(bool(csf_on)), L.opt(sc), code, cf, n_iter,
+                                   V, L.dptr(params), L.dptr(W), L.dptr(scale), L.iptr(state), L.iptr(status), L.lptr(nch),
                                    L.iptr(used)))
     if V:
         L.check(L.lib().mfx_plan_status(plan.handle(), None))   # a direction that is not a unit vector: ValueError
@@ -1421,10 +1272,9 @@ def fit2d_robust_dev(tables, d_Y, d_peaks, maxfasc, d_W0=None, loss='cutoff', c=
     import torch
     maxfasc = int(maxfasc)
     code, cf, n_iter = _robust_rule(loss, c, n_iter)
-    for t in (d_Y, d_peaks if maxfasc > 0 else None, d_W0):
-        assert t is None or (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous())
+    _f64_cuda(d_Y, d_peaks if maxfasc > 0 else None, d_W0)
     V = _fit2d_shapes(tables, d_Y.shape, d_peaks.shape if maxfasc > 0 else (d_Y.shape[0], 0), maxfasc)
-    w0_stride = _w2d_stride(tables, V, d_W0.shape) if d_W0 is not None else 0
+    w0_stride = _w_stride(tables.M, V, d_W0.shape) if d_W0 is not None else 0
     dev = d_Y.device
     params = torch.empty((V, num_params(maxfasc, False, False)), dtype=torch.float64, device=dev)
     W = torch.empty((V, tables.M), dtype=torch.float64, device=dev)
@@ -1434,8 +1284,8 @@ def fit2d_robust_dev(tables, d_Y, d_peaks, maxfasc, d_W0=None, loss='cutoff', c=
     wstat = torch.empty((V,), dtype=torch.int32, device=dev)
     nch = torch.zeros((n_iter,), dtype=torch.int32, device=dev)
     st = torch.cuda.current_stream(dev).cuda_stream
-    L.check(L.lib().mfx_rfit2d_batch_dev(tables.handle(), d_Y.data_ptr(), d_W0.data_ptr() if d_W0 is not None else None,
-                                         w0_stride, d_peaks.data_ptr() if maxfasc > 0 else None, maxfasc, code, cf, n_iter, V,
+    L.check(L.lib().mfx_rfit2d_batch_dev(tables.handle(), d_Y.data_ptr(), _tptr(d_W0), w0_stride,
+                                         d_peaks.data_ptr() if maxfasc > 0 else None, maxfasc, code, cf, n_iter, V,
                                          params.data_ptr(), W.data_ptr(), scale.data_ptr(), state.data_ptr(), dstat.data_ptr(),
                                          wstat.data_ptr(), nch.data_ptr() if n_iter > 0 else None, st))
     return params, W, {'scale': scale, 'state': state, 'dir_status': dstat, 'status': wstat, 'n_changed': nch}
@@ -1452,28 +1302,12 @@ def fit2d_robust(tables, Y, K, csf, peaks, maxfasc, csf_on, sig_csf=None, W0=Non
     results are those of all n_iter iterations."""
     code, cf, n_iter = _robust_rule(loss, c, n_iter)
     Y = L.f64c(Y)
-    W0 = L.f64c(W0) if W0 is not None else None
+    W0 = L.f64c_opt(W0)
     maxfasc = int(maxfasc)
     pk = L.f64c(peaks).reshape(Y.shape[0], -1) if (maxfasc > 0 and Y.ndim == 2) else np.zeros((Y.shape[0], 0))
     V = _fit2d_shapes(tables, Y.shape, pk.shape, maxfasc)
-    w0_stride = _w2d_stride(tables, V, W0.shape) if W0 is not None else 0
-    K = np.ascontiguousarray(np.asarray(K).reshape(-1), dtype=np.int32)
-    if K.shape != (V,):
-        raise ValueError("K should have one entry per voxel")
-    if V and (K.min() < 0 or K.max() > maxfasc):
-        raise ValueError("K should lie in 0..maxfasc = %d" % maxfasc)
-    cs = None
-    if csf is not None:
-        cs = np.ascontiguousarray(np.asarray(csf).reshape(-1).astype(bool), dtype=np.uint8)
-        if cs.shape != (V,):
-            raise ValueError("csf should have one entry per voxel")
-    sc = L.f64c(sig_csf).reshape(-1) if sig_csf is not None else None
-    if cs is not None and np.any(cs) and (not csf_on or sc is None):
-        raise ValueError("voxels flagged CSF need csf_on and sig_csf")
-    if csf_on and sc is None:
-        raise ValueError("csf_on needs sig_csf")
-    if sc is not None and sc.shape[0] != tables.M:
-        raise ValueError("sig_csf has %d entries, protocol has %d" % (sc.shape[0], tables.M))
+    w0_stride = _w_stride(tables.M, V, W0.shape) if W0 is not None else 0
+    K, cs, sc = _mixed_args(tables.M, V, maxfasc, K, csf, csf_on, sig_csf, need_sig=True)
     M = tables.M
     params = np.zeros((V, num_params(maxfasc, bool(csf_on), False)))
     W = np.zeros((V, M))
@@ -1483,9 +1317,8 @@ def fit2d_robust(tables, Y, K, csf, peaks, maxfasc, csf_on, sig_csf=None, W0=Non
     wstat = np.zeros(V, dtype=np.int32)
     nch = np.zeros(max(n_iter, 1), dtype=np.int64)
     used = np.zeros(1, dtype=np.int32)
-    L.check(L.lib().mfx_rfit2d_batch(tables.handle(), L.dptr(Y), L.dptr(W0) if W0 is not None else None, w0_stride, L.iptr(K),
-                                     L.bptr(cs) if cs is not None else None, L.dptr(pk) if maxfasc > 0 else None, maxfasc,
-                                     int(bool(csf_on)), L.dptr(sc) if sc is not None else None, code, cf, n_iter, V,
+    L.check(L.lib().mfx_rfit2d_batch(tables.handle(), L.dptr(Y), L.opt(W0), w0_stride, L.iptr(K), L.opt(cs, L.bptr),
+                                     L.dptr(pk) if maxfasc > 0 else None, maxfasc, int(bool(csf_on)), L.opt(sc), code, cf, n_iter, V,
                                      L.dptr(params), L.dptr(W), L.dptr(scale), L.iptr(state), L.iptr(dstat), L.iptr(wstat),
                                      L.lptr(nch), L.iptr(used)))
     return params, W, {'scale': scale, 'state': state, 'status': wstat, 'dir_status': dstat,
@@ -1564,8 +1397,7 @@ def boot_resample_dev(d_Y, d_P, d_params, maxfasc, csf_on=False, ear_on=False, B
     maxfasc = int(maxfasc)
     if maxfasc < 0 or maxfasc > 3:
         raise ValueError("maxfasc must be 0..3")
-    for t in (d_Y, d_P, d_params, d_peaks):
-        assert t is None or (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous())
+    _f64_cuda(d_Y, d_P, d_params, d_peaks)
     if d_Y.dim() != 2 or d_Y.shape[1] < 1:
         raise ValueError("data should have shape (voxels, measurements), got %s" % (tuple(d_Y.shape),))
     V, M = d_Y.shape
@@ -1593,11 +1425,9 @@ def boot_resample_dev(d_Y, d_P, d_params, maxfasc, csf_on=False, ear_on=False, B
     st = torch.cuda.current_stream(dev).cuda_stream
     with torch.cuda.device(dev):
         L.check(L.lib().mfx_boot_resample_dev(M, d_Y.data_ptr(), d_P.data_ptr(), d_params.data_ptr(), maxfasc, int(bool(csf_on)),
-                                              int(bool(ear_on)), d_peaks.data_ptr() if d_peaks is not None else None,
-                                              d_groups.data_ptr() if code == 1 else None,
-                                              d_vox.data_ptr() if d_vox is not None else None, V, B, code, int(bool(inflate)),
-                                              int(seed) & _U64, int(offset) & _U64, Ys.data_ptr(),
-                                              pk.data_ptr() if pk is not None else None, status.data_ptr(), st))
+                                              int(bool(ear_on)), _tptr(d_peaks), d_groups.data_ptr() if code == 1 else None,
+                                              _tptr(d_vox), V, B, code, int(bool(inflate)), int(seed) & _U64,
+                                              int(offset) & _U64, Ys.data_ptr(), _tptr(pk), status.data_ptr(), st))
     return Ys, pk, status
 
 
@@ -1613,15 +1443,15 @@ def boot_reduce_dev(d_X, d_valid, q=()):
     _, _, qa = _boot_rule(B, 'wild', q)
     if tuple(d_valid.shape) != (V, B, Cn):
         raise ValueError("valid should have the shape of X %s, got %s" % ((V, B, Cn), tuple(d_valid.shape)))
-    assert d_X.is_cuda and d_X.dtype == torch.float64 and d_X.is_contiguous()
+    _f64_cuda(d_X)
     assert d_valid.is_cuda and d_valid.dtype in (torch.uint8, torch.bool) and d_valid.is_contiguous()
     dev = d_X.device
     d_q = torch.from_numpy(qa).to(dev) if qa.size else None
     stats = torch.empty((V, Cn, BOOT_NSTAT + qa.size), dtype=torch.float64, device=dev)
     st = torch.cuda.current_stream(dev).cuda_stream
     with torch.cuda.device(dev):
-        L.check(L.lib().mfx_boot_reduce_dev(d_X.data_ptr(), d_valid.data_ptr(), V, B, Cn, d_q.data_ptr() if d_q is not None else None,
-                                            int(qa.size), stats.data_ptr(), st))
+        L.check(L.lib().mfx_boot_reduce_dev(d_X.data_ptr(), d_valid.data_ptr(), V, B, Cn, _tptr(d_q), int(qa.size), stats.data_ptr(),
+                                            st))
     return stats
 
 
@@ -1641,9 +1471,8 @@ def fit_bootstrap_dev(plan, d_Y, d_peaks, maxfasc, csf_on=False, ear_on=False, d
     maxfasc = int(maxfasc)
     if maxfasc < 0 or maxfasc > 3:
         raise ValueError("maxfasc must be 0..3")
-    for t in (d_Y, d_peaks if maxfasc > 0 else None, d_sig_csf if csf_on else None, d_sig_ear if ear_on else None, d_props,
-              d_params, d_pred):
-        assert t is None or (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous())
+    _f64_cuda(d_Y, d_peaks if maxfasc > 0 else None, d_sig_csf if csf_on else None, d_sig_ear if ear_on else None, d_props,
+              d_params, d_pred)
     if d_Y.dim() != 2 or d_Y.shape[1] != plan.M:
         raise ValueError("data should have shape (voxels, %d), got %s" % (plan.M, tuple(d_Y.shape)))
     V, M = d_Y.shape
@@ -1681,15 +1510,14 @@ def fit_bootstrap_dev(plan, d_Y, d_peaks, maxfasc, csf_on=False, ear_on=False, d
     status = torch.zeros((V,), dtype=torch.int32, device=dev)
     reps = torch.empty((V, B, npar), dtype=torch.float64, device=dev) if keep else None
     st = torch.cuda.current_stream(dev).cuda_stream
-    ptr = lambda t: t.data_ptr() if t is not None else None
     with torch.cuda.device(dev):
-        L.check(L.lib().mfx_boot_fit_dev(plan.handle(), d_Y.data_ptr(), ptr(d_peaks) if maxfasc > 0 else None, maxfasc,
-                                         int(bool(csf_on)), int(bool(ear_on)), ptr(d_sig_csf) if csf_on else None,
-                                         ptr(d_sig_ear) if ear_on else None, int(E), ptr(d_params), ptr(d_pred),
-                                         ptr(d_groups) if code == 1 else None, ptr(d_vox), V, B, code, int(bool(inflate)),
-                                         int(seed) & _U64, int(offset) & _U64, ptr(d_props), nprop, ptr(d_q), int(qa.size),
+        L.check(L.lib().mfx_boot_fit_dev(plan.handle(), d_Y.data_ptr(), _tptr(d_peaks) if maxfasc > 0 else None, maxfasc,
+                                         int(bool(csf_on)), int(bool(ear_on)), _tptr(d_sig_csf) if csf_on else None,
+                                         _tptr(d_sig_ear) if ear_on else None, int(E), _tptr(d_params), _tptr(d_pred),
+                                         _tptr(d_groups) if code == 1 else None, _tptr(d_vox), V, B, code, int(bool(inflate)),
+                                         int(seed) & _U64, int(offset) & _U64, _tptr(d_props), nprop, _tptr(d_q), int(qa.size),
                                          int(max_bytes), stats.data_ptr(), agree.data_ptr() if maxfasc > 0 else None,
-                                         status.data_ptr(), ptr(reps), st))
+                                         status.data_ptr(), _tptr(reps), st))
     return {'stats': stats, 'agree': agree, 'status': status, 'replicates': reps, 'columns': cols}
 
 
@@ -1714,11 +1542,7 @@ def fit_bootstrap(plan, Y, K, csf, ear, peaks, maxfasc, csf_on, ear_on, sig_csf=
     V, M = Y.shape
     csf_on, ear_on = bool(csf_on), bool(ear_on)
     npar = num_params(maxfasc, csf_on, ear_on)
-    K = np.ascontiguousarray(np.asarray(K).reshape(-1), dtype=np.int32)
-    if K.shape != (V,):
-        raise ValueError("K should have one entry per voxel")
-    if V and (K.min() < 0 or K.max() > maxfasc):
-        raise ValueError("K should lie in 0..maxfasc = %d" % maxfasc)
+    K = _k_arg(V, maxfasc, K)
     flags = []
     for name, f, on in (("csf", csf, csf_on), ("ear", ear, ear_on)):
         a = None
@@ -1735,7 +1559,7 @@ def fit_bootstrap(plan, Y, K, csf, ear, peaks, maxfasc, csf_on, ear_on, sig_csf=
         if pk.shape != (V, 3 * maxfasc):
             raise ValueError("peaks should have shape (%d, %d)" % (V, 3 * maxfasc))
     sc = L.f64c(sig_csf).reshape(-1) if sig_csf is not None else None
-    se = L.f64c(sig_ear) if sig_ear is not None else None
+    se = L.f64c_opt(sig_ear)
     if csf_on and (sc is None or sc.shape[0] != M):
         raise ValueError("csf_on needs sig_csf with %d entries" % M)
     if ear_on and (se is None or se.shape != (M, E) or E < 1):
@@ -1763,13 +1587,12 @@ def fit_bootstrap(plan, Y, K, csf, ear, peaks, maxfasc, csf_on, ear_on, sig_csf=
     agree = np.zeros((V, maxfasc), dtype=np.int32)
     status = np.zeros(V, dtype=np.int32)
     reps = np.zeros((V, B, npar)) if keep else None
-    opt = lambda a, f: f(a) if a is not None else None
-    L.check(L.lib().mfx_boot_fit(plan.handle(), L.dptr(Y), L.iptr(K), opt(flags[0], L.bptr), opt(flags[1], L.bptr), opt(pk, L.dptr),
-                                 maxfasc, int(csf_on), int(ear_on), opt(sc, L.dptr) if csf_on else None,
-                                 opt(se, L.dptr) if ear_on else None, int(E), opt(p0, L.dptr), opt(gr, L.iptr), opt(vx, L.lptr), V, B,
-                                 code, int(bool(inflate)), int(seed) & _U64, int(offset) & _U64, opt(pr, L.dptr), nprop,
+    L.check(L.lib().mfx_boot_fit(plan.handle(), L.dptr(Y), L.iptr(K), L.opt(flags[0], L.bptr), L.opt(flags[1], L.bptr), L.opt(pk),
+                                 maxfasc, int(csf_on), int(ear_on), L.opt(sc) if csf_on else None,
+                                 L.opt(se) if ear_on else None, int(E), L.opt(p0), L.opt(gr, L.iptr), L.opt(vx, L.lptr), V, B,
+                                 code, int(bool(inflate)), int(seed) & _U64, int(offset) & _U64, L.opt(pr), nprop,
                                  L.dptr(qa) if qa.size else None, int(qa.size), int(max_bytes), L.dptr(stats),
-                                 L.iptr(agree) if maxfasc > 0 else None, L.iptr(status), opt(reps, L.dptr)))
+                                 L.iptr(agree) if maxfasc > 0 else None, L.iptr(status), L.opt(reps)))
     if V:
         L.check(L.lib().mfx_plan_status(plan.handle(), None))   # a direction that is not a unit vector: ValueError
     return {'stats': stats, 'agree': agree, 'status': status, 'replicates': reps, 'columns': cols}
