@@ -75,6 +75,10 @@ ROBUST2D_EXPORTS = ["mfx_robust2d_abi_version", "mfx_rfit2d_batch_dev", "mfx_rfi
 BOOT_EXPORTS = ["mfx_boot_abi_version", "mfx_boot_resample_dev", "mfx_boot_gather_dev", "mfx_boot_reduce_dev",
                 "mfx_boot_fit_dev", "mfx_boot_fit"]
 
+# every symbol include/mfx_boot2d.h declares (bootstrap of 2-D protocols, fits shared per voxel; versioned on its own)
+BOOT2D_EXPORTS = ["mfx_boot2d_abi_version", "mfx_boot2d_rep_tile", "mfx_boot2d_debug_set_force_plain",
+                  "mfx_boot2d_fit_rows_dev", "mfx_boot2d_fit_dev", "mfx_boot2d_fit"]
+
 
 class MfxError(RuntimeError):
     pass
@@ -244,6 +248,15 @@ def lib():
                                    C.c_int, C.c_int, C.c_uint64, C.c_uint64, vp, C.c_int, vp, C.c_int, C.c_int64, vp, vp, vp, vp, vp]
     L.mfx_boot_fit.argtypes = [vp, dp, ip, bp, bp, dp, C.c_int, C.c_int, C.c_int, dp, dp, C.c_int, dp, ip, lp, C.c_int64, C.c_int,
                                C.c_int, C.c_int, C.c_uint64, C.c_uint64, dp, C.c_int, dp, C.c_int, C.c_int64, dp, ip, ip, dp]
+    L.mfx_boot2d_abi_version.restype = C.c_int
+    L.mfx_boot2d_rep_tile.restype = C.c_int
+    L.mfx_boot2d_debug_set_force_plain.argtypes = [C.c_int]
+    L.mfx_boot2d_debug_set_force_plain.restype = None
+    L.mfx_boot2d_fit_rows_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int64, C.c_int, vp, vp, vp]
+    L.mfx_boot2d_fit_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                     C.c_uint64, C.c_uint64, vp, C.c_int, vp, C.c_int, C.c_int64, vp, vp, vp, vp, vp, vp]
+    L.mfx_boot2d_fit.argtypes = [vp, dp, ip, bp, dp, C.c_int, C.c_int, dp, dp, ip, lp, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                 C.c_uint64, C.c_uint64, dp, C.c_int, dp, C.c_int, C.c_int64, dp, ip, ip, ip, dp]
     _lib = L
     return L
 

@@ -622,6 +622,28 @@ class RotateAtom2DTables:
         ``robust_scale``, ``n_rejected`` and ``outlier_mask()``."""
         return _fit2d(self, data, peaks, numfasc, csf_mask, sig_csf, on_error, weights, robust)
 
+    def bootstrap(self, data, peaks, numfasc, fit=None, csf_mask=None, sig_csf=None, on_error='raise', *, B=200, kind='wild',
+                  seed=0, inflate=True, q=(0.025, 0.975), props=None, voxels=None, keep=False, groups=None):
+        """Model-free uncertainty of every estimated parameter (``engine.fit2d_bootstrap``, include/mfx_boot2d.h; the rule is
+        that of include/mfx_boot.h): the residuals of each voxel's own fit - ``fit``, a :class:`Fit2DResult` of these
+        voxels, or a fit made here - are resampled into ``B`` replicate signals, every replicate is fitted as ``fit`` fits
+        it, bit for bit, and the B parameter rows of a voxel are reduced to statistics, all on the device.  ``data``,
+        ``peaks``, ``numfasc``, ``csf_mask``, ``sig_csf`` as for ``fit``; every voxel class is served.  The replicates of a
+        voxel share its directions: for one and two fascicles without a CSF column the rotated dictionaries' column norms
+        and cross-Gram are formed once per voxel, not once per replicate.  ``kind`` 'wild' flips the sign of every
+        residual at random; 'residual' draws, for every measurement, a residual of its group - ``groups`` [M] integers,
+        default ``engine.boot_groups(sch_mat)``: rows sharing (G, Delta, delta); a group of one row redraws its own
+        residual, so that row is its prediction plus its (inflated) residual in every replicate.  ``inflate`` scales the
+        residuals by sqrt(M / (M - number of active compartments)).  ``q``: the quantiles kept.  ``props``: a dict
+        mapping a name to an [N] array of atom properties, whose values at the chosen atoms are bootstrapped too.
+        ``voxels``: positions in this batch (default: all); the random stream is keyed by the batch position, so a subset
+        gives the replicates the whole batch gives.  ``keep``: also return the replicate parameter rows.  A voxel with a
+        failing direction: ``on_error='raise'`` raises the reference's exception for the lowest of them, ``'nan'`` keeps
+        its record in ``dir_status``, status 2 and NaN statistics.  A ``fit`` made with ``weights=`` or ``robust=`` raises
+        NotImplementedError.  Returns a :class:`Bootstrap2DResult`."""
+        return _boot2d(self, data, peaks, numfasc, fit, csf_mask, sig_csf, on_error, B, kind, seed, inflate, q, props, voxels,
+                       keep, groups)
+
     def _predict_args(self, fit_or_params, peaks, sig_csf):
         """Argument checks of predict / residuals / simulate (before any device call): (params, peaks, maxfasc, csf_on, sig_csf)."""
         params = fit_or_params.params if isinstance(fit_or_params, Fit2DResult) else fit_or_params
@@ -841,6 +863,114 @@ class Fit2DResult:
             raise RuntimeError("this fit is not a robust fit (fit(..., robust=...)): it has rejected nothing")
         base = np.ones(self.weights.shape[1], dtype=bool) if self._robust_base is None else np.asarray(self._robust_base) > 0
         return base & (self.weights == 0)
+
+
+class Bootstrap2DResult:
+    """Result of ``RotateAtom2DTables.bootstrap``: flat arrays over the bootstrapped voxels, as :class:`Fit2DResult`'s.
+    ``mean(name)``, ``std(name)``, ``min(name)``, ``max(name)``, ``quantile(name, q)`` and ``n_valid(name)`` are taken over
+    the replicates of a voxel: ``name`` is one of the ``props`` given ([n, maxfasc]; a replicate counts for fascicle k only
+    where its weight nu_k is positive - ``n_valid`` says how many did), 'frac' (the fascicle weights, [n, maxfasc]), or
+    'M0', 'frac_csf', 'MSE' ([n]); these count every replicate.  ``agreement`` [n, maxfasc]: the share of replicates that
+    chose the own fit's atom with a positive weight; ``status`` [n]: 0 fine, 1 no degree of freedom, 2 original row not
+    usable (a non-finite measurement, a failing direction); ``dir_status`` [n, 5]: the failing directions' records of
+    :class:`Fit2DResult`; ``stats`` [n, C, 5 + Q] with ``columns``, the table the members are cut from; ``replicates``
+    [n, B, num_params] with ``keep=True``, else None; ``B``, ``seed``, ``q``, ``voxels`` (the batch positions the rows
+    stand for)."""
+
+    def __init__(self, res, prop_names, q, voxels, maxfasc, csf_on, B, seed):
+        self.stats, self.columns, self.replicates = res['stats'], res['columns'], res['replicates']
+        self.status, self.dir_status = res['status'], res['dir_status']
+        self.B, self.seed, self.q, self.voxels = int(B), seed, np.asarray(q, dtype=np.float64), voxels
+        self.maxfasc, self.csf_on = int(maxfasc), bool(csf_on)
+        self._names = list(prop_names)
+        self.agreement = res['agree'].astype(np.float64) / float(B)
+
+    def _cols(self, name):
+        """(column indices, per fascicle?) of a statistic's name."""
+        if name in self._names:
+            t = self._names.index(name)
+            return [self.columns.index(('prop', k, t)) for k in range(self.maxfasc)], True
+        if name == 'frac':
+            return [self.columns.index('nu_%d' % k) for k in range(self.maxfasc)], True
+        single = {'M0': 'M0', 'MSE': 'MSE'}
+        if self.csf_on:
+            single['frac_csf'] = 'nu_csf'
+        if name in single:
+            return [self.columns.index(single[name])], False
+        raise ValueError("unknown bootstrap statistic %s (have: %s)" % (name, ", ".join(self._names + ['frac'] + sorted(single))))
+
+    def _stat(self, name, i):
+        cols, per_fasc = self._cols(name)
+        return self.stats[:, cols, i] if per_fasc else self.stats[:, cols[0], i]
+
+    def n_valid(self, name):
+        return self._stat(name, 0).astype(np.int64)
+
+    def mean(self, name):
+        return self._stat(name, 1)
+
+    def std(self, name):
+        return self._stat(name, 2)
+
+    def min(self, name):
+        return self._stat(name, 3)
+
+    def max(self, name):
+        return self._stat(name, 4)
+
+    def quantile(self, name, q):
+        """The quantile ``q`` - one of those the bootstrap was asked for (``self.q``) - by linear interpolation."""
+        hit = np.flatnonzero(self.q == float(q))
+        if hit.size == 0:
+            raise ValueError("quantile %r was not asked for (have: %s)" % (q, ", ".join("%g" % x for x in self.q)))
+        return self._stat(name, 5 + int(hit[0]))
+
+
+def _boot2d(T, data, peaks, numfasc, fit, csf_mask, sig_csf, on_error, B, kind, seed, inflate, q, props, voxels, keep, groups,
+            max_bytes=None):
+    """RotateAtom2DTables.bootstrap: every argument is checked before any device call."""
+    B, code, qa = engine._boot_rule(B, kind, q, seed)
+    data, peaks, numfasc, maxfasc = _soft2d_args(T, data, peaks, numfasc, on_error)
+    if maxfasc > 3:
+        raise NotImplementedError("the 2-D protocol fit serves at most 3 fascicles per voxel (peaks holds %d)" % maxfasc)
+    V = data.shape[0]
+    csf = None
+    if csf_mask is not None:
+        csf = np.asarray(csf_mask).astype(bool)
+        if csf.shape != (V,):
+            raise ValueError("csf_mask should have one entry per voxel")
+    csf_on = csf is not None
+    if csf_on and np.any(csf) and sig_csf is None:
+        raise ValueError("voxels flagged CSF need sig_csf")
+    if sig_csf is not None and np.asarray(sig_csf).size != T.M:
+        raise ValueError("sig_csf has %d entries, protocol has %d" % (np.asarray(sig_csf).size, T.M))
+    if csf_on and sig_csf is None:
+        sig_csf = np.zeros(T.M)   # (no voxel is flagged: never read)
+    p0 = None
+    if fit is not None:
+        if not isinstance(fit, Fit2DResult):
+            raise ValueError("fit should be the Fit2DResult of these voxels")
+        if fit.weights is not None or fit.robust_info is not None:
+            raise NotImplementedError("bootstrap of a weighted or robust fit is not served")
+        if fit.params.shape[0] != V or fit.maxfasc != maxfasc or fit.csf_on != csf_on:
+            raise ValueError("fit should hold the same %d voxels in the layout of these arguments (maxfasc = %d, csf %s)"
+                             % (V, maxfasc, csf_on))
+        p0 = fit.params
+    props = _soft2d_props(T, props)
+    names = list(props)
+    pr = np.stack([props[n] for n in names]) if names else None
+    if code == 1 and groups is None:
+        groups = np.unique(T._arrays['sch'][:, 3:6], axis=0, return_inverse=True)[1].reshape(-1)
+    gr = engine._boot_groups_arg(code, groups, T.M, None)
+    vox = np.arange(V) if voxels is None else np.asarray(voxels, dtype=np.int64).reshape(-1)
+    if vox.size and (vox.min() < 0 or vox.max() >= V):
+        raise ValueError("voxels should be positions in the batch (0..%d)" % (V - 1))
+    extra = {} if max_bytes is None else {'max_bytes': max_bytes}
+    res = engine.fit2d_bootstrap(T, data[vox], numfasc[vox], csf[vox] if csf_on else None, peaks[vox], maxfasc, csf_on, sig_csf,
+                                 B=B, kind=kind, seed=seed, inflate=inflate, q=qa, props=pr, groups=gr,
+                                 params=np.ascontiguousarray(p0[vox]) if p0 is not None else None, vox=vox, keep=keep, **extra)
+    _soft2d_raise(T, res['dir_status'], on_error)
+    return Bootstrap2DResult(res, names, qa, vox, maxfasc, csf_on, B, seed)
 
 
 def _w2d_weights(T, weights, V):
