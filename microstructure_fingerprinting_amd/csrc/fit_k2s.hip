@@ -51,6 +51,11 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 //             (Cauchy-Schwarz), the hi.lo / lo.hi addends 2^-10 of it:  39 x 5.1 x 2^-24 x 1.002                -> 1.19e-5
 //   total 1.43e-5 <= MFX_S_DC.  (Measured: worst 1.14e-6 over 46 M adversarial pairs, tools/micro/split_mfma_error.hip;
 //   and every voxel audits one pseudo-random pair of its own, k2s_shared.h.)
+//   The 16-row form of the shared last row tile (k2s_round.h) runs v_mfma_f32_16x16x32_f16: 33 addends per instruction,
+//   3 (KS + 1) / 2 dependent instructions (21 at KS = 13).  The same families through that instruction: kappa_16 = 5.20
+//   (profiles/tail16_micro_mfma_sum_model.txt), and 21 x 5.20 = 109 <= 39 x 5.1 = 199 (kappa_16 <= 9.4 would do; likewise
+//   24 x 5.20 <= 48 x 5.1 at KS = 16): the statement holds unchanged and that tile screens with the same DC.  Measured with
+//   the kernel's split and order at K = 208: worst |c~ - c| 1.16e-6 (1.18e-6 at K = 256; profiles/tail16_micro_split_mfma_error.txt).
 #ifndef MFX_S_DC
 #define MFX_S_DC 1.5e-5
 #endif
@@ -121,6 +126,7 @@ __device__ __forceinline__ void mfx_split16(float f, _Float16& hi, _Float16& lo)
 }
 
 #include "k2s_shared.h"
+#include "k2s_tail16_map.h"
 
 // BR: the protocol has G-bracketed rows (screening through the plan's virtual shells, exact stage as mfx_eval_br)
 // NB: LDS images of D2 chunks: 3 (one workgroup barrier per chunk) where they fit beside the rest, else 2 (two barriers)

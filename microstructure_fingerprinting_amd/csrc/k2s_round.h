@@ -13,6 +13,12 @@
     // same read of the table (ranking only, as in phase 1; a lane sums its half of the rows, the halves meet
     // through one cross-lane exchange): the L2 -> L1 fill rate bounds these passes, not the arithmetic.
     h8 afh[KS], afl[KS];
+#if K2S_ROUND_MODE == 1
+    // 16-ROW FORM (the fused pass only): a last row tile with at most 16 atoms (N = 782: 14) runs on v_mfma_f32_16x16x32_f16;
+    // its A operand is made where it is used, in the tail branch below
+    const bool t16 = N - 32 * (ntiles - 1) <= 16;   // wave-uniform
+    if (!t16)
+#endif
     {
       const int n = rtc * 32 + lr;
       const int nn = min(n, ldn - 1);
@@ -112,6 +118,88 @@
 #else
 #define MFX_SCAN_T(k) do { } while (0)
 #endif
+    // the FP64 criteria of ONE register group with a passing pair: row atom i, column atom j (per lane), the raw accumulator
+    // value and the column statistics.  One out-of-line copy for the sweeps, the shared tile and its 16-row form.
+    auto scan_pair = [&](const int i, const int j, const float accv, const double z2, const double n2d) {
+      const double n12 = (double)s_cs[i] * n2d;
+      const double c = n12 > 0.0 ? (double)accv * mfx_rcp_nr(n12) : 0.0;
+      const double z1 = (double)s_Zf[i];
+      const double e1 = fma(-c, z2, z1);
+      const double e2 = fma(-c, z1, z2);
+      const double den = fma(-c, c, 1.0);
+      const double num = fma(z2, e2, z1 * e1);
+      const bool pos = (e1 > -etol) & (e2 > -etol);      // false for padded atoms (z = -inf)
+      // (dS/dc = -2 w1 w2 <= |y|^2 needs c >= 0; pairs at an obtuse angle - no physical dictionary has them -
+      // go through the interval bound like the ill-conditioned ones)
+      const bool wellc = (den >= MFX_S_DENMIN) & (c >= 0.0);
+      const bool hit = pos & wellc & (fma(-thr, den, num) >= 0.0);
+      const bool near = pos & !wellc;
+      if (!__any(hit | near)) return;
+      double S = -1.0;
+      if (hit) {
+        S = num * mfx_rcp_nr(den);
+      } else if (near) {
+        // ill-conditioned pair: interval upper bound of S over |c - c~| <= DC;
+        // S = z2^2 + e1^2/den = z1^2 + e2^2/den for two positive weights
+        const double dlo = den - 2.0 * dc_eff - dc_eff * dc_eff;
+        const double u1 = fabs(e1) + etol, u2 = fabs(e2) + etol;
+        S = (dlo > 0.0 && c > -0.5) ? fmin(fma(z2, z2, u1 * u1 / dlo), fma(z1, z1, u2 * u2 / dlo)) + mrg : 1e300;
+      }
+      // raise the threshold with the best SCORE of this wave instruction first (an interval bound is not
+      // a score and never raises it), then append only what still reaches it: no burst of stale entries
+      bool feas = hit;
+      double q1x = 0.0, q2x = 0.0;   // (XC) u / |d'| of the two atoms
+      if constexpr (XC) {
+        // a relaxed score may raise the threshold only if it is the score of a feasible support: x's weight
+        // w_x = yx - w1 u1 - w2 u2, w_i = e_i / (den |d_i'|), clearly non-negative (e carries an error <= etol,
+        // u/|d'| <= 4)
+        q1x = (double)s_uf[i] * mfx_rcp_nr(fmax((double)s_cs[i], 1e-300));
+        q2x = (double)s_uf[NP + j] * mfx_rcp_nr(fmax(n2d, 1e-300));
+        feas = hit && (fma(-e2, q2x, fma(-e1, q1x, yx * den)) >= 8.0 * etol);
+      }
+      double sraise = feas ? S : 0.0;
+      double slist = S;   // what the pair is listed with: an upper bound of the best score of its supports with BOTH atoms
+      if constexpr (XC) {
+        // x would get a negative weight: the pair's PLAIN two-atom score (x left out) is feasible and raises the
+        // threshold instead - without it a voxel with no x signal never leaves the single-atom threshold, floods
+        // the ring and ends up on the FP64 kernel.  Unprojected statistics from the projected ones:
+        // |d|^2 = |d'|^2 + u^2, d.y = z' |d'| + u yx, d1.d2 = d1'.d2' + u1 u2; scores here are minus yx^2.
+        if (__any(hit && !feas)) {
+          const double n1p = (double)s_cs[i], u1 = (double)s_uf[i], u2 = (double)s_uf[NP + j];
+          const double m1 = fma(u1, u1, n1p * n1p), m2 = fma(u2, u2, n2d * n2d);
+          const double i1 = mfx_rcp_nr(fmax(sqrt(m1), 1e-300)), i2 = mfx_rcp_nr(fmax(sqrt(m2), 1e-300));
+          const double w1 = fma(u1, yx, z1 * n1p) * i1, w2 = fma(u2, yx, z2 * n2d) * i2;   // d.y / |d|
+          const double c0 = fma(u1, u2, (double)accv) * i1 * i2;
+          const double f1 = fma(-c0, w2, w1), f2 = fma(-c0, w1, w2), den0 = fma(-c0, c0, 1.0);
+          const bool ok0 = hit && !feas && (f1 > etol) && (f2 > etol) && (den0 >= MFX_S_DENMIN) && (c0 >= 0.0) && (m1 > 0.0) && (m2 > 0.0);
+          if (ok0) sraise = fma(w2, f2, w1 * f1) * mfx_rcp_nr(den0) - yx * yx;
+          // A pair whose relaxed optimum CLEARLY gives x a negative weight (both atoms clearly active in it) has x
+          // inactive in its NNLS optimum: that optimum is the plain two-atom problem's.  Listed with the plain score
+          // then, or - one atom clearly inactive there - not at all (supports with one atom are the list kernel's
+          // own).  Without this a flagged voxel WITHOUT x signal lists every pair its loose relaxed bound lets
+          // through: 17 % of such voxels overflowed their list and went to the FP64 kernel.
+          const bool xneg = hit && (e1 > etol) && (e2 > etol) && (fma(-e2, q2x, fma(-e1, q1x, yx * den)) <= -8.0 * etol) &&
+                            (den0 >= MFX_S_DENMIN) && (c0 >= 0.0) && (m1 > 0.0) && (m2 > 0.0);
+          if (xneg) {
+            if (ok0) slist = sraise + mrg;
+            else if (f1 < -etol || f2 < -etol) slist = -1.0;
+          }
+        }
+      }
+      const double smax = mfx_wave_max_down(fmax(sraise, 0.0));
+      if (smax - 2.0 * mrg > thr) {
+        thr = smax - 2.0 * mrg;
+        if (lane == 0) atomicMax(&s_thr[0], mfx_nonneg_bits(thr));
+      }
+      if ((hit | near) && slist >= thr) push(slist, i, hit ? j : (j | MFX_S_BOUND));
+#ifdef MFX_STAMPS_SCAN
+      if (a.stamps && round == 0 && dbg_calls == 1 && wave == 0 && lane == 0) {
+        unsigned long long* st = a.stamps + (size_t)blockIdx.x * 16;
+        if (st[15] < 8) st[4 + st[15]] = __builtin_amdgcn_s_memtime();   // end of the first 8 evaluated groups
+        ++st[15];
+      }
+#endif
+    };
     auto scan_main = [&](const f32x16& acc, int ct) {
 #ifdef MFX_STAMPS_SCAN
       ++dbg_calls;
@@ -187,85 +275,7 @@
 #ifdef MFX_STAMPS_RND
             ++dbg_groups;
 #endif
-            const int i = rt * 32 + (g & 3) + 8 * (g >> 2) + 4 * lh;
-            const double n12 = (double)s_cs[i] * n2d;
-            const double c = n12 > 0.0 ? (double)acc[g] * mfx_rcp_nr(n12) : 0.0;
-            const double z1 = (double)s_Zf[i];
-            const double e1 = fma(-c, z2, z1);
-            const double e2 = fma(-c, z1, z2);
-            const double den = fma(-c, c, 1.0);
-            const double num = fma(z2, e2, z1 * e1);
-            const bool pos = (e1 > -etol) & (e2 > -etol);      // false for padded atoms (z = -inf)
-            // (dS/dc = -2 w1 w2 <= |y|^2 needs c >= 0; pairs at an obtuse angle - no physical dictionary has them -
-            // go through the interval bound like the ill-conditioned ones)
-            const bool wellc = (den >= MFX_S_DENMIN) & (c >= 0.0);
-            const bool hit = pos & wellc & (fma(-thr, den, num) >= 0.0);
-            const bool near = pos & !wellc;
-            if (!__any(hit | near)) continue;
-            double S = -1.0;
-            if (hit) {
-              S = num * mfx_rcp_nr(den);
-            } else if (near) {
-              // ill-conditioned pair: interval upper bound of S over |c - c~| <= DC;
-              // S = z2^2 + e1^2/den = z1^2 + e2^2/den for two positive weights
-              const double dlo = den - 2.0 * dc_eff - dc_eff * dc_eff;
-              const double u1 = fabs(e1) + etol, u2 = fabs(e2) + etol;
-              S = (dlo > 0.0 && c > -0.5) ? fmin(fma(z2, z2, u1 * u1 / dlo), fma(z1, z1, u2 * u2 / dlo)) + mrg : 1e300;
-            }
-            // raise the threshold with the best SCORE of this wave instruction first (an interval bound is not
-            // a score and never raises it), then append only what still reaches it: no burst of stale entries
-            bool feas = hit;
-            double q1x = 0.0, q2x = 0.0;   // (XC) u / |d'| of the two atoms
-            if constexpr (XC) {
-              // a relaxed score may raise the threshold only if it is the score of a feasible support: x's weight
-              // w_x = yx - w1 u1 - w2 u2, w_i = e_i / (den |d_i'|), clearly non-negative (e carries an error <= etol,
-              // u/|d'| <= 4)
-              q1x = (double)s_uf[i] * mfx_rcp_nr(fmax((double)s_cs[i], 1e-300));
-              q2x = (double)s_uf[NP + j] * mfx_rcp_nr(fmax(n2d, 1e-300));
-              feas = hit && (fma(-e2, q2x, fma(-e1, q1x, yx * den)) >= 8.0 * etol);
-            }
-            double sraise = feas ? S : 0.0;
-            double slist = S;   // what the pair is listed with: an upper bound of the best score of its supports with BOTH atoms
-            if constexpr (XC) {
-              // x would get a negative weight: the pair's PLAIN two-atom score (x left out) is feasible and raises the
-              // threshold instead - without it a voxel with no x signal never leaves the single-atom threshold, floods
-              // the ring and ends up on the FP64 kernel.  Unprojected statistics from the projected ones:
-              // |d|^2 = |d'|^2 + u^2, d.y = z' |d'| + u yx, d1.d2 = d1'.d2' + u1 u2; scores here are minus yx^2.
-              if (__any(hit && !feas)) {
-                const double n1p = (double)s_cs[i], u1 = (double)s_uf[i], u2 = (double)s_uf[NP + j];
-                const double m1 = fma(u1, u1, n1p * n1p), m2 = fma(u2, u2, n2d * n2d);
-                const double i1 = mfx_rcp_nr(fmax(sqrt(m1), 1e-300)), i2 = mfx_rcp_nr(fmax(sqrt(m2), 1e-300));
-                const double w1 = fma(u1, yx, z1 * n1p) * i1, w2 = fma(u2, yx, z2 * n2d) * i2;   // d.y / |d|
-                const double c0 = fma(u1, u2, (double)acc[g]) * i1 * i2;
-                const double f1 = fma(-c0, w2, w1), f2 = fma(-c0, w1, w2), den0 = fma(-c0, c0, 1.0);
-                const bool ok0 = hit && !feas && (f1 > etol) && (f2 > etol) && (den0 >= MFX_S_DENMIN) && (c0 >= 0.0) && (m1 > 0.0) && (m2 > 0.0);
-                if (ok0) sraise = fma(w2, f2, w1 * f1) * mfx_rcp_nr(den0) - yx * yx;
-                // A pair whose relaxed optimum CLEARLY gives x a negative weight (both atoms clearly active in it) has x
-                // inactive in its NNLS optimum: that optimum is the plain two-atom problem's.  Listed with the plain score
-                // then, or - one atom clearly inactive there - not at all (supports with one atom are the list kernel's
-                // own).  Without this a flagged voxel WITHOUT x signal lists every pair its loose relaxed bound lets
-                // through: 17 % of such voxels overflowed their list and went to the FP64 kernel.
-                const bool xneg = hit && (e1 > etol) && (e2 > etol) && (fma(-e2, q2x, fma(-e1, q1x, yx * den)) <= -8.0 * etol) &&
-                                  (den0 >= MFX_S_DENMIN) && (c0 >= 0.0) && (m1 > 0.0) && (m2 > 0.0);
-                if (xneg) {
-                  if (ok0) slist = sraise + mrg;
-                  else if (f1 < -etol || f2 < -etol) slist = -1.0;
-                }
-              }
-            }
-            const double smax = mfx_wave_max_down(fmax(sraise, 0.0));
-            if (smax - 2.0 * mrg > thr) {
-              thr = smax - 2.0 * mrg;
-              if (lane == 0) atomicMax(&s_thr[0], mfx_nonneg_bits(thr));
-            }
-            if ((hit | near) && slist >= thr) push(slist, i, hit ? j : (j | MFX_S_BOUND));
-#ifdef MFX_STAMPS_SCAN
-            if (a.stamps && round == 0 && dbg_calls == 1 && wave == 0 && lane == 0) {
-              unsigned long long* st = a.stamps + (size_t)blockIdx.x * 16;
-              if (st[15] < 8) st[4 + st[15]] = __builtin_amdgcn_s_memtime();   // end of the first 8 evaluated groups
-              ++st[15];
-            }
-#endif
+            scan_pair(rt * 32 + (g & 3) + 8 * (g >> 2) + 4 * lh, j, acc[g], z2, n2d);
           }
         }
         MFX_SCAN_T(3);
@@ -277,10 +287,15 @@
     if (tail) continue;
 #endif
     if (tail) {
+#if K2S_ROUND_MODE == 1
+      if (!t16)
+#endif
+      {
 #ifdef MFX_STAMPS_RND
       if (a.stamps && tid == 0 && round < 4) a.stamps[(size_t)blockIdx.x * 16 + 2 * round + 1] = __builtin_amdgcn_s_memtime();
 #endif
       thr = __longlong_as_double((long long)s_thr[0]);
+      }
       // (!XC: the fused pass) D2's statistics from the values that make the B operand, as the A-operand code does for D1:
       // a lane sums its half of the rows of column n in FP64, the halves meet through one cross-lane exchange.  The wave
       // then owns the statistics of its column tiles: it writes them, folds them into its best single atom of D2 and into
@@ -290,6 +305,211 @@
       [[maybe_unused]] double* const s_bs2 = s_red + 8 + wave;
       [[maybe_unused]] int* const s_bn2 = (int*)(s_red + 16) + 8 + wave;
       if constexpr (!XC) { if (lane == 0) { *s_bs2 = 0.0; *s_bn2 = 0; } }
+#if K2S_ROUND_MODE == 1
+      if (t16) {
+        // 16-ROW FORM (the fused pass only): a last row tile with at most 16 atoms (N = 782: 14) runs on v_mfma_f32_16x16x32_f16,
+        // index maps in k2s_tail16_map.h.  Lane 16 g + c holds the rows 32 s + 8 g + j of step s: of atom c of the tile here,
+        // of the two adjacent atoms 2c, 2c+1 of a column tile - ONE 16-byte table load each - in the column loop below.  Half
+        // the A registers and wave loads of the 32-row form, whose rows 16..31 would all be zeros.
+        constexpr int NS16 = k2s_t16_steps(KS);
+        const int g16 = lane >> 4;   // lane group
+        h8 a16h[NS16], a16l[NS16];
+        {   // A operand and D1's statistics of the tile, as at the top of the round for 32 rows
+          const int n = rtc * 32 + k2s_t16_arow(lane);
+          const int nn = min(n, ldn - 1);
+          double a2 = 0.0, ay = 0.0;
+          mfx_static_for<0, NS16>([&](auto sc) {
+            constexpr int s = decltype(sc)::value;
+            // (odd KS, last step: the lane groups 2 and 3 lie beyond MP - zeros, and the constants of rows that exist)
+            const int m0 = k2s_t16_row(lane, 0, s, KS);
+            const bool inr = m0 >= 0;
+            const int mb = inr ? m0 : 32 * s;
+            float2 d[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) d[j] = tab32_at(s_rs[mb + j], nn);
+            h8 vh, vl;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+              float fv = fmaf(d[j].y, s_t0f[mb + j], d[j].x);
+              fv = inr ? fv : 0.0f;
+              const double fd = (double)fv;
+              a2 = fma(fd, fd, a2);
+              ay = fma((double)s_yf[mb + j], fd, ay);
+              _Float16 x, y;
+              mfx_split16(fv, x, y);
+              vh[j] = x; vl[j] = y;
+            }
+            asm volatile("" : "+v"(vh), "+v"(vl));   // materialise here: the conversions must not sink below all loads
+            a16h[s] = vh; a16l[s] = vl;
+            __builtin_amdgcn_sched_barrier(0);
+          });
+          // the four lane groups hold a quarter of the rows each: two exchanges, the same value in all four
+          a2 += __shfl_xor(a2, 16); ay += __shfl_xor(ay, 16);
+          a2 += __shfl_xor(a2, 32); ay += __shfl_xor(ay, 32);
+          const bool act = n < N;
+          const double nrm = sqrt(a2);
+          const double inv = (act && a2 > 0.0) ? 1.0 / nrm : 0.0;
+          const double z = ay * inv;
+          if (g16 == 0) {
+            s_Zf[n] = act ? (float)z : -1e30f;
+            s_cs[n] = (act && a2 > 0.0) ? (float)nrm : 0.0f;
+          } else if (g16 == 1) {   // slots 16..31 of the tile: no such atoms
+            s_Zf[n + 16] = -1e30f;
+            s_cs[n + 16] = 0.0f;
+          }
+          double sb = (act && z > 0.0) ? z * z : 0.0;
+#pragma unroll
+          for (int o = 8; o > 0; o >>= 1) sb = fmax(sb, __shfl_xor(sb, o));
+          sb = mfx_readlane_f64(sb, 0);
+          // a pair matters only if it beats every single atom
+          if (lane == 0 && sb - mrg > 0.0) atomicMax(&s_thr[0], mfx_nonneg_bits(sb - mrg));
+        }
+#ifdef MFX_STAMPS_RND
+        if (a.stamps && tid == 0 && round < 4) a.stamps[(size_t)blockIdx.x * 16 + 2 * round + 1] = __builtin_amdgcn_s_memtime();
+#endif
+        thr = __longlong_as_double((long long)s_thr[0]);
+        // ---- 16-row form of the column loop: the 32 atoms of a column tile as two 16-column sub-tiles, the even atoms
+        // (sub-tile 0) and the odd ones (1); a lane's 16-byte load {ylo, slope} x 2 feeds its own column of both.
+        for (int ct = wave; ct < ntiles; ct += NW) {
+          const int n0 = ct * 32 + k2s_t16_atom(lane, 0);   // this lane's atoms: n0 (sub-tile 0), n0 + 1 (sub-tile 1)
+          const int nn = min(n0, ldn - 2);                  // ldn is even: the pair stays inside the row
+          double a2[2] = {0.0, 0.0}, ay[2] = {0.0, 0.0};
+          f32x4 acc16[2];
+#pragma unroll
+          for (int t = 0; t < 2; ++t) acc16[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+          f32x4 d[2][8];   // table entries of step s (in use) and s + 1 (in flight)
+          {
+            const int mb = MP + k2s_t16_row(lane, 0, 0, KS);   // (step 0 lies inside MP for every KS >= 2)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) d[0][j] = tab32x2_at(s_rs[mb + j], nn);
+          }
+          static_assert(KS >= 2, "step 0 of the 16-row form must lie inside MP");
+          mfx_static_for<0, NS16>([&](auto sc) {
+            constexpr int s = decltype(sc)::value;
+            int lk = lane;   // (bracketed rows: an opaque copy per step keeps each LDS address next to its use, as in the 32-row form)
+            if constexpr (BR) asm volatile("" : "+v"(lk));
+            if constexpr (s + 1 < NS16) {
+              const int m1 = k2s_t16_row(lk, 0, s + 1, KS);
+              const int mb1 = MP + (m1 >= 0 ? m1 : 32 * (s + 1));
+#pragma unroll
+              for (int j = 0; j < 8; ++j) d[(s + 1) & 1][j] = tab32x2_at(s_rs[mb1 + j], nn);
+            }
+            const int m0 = k2s_t16_row(lk, 0, s, KS);
+            const bool inr = m0 >= 0;
+            const int mb = inr ? m0 : 32 * s;
+            h8 bh[2], bl[2];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+              const float t0 = s_t0f[MP + mb + j];
+              const double yj = (double)s_yf[mb + j];
+              const f32x4 e = d[s & 1][j];
+              float fv[2] = {fmaf(e[1], t0, e[0]), fmaf(e[3], t0, e[2])};
+#pragma unroll
+              for (int t = 0; t < 2; ++t) {
+                fv[t] = inr ? fv[t] : 0.0f;
+                const double fd = (double)fv[t];
+                a2[t] = fma(fd, fd, a2[t]);
+                ay[t] = fma(yj, fd, ay[t]);
+                _Float16 x, y;
+                mfx_split16(fv[t], x, y);
+                bh[t][j] = x; bl[t][j] = y;
+              }
+            }
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+              acc16[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a16h[s], bh[t], acc16[t], 0, 0, 0);
+              acc16[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a16h[s], bl[t], acc16[t], 0, 0, 0);
+              acc16[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a16l[s], bh[t], acc16[t], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+          });
+          // column statistics: the four lane groups hold a quarter of the rows each
+          float zf[2], nf[2];
+          double sbt[2];
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            a2[t] += __shfl_xor(a2[t], 16); ay[t] += __shfl_xor(ay[t], 16);
+            a2[t] += __shfl_xor(a2[t], 32); ay[t] += __shfl_xor(ay[t], 32);
+            const bool act = n0 + t < N;
+            const double nrm = sqrt(a2[t]);
+            const double inv = (act && a2[t] > 0.0) ? 1.0 / nrm : 0.0;
+            const double z = ay[t] * inv;
+            zf[t] = act ? (float)z : -1e30f;
+            nf[t] = (act && a2[t] > 0.0) ? (float)nrm : 0.0f;
+            sbt[t] = (act && z > 0.0) ? z * z : 0.0;
+          }
+          if (g16 == 0) {   // (all four groups hold the same values)
+            *(float2*)(s_Zf + NP + n0) = float2{zf[0], zf[1]};
+            *(float2*)(s_cs + NP + n0) = float2{nf[0], nf[1]};
+          }
+          double sb = sbt[0];
+          int nb = n0;
+          if (sbt[1] > sb) { sb = sbt[1]; nb = n0 + 1; }
+#pragma unroll
+          for (int o = 8; o > 0; o >>= 1) {
+            const double s2 = __shfl_xor(sb, o);
+            const int n2 = __shfl_xor(nb, o);
+            const bool take = (s2 > sb) || (s2 == sb && n2 < nb);
+            sb = take ? s2 : sb;
+            nb = take ? n2 : nb;
+          }
+          sb = mfx_readlane_f64(sb, 0);
+          nb = __builtin_amdgcn_readfirstlane(nb);
+          if (lane == 0) {
+            const double b2 = *s_bs2;
+            if (sb > b2 || (sb == b2 && sb > 0.0 && nb < *s_bn2)) { *s_bs2 = sb; *s_bn2 = nb; }
+          }
+          // a pair matters only if it beats every single atom: the threshold rises BEFORE the tile is screened
+          if (lane == 0 && sb - mrg > 0.0) atomicMax(&s_thr[0], mfx_nonneg_bits(sb - mrg));
+          __builtin_amdgcn_wave_barrier();
+          // ---- pair screen of the two 16x16 accumulator tiles: the test of scan_main, row i = rt*32 + 4 g + r, column n0 + t
+          thr = fmax(thr, __longlong_as_double((long long)s_thr[0]));
+          const float rth = __builtin_amdgcn_rsqf(fmaxf((float)thr * (1.0f - 2e-7f), 1e-30f)) * (1.0f + 4e-7f);
+          float* pqw = s_pq + wave * 64;   // [0..15] P', [16..31] Q' of the 16 rows
+          if (thr > thr_rows) {   // wave-uniform: the threshold rose since this wave's row constants were made
+            thr_rows = thr;
+            if (lane < 16) {
+              const float z1 = s_Zf[rtc * 32 + lane], n1 = s_cs[rtc * 32 + lane];
+              float P, Q;
+              pq_of(z1, rth, P, Q);
+              const bool ok = n1 > 0.0f;   // (beyond N: constants that do not pass, as in scan_main)
+              pqw[lane] = ok ? (P + DCF) * n1 : 0.0f;
+              pqw[16 + lane] = ok ? Q * ((1.0f - DCF) * n1) : 1e18f;
+            }
+          }
+          const f32x4 p1 = *(const f32x4*)(pqw + 4 * g16), q1 = *(const f32x4*)(pqw + 16 + 4 * g16);
+          float p2[2], q2[2], mm[2];
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            float P2, Q2;
+            pq_of(zf[t], rth, P2, Q2);
+            const bool colok = nf[t] > 0.0f;
+            p2[t] = colok ? (P2 + DCF) * nf[t] : -1e18f;
+            q2[t] = colok ? Q2 * ((1.0f - DCF) * nf[t]) : 1e18f;
+            float tt[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) tt[r] = fmaf(-q1[r], q2[t], fmaf(p1[r], p2[t], -acc16[t][r]));
+            mm[t] = fmaxf(fmaxf(tt[0], tt[1]), fmaxf(tt[2], tt[3]));
+          }
+          if (__any(fmaxf(mm[0], mm[1]) >= 0.0f)) {
+#ifdef MFX_STAMPS_RND
+            ++dbg_flagged;
+#endif
+#pragma unroll 1
+            for (int u = 0; u < 8; ++u) {   // register group u = 4 t + r, one by one as in scan_main
+              const int t = u >> 2, r = u & 3;
+              const float av = t ? acc16[1][r] : acc16[0][r];
+              const float p2t = t ? p2[1] : p2[0], q2t = t ? q2[1] : q2[0];
+              if (!__any(fmaf(-q1[r], q2t, fmaf(p1[r], p2t, -av)) >= 0.0f)) continue;
+#ifdef MFX_STAMPS_RND
+              ++dbg_groups;
+#endif
+              scan_pair(rt * 32 + k2s_t16_crow(lane, r), n0 + t, av, (double)(t ? zf[1] : zf[0]), (double)(t ? nf[1] : nf[0]));
+            }
+          }
+        }
+      } else
+#endif
       for (int ct = wave; ct < ntiles; ct += NW) {
         const int n = ct * 32 + lr;
         const int nn = min(n, ldn - 1);

@@ -12,6 +12,8 @@
 //     split FP32 operands) the same against the exact FP64 dot product of the FP32 operands, in cosine units.
 // Rows of A carry 32 different test cases per instruction; all columns of B carry the same b.  Build + run:
 //   hipcc -O3 --offload-arch=gfx950 -I../../microstructure_fingerprinting_amd/csrc mfma_sum_model.hip -o bin/mfma_sum_model && bin/mfma_sum_model
+// With the argument 16x16x32 the same families go through v_mfma_f32_16x16x32_f16 (32 products per instruction, 16 cases per
+// wave): the instruction of the screening kernel's 16-row form.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -45,6 +47,29 @@ __global__ __launch_bounds__(64) void one_mfma(const _Float16* __restrict__ A, c
   }
 }
 
+// the same for v_mfma_f32_16x16x32_f16: A [16 x 32] halfs (row = case), b [32] halfs (shared by the 16 columns), c [16];
+// operand and accumulator maps as in csrc/k2s_tail16_map.h
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(64) void one_mfma16(const _Float16* __restrict__ A, const _Float16* __restrict__ B, const float* __restrict__ C,
+                                                 float* __restrict__ D) {
+  const int lane = threadIdx.x, c = lane & 15, g = lane >> 4;
+  const size_t blk = blockIdx.x;
+  h8 a, b;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    a[j] = A[(blk * 16 + c) * 32 + 8 * g + j];
+    b[j] = B[blk * 32 + 8 * g + j];
+  }
+  f32x4 acc;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) acc[r] = C[blk * 16 + 4 * g + r];   // row of accumulator register r
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, acc, 0, 0, 0);
+  if (c == 0) {   // column 0
+#pragma unroll
+    for (int r = 0; r < 4; ++r) D[blk * 16 + 4 * g + r] = acc[r];
+  }
+}
+
 static float h2f(_Float16 h) { return (float)h; }
 
 struct Fam {
@@ -53,13 +78,18 @@ struct Fam {
   double kmax = 0, ksum = 0;
 };
 
-int main() {
-  const int blocks = 1 << 15;              // 32 cases each: ~1e6 cases per family
-  const size_t ncase = (size_t)blocks * 32;
+int main(int argc, char** argv) {
+  // "16x16x32" as first argument: v_mfma_f32_16x16x32_f16 (33 addends: the 16-row form of the shared last row tile, k2s_round.h)
+  const bool t16 = argc > 1 && !strcmp(argv[1], "16x16x32");
+  const int KK = t16 ? 32 : 16;   // products per instruction
+  const int RR = t16 ? 16 : 32;   // cases (rows of A) per instruction
+  printf("%s: %d products + the accumulator per instruction\n", t16 ? "v_mfma_f32_16x16x32_f16" : "v_mfma_f32_32x32x16_f16", KK);
+  const int blocks = 1 << 15;              // RR cases each: ~1e6 cases per family
+  const size_t ncase = (size_t)blocks * RR;
   std::mt19937_64 rng(987654321);
   std::uniform_real_distribution<double> U(0.0, 1.0);
   std::normal_distribution<double> Nrm(0.0, 1.0);
-  std::vector<_Float16> A(ncase * 16), B((size_t)blocks * 16);
+  std::vector<_Float16> A(ncase * KK), B((size_t)blocks * KK);
   std::vector<float> C(ncase), D(ncase);
   _Float16 *dA, *dB;
   float *dC, *dD;
@@ -69,14 +99,15 @@ int main() {
     (void)hipMemcpy(dA, A.data(), A.size() * 2, hipMemcpyHostToDevice);
     (void)hipMemcpy(dB, B.data(), B.size() * 2, hipMemcpyHostToDevice);
     (void)hipMemcpy(dC, C.data(), C.size() * 4, hipMemcpyHostToDevice);
-    hipLaunchKernelGGL(one_mfma, dim3(blocks), dim3(64), 0, 0, dA, dB, dC, dD);
+    if (t16) hipLaunchKernelGGL(one_mfma16, dim3(blocks), dim3(64), 0, 0, dA, dB, dC, dD);
+    else hipLaunchKernelGGL(one_mfma, dim3(blocks), dim3(64), 0, 0, dA, dB, dC, dD);
     (void)hipMemcpy(D.data(), dD, D.size() * 4, hipMemcpyDeviceToHost);
     Fam f; f.name = name;
     for (size_t q = 0; q < ncase; ++q) {
       long double ex = (long double)C[q];
       double mx = std::fabs((double)C[q]), sm = std::fabs((double)C[q]);
-      for (int k = 0; k < 16; ++k) {
-        const double p = (double)h2f(A[q * 16 + k]) * (double)h2f(B[(q / 32) * 16 + k]);   // exact: 11 x 11 bits
+      for (int k = 0; k < KK; ++k) {
+        const double p = (double)h2f(A[q * KK + k]) * (double)h2f(B[(q / RR) * KK + k]);   // exact: 11 x 11 bits
         ex += (long double)p;
         mx = std::fmax(mx, std::fabs(p));
         sm += std::fabs(p);
@@ -103,26 +134,26 @@ int main() {
   note(run("c = 2^24, sixteen products of 1 (exact: 2^24 + 16)"));
   // 2. one product swamps the others: 4096*4096 = 2^24 first / last, fifteen 1s, c = 0 (exact 2^24 + 15: a rounding tie)
   for (size_t q = 0; q < ncase; ++q)
-    for (int k = 0; k < 16; ++k) A[q * 16 + k] = H(k == (int)(q % 16) ? 4096.0 : 1.0);
+    for (int k = 0; k < KK; ++k) A[q * KK + k] = H(k == (int)(q % KK) ? 4096.0 : 1.0);
   for (size_t b = 0; b < (size_t)blocks; ++b)
-    for (int k = 0; k < 16; ++k) B[b * 16 + k] = H(1.0);
+    for (int k = 0; k < KK; ++k) B[b * KK + k] = H(1.0);
   // (b is shared by the 32 cases of a block: put the large factor in a only: 4096 * 1 = 2^12; c carries the 2^24)
   for (auto& v : C) v = 16777216.0f + 0.0f;
   note(run("c = 2^24, one product 2^12 at position q mod 16, fifteen products of 1"));
   // 3. cancellation: +P, -P, and small addends that a limited-width aligner would drop (P = 2^20, smalls ~ 2^-6)
   for (size_t q = 0; q < ncase; ++q)
-    for (int k = 0; k < 16; ++k) A[q * 16 + k] = H(k == 0 ? 1024.0 : (k == 1 ? -1024.0 : std::ldexp(1.0 + (double)((q * 16 + k) % 7) / 8.0, -6)));
+    for (int k = 0; k < KK; ++k) A[q * KK + k] = H(k == 0 ? 1024.0 : (k == 1 ? -1024.0 : std::ldexp(1.0 + (double)((q * KK + k) % 7) / 8.0, -6)));
   for (size_t b = 0; b < (size_t)blocks; ++b)
-    for (int k = 0; k < 16; ++k) B[b * 16 + k] = H(k < 2 ? 1024.0 : 1.0);
+    for (int k = 0; k < KK; ++k) B[b * KK + k] = H(k < 2 ? 1024.0 : 1.0);
   for (auto& v : C) v = 0.0f;
   note(run("+2^20, -2^20 and fourteen addends ~2^-6 (26 binades below), c = 0"));
   // 3b. the same with the small addends 2^-12 .. 2^-18 (32 .. 38 binades below the cancelling pair)
   for (size_t q = 0; q < ncase; ++q)
-    for (int k = 0; k < 16; ++k) A[q * 16 + k] = H(k == 0 ? 1024.0 : (k == 1 ? -1024.0 : std::ldexp(1.0 + (double)((q + k) % 5) / 8.0, -12 - (int)(q % 7))));
+    for (int k = 0; k < KK; ++k) A[q * KK + k] = H(k == 0 ? 1024.0 : (k == 1 ? -1024.0 : std::ldexp(1.0 + (double)((q + k) % 5) / 8.0, -12 - (int)(q % 7))));
   note(run("+2^20, -2^20 and fourteen addends 2^-12 .. 2^-18, c = 0"));
   // 4. dictionary-like: positive values at table scale (hi x hi of the kernel's split), c = a running positive sum
   for (size_t q = 0; q < ncase; ++q)
-    for (int k = 0; k < 16; ++k) A[q * 16 + k] = H(128.0 * (0.05 + 0.95 * U(rng)));
+    for (int k = 0; k < KK; ++k) A[q * KK + k] = H(128.0 * (0.05 + 0.95 * U(rng)));
   for (auto& v : B) v = H(128.0 * (0.05 + 0.95 * U(rng)));
   for (auto& v : C) v = (float)(128.0 * 128.0 * 16.0 * 12.0 * U(rng));
   note(run("positive, table scale (<= 128), c = positive running sum (hi.hi steps)"));

@@ -10,6 +10,8 @@
 // Prints per family: max |c~ - c|, mean (a bias that grows with K would reveal truncating accumulation), and the
 // largest error relative to sum|a b|.   Build + run:  hipcc -O3 --offload-arch=gfx950 -I../../microstructure_fingerprinting_amd/csrc
 //                                                       split_mfma_error.hip -o bin/split_mfma_error && bin/split_mfma_error
+// bin/split_mfma_error 1024 16x16x32: the same pairs through the 16-row form (v_mfma_f32_16x16x32_f16, 21 dependent instructions
+// at K = 208).
 #include "fit_k2s.hip"
 
 #include <cmath>
@@ -49,6 +51,48 @@ __global__ __launch_bounds__(64) void split_tile(const float* __restrict__ A, co
   }
 }
 
+// the 16-row form of the screening kernel's shared last row tile (k2s_round.h): the same 32 x 32 pairs on
+// v_mfma_f32_16x16x32_f16, maps of k2s_tail16_map.h - two row halves, each against the even and the odd columns, (KS + 1) / 2
+// steps of 32 rows with zeros beyond K, six instructions per step in the kernel's order
+template <int KS>
+__global__ __launch_bounds__(64) void split_tile16(const float* __restrict__ A, const float* __restrict__ B, float* __restrict__ C) {
+  constexpr int K = KS * 16, NS = k2s_t16_steps(KS);
+  const int lane = threadIdx.x;
+  for (int rh = 0; rh < 2; ++rh) {
+    const float* a = A + ((size_t)blockIdx.x * 32 + 16 * rh + k2s_t16_arow(lane)) * K;
+    f32x4 acc[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      h8 ah, al, bh[2], bl[2];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int m = k2s_t16_row(lane, j, s, KS);
+        _Float16 x, y;
+        mfx_split16(m >= 0 ? a[m] : 0.0f, x, y); ah[j] = x; al[j] = y;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          const float* b = B + ((size_t)blockIdx.x * 32 + k2s_t16_atom(lane, t)) * K;
+          mfx_split16(m >= 0 ? b[m] : 0.0f, x, y); bh[t][j] = x; bl[t][j] = y;
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[t], acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[t], acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[t], acc[t], 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        C[((size_t)blockIdx.x * 32 + 16 * rh + k2s_t16_crow(lane, r)) * 32 + k2s_t16_atom(lane, t)] = acc[t][r];
+  }
+}
+static bool g_t16 = false;   // second argument "16x16x32"
+
 struct Stat { double maxabs = 0, sum = 0, maxrel = 0; long n = 0; };
 
 template <int KS>
@@ -58,7 +102,8 @@ static Stat run_family(const char* name, std::vector<float>& A, std::vector<floa
   (void)hipMalloc(&dA, A.size() * 4); (void)hipMalloc(&dB, B.size() * 4); (void)hipMalloc(&dC, (size_t)tiles * 1024 * 4);
   (void)hipMemcpy(dA, A.data(), A.size() * 4, hipMemcpyHostToDevice);
   (void)hipMemcpy(dB, B.data(), B.size() * 4, hipMemcpyHostToDevice);
-  hipLaunchKernelGGL(split_tile<KS>, dim3(tiles), dim3(64), 0, 0, dA, dB, dC);
+  if (g_t16) hipLaunchKernelGGL(split_tile16<KS>, dim3(tiles), dim3(64), 0, 0, dA, dB, dC);
+  else hipLaunchKernelGGL(split_tile<KS>, dim3(tiles), dim3(64), 0, 0, dA, dB, dC);
   std::vector<float> C((size_t)tiles * 1024);
   (void)hipMemcpy(C.data(), dC, C.size() * 4, hipMemcpyDeviceToHost);
   (void)hipFree(dA); (void)hipFree(dB); (void)hipFree(dC);
@@ -170,6 +215,8 @@ static double sweep(int tiles) {
 
 int main(int argc, char** argv) {
   const int tiles = argc > 1 ? atoi(argv[1]) : 1024;   // 1024 tiles x 1024 pairs ~ 1e6 pairs per family
+  g_t16 = argc > 2 && !strcmp(argv[2], "16x16x32");
+  printf("%s\n", g_t16 ? "v_mfma_f32_16x16x32_f16, the 16-row form" : "v_mfma_f32_32x32x16_f16");
   double w = 0;
   w = std::fmax(w, sweep<4>(tiles));
   w = std::fmax(w, sweep<8>(tiles));
