@@ -62,6 +62,7 @@ struct SolveArgs {
   double* yrec;    // [M]
 };
 
+#ifndef MFX_SOLVE_BODIES_ONLY
 __global__ void mfx_gram_kernel(SolveArgs a) {
   if (a.run_if && !*a.run_if) return;
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -86,6 +87,7 @@ __global__ void mfx_gram_kernel(SolveArgs a) {
     *a.ncand = 0;
   }
 }
+#endif
 
 // decode tuple number t (itertools.product order: last index fastest) into absolute column indices
 __device__ __forceinline__ void mfx_decode(const SolveArgs& a, long t, int col[MFX_GK]) {
@@ -170,9 +172,9 @@ __device__ __forceinline__ double mfx_ref_ysq(const SolveArgs& a) { return (a.Kp
 // most 3.5 eps |y|^2 / d).  The smallest d over the branches the score may have taken counts (a branch below its own
 // cut - 1e-8, 1e-12 - is never taken).  Other tuple sizes: 0, as before.
 #define MFX_SCORE_ERR (16.0 * 2.220446049250313e-16)
-__device__ inline double mfx_tuple_score_err(const SolveArgs& a, const int col[MFX_GK]) {
+// the signal-independent part: the smallest relative determinant over the branches (1 where none counts)
+__device__ inline double mfx_tuple_rel(const SolveArgs& a, const int col[MFX_GK]) {
   const int n = a.Kp, N = a.Ntot;
-  if (n != 2 && n != 3) return 0.0;
   const double* G = a.G;
   auto g = [&](int p, int q) { return G[(long)col[p] * N + col[q]]; };
   double rel = 1.0;
@@ -189,7 +191,11 @@ __device__ inline double mfx_tuple_score_err(const SolveArgs& a, const int col[M
     const double pd = a11 * a22 * a33;
     if (det > 1e-12 * pd) rel = fmin(rel, det / pd);
   }
-  return MFX_SCORE_ERR * mfx_ref_ysq(a) / rel;
+  return rel;
+}
+__device__ inline double mfx_tuple_score_err(const SolveArgs& a, const int col[MFX_GK]) {
+  if (a.Kp != 2 && a.Kp != 3) return 0.0;
+  return MFX_SCORE_ERR * mfx_ref_ysq(a) / mfx_tuple_rel(a, col);
 }
 
 // lower edge of the tie window: *a.smax holds the best LOWER bound (score - error) of all tuples; a tuple is listed when
@@ -205,7 +211,7 @@ __device__ __forceinline__ double mfx_listed_score(const SolveArgs& a, double ub
 
 // pass 1: the best score of every block and of all tuples.  Nothing is selected here: which tuples reach the finalize
 // stage is decided against the maximum of ALL tuples, in mfx_tuple_collect.
-__global__ __launch_bounds__(256) void mfx_tuple_scan(SolveArgs a) {
+__device__ inline void mfx_tuple_scan_body(const SolveArgs& a) {
   __shared__ double s_sc[256], s_lb[256];
   if (a.run_if && !*a.run_if) return;
   if (a.scan_enable && !*a.scan_enable) return;   // (three-dictionary fast path: only after a candidate-list overflow)
@@ -240,7 +246,7 @@ __device__ __forceinline__ long mfx_order_key(const SolveArgs& a, long t) {
 // pass 2: every tuple inside the tie window goes to the candidate list.  Same grid as pass 1 (a block sees the tuples it
 // scored there, and scores them to the same bits: the build does not contract floating point); a block whose best lies
 // below the window has none and exits.  More than list_cap candidates: the counter's sign bit is set and stays.
-__global__ __launch_bounds__(256) void mfx_tuple_collect(SolveArgs a) {
+__device__ inline void mfx_tuple_collect_body(const SolveArgs& a) {
   if (a.run_if && !*a.run_if) return;
   if (a.scan_enable && !*a.scan_enable) return;
   const double thr = mfx_tie_threshold(a);
@@ -268,14 +274,14 @@ __global__ __launch_bounds__(256) void mfx_tuple_collect(SolveArgs a) {
 // pass 3, only after an overflow of the list (exits at once otherwise): one entry per block - of the block's tuples
 // inside the tie window the first in the reference's scan order.  The first hit among ALL tuples inside the window is
 // the first of its own block, so it is kept; the finalize stage reads nblocks entries (nblocks_dev < 0).
-__global__ __launch_bounds__(256) void mfx_tuple_overflow(SolveArgs a) {
+__device__ inline void mfx_tuple_overflow_body(const SolveArgs& a) {
   __shared__ double s_sc[256];
   __shared__ long s_key[256], s_t[256];
   if (a.run_if && !*a.run_if) return;
   if (a.scan_enable && !*a.scan_enable) return;
   if (*a.ncand >= 0) return;
   const double thr = mfx_tie_threshold(a);
-  const double bm = a.blk_max[blockIdx.x];
+  const double bm = a.blk_max ? a.blk_max[blockIdx.x] : INFINITY;   // (no per-block maxima of this partition: every block looks)
   double bs = 0.0;
   long bkey = -1, bt = -1;
   if (bm > 0.0 && !(bm < thr)) {   // (uniform over the block)
@@ -302,7 +308,7 @@ __global__ __launch_bounds__(256) void mfx_tuple_overflow(SolveArgs a) {
   }
 }
 
-__global__ __launch_bounds__(256) void mfx_tuple_finalize(SolveArgs a) {
+__device__ inline void mfx_tuple_finalize_body(const SolveArgs& a) {
   if (a.run_if && !*a.run_if) return;
   __shared__ double s_res[256];
   __shared__ long s_key[256], s_tt[256];
@@ -460,7 +466,7 @@ __global__ __launch_bounds__(256) void mfx_tuple_finalize(SolveArgs a) {
     s_key[0] = bi;
   }
   __syncthreads();
-  {  // y_recons = A[:, tot] @ w   (w * column for one sub-dictionary, mf_utils.py:277)
+  if (a.yrec) {  // y_recons = A[:, tot] @ w   (w * column for one sub-dictionary, mf_utils.py:277); the batched solver may leave it out
     int col[MFX_GK];
     mfx_decode(a, s_tt[0], col);
     for (int k = tid; k < M; k += 256) {
@@ -472,6 +478,15 @@ __global__ __launch_bounds__(256) void mfx_tuple_finalize(SolveArgs a) {
     }
   }
 }
+
+// The kernels of the one-problem launch sequence.  The bodies above are __device__ functions so that the batched solver
+// (solve_batch.hip, which defines MFX_SOLVE_BODIES_ONLY and has kernels of its own) runs them per signal on a view.
+#ifndef MFX_SOLVE_BODIES_ONLY
+__global__ __launch_bounds__(256) void mfx_tuple_scan(SolveArgs a) { mfx_tuple_scan_body(a); }
+__global__ __launch_bounds__(256) void mfx_tuple_collect(SolveArgs a) { mfx_tuple_collect_body(a); }
+__global__ __launch_bounds__(256) void mfx_tuple_overflow(SolveArgs a) { mfx_tuple_overflow_body(a); }
+__global__ __launch_bounds__(256) void mfx_tuple_finalize(SolveArgs a) { mfx_tuple_finalize_body(a); }
+#endif
 
 
 // ---- params packing for the voxel loop's generic classes (mf.py:420-450) from the solver's outputs: one 64-thread workgroup
@@ -522,7 +537,9 @@ __device__ __forceinline__ void mfx_pack_params_body(const PackArgs& a) {
     a.out[a.num_params - 1] = r2;
   }
 }
+#ifndef MFX_SOLVE_BODIES_ONLY
 __global__ __launch_bounds__(64) void mfx_pack_params_kernel(PackArgs a) {
   if (a.run_if && !*a.run_if) return;
   mfx_pack_params_body(a);
 }
+#endif

@@ -1739,6 +1739,45 @@ def fit2d_bootstrap(tables, Y, K, csf, peaks, maxfasc, csf_on, sig_csf=None, B=2
     return {'stats': stats, 'agree': agree, 'status': status, 'dir_status': dstat, 'replicates': reps, 'columns': cols}
 
 
+def solve_batch_dev(solver, d_Y, out=None, recons=True, max_bytes=0):
+    """The batched explicit-dictionary solver on the device (mfx_solve_batch_dev, include/mfx_solve.h) for a
+    mf_utils.ExhaustiveSolver: torch CUDA float64 signals d_Y [V, M] (or one [M] vector) -> (w [V, Kp] float64, sub [V, Kp]
+    int64, tot [V, Kp] int64, obj [V] float64, yrec [V, M] float64 or None without ``recons``, status [V] int32), the rows
+    ``solver.solve`` returns, bit for bit (the indices stay int64 on the device).  ``out``: a dict that may hold tensors
+    'w', 'sub', 'obj', 'yrec', 'status' of those shapes and types to write into; 'yrec' is not touched without ``recons``.
+    Enqueues on torch's current stream and returns without waiting."""
+    import torch
+    _f64_cuda(d_Y)
+    V = solver.signal_rows(d_Y.shape)
+    out = dict(out) if out is not None else {}
+    unknown = set(out) - {'w', 'sub', 'obj', 'yrec', 'status'}
+    if unknown:
+        raise ValueError("out may hold 'w', 'sub', 'obj', 'yrec', 'status', got %s" % sorted(unknown))
+    dev, Kp, M = d_Y.device, solver.Kp, solver.M
+    if dev.index is not None and dev.index != solver.device:
+        raise ValueError("signals live on %s, the solver on device %d" % (dev, solver.device))
+
+    def buf(name, shape, dtype):
+        t = out.get(name)
+        if t is None:
+            return torch.empty(shape, dtype=dtype, device=dev)
+        if not (t.is_cuda and t.dtype == dtype and t.is_contiguous()) or tuple(t.shape) != tuple(shape):
+            raise ValueError("out[%r] should be a contiguous CUDA %s tensor of shape %s, got %s of shape %s"
+                             % (name, dtype, tuple(shape), t.dtype, tuple(t.shape)))
+        return t
+    w, sub = buf('w', (V, Kp), torch.float64), buf('sub', (V, Kp), torch.int64)
+    obj, status = buf('obj', (V,), torch.float64), buf('status', (V,), torch.int32)
+    yrec = buf('yrec', (V, M), torch.float64) if recons else None
+    with torch.cuda.device(dev):
+        starts = solver.starts_on(dev)
+        if V > 0:
+            st = torch.cuda.current_stream(dev).cuda_stream
+            L.check(L.lib().mfx_solve_batch_dev(solver.handle(), d_Y.data_ptr(), V, int(max_bytes), w.data_ptr(), sub.data_ptr(),
+                                                obj.data_ptr(), _tptr(yrec), status.data_ptr(), st))
+        tot = torch.where(sub >= 0, sub + starts[None, :], sub)
+    return w, sub, tot, obj, yrec, status
+
+
 def cleanup_select(f1, f2, p1, p2, cos_min, ratio, w_keep, w_small, device=0):
     """Voxel loop of cleanup_2fascicles (mfx_cleanup_2fascicles; ref mf.py:170-335): weights f1, f2 [n] and directions p1, p2
     [n x 3] of the ROI voxels -> (peaks [n x 6], count [n])."""

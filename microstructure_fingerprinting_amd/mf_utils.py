@@ -8,6 +8,7 @@ every numeric evaluation runs in the HIP library ``libmfx.so`` (include/mfx.h):
 reference function (ref line)                  what runs where here
 =============================================  ================================================
 solve_exhaustive_posweights (ref:115)          checks on host, search on device (mfx_solve_exhaustive)
+ExhaustiveSolver / .._posweights_batch (new)   the same for many signals against one dictionary (mfx_solve_batch)
 init_PGSE_multishell_interp (ref:1959)         per-shell knot tables built once on host (NumPy),
                                                uploaded lazily to HBM (mfx_tables_create)
 interp_PGSE_from_multishell (ref:1693)         checks on host, evaluation on device (mfx_rotate)
@@ -1140,6 +1141,122 @@ def solve_exhaustive_posweights(A, y, dicsizes, printmsg=None):
         # the reference's Numba kernels return int32 index arrays (ref:218-224, 284-286, 466-468)
         sub, tot = sub.astype(np.int32), tot.astype(np.int32)
     return w, sub, tot, float(obj[0]), yrec
+
+
+def _check_dictionary(A, dicsizes):
+    """The checks of ``solve_exhaustive_posweights`` that concern the dictionary: same conditions and texts (ref:157-188)."""
+    assert isinstance(A, np.ndarray), "A should be a NumPy ndarray"
+    assert A.ndim == 2, "A should be a 2D array"
+    assert not np.any(np.all(A == 0, axis=0)), "All-zero columns detected in A"
+    assert A.size > 0, "A and y should not be empty arrays"
+    assert isinstance(dicsizes, np.ndarray), "dicsizes should be a NumPy ndarray"
+    assert np.all(dicsizes > 0), "All entries of dicsizes should be > 0"
+    assert A.shape[1] == np.sum(dicsizes), ("Number of columns of A (%d) does not equal sum of size of "
+                                            "sub-matrices in diclengths array (%d)"
+                                            % (A.shape[1], np.sum(dicsizes)))
+
+
+class ExhaustiveSolver:
+    """``solve_exhaustive_posweights`` for MANY signals against ONE dictionary (include/mfx_solve.h).
+
+    The dictionary and its Gram matrix live on the device for the life of the object; per signal only ``A^T y`` and
+    ``||y||^2`` are formed.  Row ``v`` of a batch equals, bit for bit, what ``solve_exhaustive_posweights(A, Y[v],
+    dicsizes)`` returns (the batch never takes that function's matrix-pipe screen for three large sub-dictionaries; it
+    returns what the plain scan returns there).  The checks on ``A`` and ``dicsizes`` are those of the one-problem
+    function, made here before the device is touched.  A context manager; ``close()`` releases the device memory."""
+
+    def __init__(self, A, dicsizes, device=0):
+        _check_dictionary(A, dicsizes)
+        self._A = L.f64c(A)
+        self.dicsizes = np.ascontiguousarray(dicsizes, dtype=np.int64).reshape(-1)
+        self.M = int(self._A.shape[0])
+        self.num_columns = int(self._A.shape[1])
+        self.Kp = int(self.dicsizes.size)
+        self.device = int(device)
+        self.starts = np.concatenate(([0], np.cumsum(self.dicsizes)[:-1])).astype(np.int64)
+        self._h = None
+        self._starts_dev = {}
+
+    def handle(self):
+        if self._h is None:
+            h = C.c_void_p()
+            L.check(L.lib().mfx_solve_create(L.dptr(self._A), self.num_columns, self.M, L.lptr(self.dicsizes), self.Kp,
+                                             self.device, C.byref(h)))
+            self._h = h
+        return self._h
+
+    def close(self):
+        if self._h is not None:
+            L.lib().mfx_solve_destroy(self._h)
+            self._h = None
+        self._starts_dev = {}
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def starts_on(self, dev):
+        """First column of every sub-dictionary as an int64 tensor on the torch device ``dev``, uploaded once."""
+        import torch
+        key = str(dev)
+        if key not in self._starts_dev:
+            self._starts_dev[key] = torch.from_numpy(self.starts).to(dev)
+        return self._starts_dev[key]
+
+    @property
+    def bytes_per_signal(self):
+        """Scratch bytes one signal of a batch takes on the device: what ``max_bytes`` is counted in."""
+        return int(L.lib().mfx_solve_bytes_per_signal(self.handle()))
+
+    def signal_rows(self, shape):
+        """V of signals of this shape, ``[V, M]`` or one ``[M]`` vector; a ValueError that names both shapes otherwise."""
+        shape = tuple(shape)
+        if len(shape) == 1 and shape[0] == self.M:
+            return 1
+        if len(shape) != 2 or shape[1] != self.M:
+            raise ValueError("signals should have shape (V, %d) or (%d,) for a dictionary of shape %s, got %s"
+                             % (self.M, self.M, (self.M, self.num_columns), shape))
+        return int(shape[0])
+
+    def index_dtype(self):
+        # the reference's Numba kernels return int32 index arrays for up to three sub-dictionaries (ref:218-224, 284-286, 466-468)
+        return np.int32 if self.Kp <= 3 else np.int64
+
+    def solve(self, Y, recons=True, max_bytes=0):
+        """Signals ``Y [V, M]`` (or one ``[M]`` vector: V = 1) -> ``(w [V, Kp], ind_subdic [V, Kp], ind_totdic [V, Kp],
+        min_obj [V], y_recons [V, M] or None without ``recons``, status [V])``.  status 1: the signal holds a non-finite
+        value; its weights, objective and reconstruction are NaN and its indices -1.  The signals go through the device
+        in chunks whose scratch stays within ``max_bytes`` (0: 256 MiB)."""
+        assert isinstance(Y, np.ndarray), "y should be a NumPy ndarray"
+        V = self.signal_rows(Y.shape)
+        Kp, M = self.Kp, self.M
+        w = np.zeros((V, Kp))
+        sub = np.zeros((V, Kp), dtype=np.int64)
+        obj = np.zeros(V)
+        yrec = np.zeros((V, M)) if recons else None
+        status = np.zeros(V, dtype=np.int32)
+        if V > 0:
+            Y64 = L.f64c(Y).reshape(V, M)
+            L.check(L.lib().mfx_solve_batch(self.handle(), L.dptr(Y64), V, int(max_bytes), L.dptr(w), L.lptr(sub), L.dptr(obj),
+                                            L.opt(yrec), L.iptr(status)))
+        tot = np.where(sub >= 0, sub + self.starts[None, :], -1)
+        dt = self.index_dtype()
+        return w, sub.astype(dt), tot.astype(dt), obj, yrec, status
+
+
+def solve_exhaustive_posweights_batch(A, Y, dicsizes, device=0, **kw):
+    """One-shot form of ``ExhaustiveSolver(A, dicsizes).solve(Y, **kw)``."""
+    with ExhaustiveSolver(A, dicsizes, device=device) as S:
+        return S.solve(Y, **kw)
 
 
 # ---------------------------------------------------------------------------------------------
