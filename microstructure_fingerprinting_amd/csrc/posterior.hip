@@ -1,11 +1,13 @@
 // posterior.hip -- soft fits (include/mfx_post.h): per atom of each fascicle the sum over every partner atom of
 // exp(-(F - shift) / T), normalised per voxel, and the log of the whole sum.
 //
-// mfx_post_k2_kernel   one workgroup per voxel; phases 0-2 are those of mfx_profile_k2_kernel (profile.hip): knot
-//                      descriptors and y in LDS, column statistics of both rotated dictionaries (one thread per atom),
-//                      the cross-Gram D_0^T D_1 on v_mfma_f64_16x16x4_f64 with the wave's 16 atoms of D_0 in registers
-//                      and D_1 generated chunk by chunk into LDS.  The scan keeps a sum of exponentials per row and per
-//                      column where the profile keeps a minimum:
+// mfx_post_k2_kernel   one workgroup per voxel; phases 0-2 are those of mfx_profile_k2_kernel (profile.hip), restated
+//                      here: knot descriptors and y in LDS, column statistics of both rotated dictionaries (one thread
+//                      per atom), the cross-Gram D_0^T D_1 on v_mfma_f64_16x16x4_f64 with the wave's 16 atoms of D_0 in
+//                      registers and D_1 generated chunk by chunk into LDS.  The scoring helpers, the cut, the weights'
+//                      status and the host plumbing are soft_sweep.h's, shared with profile.hip (F is the profile's value
+//                      by definition).  The scan keeps a sum of exponentials per row and per column where the profile
+//                      keeps a minimum:
 //                        per pair  the score ||y||^2 - F (p / q, or the CSF value), t = exp((score - (||y||^2 - shift)) / T):
 //                                  one division and one FP64 exp per pair.  FP64 MFMA and VALU instructions do not
 //                                  overlap on a SIMD, so the scan adds to the matrix work: about 2 900 cycles of
@@ -21,34 +23,17 @@
 // mfx_post_k1_kernel   one workgroup per voxel, one thread per atom (mfx_profile_k1_kernel's scoring).
 //
 // The status codes come from the kernels themselves: T and shift are checked in phase 0 (code 1, workgroup-uniform
-// exit), an exponent above 700 raises an LDS flag and Z is tested in the last phase (code 2).
-//
-// The scoring helpers restate those of profile.hip word for word (F is the profile's value by definition); profile.hip
-// itself is left alone so that its kernels' register allocation stays what it is.
-#include "mfx_host.h"
+// exit), then the weights (codes 3 and 4), an exponent above 700 raises an LDS flag and Z is tested in the last phase
+// (code 2).
+#include "soft_sweep.h"
 #include "../../include/mfx_post.h"
-#include "../../include/mfx_profile.h"
 #include "../../include/mfx_wsoft.h"
-
-#include <algorithm>
-#include <type_traits>
-
-// profile.hip's MFX_PROFILE_CUT restated as a compile-time constant (the 8-wave form has no register to spare for a kernel
-// argument); the entry points refuse to launch unless it equals mfx_profile_cut()
-#define MFX_POST_CUT 1e-8
 
 namespace {
 
-constexpr size_t POST_LDS_MAX = 160 * 1024;
-constexpr int POST_K1_WG = 256;
 constexpr double POST_EXP_MAX = 700.0;   // exponents above this make the shift unusable (status 2)
 
-struct PostArgs {
-  TablesDev T;
-  PlanDev P;
-  const double* Y;      // [V x M]
-  const double* peaks;  // [V x 3 K]
-  const double* xc;     // [M] the CSF column (CSF variants)
+struct PostArgs : SweepArgs {
   const double* temp;   // [V]
   const double* shift;  // [V]
   double* w;            // [V x K x N]
@@ -62,69 +47,19 @@ struct PostArgsW : PostArgs {
 };
 template <bool WGT> using PostArgsT = std::conditional_t<WGT, PostArgsW, PostArgs>;
 
-// weights of a voxel: 3 one is negative or not finite, 4 none is positive, 0 usable.  Every thread reads all M weights
-// (the address does not depend on the lane), so the answer is workgroup-uniform without a barrier.
-__device__ __forceinline__ int post_weights_status(const double* __restrict__ wv, int M) {
-  bool bad = false, pos = false;
-  for (int m = 0; m < M; ++m) {
-    const double w = wv[m];
-    bad |= !(w >= 0.0) || !(w <= 1.79769313486231570815e308);
-    pos |= w > 0.0;
-  }
-  return bad ? 3 : (pos ? 0 : 4);
-}
-
-// score s = ||y||^2 - F of one atom pair as the fraction p / q (profile.hip: prof_pair_frac)
-__device__ __forceinline__ void post_pair_frac(double cut, double A11, double A22, double A12, double Y1, double Y2, double p1,
-                                               double p2, double& p, double& q) {
-  const double d1 = fma(-A12, Y2, A22 * Y1);
-  const double d2 = fma(-A12, Y1, A11 * Y2);
-  const double pd = A11 * A22;
-  const double Det = fma(-A12, A12, pd);
-  const double num = fma(Y2, d2, Y1 * d1);
-  const bool both = (d1 > 0.0) & (d2 > 0.0) & (Det > cut * pd);
-  const bool first = p1 * A22 >= p2 * A11;
-  p = both ? num : (first ? p1 : p2);
-  q = both ? Det : (first ? A11 : A22);
-}
-
-// the same with the weights (CSF form; profile.hip: prof_pair_w)
-__device__ __forceinline__ double post_pair_w(double cut, double A11, double A22, double A12, double Y1, double Y2, double i11,
-                                              double i22, double& w1, double& w2) {
-  const double d1 = fma(-A12, Y2, A22 * Y1);
-  const double d2 = fma(-A12, Y1, A11 * Y2);
-  const double pd = A11 * A22;
-  const double Det = fma(-A12, A12, pd);
-  const bool both = (d1 > 0.0) & (d2 > 0.0) & (Det > cut * pd);
-  const double u1 = fmax(Y1, 0.0) * i11, u2 = fmax(Y2, 0.0) * i22;
-  const double s1 = Y1 * u1, s2 = Y2 * u2;
-  const bool first = s1 >= s2;
-  const double iD = both ? 1.0 / Det : 0.0;
-  w1 = both ? d1 * iD : (first ? u1 : 0.0);
-  w2 = both ? d2 * iD : (first ? 0.0 : u2);
-  return both ? fma(Y2, d2, Y1 * d1) * iD : (first ? s1 : s2);
-}
-
-// statistics of an atom with the CSF column x projected out (profile.hip: prof_primed)
-__device__ __forceinline__ void post_primed(double cut, double A, double Yv, double X, double ixx, double xy, double& Ap,
-                                            double& Yp, double& iAp) {
-  const double xs = X * ixx;
-  Ap = fma(-xs, X, A);
-  Yp = fma(-xs, xy, Yv);
-  const bool ok = Ap > cut * A;
-  Ap = ok ? Ap : 0.0;
-  Yp = ok ? Yp : 0.0;
-  iAp = ok ? 1.0 / Ap : 0.0;
-}
-
 __device__ __forceinline__ bool post_finite(double x) { return fabs(x) <= 1.79769313486231570815e308; }   // false for NaN
 
-// status 1: the voxel's rows and log_sum become NaN (every thread of the workgroup takes part)
+// a voxel without a result: its rows and log_sum become NaN, its status `code` (every thread of the workgroup takes part)
 __device__ __forceinline__ void post_nan_rows(const PostArgs& a, size_t vox, int K, int N, int code, int tid, int wg) {
   const double nan = __builtin_nan("");
   for (int n = tid; n < K * N; n += wg) a.w[vox * K * N + n] = nan;
   if (tid == 0) { a.log_sum[vox] = nan; a.status[vox] = code; }
 }
+
+// the K = 2 kernel's own LDS behind the common front of soft_sweep.h, for the host.  Doubles: the row sums R0 and the running column sums R1, [NP]
+// each, and the waves' column sums of one chunk, [2][NW][CW]; ints: the flag (and one of padding).
+constexpr int post_own_dbl(int NP, int nw, int cw) { return 2 * NP + 2 * nw * cw; }
+constexpr int POST_OWN_INT = 2;
 
 // NW waves per workgroup, TILES 16-atom column tiles per D_1 chunk, NBUF LDS buffers for the chunks: the profile's
 // configurations (profile.hip).  WGT: rows scaled by s = sqrt(W) as they are generated (include/mfx_wsoft.h): one more
@@ -144,7 +79,6 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void mfx_post_k2_kernel(P
   const int ntiles = NP >> 4;
   const double2* __restrict__ tab = a.T.tab;
   const size_t vox = blockIdx.x;
-  constexpr double cut = MFX_POST_CUT;
 
   // ---- LDS carve-up (post_lds_bytes below mirrors it)
   double* sB = smem;                              // [NBUF][TILES][MPS][16]
@@ -179,7 +113,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void mfx_post_k2_kernel(P
     return;
   }
   if constexpr (WGT) {   // status 3 / 4 leave here, workgroup-uniform
-    if (const int code = post_weights_status(a.W + vox * a.wstride, M)) {
+    if (const int code = sweep_weights_status(a.W + vox * a.wstride, M)) {
       post_nan_rows(a, vox, 2, N, code, tid, WG);
       return;
     }
@@ -302,7 +236,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void mfx_post_k2_kernel(P
         const double X = s_X1[i];
         A11u[r] = A; Y1u[r] = Yv; X1r[r] = X; X1s[r] = X * ixx;
         i11u[r] = A > 0.0 ? 1.0 / A : 0.0;
-        post_primed(cut, A, Yv, X, ixx, xy, A11r[r], Y1r[r], i11p[r]);
+        sweep_primed(A, Yv, X, ixx, xy, A11r[r], Y1r[r], i11p[r]);
         p1r[r] = 0.0;
       } else {
         A11r[r] = A; Y1r[r] = Yv;
@@ -348,7 +282,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void mfx_post_k2_kernel(P
           if constexpr (CSF) {
             X2 = colok ? s_X2[jq] : 0.0; A22u = A22; Y2u = Y2;
             i22u = A22 > 0.0 ? 1.0 / A22 : 0.0;
-            post_primed(cut, A22u, Y2u, X2, ixx, xy, A22, Y2, i22p);
+            sweep_primed(A22u, Y2u, X2, ixx, xy, A22, Y2, i22p);
           } else {
             const double yp = fmax(Y2, 0.0);
             p2 = yp * yp;
@@ -360,13 +294,13 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void mfx_post_k2_kernel(P
               // x projected out: the two-variable form on the primed quantities, then the sign of w_x decides
               double w1, w2, v1, v2;
               const double A12p = fma(-X1s[r], X2, acc[r]);
-              const double sp = post_pair_w(cut, A11r[r], A22, A12p, Y1r[r], Y2, i11p[r], i22p, w1, w2);
+              const double sp = sweep_pair_w(A11r[r], A22, A12p, Y1r[r], Y2, i11p[r], i22p, w1, w2);
               const double wxn = fma(-w2, X2, fma(-w1, X1r[r], xy));   // w_x times x.x
-              const double su = post_pair_w(cut, A11u[r], A22u, acc[r], Y1u[r], Y2u, i11u[r], i22u, v1, v2);
+              const double su = sweep_pair_w(A11u[r], A22u, acc[r], Y1u[r], Y2u, i11u[r], i22u, v1, v2);
               s = (wxn >= 0.0) ? sx + sp : su;
             } else {
               double p, q;
-              post_pair_frac(cut, A11r[r], A22, acc[r], Y1r[r], Y2, p1r[r], p2, p, q);
+              sweep_pair_frac(A11r[r], A22, acc[r], Y1r[r], Y2, p1r[r], p2, p, q);
               s = q > 0.0 ? p / q : 0.0;
             }
             const bool ok = (4 * r < nrow) & colok;
@@ -428,12 +362,11 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void mfx_post_k2_kernel(P
 
 // K = 1: one workgroup per voxel, one thread per atom; the unnormalised t(i) wait in the output row for Z
 template <bool CSF, bool WGT = false>
-__global__ __launch_bounds__(POST_K1_WG) void mfx_post_k1_kernel(PostArgsT<WGT> a) {
+__global__ __launch_bounds__(SWEEP_K1_WG) void mfx_post_k1_kernel(PostArgsT<WGT> a) {
   extern __shared__ double smem[];
   const int tid = threadIdx.x;
   const int M = a.P.M, N = a.T.N, ldn = a.T.ldn;
   const size_t vox = blockIdx.x;
-  constexpr double cut = MFX_POST_CUT;
   double* s_y = smem;          // [M]
   double* s_x = s_y + M;       // [M]
   double* s_t0 = s_x + M;      // [M]
@@ -447,17 +380,17 @@ __global__ __launch_bounds__(POST_K1_WG) void mfx_post_k1_kernel(PostArgsT<WGT> 
   const double Tv = a.temp[vox], shift = a.shift[vox];
   if (tid == 0) mfx_check_dir(a.P, pk, (int)vox);
   if (!(Tv > 0.0) || !post_finite(Tv) || !post_finite(shift)) {
-    post_nan_rows(a, vox, 1, N, 1, tid, POST_K1_WG);
+    post_nan_rows(a, vox, 1, N, 1, tid, SWEEP_K1_WG);
     return;
   }
   if constexpr (WGT) {
-    if (const int code = post_weights_status(a.W + vox * a.wstride, M)) {
-      post_nan_rows(a, vox, 1, N, code, tid, POST_K1_WG);
+    if (const int code = sweep_weights_status(a.W + vox * a.wstride, M)) {
+      post_nan_rows(a, vox, 1, N, code, tid, SWEEP_K1_WG);
       return;
     }
   }
   const double iT = 1.0 / Tv;
-  for (int m = tid; m < M; m += POST_K1_WG) {
+  for (int m = tid; m < M; m += SWEEP_K1_WG) {
     if constexpr (WGT) {
       const double s = sqrt(a.W[vox * a.wstride + m]);
       s_w[m] = s;
@@ -481,7 +414,7 @@ __global__ __launch_bounds__(POST_K1_WG) void mfx_post_k1_kernel(PostArgsT<WGT> 
   const double c0 = y_sq - shift;
   double* wrow = a.w + vox * N;
   bool over = false;
-  for (int n = tid; n < N; n += POST_K1_WG) {
+  for (int n = tid; n < N; n += SWEEP_K1_WG) {
     double a2 = 0.0, ay = 0.0, ax = 0.0;
     for (int m = 0; m < M; ++m) {
       RowDesc rd;
@@ -496,7 +429,7 @@ __global__ __launch_bounds__(POST_K1_WG) void mfx_post_k1_kernel(PostArgsT<WGT> 
     double s = a2 > 0.0 ? yp * yp / a2 : 0.0;
     if constexpr (CSF) {
       double Ap, Yp, iAp;
-      post_primed(cut, a2, ay, ax, ixx, xy, Ap, Yp, iAp);
+      sweep_primed(a2, ay, ax, ixx, xy, Ap, Yp, iAp);
       const double w1 = fmax(Yp, 0.0) * iAp;
       if (fma(-w1, ax, xy) >= 0.0) s = xy * xy * ixx + Yp * w1;
     }
@@ -510,162 +443,88 @@ __global__ __launch_bounds__(POST_K1_WG) void mfx_post_k1_kernel(PostArgsT<WGT> 
   for (int i = 0; i < N; ++i) Z += wrow[i];   // index order, every thread the same value
   __syncthreads();   // every thread has read the unnormalised row before it is overwritten
   if (s_flag[0] != 0 || !(Z > 0.0) || !post_finite(Z)) {
-    post_nan_rows(a, vox, 1, N, 2, tid, POST_K1_WG);
+    post_nan_rows(a, vox, 1, N, 2, tid, SWEEP_K1_WG);
     return;
   }
-  for (int n = tid; n < N; n += POST_K1_WG) wrow[n] = wrow[n] / Z;
+  for (int n = tid; n < N; n += SWEEP_K1_WG) wrow[n] = wrow[n] / Z;
   if (tid == 0) {
     a.log_sum[vox] = log(Z) - shift / Tv;
     a.status[vox] = 0;
   }
 }
 
-size_t post_lds_bytes(int ksteps, bool bracket, bool csf, int NP, int nw, int tiles, int nbuf, bool wgt = false) {
-  const size_t MP = (size_t)ksteps * 4, MPS = MP, cw = 16 * (size_t)tiles;
-  const size_t dbl = (size_t)nbuf * tiles * MPS * 16 + MP + (csf ? MP : 0) + (wgt ? MP : 0) + 2 * MP + (bracket ? 4 * MP : 0) +
-                     (size_t)NP * (4 + (csf ? 2 : 0) + 2) + 2 * nw * cw;
-  const size_t ints = 2 * MP + (bracket ? 2 * MP : 0) + 2;
-  return dbl * 8 + ints * 4;
+size_t post_lds_bytes(int ksteps, bool bracket, bool csf, int NP, int nw, int tiles, int nbuf, bool wgt) {
+  return sweep_lds_bytes(ksteps, NP, bracket, csf, wgt, nbuf, tiles, post_own_dbl(NP, nw, 16 * tiles), POST_OWN_INT);
 }
-
-template <int KS, bool BR, bool CSF, int NW, int TILES, int NBUF, bool WGT>
-int post_launch_t(const PostArgsW& a, int nvox, hipStream_t st) {
-  const size_t lds = post_lds_bytes(KS, BR, CSF, a.T.ldn, NW, TILES, NBUF, WGT);
-  auto kern = mfx_post_k2_kernel<KS, BR, CSF, NW, TILES, NBUF, WGT>;
-  const PostArgsT<WGT> ka = a;   // the unweighted kernels take the PostArgs part
-  HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3(nvox), dim3(NW * 64), lds, st, ka);
-  HIPCHK(hipGetLastError());
-  return MFX_OK;
+// the family's LDS bytes of a configuration, for sweep_pick and sweep_max_atoms
+auto post_lds(bool br, bool csf, bool wgt) {
+  return [=](const SweepCfg& c, int NP) { return post_lds_bytes(c.ks, br, csf, NP, c.nw, c.tiles, c.nbuf, wgt); };
 }
+int post_max_atoms(int M, bool br, bool csf, bool wgt = false) { return sweep_max_atoms(M, br, csf, post_lds(br, csf, wgt)); }
 
-// the configurations of M <= 200 in the order they are tried: {KSTEPS, NW, TILES, NBUF}; longer protocols: {140, 4, 1, 1}
-struct PostCfg { int ks, nw, tiles, nbuf; };
-constexpr PostCfg POST_CFG_200[3] = {{50, 8, 2, 2}, {50, 4, 1, 2}, {50, 4, 1, 1}};
-
-int post_pick(int M, bool br, bool csf, int NP, bool wgt = false) {   // index into POST_CFG_200, 3: the long-protocol form, -1: none fits
-  if (M <= 200) {
-    for (int c = (csf || br) ? 1 : 0; c < 3; ++c)   // the CSF scan and bracketed rows take one wave per SIMD, as in the profile
-      if (post_lds_bytes(50, br, csf, NP, POST_CFG_200[c].nw, POST_CFG_200[c].tiles, POST_CFG_200[c].nbuf, wgt) <= POST_LDS_MAX) return c;
-    return -1;
+template <bool WGT>
+struct PostLaunch {
+  const PostArgsW& a;
+  int nvox;
+  hipStream_t st;
+  template <int KS, bool BR, bool CSF, int NW, int TILES, int NBUF>
+  int run() const {
+    const PostArgsT<WGT> ka = a;   // the unweighted kernels take the PostArgs part
+    return sweep_launch(mfx_post_k2_kernel<KS, BR, CSF, NW, TILES, NBUF, WGT>, ka, nvox, NW * 64,
+                        post_lds_bytes(KS, BR, CSF, a.T.ldn, NW, TILES, NBUF, WGT), true, st);
   }
-  return post_lds_bytes(140, br, csf, NP, 4, 1, 1, wgt) <= POST_LDS_MAX ? 3 : -1;
-}
-
-int post_max_atoms(int M, bool br, bool csf, bool wgt = false) {
-  int n = 0;
-  while (n < (1 << 20) && post_pick(M, br, csf, n + 16, wgt) >= 0) n += 16;
-  return n;
-}
-
-template <bool BR, bool CSF, bool WGT>
-int post_launch_cfg(int cfg, const PostArgsW& a, int nvox, hipStream_t st) {
-  switch (cfg) {
-    case 0:
-      if constexpr (!CSF && !BR) return post_launch_t<50, BR, CSF, 8, 2, 2, WGT>(a, nvox, st);
-      return mfx_fail(MFX_ERR_ARG, "posterior: no such configuration");
-    case 1: return post_launch_t<50, BR, CSF, 4, 1, 2, WGT>(a, nvox, st);
-    case 2: return post_launch_t<50, BR, CSF, 4, 1, 1, WGT>(a, nvox, st);
-    default: return post_launch_t<140, BR, CSF, 4, 1, 1, WGT>(a, nvox, st);
-  }
-}
+};
 
 template <bool WGT>
 int post_launch_k2(const PostArgsW& a, int nvox, bool csf, hipStream_t st, const char* fn) {
-  const int M = a.P.M;
-  const bool br = a.P.any_bracket != 0;
-  const int cfg = post_pick(M, br, csf, a.T.ldn, WGT);
-  if (cfg < 0)
-    return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: N = %d atoms exceed the %d that fit in LDS for this protocol (M = %d)", fn, a.T.N,
-                    post_max_atoms(M, br, csf, WGT), M);
-  if (br) return csf ? post_launch_cfg<true, true, WGT>(cfg, a, nvox, st) : post_launch_cfg<true, false, WGT>(cfg, a, nvox, st);
-  return csf ? post_launch_cfg<false, true, WGT>(cfg, a, nvox, st) : post_launch_cfg<false, false, WGT>(cfg, a, nvox, st);
+  return sweep_launch_k2(fn, "posterior", a, csf, post_lds(a.P.any_bracket != 0, csf, WGT), PostLaunch<WGT>{a, nvox, st});
 }
 
 template <bool WGT>
 int post_launch_k1(const PostArgsW& a, int nvox, bool csf, hipStream_t st) {
-  const size_t lds = (size_t)a.P.M * ((WGT ? 5 : 4) * sizeof(double) + 2 * sizeof(int)) + 2 * sizeof(int);
+  const size_t lds = sweep_k1_lds_bytes(a.P.M, WGT, POST_OWN_INT);
   const PostArgsT<WGT> ka = a;
-  if (csf) hipLaunchKernelGGL((mfx_post_k1_kernel<true, WGT>), dim3((unsigned)nvox), dim3(POST_K1_WG), lds, st, ka);
-  else hipLaunchKernelGGL((mfx_post_k1_kernel<false, WGT>), dim3((unsigned)nvox), dim3(POST_K1_WG), lds, st, ka);
-  HIPCHK(hipGetLastError());
-  return MFX_OK;
-}
-
-int post_check_args(const char* fn, const mfx_plan* p, const void* Y, const void* peaks, int K, int csf_on, const void* sig_csf,
-                    const void* T, const void* shift, int64_t V, const void* w, const void* log_sum, const void* status) {
-  if (!p || V < 0 || (V > 0 && (!Y || !peaks || !T || !shift || !w || !log_sum || !status)))
-    return mfx_fail(MFX_ERR_ARG, "%s: bad argument", fn);
-  if (K != 1 && K != 2)
-    return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: K must be 1 or 2 (got %d): three fascicles and voxels without one are out of scope", fn, K);
-  if (csf_on && !sig_csf) return mfx_fail(MFX_ERR_ARG, "%s: csf_on without sig_csf", fn);
-  if (V > 0x7fffffff) return mfx_fail(MFX_ERR_ARG, "%s: V too large for one call", fn);
-  return MFX_OK;
+  if (csf) return sweep_launch(mfx_post_k1_kernel<true, WGT>, ka, nvox, SWEEP_K1_WG, lds, false, st);
+  return sweep_launch(mfx_post_k1_kernel<false, WGT>, ka, nvox, SWEEP_K1_WG, lds, false, st);
 }
 
 // shared body of the device entry points; wgt: d_W [V x M] (w_stride = M) or [M] (w_stride = 0) scales the rows
 int post_enqueue(const char* fn, const mfx_plan* p, const double* d_Y, const double* d_peaks, int K, int csf_on,
                  const double* d_sig_csf, const double* d_T, const double* d_shift, int64_t V, double* d_w, double* d_log_sum,
                  int32_t* d_status, void* stream, bool wgt = false, const double* d_W = nullptr, int64_t w_stride = 0) {
-  if (mfx_device_count() <= 0) return mfx_no_device();
-  if (int rc = post_check_args(fn, p, d_Y, d_peaks, K, csf_on, d_sig_csf, d_T, d_shift, V, d_w, d_log_sum, d_status)) return rc;
   PostArgsW a{};
-  int device = 0;
-  mfx_plan_view(p, &a.T, &a.P, &device);
-  if (a.P.M > 560) return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: supports M <= 560 (got %d)", fn, a.P.M);
-  if (wgt && V > 0 && !d_W) return mfx_fail(MFX_ERR_ARG, "%s: bad argument", fn);
-  if (wgt && w_stride != 0 && w_stride != a.P.M)
-    return mfx_fail(MFX_ERR_ARG, "%s: w_stride should be M = %d or 0 (got %lld)", fn, a.P.M, (long long)w_stride);
-  if (mfx_profile_cut() != MFX_POST_CUT) return mfx_fail(MFX_ERR_HIP, "%s: built with a cut other than the profile's", fn);
-  if (V == 0) return MFX_OK;
-  if (int rc = mfx_require_device(device)) return rc;
-  a.Y = d_Y; a.peaks = d_peaks; a.xc = csf_on ? d_sig_csf : nullptr; a.temp = d_T; a.shift = d_shift;
-  a.w = d_w; a.log_sum = d_log_sum; a.status = d_status;
-  a.W = d_W; a.wstride = w_stride;
+  bool run = false;
+  if (int rc = sweep_enqueue_head(fn, p, d_Y, d_peaks, K, csf_on, d_sig_csf, V, d_T && d_shift && d_w && d_log_sum && d_status, wgt,
+                                  d_W, w_stride, &a, &run)) return rc;
+  if (!run) return MFX_OK;
+  a.temp = d_T; a.shift = d_shift; a.w = d_w; a.log_sum = d_log_sum; a.status = d_status;
   hipStream_t st = (hipStream_t)stream;
   if (K == 2) return wgt ? post_launch_k2<true>(a, (int)V, csf_on != 0, st, fn) : post_launch_k2<false>(a, (int)V, csf_on != 0, st, fn);
   return wgt ? post_launch_k1<true>(a, (int)V, csf_on != 0, st) : post_launch_k1<false>(a, (int)V, csf_on != 0, st);
 }
 
-// shared body of the host entry points
+// shared body of the host entry points; the device count always comes before the plan
 int post_host(const char* fn, const mfx_plan* p, const double* Y, const double* peaks, int K, int csf_on, const double* sig_csf,
               const double* T, const double* shift, int64_t V, double* w, double* log_sum, int32_t* status, bool wgt = false,
               const double* W = nullptr, int64_t w_stride = 0) {
-  if (mfx_device_count() <= 0) return mfx_no_device();   // before the plan is looked at
-  if (int rc = post_check_args(fn, p, Y, peaks, K, csf_on, sig_csf, T, shift, V, w, log_sum, status)) return rc;
-  if (V == 0) return MFX_OK;
-  TablesDev Td;
-  PlanDev P;
-  int device = 0;
-  mfx_plan_view(p, &Td, &P, &device);
-  if (wgt && (!W || (w_stride != 0 && w_stride != P.M)))
-    return mfx_fail(MFX_ERR_ARG, "%s: W should be given with w_stride M = %d or 0 (got %lld)", fn, P.M, (long long)w_stride);
-  if (int rc = mfx_require_device(device)) return rc;
-  const size_t M = P.M, N = Td.N, nout = (size_t)V * K * N;
-  const size_t nW = wgt ? (w_stride ? (size_t)V * M : M) : 0;
-  DevMem dY, dpk, dx, dT, dsh, dw, dls, dst, dW;
-  HIPCHK(dY.alloc(sizeof(double) * V * M));
-  HIPCHK(dpk.alloc(sizeof(double) * V * 3 * K));
-  HIPCHK(dx.alloc(sizeof(double) * M));
-  HIPCHK(dT.alloc(sizeof(double) * V));
-  HIPCHK(dsh.alloc(sizeof(double) * V));
-  HIPCHK(dw.alloc(sizeof(double) * nout));
-  HIPCHK(dls.alloc(sizeof(double) * V));
-  HIPCHK(dst.alloc(sizeof(int32_t) * V));
-  HIPCHK(dW.alloc(sizeof(double) * nW));
-  HIPCHK(hipMemcpy(dY.p, Y, sizeof(double) * V * M, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dpk.p, peaks, sizeof(double) * V * 3 * K, hipMemcpyHostToDevice));
-  if (csf_on) HIPCHK(hipMemcpy(dx.p, sig_csf, sizeof(double) * M, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dT.p, T, sizeof(double) * V, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dsh.p, shift, sizeof(double) * V, hipMemcpyHostToDevice));
-  if (wgt) HIPCHK(hipMemcpy(dW.p, W, sizeof(double) * nW, hipMemcpyHostToDevice));
-  if (int rc = post_enqueue(fn, p, dY.as<double>(), dpk.as<double>(), K, csf_on, csf_on ? dx.as<double>() : nullptr, dT.as<double>(),
-                            dsh.as<double>(), V, dw.as<double>(), dls.as<double>(), dst.as<int32_t>(), nullptr, wgt,
-                            dW.as<double>(), w_stride)) return rc;
+  SweepHostIn in;
+  bool run = false;
+  if (int rc = in.stage(fn, p, Y, peaks, K, csf_on, sig_csf, V, T && shift && w && log_sum && status, true, wgt, W, w_stride, &run))
+    return rc;
+  if (!run) return MFX_OK;
+  DevBuf<double> dT, dsh, dw, dls;
+  DevBuf<int32_t> dst;
+  HIPCHK(dT.upload(T, (size_t)V));
+  HIPCHK(dsh.upload(shift, (size_t)V));
+  HIPCHK(dw.alloc_n((size_t)V * K * in.N));
+  HIPCHK(dls.alloc_n((size_t)V));
+  HIPCHK(dst.alloc_n((size_t)V));
+  if (int rc = post_enqueue(fn, p, in.Y.get(), in.peaks.get(), K, csf_on, in.x.get(), dT.get(), dsh.get(), V, dw.get(), dls.get(),
+                            dst.get(), nullptr, wgt, in.W.get(), w_stride)) return rc;
   if (int rc = mfx_plan_status(p, nullptr)) return rc;   // waits; a direction that is not a unit vector
-  HIPCHK(hipMemcpy(w, dw.p, sizeof(double) * nout, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(log_sum, dls.p, sizeof(double) * V, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(status, dst.p, sizeof(int32_t) * V, hipMemcpyDeviceToHost));
+  HIPCHK(dw.download(w));
+  HIPCHK(dls.download(log_sum));
+  HIPCHK(dst.download(status));
   return MFX_OK;
 }
 
@@ -674,13 +533,7 @@ int post_host(const char* fn, const mfx_plan* p, const double* Y, const double* 
 extern "C" int mfx_post_abi_version(void) { return 1; }
 
 extern "C" int mfx_post_max_atoms(const mfx_plan* p, int csf_on) {
-  if (!p) return 0;
-  TablesDev T;
-  PlanDev P;
-  int device = 0;
-  mfx_plan_view(p, &T, &P, &device);
-  if (P.M > 560) return 0;
-  return post_max_atoms(P.M, P.any_bracket != 0, csf_on != 0);
+  return sweep_plan_max_atoms(p, [=](int M, bool br) { return post_max_atoms(M, br, csf_on != 0); });
 }
 
 extern "C" int mfx_post_dev(const mfx_plan* p, const double* d_Y, const double* d_peaks, int K, int csf_on,
@@ -700,14 +553,10 @@ int mfx_wsoft_prof_max_atoms(int M, bool br, bool csf, bool land);   // profile.
 extern "C" int mfx_wsoft_abi_version(void) { return 1; }
 
 extern "C" int mfx_wsoft_max_atoms(const mfx_plan* p, int csf_on, int what) {
-  if (!p || what < 0 || what > 2) return 0;
-  TablesDev T;
-  PlanDev P;
-  int device = 0;
-  mfx_plan_view(p, &T, &P, &device);
-  if (P.M > 560) return 0;
-  if (what == 0) return post_max_atoms(P.M, P.any_bracket != 0, csf_on != 0, true);
-  return mfx_wsoft_prof_max_atoms(P.M, P.any_bracket != 0, csf_on != 0, what == 2);
+  if (what < 0 || what > 2) return 0;
+  return sweep_plan_max_atoms(p, [=](int M, bool br) {
+    return what == 0 ? post_max_atoms(M, br, csf_on != 0, true) : mfx_wsoft_prof_max_atoms(M, br, csf_on != 0, what == 2);
+  });
 }
 
 extern "C" int mfx_wpost_dev(const mfx_plan* p, const double* d_Y, const double* d_W, int64_t w_stride, const double* d_peaks, int K,

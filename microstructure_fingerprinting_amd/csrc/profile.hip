@@ -23,30 +23,18 @@
 //                         MFMAs of the current one where two LDS buffers fit); its pipelined k-loop is not ported.
 // mfx_profile_k1_kernel   one workgroup per voxel, one thread per atom: ||y||^2 - max(Y, 0)^2 / A (and the CSF form).
 //
-// Arithmetic: Gram entries and statistics in plain FP64 (separate products and sums, MFMA for the cross terms);
-// the closed forms use fma() like the fit's ranking math.  Error of a pair's value: each of the six Gram quantities
-// carries at most M eps |a||b|, carried through (z1^2 - 2 c z1 z2 + z2^2) / (1 - c^2); tests hold the kernel to
-// 16 M eps ||y||^2 / (1 - c^2).
-#include "mfx_host.h"
+// The scoring helpers, the cut, the weights' scan and the host plumbing are soft_sweep.h's, shared with posterior.hip,
+// whose K = 2 kernel restates phases 0-2 of this one.
+//
+// Error of a pair's value: each of the six Gram quantities carries at most M eps |a||b|, carried through
+// (z1^2 - 2 c z1 z2 + z2^2) / (1 - c^2); tests hold the kernel to 16 M eps ||y||^2 / (1 - c^2).
+#include "soft_sweep.h"
 #include "../../include/mfx_profile.h"
 #include "../../include/mfx_wsoft.h"
 
-#include <algorithm>
-#include <type_traits>
-
-#define MFX_PROFILE_CUT 1e-8   // pairs with 1 - c^2 <= this are scored as their better single atom (the fit's MFX_DET_REL)
-
 namespace {
 
-constexpr size_t PROF_LDS_MAX = 160 * 1024;
-constexpr int PROF_K1_WG = 256;
-
-struct ProfArgs {
-  TablesDev T;
-  PlanDev P;
-  const double* Y;      // [V x M]
-  const double* peaks;  // [V x 3 K]
-  const double* xc;     // [M] the CSF column (CSF variants)
+struct ProfArgs : SweepArgs {
   double* obj;          // profile: [V x K x N]; landscape: [V x N x N]
   int* partner;         // [V x K x N] or null
 };
@@ -57,18 +45,7 @@ struct ProfArgsW : ProfArgs {
 };
 template <bool WGT> using ProfArgsT = std::conditional_t<WGT, ProfArgsW, ProfArgs>;
 
-// true when the voxel's weights are unusable (one negative or not finite, or none positive).  Every thread reads all M
-// weights (the address does not depend on the lane), so the answer is workgroup-uniform without a barrier.
-__device__ __forceinline__ bool prof_weights_unusable(const double* __restrict__ wv, int M) {
-  bool bad = false, pos = false;
-  for (int m = 0; m < M; ++m) {
-    const double w = wv[m];
-    bad |= !(w >= 0.0) || !(w <= 1.79769313486231570815e308);
-    pos |= w > 0.0;
-  }
-  return bad || !pos;
-}
-// such a voxel: NaN values, partner -1 (every thread of the workgroup takes part)
+// a voxel with unusable weights: NaN values, partner -1 (every thread of the workgroup takes part)
 __device__ __forceinline__ void prof_nan_rows(const ProfArgs& a, size_t vox, size_t n_out, int tid, int wg) {
   const double nan = __builtin_nan("");
   for (size_t n = tid; n < n_out; n += wg) {
@@ -77,50 +54,10 @@ __device__ __forceinline__ void prof_nan_rows(const ProfArgs& a, size_t vox, siz
   }
 }
 
-// score s = ||y||^2 - F of one atom pair as the fraction p / q (q > 0 whenever p > 0).  p1 = max(Y1, 0)^2 and
-// p2 likewise are the single atoms' numerators (denominators A11, A22).
-__device__ __forceinline__ void prof_pair_frac(double A11, double A22, double A12, double Y1, double Y2, double p1, double p2,
-                                               double& p, double& q) {
-  const double d1 = fma(-A12, Y2, A22 * Y1);   // w1 Det, mf_utils.py:425
-  const double d2 = fma(-A12, Y1, A11 * Y2);   // w2 Det
-  const double pd = A11 * A22;
-  const double Det = fma(-A12, A12, pd);
-  const double num = fma(Y2, d2, Y1 * d1);     // Y1 w1 + Y2 w2, times Det
-  const bool both = (d1 > 0.0) & (d2 > 0.0) & (Det > MFX_PROFILE_CUT * pd);
-  const bool first = p1 * A22 >= p2 * A11;     // the better single atom (ties: the row's)
-  p = both ? num : (first ? p1 : p2);
-  q = both ? Det : (first ? A11 : A22);
-}
-
-// the same with the weights (CSF form): i11 = 1 / A11 (0 for a null atom), returns the score
-__device__ __forceinline__ double prof_pair_w(double A11, double A22, double A12, double Y1, double Y2, double i11, double i22,
-                                              double& w1, double& w2) {
-  const double d1 = fma(-A12, Y2, A22 * Y1);
-  const double d2 = fma(-A12, Y1, A11 * Y2);
-  const double pd = A11 * A22;
-  const double Det = fma(-A12, A12, pd);
-  const bool both = (d1 > 0.0) & (d2 > 0.0) & (Det > MFX_PROFILE_CUT * pd);
-  const double u1 = fmax(Y1, 0.0) * i11, u2 = fmax(Y2, 0.0) * i22;   // single-atom weights
-  const double s1 = Y1 * u1, s2 = Y2 * u2;
-  const bool first = s1 >= s2;
-  const double iD = both ? 1.0 / Det : 0.0;
-  w1 = both ? d1 * iD : (first ? u1 : 0.0);
-  w2 = both ? d2 * iD : (first ? 0.0 : u2);
-  return both ? fma(Y2, d2, Y1 * d1) * iD : (first ? s1 : s2);
-}
-
-// statistics of an atom with the CSF column x projected out: A' = A - X^2 / xx, Y' = Y - X xy / xx; an atom
-// parallel to x (A' within the cut of 0) becomes a null atom
-__device__ __forceinline__ void prof_primed(double A, double Yv, double X, double ixx, double xy, double& Ap, double& Yp,
-                                            double& iAp) {
-  const double xs = X * ixx;
-  Ap = fma(-xs, X, A);
-  Yp = fma(-xs, xy, Yv);
-  const bool ok = Ap > MFX_PROFILE_CUT * A;
-  Ap = ok ? Ap : 0.0;
-  Yp = ok ? Yp : 0.0;
-  iAp = ok ? 1.0 / Ap : 0.0;
-}
+// the K = 2 kernel's own LDS behind the common front of soft_sweep.h (none of it in the landscape form), for the host.  Doubles: the running column
+// best as a fraction, [NP] each, and the waves' column bests of one chunk, [2][NW][CW] each; ints: their atom indices.
+constexpr int prof_own_dbl(bool land, int NP, int nw, int cw) { return land ? 0 : 2 * NP + 2 * 2 * nw * cw; }
+constexpr int prof_own_int(bool land, int NP, int nw, int cw) { return land ? 0 : NP + 2 * nw * cw; }
 
 // NW waves per workgroup, TILES 16-atom column tiles per D_1 chunk, NBUF LDS buffers for the chunks (as fit_k2.hip):
 // (8, 2, 2) for exact-G protocols of M <= 200 without CSF where it fits; (4, 1, 2) and (4, 1, 1) - one wave per SIMD with the whole register
@@ -172,7 +109,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void mfx_profile_k2_kerne
   const double* __restrict__ yv = a.Y + vox * M;
   const double* __restrict__ pk = a.peaks + vox * 6;
   if constexpr (WGT) {   // unusable weights leave here, workgroup-uniform
-    if (prof_weights_unusable(a.W + vox * a.wstride, M)) {
+    if (sweep_weights_unusable(a.W + vox * a.wstride, M)) {
       if (tid < 2) mfx_check_dir(a.P, pk + 3 * tid, (int)vox);
       prof_nan_rows(a, vox, (size_t)(LAND ? N : 2) * N, tid, WG);
       return;
@@ -297,7 +234,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void mfx_profile_k2_kerne
         const double X = s_X1[i];
         A11u[r] = A; Y1u[r] = Yv; X1r[r] = X; X1s[r] = X * ixx;
         i11u[r] = A > 0.0 ? 1.0 / A : 0.0;
-        prof_primed(A, Yv, X, ixx, xy, A11r[r], Y1r[r], i11p[r]);
+        sweep_primed(A, Yv, X, ixx, xy, A11r[r], Y1r[r], i11p[r]);
         p1r[r] = 0.0;
       } else {
         A11r[r] = A; Y1r[r] = Yv;
@@ -343,7 +280,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void mfx_profile_k2_kerne
           if constexpr (CSF) {
             X2 = s_X2[jq]; A22u = A22; Y2u = Y2;
             i22u = A22 > 0.0 ? 1.0 / A22 : 0.0;
-            prof_primed(A22u, Y2u, X2, ixx, xy, A22, Y2, i22p);
+            sweep_primed(A22u, Y2u, X2, ixx, xy, A22, Y2, i22p);
           } else {
             const double yp = fmax(Y2, 0.0);
             p2 = yp * yp;
@@ -355,13 +292,13 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void mfx_profile_k2_kerne
               // x projected out: the two-variable form on the primed quantities, then the sign of w_x decides
               double w1, w2, v1, v2;
               const double A12p = fma(-X1s[r], X2, acc[r]);
-              const double sp = prof_pair_w(A11r[r], A22, A12p, Y1r[r], Y2, i11p[r], i22p, w1, w2);
+              const double sp = sweep_pair_w(A11r[r], A22, A12p, Y1r[r], Y2, i11p[r], i22p, w1, w2);
               const double wxn = fma(-w2, X2, fma(-w1, X1r[r], xy));   // w_x times x.x
-              const double su = prof_pair_w(A11u[r], A22u, acc[r], Y1u[r], Y2u, i11u[r], i22u, v1, v2);
+              const double su = sweep_pair_w(A11u[r], A22u, acc[r], Y1u[r], Y2u, i11u[r], i22u, v1, v2);
               p = (wxn >= 0.0) ? sx + sp : su;
               q = 1.0;
             } else {
-              prof_pair_frac(A11r[r], A22, acc[r], Y1r[r], Y2, p1r[r], p2, p, q);
+              sweep_pair_frac(A11r[r], A22, acc[r], Y1r[r], Y2, p1r[r], p2, p, q);
             }
             const bool ok = rowok[r] & colok;
             if constexpr (LAND) {
@@ -455,7 +392,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void mfx_profile_k2_kerne
 
 // K = 1: one workgroup per voxel, one thread per atom
 template <bool CSF, bool WGT = false>
-__global__ __launch_bounds__(PROF_K1_WG) void mfx_profile_k1_kernel(ProfArgsT<WGT> a) {
+__global__ __launch_bounds__(SWEEP_K1_WG) void mfx_profile_k1_kernel(ProfArgsT<WGT> a) {
   extern __shared__ double smem[];
   const int tid = threadIdx.x;
   const int M = a.P.M, N = a.T.N, ldn = a.T.ldn;
@@ -470,13 +407,13 @@ __global__ __launch_bounds__(PROF_K1_WG) void mfx_profile_k1_kernel(ProfArgsT<WG
   const double* __restrict__ yv = a.Y + vox * M;
   const double* __restrict__ pk = a.peaks + vox * 3;
   if constexpr (WGT) {
-    if (prof_weights_unusable(a.W + vox * a.wstride, M)) {
+    if (sweep_weights_unusable(a.W + vox * a.wstride, M)) {
       if (tid == 0) mfx_check_dir(a.P, pk, (int)vox);
-      prof_nan_rows(a, vox, (size_t)N, tid, PROF_K1_WG);
+      prof_nan_rows(a, vox, (size_t)N, tid, SWEEP_K1_WG);
       return;
     }
   }
-  for (int m = tid; m < M; m += PROF_K1_WG) {
+  for (int m = tid; m < M; m += SWEEP_K1_WG) {
     if constexpr (WGT) {
       const double s = sqrt(a.W[vox * a.wstride + m]);
       s_w[m] = s;
@@ -497,7 +434,7 @@ __global__ __launch_bounds__(PROF_K1_WG) void mfx_profile_k1_kernel(ProfArgsT<WG
     if constexpr (CSF) { xx += s_x[m] * s_x[m]; xy += s_x[m] * s_y[m]; }
   }
   const double ixx = (CSF && xx > 0.0) ? 1.0 / xx : 0.0;
-  for (int n = tid; n < N; n += PROF_K1_WG) {
+  for (int n = tid; n < N; n += SWEEP_K1_WG) {
     double a2 = 0.0, ay = 0.0, ax = 0.0;
     for (int m = 0; m < M; ++m) {
       RowDesc rd;
@@ -512,7 +449,7 @@ __global__ __launch_bounds__(PROF_K1_WG) void mfx_profile_k1_kernel(ProfArgsT<WG
     double s = a2 > 0.0 ? yp * yp / a2 : 0.0;
     if constexpr (CSF) {
       double Ap, Yp, iAp;
-      prof_primed(a2, ay, ax, ixx, xy, Ap, Yp, iAp);
+      sweep_primed(a2, ay, ax, ixx, xy, Ap, Yp, iAp);
       const double w1 = fmax(Yp, 0.0) * iAp;
       if (fma(-w1, ax, xy) >= 0.0) s = xy * xy * ixx + Yp * w1;
     }
@@ -521,148 +458,78 @@ __global__ __launch_bounds__(PROF_K1_WG) void mfx_profile_k1_kernel(ProfArgsT<WG
   }
 }
 
-size_t prof_lds_bytes(int ksteps, bool bracket, bool csf, bool land, int NP, int nw, int tiles, int nbuf, bool wgt = false) {
-  const size_t MP = (size_t)ksteps * 4, MPS = MP, cw = 16 * (size_t)tiles;
-  const size_t dbl = (size_t)nbuf * tiles * MPS * 16 + MP + (csf ? MP : 0) + (wgt ? MP : 0) + 2 * MP + (bracket ? 4 * MP : 0) +
-                     (size_t)NP * (4 + (csf ? 2 : 0) + (land ? 0 : 2)) + (land ? 0 : 2 * 2 * nw * cw);
-  const size_t ints = 2 * MP + (bracket ? 2 * MP : 0) + (land ? 0 : (size_t)NP + 2 * nw * cw);
-  return dbl * 8 + ints * 4;
+size_t prof_lds_bytes(int ksteps, bool bracket, bool csf, bool land, int NP, int nw, int tiles, int nbuf, bool wgt) {
+  return sweep_lds_bytes(ksteps, NP, bracket, csf, wgt, nbuf, tiles, prof_own_dbl(land, NP, nw, 16 * tiles),
+                         prof_own_int(land, NP, nw, 16 * tiles));
 }
-
-template <int KS, bool BR, bool CSF, bool LAND, int NW, int TILES, int NBUF, bool WGT>
-int prof_launch_t(const ProfArgsW& a, int nvox, hipStream_t st) {
-  const size_t lds = prof_lds_bytes(KS, BR, CSF, LAND, a.T.ldn, NW, TILES, NBUF, WGT);
-  auto kern = mfx_profile_k2_kernel<KS, BR, CSF, LAND, NW, TILES, NBUF, WGT>;
-  const ProfArgsT<WGT> ka = a;   // the unweighted kernels take the ProfArgs part
-  HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3(nvox), dim3(NW * 64), lds, st, ka);
-  HIPCHK(hipGetLastError());
-  return MFX_OK;
+// the family's LDS bytes of a configuration, for sweep_pick and sweep_max_atoms
+auto prof_lds(bool br, bool csf, bool land, bool wgt) {
+  return [=](const SweepCfg& c, int NP) { return prof_lds_bytes(c.ks, br, csf, land, NP, c.nw, c.tiles, c.nbuf, wgt); };
 }
+int prof_max_atoms(int M, bool br, bool csf, bool land, bool wgt = false) { return sweep_max_atoms(M, br, csf, prof_lds(br, csf, land, wgt)); }
 
-// the configurations of M <= 200 in the order they are tried: {KSTEPS, NW, TILES, NBUF}; longer protocols: {140, 4, 1, 1}
-struct ProfCfg { int ks, nw, tiles, nbuf; };
-constexpr ProfCfg PROF_CFG_200[3] = {{50, 8, 2, 2}, {50, 4, 1, 2}, {50, 4, 1, 1}};
-
-int prof_pick(int M, bool br, bool csf, bool land, int NP, bool wgt = false) {   // index into PROF_CFG_200, 3: the long-protocol form, -1: none fits
-  if (M <= 200) {
-    for (int c = (csf || br) ? 1 : 0; c < 3; ++c)   // the CSF scan and bracketed rows do not fit the 256 registers of the 8-wave form
-      if (prof_lds_bytes(50, br, csf, land, NP, PROF_CFG_200[c].nw, PROF_CFG_200[c].tiles, PROF_CFG_200[c].nbuf, wgt) <= PROF_LDS_MAX) return c;
-    return -1;
+template <bool LAND, bool WGT>
+struct ProfLaunch {
+  const ProfArgsW& a;
+  int nvox;
+  hipStream_t st;
+  template <int KS, bool BR, bool CSF, int NW, int TILES, int NBUF>
+  int run() const {
+    const ProfArgsT<WGT> ka = a;   // the unweighted kernels take the ProfArgs part
+    return sweep_launch(mfx_profile_k2_kernel<KS, BR, CSF, LAND, NW, TILES, NBUF, WGT>, ka, nvox, NW * 64,
+                        prof_lds_bytes(KS, BR, CSF, LAND, a.T.ldn, NW, TILES, NBUF, WGT), true, st);
   }
-  return prof_lds_bytes(140, br, csf, land, NP, 4, 1, 1, wgt) <= PROF_LDS_MAX ? 3 : -1;
-}
-
-int prof_max_atoms(int M, bool br, bool csf, bool land, bool wgt = false) {
-  int n = 0;
-  while (n < (1 << 20) && prof_pick(M, br, csf, land, n + 16, wgt) >= 0) n += 16;
-  return n;
-}
-
-template <bool BR, bool CSF, bool LAND, bool WGT>
-int prof_launch_cfg(int cfg, const ProfArgsW& a, int nvox, hipStream_t st) {
-  switch (cfg) {
-    case 0:
-      if constexpr (!CSF && !BR) return prof_launch_t<50, BR, CSF, LAND, 8, 2, 2, WGT>(a, nvox, st);
-      return mfx_fail(MFX_ERR_ARG, "profile: no such configuration");
-    case 1: return prof_launch_t<50, BR, CSF, LAND, 4, 1, 2, WGT>(a, nvox, st);
-    case 2: return prof_launch_t<50, BR, CSF, LAND, 4, 1, 1, WGT>(a, nvox, st);
-    default: return prof_launch_t<140, BR, CSF, LAND, 4, 1, 1, WGT>(a, nvox, st);
-  }
-}
+};
 
 template <bool WGT>
 int prof_launch_k2(const ProfArgsW& a, int nvox, bool csf, bool land, hipStream_t st, const char* fn) {
-  const int M = a.P.M;
-  const bool br = a.P.any_bracket != 0;
-  if (M > 560) return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: the K = 2 kernel supports M <= 560 (got %d)", fn, M);
-  const int cfg = prof_pick(M, br, csf, land, a.T.ldn, WGT);
-  if (cfg < 0)
-    return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: N = %d atoms exceed the %d that fit in LDS for this protocol (M = %d)", fn, a.T.N,
-                    prof_max_atoms(M, br, csf, land, WGT), M);
-  if (br) {
-    if (csf) return land ? prof_launch_cfg<true, true, true, WGT>(cfg, a, nvox, st) : prof_launch_cfg<true, true, false, WGT>(cfg, a, nvox, st);
-    return land ? prof_launch_cfg<true, false, true, WGT>(cfg, a, nvox, st) : prof_launch_cfg<true, false, false, WGT>(cfg, a, nvox, st);
-  }
-  if (csf) return land ? prof_launch_cfg<false, true, true, WGT>(cfg, a, nvox, st) : prof_launch_cfg<false, true, false, WGT>(cfg, a, nvox, st);
-  return land ? prof_launch_cfg<false, false, true, WGT>(cfg, a, nvox, st) : prof_launch_cfg<false, false, false, WGT>(cfg, a, nvox, st);
+  if (a.P.M > 560) return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: the K = 2 kernel supports M <= 560 (got %d)", fn, a.P.M);
+  const auto lds = prof_lds(a.P.any_bracket != 0, csf, land, WGT);
+  if (land) return sweep_launch_k2(fn, "profile", a, csf, lds, ProfLaunch<true, WGT>{a, nvox, st});
+  return sweep_launch_k2(fn, "profile", a, csf, lds, ProfLaunch<false, WGT>{a, nvox, st});
 }
 
 template <bool WGT>
 int prof_launch_k1(const ProfArgsW& a, int nvox, bool csf, hipStream_t st) {
-  const size_t lds = (size_t)a.P.M * ((WGT ? 5 : 4) * sizeof(double) + 2 * sizeof(int));
+  const size_t lds = sweep_k1_lds_bytes(a.P.M, WGT, 0);
   const ProfArgsT<WGT> ka = a;
-  if (csf) hipLaunchKernelGGL((mfx_profile_k1_kernel<true, WGT>), dim3((unsigned)nvox), dim3(PROF_K1_WG), lds, st, ka);
-  else hipLaunchKernelGGL((mfx_profile_k1_kernel<false, WGT>), dim3((unsigned)nvox), dim3(PROF_K1_WG), lds, st, ka);
-  HIPCHK(hipGetLastError());
-  return MFX_OK;
-}
-
-int prof_check_args(const char* fn, const mfx_plan* p, const void* Y, const void* peaks, int K, int csf_on, const void* sig_csf,
-                    int64_t V, const void* out) {
-  if (!p || V < 0 || (V > 0 && (!Y || !peaks || !out))) return mfx_fail(MFX_ERR_ARG, "%s: bad argument", fn);
-  if (K != 1 && K != 2)
-    return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: K must be 1 or 2 (got %d): three fascicles and voxels without one are out of scope", fn, K);
-  if (csf_on && !sig_csf) return mfx_fail(MFX_ERR_ARG, "%s: csf_on without sig_csf", fn);
-  if (V > 0x7fffffff) return mfx_fail(MFX_ERR_ARG, "%s: V too large for one call", fn);
-  return MFX_OK;
+  if (csf) return sweep_launch(mfx_profile_k1_kernel<true, WGT>, ka, nvox, SWEEP_K1_WG, lds, false, st);
+  return sweep_launch(mfx_profile_k1_kernel<false, WGT>, ka, nvox, SWEEP_K1_WG, lds, false, st);
 }
 
 // shared body of the device entry points; wgt: d_W [V x M] (w_stride = M) or [M] (w_stride = 0) scales the rows
 int prof_enqueue(const char* fn, const mfx_plan* p, const double* d_Y, const double* d_peaks, int K, int csf_on,
                  const double* d_sig_csf, int64_t V, double* d_obj, int32_t* d_partner, bool land, void* stream, bool wgt = false,
                  const double* d_W = nullptr, int64_t w_stride = 0) {
-  if (mfx_device_count() <= 0) return mfx_no_device();
-  if (int rc = prof_check_args(fn, p, d_Y, d_peaks, K, csf_on, d_sig_csf, V, d_obj)) return rc;
   ProfArgsW a{};
-  int device = 0;
-  mfx_plan_view(p, &a.T, &a.P, &device);
-  if (a.P.M > 560) return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: supports M <= 560 (got %d)", fn, a.P.M);
-  if (wgt && V > 0 && !d_W) return mfx_fail(MFX_ERR_ARG, "%s: bad argument", fn);
-  if (wgt && w_stride != 0 && w_stride != a.P.M)
-    return mfx_fail(MFX_ERR_ARG, "%s: w_stride should be M = %d or 0 (got %lld)", fn, a.P.M, (long long)w_stride);
-  if (V == 0) return MFX_OK;
-  if (int rc = mfx_require_device(device)) return rc;
-  a.Y = d_Y; a.peaks = d_peaks; a.xc = csf_on ? d_sig_csf : nullptr; a.obj = d_obj; a.partner = d_partner;
-  a.W = d_W; a.wstride = w_stride;
+  bool run = false;
+  if (int rc = sweep_enqueue_head(fn, p, d_Y, d_peaks, K, csf_on, d_sig_csf, V, d_obj != nullptr, wgt, d_W, w_stride, &a, &run)) return rc;
+  if (!run) return MFX_OK;
+  a.obj = d_obj; a.partner = d_partner;
   hipStream_t st = (hipStream_t)stream;
   if (K == 2)
     return wgt ? prof_launch_k2<true>(a, (int)V, csf_on != 0, land, st, fn) : prof_launch_k2<false>(a, (int)V, csf_on != 0, land, st, fn);
   return wgt ? prof_launch_k1<true>(a, (int)V, csf_on != 0, st) : prof_launch_k1<false>(a, (int)V, csf_on != 0, st);
 }
 
-// shared body of the host entry points: out [V x rows x N] with rows = K (profile) or N (landscape)
+// shared body of the host entry points: out [V x rows x N] with rows = K (profile) or N (landscape).  The device count
+// comes before the plan only in the weighted forms.
 int prof_host(const char* fn, const mfx_plan* p, const double* Y, const double* peaks, int K, int csf_on, const double* sig_csf,
               int64_t V, double* obj, int32_t* partner, bool land, bool wgt = false, const double* W = nullptr, int64_t w_stride = 0) {
-  if (wgt && mfx_device_count() <= 0) return mfx_no_device();   // before the plan is looked at
-  if (int rc = prof_check_args(fn, p, Y, peaks, K, csf_on, sig_csf, V, obj)) return rc;
-  if (V == 0) return MFX_OK;
-  TablesDev T;
-  PlanDev P;
-  int device = 0;
-  mfx_plan_view(p, &T, &P, &device);
-  if (wgt && (!W || (w_stride != 0 && w_stride != P.M)))
-    return mfx_fail(MFX_ERR_ARG, "%s: W should be given with w_stride M = %d or 0 (got %lld)", fn, P.M, (long long)w_stride);
-  if (int rc = mfx_require_device(device)) return rc;
-  const size_t M = P.M, N = T.N, nout = (size_t)V * (land ? N : (size_t)K) * N;
-  const size_t nW = wgt ? (w_stride ? (size_t)V * M : M) : 0;
-  DevMem dY, dpk, dx, dobj, dpar, dW;
-  HIPCHK(dY.alloc(sizeof(double) * V * M));
-  HIPCHK(dpk.alloc(sizeof(double) * V * 3 * K));
-  HIPCHK(dx.alloc(sizeof(double) * M));
-  HIPCHK(dobj.alloc(sizeof(double) * nout));
-  HIPCHK(dpar.alloc(partner ? sizeof(int32_t) * nout : 0));
-  HIPCHK(dW.alloc(sizeof(double) * nW));
-  HIPCHK(hipMemcpy(dY.p, Y, sizeof(double) * V * M, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dpk.p, peaks, sizeof(double) * V * 3 * K, hipMemcpyHostToDevice));
-  if (csf_on) HIPCHK(hipMemcpy(dx.p, sig_csf, sizeof(double) * M, hipMemcpyHostToDevice));
-  if (wgt) HIPCHK(hipMemcpy(dW.p, W, sizeof(double) * nW, hipMemcpyHostToDevice));
-  if (int rc = prof_enqueue(fn, p, dY.as<double>(), dpk.as<double>(), K, csf_on, csf_on ? dx.as<double>() : nullptr, V,
-                            dobj.as<double>(), partner ? dpar.as<int32_t>() : nullptr, land, nullptr, wgt, dW.as<double>(),
-                            w_stride)) return rc;
+  SweepHostIn in;
+  bool run = false;
+  if (int rc = in.stage(fn, p, Y, peaks, K, csf_on, sig_csf, V, obj != nullptr, wgt, wgt, W, w_stride, &run)) return rc;
+  if (!run) return MFX_OK;
+  const size_t nout = (size_t)V * (land ? in.N : (size_t)K) * in.N;
+  DevBuf<double> dobj;
+  DevBuf<int32_t> dpar;   // stays null without partner
+  HIPCHK(dobj.alloc_n(nout));
+  if (partner) HIPCHK(dpar.alloc_n(nout));
+  if (int rc = prof_enqueue(fn, p, in.Y.get(), in.peaks.get(), K, csf_on, in.x.get(), V, dobj.get(), dpar.get(), land, nullptr, wgt,
+                            in.W.get(), w_stride)) return rc;
   if (int rc = mfx_plan_status(p, nullptr)) return rc;   // waits; a direction that is not a unit vector
-  HIPCHK(hipMemcpy(obj, dobj.p, sizeof(double) * nout, hipMemcpyDeviceToHost));
-  if (partner) HIPCHK(hipMemcpy(partner, dpar.p, sizeof(int32_t) * nout, hipMemcpyDeviceToHost));
+  HIPCHK(dobj.download(obj));
+  if (partner) HIPCHK(dpar.download(partner));
   return MFX_OK;
 }
 
@@ -673,13 +540,7 @@ extern "C" int mfx_profile_abi_version(void) { return 1; }
 extern "C" double mfx_profile_cut(void) { return MFX_PROFILE_CUT; }
 
 extern "C" int mfx_profile_max_atoms(const mfx_plan* p, int csf_on, int landscape) {
-  if (!p) return 0;
-  TablesDev T;
-  PlanDev P;
-  int device = 0;
-  mfx_plan_view(p, &T, &P, &device);
-  if (P.M > 560) return 0;
-  return prof_max_atoms(P.M, P.any_bracket != 0, csf_on != 0, landscape != 0);
+  return sweep_plan_max_atoms(p, [=](int M, bool br) { return prof_max_atoms(M, br, csf_on != 0, landscape != 0); });
 }
 
 extern "C" int mfx_profile_dev(const mfx_plan* p, const double* d_Y, const double* d_peaks, int K, int csf_on,
