@@ -70,6 +70,15 @@ int mfx_post_abi_version(void);
 int mfx_post_max_atoms(const mfx_plan* p, int csf_on);
 
 /*
+ * Debug: which K = 2 kernel the calling thread's last launch through this header or mfx_wpost* of
+ * mfx_wsoft.h was.  form[8] = (KSTEPS, NW, TILES, NBUF, BR, CSF, LAND, WGT) as
+ * mfx_profile_debug_last_config of mfx_profile.h gives it, LAND always 0.  Returns 1, or 0 with
+ * form untouched before the thread's first such launch.  K = 1 calls and calls refused before the
+ * launch leave the record as it is.  Since 2.
+ */
+int mfx_post_debug_last_config(int* form);
+
+/*
  * d_Y [V x M], d_peaks [V x 3 K], d_sig_csf [M] (csf_on), d_T [V], d_shift [V]; d_w [V x K x N]
  * float64, d_log_sum [V] float64, d_status [V] int32.  One workgroup per voxel; nothing of size
  * N x N is stored.

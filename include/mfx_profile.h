@@ -70,6 +70,16 @@ double mfx_profile_cut(void);
 int mfx_profile_max_atoms(const mfx_plan* p, int csf_on, int landscape);
 
 /*
+ * Debug: which K = 2 kernel the calling thread's last launch through this header or the weighted
+ * forms of mfx_wsoft.h (mfx_wprofile*, mfx_wpair_objectives*) was.  form[8] = (KSTEPS, NW, TILES,
+ * NBUF, BR, CSF, LAND, WGT): k-steps of 4 rows (the padded M is 4 KSTEPS), waves per workgroup,
+ * 16-atom column tiles per chunk, LDS chunk buffers, G-bracketed rows, the CSF form, the landscape
+ * form, measurement weights.  Returns 1, or 0 with form untouched before the thread's first such
+ * launch.  K = 1 calls and calls refused before the launch leave the record as it is.  Since 2.
+ */
+int mfx_profile_debug_last_config(int* form);
+
+/*
  * Profile.  d_Y [V x M], d_peaks [V x 3 K], d_sig_csf [M] (csf_on), d_obj [V x K x N] float64,
  * d_partner [V x K x N] int32 or NULL.  One workgroup per voxel; no global atomics, nothing of
  * size N x N is stored.  The result does not depend on the launch (fixed reduction orders).

@@ -44,10 +44,10 @@ PREDICT_EXPORTS = ["mfx_predict_abi_version", "mfx_predict_dev", "mfx_predict", 
 
 # every symbol include/mfx_profile.h declares (objective profiles; versioned on its own)
 PROFILE_EXPORTS = ["mfx_profile_abi_version", "mfx_profile_cut", "mfx_profile_max_atoms", "mfx_profile_dev", "mfx_profile",
-                   "mfx_pair_objectives_dev", "mfx_pair_objectives"]
+                   "mfx_pair_objectives_dev", "mfx_pair_objectives", "mfx_profile_debug_last_config"]
 
 # every symbol include/mfx_post.h declares (soft fits: posterior weights per atom; versioned on its own)
-POST_EXPORTS = ["mfx_post_abi_version", "mfx_post_max_atoms", "mfx_post_dev", "mfx_post"]
+POST_EXPORTS = ["mfx_post_abi_version", "mfx_post_max_atoms", "mfx_post_dev", "mfx_post", "mfx_post_debug_last_config"]
 
 # every symbol include/mfx_wsoft.h declares (profiles and soft fits of a weighted fit; versioned on its own)
 WSOFT_EXPORTS = ["mfx_wsoft_abi_version", "mfx_wsoft_max_atoms", "mfx_wpost_dev", "mfx_wpost", "mfx_wprofile_dev", "mfx_wprofile",
@@ -198,10 +198,12 @@ def lib():
     L.mfx_profile.argtypes = [vp, dp, dp, C.c_int, C.c_int, dp, C.c_int64, dp, ip]
     L.mfx_pair_objectives_dev.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int64, vp, vp]
     L.mfx_pair_objectives.argtypes = [vp, dp, dp, C.c_int, dp, C.c_int64, dp]
+    L.mfx_profile_debug_last_config.argtypes = [ip]
     L.mfx_post_abi_version.restype = C.c_int
     L.mfx_post_max_atoms.argtypes = [vp, C.c_int]
     L.mfx_post_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int64, vp, vp, vp, vp]
     L.mfx_post.argtypes = [vp, dp, dp, C.c_int, C.c_int, dp, dp, dp, C.c_int64, dp, dp, ip]
+    L.mfx_post_debug_last_config.argtypes = [ip]
     L.mfx_wsoft_abi_version.restype = C.c_int
     L.mfx_wsoft_max_atoms.argtypes = [vp, C.c_int, C.c_int]
     L.mfx_wpost_dev.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int64, vp, vp, vp, vp]

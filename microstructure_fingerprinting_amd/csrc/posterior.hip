@@ -470,6 +470,7 @@ struct PostLaunch {
   template <int KS, bool BR, bool CSF, int NW, int TILES, int NBUF>
   int run() const {
     const PostArgsT<WGT> ka = a;   // the unweighted kernels take the PostArgs part
+    sweep_record(KS, NW, TILES, NBUF, BR, CSF, false, WGT);
     return sweep_launch(mfx_post_k2_kernel<KS, BR, CSF, NW, TILES, NBUF, WGT>, ka, nvox, NW * 64,
                         post_lds_bytes(KS, BR, CSF, a.T.ldn, NW, TILES, NBUF, WGT), true, st);
   }
@@ -530,7 +531,9 @@ int post_host(const char* fn, const mfx_plan* p, const double* Y, const double* 
 
 }  // namespace
 
-extern "C" int mfx_post_abi_version(void) { return 1; }
+extern "C" int mfx_post_abi_version(void) { return 2; }
+
+extern "C" int mfx_post_debug_last_config(int* form) { return sweep_last_form(form); }
 
 extern "C" int mfx_post_max_atoms(const mfx_plan* p, int csf_on) {
   return sweep_plan_max_atoms(p, [=](int M, bool br) { return post_max_atoms(M, br, csf_on != 0); });

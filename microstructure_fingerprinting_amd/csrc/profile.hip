@@ -476,6 +476,7 @@ struct ProfLaunch {
   template <int KS, bool BR, bool CSF, int NW, int TILES, int NBUF>
   int run() const {
     const ProfArgsT<WGT> ka = a;   // the unweighted kernels take the ProfArgs part
+    sweep_record(KS, NW, TILES, NBUF, BR, CSF, LAND, WGT);
     return sweep_launch(mfx_profile_k2_kernel<KS, BR, CSF, LAND, NW, TILES, NBUF, WGT>, ka, nvox, NW * 64,
                         prof_lds_bytes(KS, BR, CSF, LAND, a.T.ldn, NW, TILES, NBUF, WGT), true, st);
   }
@@ -535,7 +536,9 @@ int prof_host(const char* fn, const mfx_plan* p, const double* Y, const double* 
 
 }  // namespace
 
-extern "C" int mfx_profile_abi_version(void) { return 1; }
+extern "C" int mfx_profile_abi_version(void) { return 2; }
+
+extern "C" int mfx_profile_debug_last_config(int* form) { return sweep_last_form(form); }
 
 extern "C" double mfx_profile_cut(void) { return MFX_PROFILE_CUT; }
 

@@ -6,7 +6,8 @@
 //   device  SweepArgs (the leading kernel arguments), the cut, the three scoring helpers and the verdict on a voxel's weights.
 //           __device__ __forceinline__: nothing becomes a call.
 //   host    the LDS byte count of the kernels' common front (sweep_front), the configuration table and its chooser
-//           (sweep_pick, sweep_max_atoms, sweep_dispatch, sweep_launch_k2, sweep_launch), the argument checks of the entry
+//           (sweep_pick, sweep_max_atoms, sweep_dispatch, sweep_launch_k2, sweep_launch), the record of the last form
+//           launched (sweep_record, sweep_last_form: the debug hooks of both headers), the argument checks of the entry
 //           points in their order (sweep_enqueue_head, SweepHostIn::stage) and the host staging on DevBuf.
 // The sweep's front end inside the kernels (phases 0 and 1, the chunk generator, the A operand, the operands of a pair)
 // is still written out in both files: moved into functions here, it changed the register allocation of every kernel
@@ -164,6 +165,27 @@ int sweep_max_atoms(int M, bool br, bool csf, Lds lds) {
   int n = 0;
   while (n < (1 << 20) && sweep_pick(M, br, csf, n + 16, lds) >= 0) n += 16;
   return n;
+}
+
+// the form of the calling thread's last K = 2 launch of this family (this header is included once per family, so each
+// has its own record), for mfx_*_debug_last_config: written by the launch functors, where the template arguments are
+// known, before the launch itself
+struct SweepForm { int ks, nw, tiles, nbuf, br, csf, land, wgt; };
+thread_local SweepForm g_sweep_last_form = {};
+thread_local bool g_sweep_launched = false;
+inline void sweep_record(int ks, int nw, int tiles, int nbuf, bool br, bool csf, bool land, bool wgt) {
+  g_sweep_last_form = {ks, nw, tiles, nbuf, br, csf, land, wgt};
+  g_sweep_launched = true;
+}
+// form[8] = (KSTEPS, NW, TILES, NBUF, BR, CSF, LAND, WGT); 0 (and form untouched) before the thread's first launch
+inline int sweep_last_form(int* form) {
+  if (!g_sweep_launched) return 0;
+  if (form) {
+    const SweepForm& f = g_sweep_last_form;
+    const int v[8] = {f.ks, f.nw, f.tiles, f.nbuf, f.br, f.csf, f.land, f.wgt};
+    std::copy(v, v + 8, form);
+  }
+  return 1;
 }
 
 // launch.run<KS, BR, CSF, NW, TILES, NBUF>() of configuration cfg

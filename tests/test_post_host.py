@@ -28,10 +28,10 @@ def test_header_binding_and_library_are_in_step():
     assert decl == sorted(_lib.POST_EXPORTS)
     for name in decl:
         assert hasattr(lib, name), "libmfx.so lacks %s declared in include/mfx_post.h" % name
-    assert lib.mfx_post_abi_version() == 1
+    assert lib.mfx_post_abi_version() == 2
     # the other headers, their binding lists and versions are as they were
     assert _declared("mfx.h") == sorted(_lib.EXPORTS) and lib.mfx_abi_version() == 3
-    assert _declared("mfx_profile.h") == sorted(_lib.PROFILE_EXPORTS) and lib.mfx_profile_abi_version() == 1
+    assert _declared("mfx_profile.h") == sorted(_lib.PROFILE_EXPORTS) and lib.mfx_profile_abi_version() == 2
     for other in (_lib.EXPORTS, _lib.PREDICT_EXPORTS, _lib.MCF_EXPORTS, _lib.ROT2D_EXPORTS, _lib.PROFILE_EXPORTS,
                   _lib.FIT2D_EXPORTS, _lib.WFIT_EXPORTS):
         assert not set(_lib.POST_EXPORTS) & set(other)

@@ -30,7 +30,7 @@ def other_versions(lib):
 
 
 OTHER_VERSIONS = {"mfx_abi_version": 3, "mfx_mcf_abi_version": 1, "mfx_rot2d_abi_version": 1, "mfx_fit2d_abi_version": 1,
-                  "mfx_wfit_abi_version": 1, "mfx_predict_abi_version": 1, "mfx_profile_abi_version": 1, "mfx_post_abi_version": 1,
+                  "mfx_wfit_abi_version": 1, "mfx_predict_abi_version": 1, "mfx_profile_abi_version": 2, "mfx_post_abi_version": 2,
                   "mfx_wsoft_abi_version": 1, "mfx_soft2d_abi_version": 1, "mfx_w2d_abi_version": 1, "mfx_robust_abi_version": 1}
 
 

@@ -26,7 +26,7 @@ def test_header_declares_the_bound_symbols():
     assert decl == sorted(_lib.PROFILE_EXPORTS)
     for name in decl:
         assert hasattr(lib, name), "libmfx.so lacks %s declared in include/mfx_profile.h" % name
-    assert lib.mfx_profile_abi_version() == 1
+    assert lib.mfx_profile_abi_version() == 2
     assert 0.0 < lib.mfx_profile_cut() <= 1e-6
     # mfx.h, its binding list and its version are as they were
     assert _declared("mfx.h") == sorted(_lib.EXPORTS)

@@ -44,13 +44,13 @@ def test_header_binding_and_library_are_in_step():
     # the other headers, their binding lists and versions are as they were
     for header, lst, version in (("mfx.h", _lib.EXPORTS, (lib.mfx_abi_version, 3)),
                                  ("mfx_fit2d.h", _lib.FIT2D_EXPORTS, (lib.mfx_fit2d_abi_version, 1)),
-                                 ("mfx_post.h", _lib.POST_EXPORTS, (lib.mfx_post_abi_version, 1)),
-                                 ("mfx_profile.h", _lib.PROFILE_EXPORTS, (lib.mfx_profile_abi_version, 1)),
+                                 ("mfx_post.h", _lib.POST_EXPORTS, (lib.mfx_post_abi_version, 2)),
+                                 ("mfx_profile.h", _lib.PROFILE_EXPORTS, (lib.mfx_profile_abi_version, 2)),
                                  ("mfx_rot2d.h", _lib.ROT2D_EXPORTS, (lib.mfx_rot2d_abi_version, 1)),
                                  ("mfx_wsoft.h", _lib.WSOFT_EXPORTS, (lib.mfx_wsoft_abi_version, 1))):
         assert _declared(header) == sorted(lst), header
         assert version[0]() == version[1], header
-    assert len(_lib.EXPORTS) == 41 and len(_lib.FIT2D_EXPORTS) == 5 and len(_lib.POST_EXPORTS) == 4 and len(_lib.PROFILE_EXPORTS) == 7
+    assert len(_lib.EXPORTS) == 41 and len(_lib.FIT2D_EXPORTS) == 5 and len(_lib.POST_EXPORTS) == 5 and len(_lib.PROFILE_EXPORTS) == 8
 
 
 def test_header_states_the_definitions():

@@ -27,17 +27,19 @@ def test_header_binding_and_library_are_in_step():
         assert hasattr(lib, name), "libmfx.so lacks %s declared in include/mfx_wsoft.h" % name
     assert lib.mfx_wsoft_abi_version() == 1
     # the other headers, their binding lists and versions are as they were
-    others = {"mfx.h": (_lib.EXPORTS, "mfx_abi_version", 3), "mfx_profile.h": (_lib.PROFILE_EXPORTS, "mfx_profile_abi_version", 1),
-              "mfx_post.h": (_lib.POST_EXPORTS, "mfx_post_abi_version", 1), "mfx_wfit.h": (_lib.WFIT_EXPORTS, "mfx_wfit_abi_version", 1),
+    others = {"mfx.h": (_lib.EXPORTS, "mfx_abi_version", 3), "mfx_profile.h": (_lib.PROFILE_EXPORTS, "mfx_profile_abi_version", 2),
+              "mfx_post.h": (_lib.POST_EXPORTS, "mfx_post_abi_version", 2), "mfx_wfit.h": (_lib.WFIT_EXPORTS, "mfx_wfit_abi_version", 1),
               "mfx_predict.h": (_lib.PREDICT_EXPORTS, "mfx_predict_abi_version", 1), "mfx_mcf.h": (_lib.MCF_EXPORTS, "mfx_mcf_abi_version", 1),
               "mfx_rot2d.h": (_lib.ROT2D_EXPORTS, "mfx_rot2d_abi_version", 1), "mfx_fit2d.h": (_lib.FIT2D_EXPORTS, "mfx_fit2d_abi_version", 1)}
     for header, (exports, version, want) in others.items():
         assert _declared(header) == sorted(exports), header
         assert getattr(lib, version)() == want, header
         assert not set(_lib.WSOFT_EXPORTS) & set(exports), header
-    assert _lib.POST_EXPORTS == ["mfx_post_abi_version", "mfx_post_max_atoms", "mfx_post_dev", "mfx_post"]
+    assert _lib.POST_EXPORTS == ["mfx_post_abi_version", "mfx_post_max_atoms", "mfx_post_dev", "mfx_post",
+                                 "mfx_post_debug_last_config"]
     assert _lib.PROFILE_EXPORTS == ["mfx_profile_abi_version", "mfx_profile_cut", "mfx_profile_max_atoms", "mfx_profile_dev",
-                                    "mfx_profile", "mfx_pair_objectives_dev", "mfx_pair_objectives"]
+                                    "mfx_profile", "mfx_pair_objectives_dev", "mfx_pair_objectives",
+                                    "mfx_profile_debug_last_config"]
     for what in (0, 1, 2, 3):
         assert lib.mfx_wsoft_max_atoms(None, 0, what) == 0
 
