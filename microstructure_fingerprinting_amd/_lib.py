@@ -83,6 +83,11 @@ BOOT2D_EXPORTS = ["mfx_boot2d_abi_version", "mfx_boot2d_rep_tile", "mfx_boot2d_d
 SOLVE_EXPORTS = ["mfx_solve_abi_version", "mfx_solve_create", "mfx_solve_destroy", "mfx_solve_num_columns",
                  "mfx_solve_bytes_per_signal", "mfx_solve_batch_dev", "mfx_solve_batch", "mfx_solve_debug_set_force_generic"]
 
+# every symbol include/mfx_solve_soft.h declares (objective profiles and posteriors on a solver handle; versioned on its own)
+SOLVE_SOFT_EXPORTS = ["mfx_solve_soft_abi_version", "mfx_solve_soft_served", "mfx_solve_soft_bytes_per_signal",
+                      "mfx_solve_profile_dev", "mfx_solve_profile", "mfx_solve_post_dev", "mfx_solve_post"]
+SOLVE_SOFT_PROFILE, SOLVE_SOFT_POST = 0, 1   # `what` of mfx_solve_soft_bytes_per_signal
+
 
 class MfxError(RuntimeError):
     pass
@@ -275,6 +280,14 @@ def lib():
     L.mfx_solve_batch.argtypes = [vp, dp, C.c_int64, C.c_int64, dp, lp, dp, dp, ip]
     L.mfx_solve_debug_set_force_generic.argtypes = [C.c_int]
     L.mfx_solve_debug_set_force_generic.restype = None
+    L.mfx_solve_soft_abi_version.restype = C.c_int
+    L.mfx_solve_soft_served.argtypes = [vp]
+    L.mfx_solve_soft_bytes_per_signal.argtypes = [vp, C.c_int]
+    L.mfx_solve_soft_bytes_per_signal.restype = C.c_int64
+    L.mfx_solve_profile_dev.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp]
+    L.mfx_solve_profile.argtypes = [vp, dp, C.c_int64, C.c_int64, dp, dp, ip, ip, ip]
+    L.mfx_solve_post_dev.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
+    L.mfx_solve_post.argtypes = [vp, dp, C.c_int64, dp, dp, C.c_int64, dp, dp, dp, dp, ip]
     _lib = L
     return L
 

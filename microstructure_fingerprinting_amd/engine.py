@@ -1778,6 +1778,98 @@ def solve_batch_dev(solver, d_Y, out=None, recons=True, max_bytes=0):
     return w, sub, tot, obj, yrec, status
 
 
+def solve_soft_sizes(solver):
+    """(n1, n2) of the sub-dictionaries a solver's soft answers cover (n2 = 0 with one sub-dictionary; a third
+    sub-dictionary of one column is the CSF column and has no row of its own); NotImplementedError with the library's
+    message for a class they do not serve.  Touches the handle, nothing else."""
+    L.check(L.lib().mfx_solve_soft_served(solver.handle()))
+    return int(solver.dicsizes[0]), (int(solver.dicsizes[1]) if solver.Kp > 1 else 0)
+
+
+def _solve_soft_head(solver, d_Y, out, names):
+    """The argument checks of ``solve_batch_dev`` for the two entry points below: (V, the torch device, out as a dict)."""
+    V = solver.signal_rows(d_Y.shape)
+    out = dict(out) if out is not None else {}
+    unknown = set(out) - set(names)
+    if unknown:
+        raise ValueError("out may hold %s, got %s" % (", ".join(repr(n) for n in names), sorted(unknown)))
+    dev = d_Y.device
+    if dev.index is not None and dev.index != solver.device:
+        raise ValueError("signals live on %s, the solver on device %d" % (dev, solver.device))
+    return V, dev, out
+
+
+def _solve_soft_buf(out, dev, name, shape, dtype):
+    import torch
+    t = out.get(name)
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if not (t.is_cuda and t.dtype == dtype and t.is_contiguous()) or tuple(t.shape) != tuple(shape):
+        raise ValueError("out[%r] should be a contiguous CUDA %s tensor of shape %s, got %s of shape %s"
+                         % (name, dtype, tuple(shape), t.dtype, tuple(t.shape)))
+    return t
+
+
+def solve_profile_dev(solver, d_Y, partner=False, out=None, max_bytes=0):
+    """Objective profiles of a mf_utils.ExhaustiveSolver on the device (mfx_solve_profile_dev, include/mfx_solve_soft.h):
+    torch CUDA float64 signals d_Y [V, M] (or one [M] vector) -> ``(obj, partner, status)``: obj a list with one [V, n_k]
+    float64 tensor per served sub-dictionary (obj[0][v, i] = min_j F(i, j), obj[1][v, j] = min_i F(i, j); one
+    sub-dictionary: [F(i)]), partner the arg-min indices as int32 tensors of the same shapes (-1 with one
+    sub-dictionary) or None without ``partner``, status [V] int32 (0 ok, 5 a non-finite signal: NaN rows, partners -1).
+    ``out``: a dict that may hold tensors 'obj0', 'obj1', 'partner0', 'partner1', 'status' to write into.  Enqueues on
+    torch's current stream and returns without waiting."""
+    import torch
+    _f64_cuda(d_Y)
+    V, dev, out = _solve_soft_head(solver, d_Y, out, ('obj0', 'obj1', 'partner0', 'partner1', 'status'))
+    n1, n2 = solve_soft_sizes(solver)
+    obj = [_solve_soft_buf(out, dev, 'obj0', (V, n1), torch.float64)]
+    if n2:
+        obj.append(_solve_soft_buf(out, dev, 'obj1', (V, n2), torch.float64))
+    par = None
+    if partner:
+        par = [_solve_soft_buf(out, dev, 'partner%d' % k, (V, n), torch.int32) for k, n in enumerate((n1, n2)[:len(obj)])]
+    status = _solve_soft_buf(out, dev, 'status', (V,), torch.int32)
+    if V > 0:
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            L.check(L.lib().mfx_solve_profile_dev(solver.handle(), d_Y.data_ptr(), V, int(max_bytes), obj[0].data_ptr(),
+                                                  _tptr(obj[1] if n2 else None), _tptr(par[0] if par else None),
+                                                  _tptr(par[1] if par and n2 else None), status.data_ptr(), st))
+    return obj, par, status
+
+
+def solve_posterior_dev(solver, d_Y, d_T, d_shift=None, out=None, max_bytes=0):
+    """Posterior weights of a mf_utils.ExhaustiveSolver on the device (mfx_solve_post_dev, include/mfx_solve_soft.h): torch
+    CUDA float64 signals d_Y [V, M] (or one [M] vector), temperatures d_T [V] (2 sigma^2), d_shift [V] a value near each
+    signal's smallest objective or None (the library takes min F itself) -> ``(w, log_sum, min_obj, status)``: w a list
+    with one [V, n_k] float64 tensor per served sub-dictionary, log_sum [V] = log sum exp(-F / T), min_obj [V] = min F,
+    status [V] int32 (0 ok, 1 unusable T or shift, 2 an exponent above 700 or a vanishing sum, 5 a non-finite signal;
+    rows of such signals are NaN).  ``out``: a dict that may hold tensors 'w0', 'w1', 'log_sum', 'min_obj', 'status' to
+    write into.  Enqueues on torch's current stream and returns without waiting."""
+    import torch
+    _f64_cuda(d_Y, d_T, d_shift)
+    V, dev, out = _solve_soft_head(solver, d_Y, out, ('w0', 'w1', 'log_sum', 'min_obj', 'status'))
+    for t, what in ((d_T, "T"), (d_shift, "shift")):
+        if t is not None and tuple(t.shape) != (V,):
+            raise ValueError("%s should have one entry per signal (%d), got shape %s" % (what, V, tuple(t.shape)))
+        if t is not None and t.device != dev:
+            raise ValueError("%s lives on %s, the signals on %s" % (what, t.device, dev))
+    n1, n2 = solve_soft_sizes(solver)
+    w = [_solve_soft_buf(out, dev, 'w0', (V, n1), torch.float64)]
+    if n2:
+        w.append(_solve_soft_buf(out, dev, 'w1', (V, n2), torch.float64))
+    log_sum = _solve_soft_buf(out, dev, 'log_sum', (V,), torch.float64)
+    min_obj = _solve_soft_buf(out, dev, 'min_obj', (V,), torch.float64)
+    status = _solve_soft_buf(out, dev, 'status', (V,), torch.int32)
+    if V > 0:
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            L.check(L.lib().mfx_solve_post_dev(solver.handle(), d_Y.data_ptr(), V, d_T.data_ptr(), _tptr(d_shift), int(max_bytes),
+                                               w[0].data_ptr(), _tptr(w[1] if n2 else None), log_sum.data_ptr(),
+                                               min_obj.data_ptr(), status.data_ptr(), st))
+    return w, log_sum, min_obj, status
+
+
 def cleanup_select(f1, f2, p1, p2, cos_min, ratio, w_keep, w_small, device=0):
     """Voxel loop of cleanup_2fascicles (mfx_cleanup_2fascicles; ref mf.py:170-335): weights f1, f2 [n] and directions p1, p2
     [n x 3] of the ROI voxels -> (peaks [n x 6], count [n])."""

@@ -1252,6 +1252,135 @@ class ExhaustiveSolver:
         dt = self.index_dtype()
         return w, sub.astype(dt), tot.astype(dt), obj, yrec, status
 
+    # ---- the soft answers beside the arg-min (include/mfx_solve_soft.h)
+    def soft_bytes_per_signal(self, what):
+        """Scratch bytes one signal takes in ``profile`` (what='profile') or ``posterior`` (what='posterior')."""
+        code = {'profile': L.SOLVE_SOFT_PROFILE, 'posterior': L.SOLVE_SOFT_POST}[what]
+        return int(L.lib().mfx_solve_soft_bytes_per_signal(self.handle(), code))
+
+    def _soft_signals(self, Y):
+        assert isinstance(Y, np.ndarray), "y should be a NumPy ndarray"
+        V = self.signal_rows(Y.shape)
+        return V, L.f64c(Y).reshape(V, self.M)
+
+    def _soft_props(self, props, sizes):
+        """``props`` {name: values} as {name: [values of every served sub-dictionary]}: one array shared by the
+        sub-dictionaries where their sizes agree, or a list with one array each."""
+        res = {}
+        for name, vals in (props or {}).items():
+            if isinstance(vals, (list, tuple)) and len(vals) == len(sizes) and all(np.ndim(x) == 1 for x in vals):
+                per = [np.asarray(x, dtype=np.float64) for x in vals]
+            else:
+                per = [np.asarray(vals, dtype=np.float64).reshape(-1)] * len(sizes)
+            for k, (x, n) in enumerate(zip(per, sizes)):
+                if x.shape != (n,):
+                    raise ValueError("property %r of sub-dictionary %d should have %d values, got shape %s" % (name, k, n, x.shape))
+            res[name] = per
+        return res
+
+    def profile(self, Y, partner=False, props=None, max_bytes=0):
+        """Objective profiles of signals ``Y [V, M]`` (or one ``[M]`` vector): for every atom of each sub-dictionary
+        the best objective any partner atom reaches with it.  Served: one sub-dictionary, two, and three whose last has
+        one column (that column is always in the fit, like the CSF compartment); NotImplementedError otherwise.
+        ``props``: {name: values} per-atom properties for ``by_property`` / ``interval``.  Returns a ``SolverProfile``."""
+        V, Y64 = self._soft_signals(Y)
+        sizes = [int(n) for n in self.dicsizes[:min(self.Kp, 2)]]
+        pr = self._soft_props(props, sizes)
+        engine.solve_soft_sizes(self)
+        obj = [np.zeros((V, n)) for n in sizes]
+        par = [np.zeros((V, n), dtype=np.int32) for n in sizes] if partner else None
+        status = np.zeros(V, dtype=np.int32)
+        if V > 0:
+            two = len(sizes) > 1
+            L.check(L.lib().mfx_solve_profile(self.handle(), L.dptr(Y64), V, int(max_bytes), L.dptr(obj[0]),
+                                              L.dptr(obj[1]) if two else None, L.iptr(par[0]) if par else None,
+                                              L.iptr(par[1]) if par and two else None, L.iptr(status)))
+        return SolverProfile(obj, par, status, pr)
+
+    def posterior(self, Y, sigma=None, shift=None, props=None, max_bytes=0):
+        """Posterior weights of every atom of each served sub-dictionary given the noise level: w proportional to the sum
+        over all partner atoms of exp(-F / 2 sigma^2).  ``sigma``: the noise standard deviation, a scalar or ``[V]``
+        (default: the residual variance of the best fit, sigma^2 = min F / (M - Kp); a signal with min F <= 0 or
+        M <= Kp gets status 1).  ``shift`` ``[V]``: a value near each signal's smallest objective (default: min F itself).
+        Returns a ``SolverPosterior``."""
+        V, Y64 = self._soft_signals(Y)
+        sizes = [int(n) for n in self.dicsizes[:min(self.Kp, 2)]]
+        pr = self._soft_props(props, sizes)
+        sig = engine._per_voxel(sigma, V, "sigma") if sigma is not None else None
+        sh = engine._per_voxel(shift, V, "shift") if shift is not None else None
+        engine.solve_soft_sizes(self)
+        w = [np.zeros((V, n)) for n in sizes]
+        log_sum, min_obj, status = np.zeros(V), np.zeros(V), np.zeros(V, dtype=np.int32)
+        T = np.zeros(V)
+        if V > 0:
+            two = len(sizes) > 1
+            if sig is None:
+                # min F first: a call at T = 1 (its shift is min F, so no exponent is positive), of which min_obj is kept
+                L.check(L.lib().mfx_solve_post(self.handle(), L.dptr(Y64), V, L.dptr(np.ones(V)), None, int(max_bytes), L.dptr(w[0]),
+                                               L.dptr(w[1]) if two else None, L.dptr(log_sum), L.dptr(min_obj), L.iptr(status)))
+                dof = self.M - self.Kp
+                with np.errstate(invalid='ignore', divide='ignore'):
+                    sig = np.where((min_obj > 0) & (dof > 0), np.sqrt(min_obj / max(dof, 1)), np.nan)
+            T = np.ascontiguousarray(2.0 * sig ** 2)
+            L.check(L.lib().mfx_solve_post(self.handle(), L.dptr(Y64), V, L.dptr(T), L.opt(sh), int(max_bytes), L.dptr(w[0]),
+                                           L.dptr(w[1]) if two else None, L.dptr(log_sum), L.dptr(min_obj), L.iptr(status)))
+        return SolverPosterior(w, log_sum, min_obj, status, T, self.M, pr)
+
+    def posterior_moments(self, Y, values, sigma=None, k=0):
+        """(mean, std) ``[V]`` of the per-atom property ``values`` of sub-dictionary ``k`` under ``posterior(Y, sigma)``."""
+        return posterior_moments(self.posterior(Y, sigma=sigma).weights[k], values)
+
+
+class _SolverSoft(object):
+    def _values(self, name, k):
+        if name not in self._props:
+            raise KeyError("no property %r (given: %s)" % (name, sorted(self._props)))
+        return self._props[name][k]
+
+
+class SolverProfile(_SolverSoft):
+    """Result of ``ExhaustiveSolver.profile``: ``obj`` a list with one ``[V, n_k]`` array per served sub-dictionary,
+    ``partner`` the arg-min partner indices likewise (or None), ``status`` ``[V]`` (0 ok, 5 a non-finite signal)."""
+
+    def __init__(self, obj, partner, status, props):
+        self.obj, self.partner, self.status, self._props = obj, partner, status, props
+
+    def by_property(self, name, k=0):
+        """(levels, obj_by_level [V, len(levels)]) of sub-dictionary ``k`` (``profile_by_property``)."""
+        return profile_by_property(self.obj[k], self._values(name, k))
+
+    def interval(self, name, rel=0.0, delta=0.0, k=0):
+        """(lo, hi, count) ``[V]``: the range of ``name`` that fits within the margin of the optimum (``profile_interval``)."""
+        return profile_interval(self.obj[k], self._values(name, k), rel=rel, delta=delta)
+
+
+class SolverPosterior(_SolverSoft):
+    """Result of ``ExhaustiveSolver.posterior``: ``weights`` a list with one ``[V, n_k]`` array per served
+    sub-dictionary (each row sums to 1), ``log_sum`` ``[V]`` = log sum exp(-F / T), ``min_obj`` ``[V]`` = min F, ``status``
+    ``[V]`` (the codes of include/mfx_solve_soft.h), ``T`` ``[V]`` = 2 sigma^2."""
+
+    def __init__(self, weights, log_sum, min_obj, status, T, M, props):
+        self.weights, self.log_sum, self.min_obj, self.status, self.T = weights, log_sum, min_obj, status, T
+        self._M, self._props = M, props
+
+    def mean(self, name, k=0):
+        return posterior_moments(self.weights[k], self._values(name, k))[0]
+
+    def std(self, name, k=0):
+        return posterior_moments(self.weights[k], self._values(name, k))[1]
+
+    def quantile(self, name, q, k=0):
+        return posterior_quantile(self.weights[k], self._values(name, k), q)
+
+    def by_property(self, name, k=0):
+        return posterior_by_property(self.weights[k], self._values(name, k))
+
+    def log_evidence(self):
+        """log_sum - sum_k log n_k - (M / 2) log(pi T) per signal: the log of the Gaussian likelihood averaged over a
+        uniform prior on the tuples of atoms (a profile-likelihood evidence: the weights are maximised per tuple)."""
+        with np.errstate(invalid='ignore', divide='ignore'):
+            return self.log_sum - sum(np.log(w.shape[-1]) for w in self.weights) - 0.5 * self._M * np.log(np.pi * self.T)
+
 
 def solve_exhaustive_posweights_batch(A, Y, dicsizes, device=0, **kw):
     """One-shot form of ``ExhaustiveSolver(A, dicsizes).solve(Y, **kw)``."""
