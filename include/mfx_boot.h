@@ -52,7 +52,8 @@
  * n = 0 gives NaN everywhere but in n.  B <= MFX_BOOT_MAX_B (the B values of a column are held in LDS) and
  * Q <= MFX_BOOT_MAX_Q, else MFX_ERR_UNSUPPORTED before any launch.  Protocols of more than 8192 measurements return
  * MFX_ERR_UNSUPPORTED.
- * Not served: weighted and robust fits.  (2-D protocols: mfx_boot2d.h, by this rule, value table and statistics.)
+ * Not served: weighted and robust fits; mfx_wboot.h bootstraps them with the fit's weights held fixed.  (2-D
+ * protocols: mfx_boot2d.h, by this rule, value table and statistics.)
  */
 #ifndef MFX_BOOT_H
 #define MFX_BOOT_H

@@ -79,6 +79,10 @@ BOOT_EXPORTS = ["mfx_boot_abi_version", "mfx_boot_resample_dev", "mfx_boot_gathe
 BOOT2D_EXPORTS = ["mfx_boot2d_abi_version", "mfx_boot2d_rep_tile", "mfx_boot2d_debug_set_force_plain",
                   "mfx_boot2d_fit_rows_dev", "mfx_boot2d_fit_dev", "mfx_boot2d_fit"]
 
+# every symbol include/mfx_wboot.h declares (bootstrap conditional on a fit's measurement weights; versioned on its own)
+WBOOT_EXPORTS = ["mfx_wboot_abi_version", "mfx_wboot_rep_tile", "mfx_wboot_debug_set_force_plain", "mfx_wboot_resample_dev",
+                 "mfx_wboot_fit_rows_dev", "mfx_wboot_fit_dev", "mfx_wboot_fit"]
+
 # every symbol include/mfx_solve.h declares (batched explicit-dictionary solver: many signals, one dictionary; versioned on its own)
 SOLVE_EXPORTS = ["mfx_solve_abi_version", "mfx_solve_create", "mfx_solve_destroy", "mfx_solve_num_columns",
                  "mfx_solve_bytes_per_signal", "mfx_solve_batch_dev", "mfx_solve_batch", "mfx_solve_debug_set_force_generic"]
@@ -268,6 +272,17 @@ def lib():
                                      C.c_uint64, C.c_uint64, vp, C.c_int, vp, C.c_int, C.c_int64, vp, vp, vp, vp, vp, vp]
     L.mfx_boot2d_fit.argtypes = [vp, dp, ip, bp, dp, C.c_int, C.c_int, dp, dp, ip, lp, C.c_int64, C.c_int, C.c_int, C.c_int,
                                  C.c_uint64, C.c_uint64, dp, C.c_int, dp, C.c_int, C.c_int64, dp, ip, ip, ip, dp]
+    L.mfx_wboot_abi_version.restype = C.c_int
+    L.mfx_wboot_rep_tile.restype = C.c_int
+    L.mfx_wboot_debug_set_force_plain.argtypes = [C.c_int]
+    L.mfx_wboot_debug_set_force_plain.restype = None
+    L.mfx_wboot_resample_dev.argtypes = [C.c_int, vp, vp, vp, C.c_int64, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int64, C.c_int,
+                                         C.c_int, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp, vp]
+    L.mfx_wboot_fit_rows_dev.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int, C.c_int64, C.c_int, vp, vp, vp]
+    L.mfx_wboot_fit_dev.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int64, C.c_int, C.c_int,
+                                    C.c_int, C.c_uint64, C.c_uint64, vp, C.c_int, vp, C.c_int, C.c_int64, vp, vp, vp, vp, vp]
+    L.mfx_wboot_fit.argtypes = [vp, dp, dp, C.c_int64, ip, bp, dp, C.c_int, C.c_int, dp, dp, ip, lp, C.c_int64, C.c_int, C.c_int,
+                                C.c_int, C.c_uint64, C.c_uint64, dp, C.c_int, dp, C.c_int, C.c_int64, dp, ip, ip, dp]
     L.mfx_solve_abi_version.restype = C.c_int
     L.mfx_solve_create.argtypes = [dp, C.c_int64, C.c_int, lp, C.c_int, C.c_int, C.POINTER(vp)]
     L.mfx_solve_destroy.argtypes = [vp]

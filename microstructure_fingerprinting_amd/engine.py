@@ -1598,6 +1598,191 @@ def fit_bootstrap(plan, Y, K, csf, ear, peaks, maxfasc, csf_on, ear_on, sig_csf=
     return {'stats': stats, 'agree': agree, 'status': status, 'replicates': reps, 'columns': cols}
 
 
+def _wboot_dev_opts(M, V, code, d_groups, d_vox, scheme=None, dev=None):
+    """The optional device arguments of the weighted bootstrap's entry points, checked: the groups of the residual kind
+    (int32 [M]; derived from ``scheme`` where one is given and d_groups is not) and the batch indices (int64 [V])."""
+    import torch
+    if code == 1:
+        if d_groups is None:
+            if scheme is None:
+                raise ValueError("the residual bootstrap needs groups")
+            d_groups = torch.from_numpy(_boot_groups_arg(code, None, M, scheme)).to(dev)
+        assert d_groups.is_cuda and d_groups.dtype == torch.int32 and d_groups.is_contiguous()
+        if tuple(d_groups.shape) != (M,):
+            raise ValueError("groups should be %d integers (one per measurement), got shape %s" % (M, tuple(d_groups.shape)))
+    if d_vox is not None:
+        assert d_vox.is_cuda and d_vox.dtype == torch.int64 and d_vox.is_contiguous()
+        if tuple(d_vox.shape) != (V,):
+            raise ValueError("vox should have one entry per voxel")
+    return d_groups
+
+
+def wboot_resample_dev(d_Y, d_P, d_W, d_params, maxfasc, csf_on=False, B=200, kind='wild', seed=0, inflate=True, offset=0,
+                       d_groups=None, d_peaks=None, d_vox=None):
+    """The resampling rule of the bootstrap conditional on measurement weights, on the device (mfx_wboot_resample_dev;
+    include/mfx_wboot.h states it operation by operation): ``boot_resample_dev`` with weights d_W [V, M] or [M] (>= 0) and
+    parameter rows d_params [V, num_params(maxfasc, csf_on, False)] of the weighted fit.  A row of weight 0 is left as
+    measured; the wild kind flips the residuals of the other rows; the residual kind draws among the rows of positive
+    weight of a group, in units of sqrt(W).  -> (Ystar [V, B, M], peaks [V B, 3 maxfasc] or None, status [V] int32: 0 fine,
+    1 no degree of freedom among the rows of positive weight, 2 data or prediction not finite, 3 a weight negative or
+    not finite, 4 no positive weight).  Enqueues on torch's current stream and returns without waiting."""
+    import torch
+    B, code, _ = _boot_rule(B, kind, (), seed, offset, reduce=False)
+    maxfasc = int(maxfasc)
+    if maxfasc < 0 or maxfasc > 3:
+        raise ValueError("maxfasc must be 0..3")
+    _f64_cuda(d_Y, d_P, d_W, d_params, d_peaks)
+    if d_Y.dim() != 2 or d_Y.shape[1] < 1:
+        raise ValueError("data should have shape (voxels, measurements), got %s" % (tuple(d_Y.shape),))
+    V, M = d_Y.shape
+    if tuple(d_P.shape) != (V, M):
+        raise ValueError("prediction should have the data's shape (%d, %d), got %s" % (V, M, tuple(d_P.shape)))
+    w_stride = _w_stride(M, V, d_W.shape)
+    npar = num_params(maxfasc, csf_on, False)
+    if tuple(d_params.shape) != (V, npar):
+        raise ValueError("params should have shape (%d, %d), got %s" % (V, npar, tuple(d_params.shape)))
+    if d_peaks is not None and (maxfasc == 0 or tuple(d_peaks.shape) != (V, 3 * maxfasc)):
+        raise ValueError("peaks should have shape (%d, %d)" % (V, 3 * maxfasc))
+    d_groups = _wboot_dev_opts(M, V, code, d_groups, d_vox)
+    dev = d_Y.device
+    Ys = torch.empty((V, B, M), dtype=torch.float64, device=dev)
+    pk = torch.empty((V * B, 3 * maxfasc), dtype=torch.float64, device=dev) if d_peaks is not None else None
+    status = torch.empty((V,), dtype=torch.int32, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        L.check(L.lib().mfx_wboot_resample_dev(M, d_Y.data_ptr(), d_P.data_ptr(), d_W.data_ptr(), w_stride, d_params.data_ptr(),
+                                               maxfasc, int(bool(csf_on)), _tptr(d_peaks), _tptr(d_groups) if code == 1 else None,
+                                               _tptr(d_vox), V, B, code, int(bool(inflate)), int(seed) & _U64, int(offset) & _U64,
+                                               Ys.data_ptr(), _tptr(pk), status.data_ptr(), st))
+    return Ys, pk, status
+
+
+def fit_weighted_replicates_dev(plan, d_Ystar, d_W, d_peaks, maxfasc):
+    """The replicate weighted fit on the device (mfx_wboot_fit_rows_dev, include/mfx_wboot.h) of ONE voxel class (every
+    voxel ``maxfasc`` fascicles, no CSF column): B signals per voxel on the voxel's weights and directions.  torch CUDA
+    float64 tensors d_Ystar [V, B, M], d_W [V, M] or [M], d_peaks [V, 3 maxfasc] -> (params [V, B, num_params(maxfasc,
+    False, False)], status [V] int32 as ``fit_weighted_dev`` gives it for the voxel's weights).  Every row equals, bit for
+    bit, the row ``fit_weighted_dev`` returns for that signal with those weights and directions; for two fascicles the
+    weighted cross-Gram of a voxel is formed once, not once per row.  Enqueues on torch's current stream and returns
+    without waiting."""
+    import torch
+    maxfasc = int(maxfasc)
+    _f64_cuda(d_Ystar, d_W, d_peaks if maxfasc > 0 else None)
+    if d_Ystar.dim() != 3 or d_Ystar.shape[1] < 1:
+        raise ValueError("replicate signals should have shape (voxels, B >= 1, %d), got %s" % (plan.M, tuple(d_Ystar.shape)))
+    V, B, M = d_Ystar.shape
+    _, w_stride = _wfit_shapes(plan, (V, M), d_W.shape, d_peaks.shape if maxfasc > 0 else (V, 0), maxfasc)
+    dev = d_Ystar.device
+    out = torch.empty((V, B, num_params(maxfasc, False, False)), dtype=torch.float64, device=dev)
+    status = torch.empty((V,), dtype=torch.int32, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        L.check(L.lib().mfx_wboot_fit_rows_dev(plan.handle(), d_Ystar.data_ptr(), d_W.data_ptr(), w_stride,
+                                               _tptr(d_peaks) if maxfasc > 0 else None, maxfasc, V, B, out.data_ptr(),
+                                               status.data_ptr(), st))
+    return out, status
+
+
+def fit_weighted_bootstrap_dev(plan, d_Y, d_W, d_peaks, maxfasc, csf_on=False, d_sig_csf=None, B=200, kind='wild', seed=0,
+                               inflate=True, offset=0, q=(0.025, 0.975), d_props=None, d_groups=None, d_params=None, d_pred=None,
+                               d_vox=None, max_bytes=BOOT_DEFAULT_BYTES, keep=False):
+    """Device-resident bootstrap conditional on measurement weights (mfx_wboot_fit_dev) of ONE voxel class (every voxel:
+    K == maxfasc, csf == csf_on), arguments as ``fit_bootstrap_dev`` takes them, without EAR, plus the weights d_W [V, M]
+    or [M].  The weights are held fixed: the own weighted fit (``d_params``, fitted here if None) is predicted, its
+    residuals are resampled by the rule of ``wboot_resample_dev``, the replicates are fitted with the same weights
+    (``fit_weighted_replicates_dev``) and reduced.  Returns the dict of ``fit_bootstrap_dev`` (the MSE column is the
+    weighted MSE; status as ``wboot_resample_dev``).  Enqueues on torch's current stream and returns without waiting."""
+    import torch
+    B, code, qa = _boot_rule(B, kind, q, seed, offset)
+    maxfasc = int(maxfasc)
+    _f64_cuda(d_Y, d_W, d_peaks if maxfasc > 0 else None, d_sig_csf if csf_on else None, d_props, d_params, d_pred)
+    V, w_stride = _wfit_shapes(plan, d_Y.shape, d_W.shape, d_peaks.shape if maxfasc > 0 else (d_Y.shape[0], 0), maxfasc)
+    M = plan.M
+    npar = num_params(maxfasc, csf_on, False)
+    if csf_on and (d_sig_csf is None or d_sig_csf.numel() != M):
+        raise ValueError("csf_on needs sig_csf with %d entries" % M)
+    if d_params is not None and tuple(d_params.shape) != (V, npar):
+        raise ValueError("params should have shape (%d, %d), got %s" % (V, npar, tuple(d_params.shape)))
+    if d_pred is not None and (d_params is None or tuple(d_pred.shape) != (V, M)):
+        raise ValueError("a prediction needs the parameters it was made from and the data's shape (%d, %d)" % (V, M))
+    nprop = 0
+    if d_props is not None:
+        if d_props.dim() != 2 or d_props.shape[1] != plan.tables.N:
+            raise ValueError("props should have shape (nprop, %d), got %s" % (plan.tables.N, tuple(d_props.shape)))
+        nprop = int(d_props.shape[0])
+    dev = d_Y.device
+    d_groups = _wboot_dev_opts(M, V, code, d_groups, d_vox, plan.scheme, dev)
+    cols = boot_columns(maxfasc, csf_on, False, nprop)
+    d_q = torch.from_numpy(qa).to(dev) if qa.size else None
+    stats = torch.empty((V, len(cols), BOOT_NSTAT + qa.size), dtype=torch.float64, device=dev)
+    agree = torch.zeros((V, maxfasc), dtype=torch.int32, device=dev)
+    status = torch.zeros((V,), dtype=torch.int32, device=dev)
+    reps = torch.empty((V, B, npar), dtype=torch.float64, device=dev) if keep else None
+    st = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        L.check(L.lib().mfx_wboot_fit_dev(plan.handle(), d_Y.data_ptr(), d_W.data_ptr(), w_stride,
+                                          _tptr(d_peaks) if maxfasc > 0 else None, maxfasc, int(bool(csf_on)),
+                                          _tptr(d_sig_csf) if csf_on else None, _tptr(d_params), _tptr(d_pred),
+                                          _tptr(d_groups) if code == 1 else None, _tptr(d_vox), V, B, code, int(bool(inflate)),
+                                          int(seed) & _U64, int(offset) & _U64, _tptr(d_props), nprop, _tptr(d_q), int(qa.size),
+                                          int(max_bytes), stats.data_ptr(), agree.data_ptr() if maxfasc > 0 else None,
+                                          status.data_ptr(), _tptr(reps), st))
+    return {'stats': stats, 'agree': agree, 'status': status, 'replicates': reps, 'columns': cols}
+
+
+def fit_weighted_bootstrap(plan, Y, W, K, csf, peaks, maxfasc, csf_on, sig_csf=None, B=200, kind='wild', seed=0, inflate=True,
+                           offset=0, q=(0.025, 0.975), props=None, groups=None, params=None, vox=None,
+                           max_bytes=BOOT_DEFAULT_BYTES, keep=False):
+    """Bootstrap conditional on measurement weights of a mixed set of voxels on NumPy arrays (mfx_wboot_fit), arguments
+    as ``fit_weighted`` takes them and the options of ``fit_bootstrap``: every voxel class of the weighted fit is served
+    (K in 0..maxfasc, CSF; no EAR).  The weights W [V, M] or [M] - those of a weighted fit, or the final weights of a robust
+    fit - are held fixed in every replicate: nothing is rejected anew, so the result is conditional on them.  ``params``
+    [V, num_params(maxfasc, csf_on, False)]: the voxels' own weighted fit (fitted here if None).  Returns the dict of
+    ``fit_bootstrap``; status 0 fine, 1 no degree of freedom among the rows of positive weight, 2 original row not usable,
+    3 a weight negative or not finite, 4 no positive weight."""
+    B, code, qa = _boot_rule(B, kind, q, seed, offset)
+    maxfasc = int(maxfasc)
+    Y = L.f64c(Y)
+    W = L.f64c(W)
+    pk = L.f64c(peaks).reshape(Y.shape[0], -1) if (maxfasc > 0 and Y.ndim == 2) else np.zeros((Y.shape[0], 0))
+    V, w_stride = _wfit_shapes(plan, Y.shape, W.shape, pk.shape, maxfasc)
+    M = plan.M
+    csf_on = bool(csf_on)
+    K, cs, sc = _mixed_args(M, V, maxfasc, K, csf, csf_on, sig_csf, need_sig=True)
+    npar = num_params(maxfasc, csf_on, False)
+    p0 = None
+    if params is not None:
+        p0 = L.f64c(params)
+        if p0.shape != (V, npar):
+            raise ValueError("params should have shape (%d, %d), got %s" % (V, npar, p0.shape))
+    vx = None
+    if vox is not None:
+        vx = np.ascontiguousarray(np.asarray(vox).reshape(-1), dtype=np.int64)
+        if vx.shape != (V,):
+            raise ValueError("vox should have one entry per voxel")
+    pr, nprop = None, 0
+    if props is not None:
+        pr = np.atleast_2d(L.f64c(props))
+        N = getattr(getattr(plan, 'tables', None), 'N', pr.shape[1])
+        if pr.ndim != 2 or pr.shape[1] != N:
+            raise ValueError("props should have shape (nprop, %d), got %s" % (N, pr.shape))
+        nprop = pr.shape[0]
+    gr = _boot_groups_arg(code, groups, M, getattr(plan, 'scheme', None))
+    cols = boot_columns(maxfasc, csf_on, False, nprop)
+    stats = np.zeros((V, len(cols), BOOT_NSTAT + qa.size))
+    agree = np.zeros((V, maxfasc), dtype=np.int32)
+    status = np.zeros(V, dtype=np.int32)
+    reps = np.zeros((V, B, npar)) if keep else None
+    L.check(L.lib().mfx_wboot_fit(plan.handle(), L.dptr(Y), L.dptr(W), w_stride, L.iptr(K), L.opt(cs, L.bptr),
+                                  L.dptr(pk) if maxfasc > 0 else None, maxfasc, int(csf_on), L.opt(sc) if csf_on else None, L.opt(p0),
+                                  L.opt(gr, L.iptr), L.opt(vx, L.lptr), V, B, code, int(bool(inflate)), int(seed) & _U64,
+                                  int(offset) & _U64, L.opt(pr), nprop, L.dptr(qa) if qa.size else None, int(qa.size), int(max_bytes),
+                                  L.dptr(stats), L.iptr(agree) if maxfasc > 0 else None, L.iptr(status), L.opt(reps)))
+    if V:
+        L.check(L.lib().mfx_plan_status(plan.handle(), None))   # a direction that is not a unit vector: ValueError
+    return {'stats': stats, 'agree': agree, 'status': status, 'replicates': reps, 'columns': cols}
+
+
 def _boot2d_maxfasc(maxfasc):
     maxfasc = int(maxfasc)
     if maxfasc < 0 or maxfasc > 3:

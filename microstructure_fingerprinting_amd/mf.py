@@ -839,7 +839,7 @@ class MFModelFit():
         return to_map(mean), to_map(std)
 
     def bootstrap(self, data, B=200, *, kind='wild', seed=0, inflate=True, q=(0.025, 0.975), voxels=None, keep=False,
-                  groups=None):
+                  groups=None, fixed_weights=False):
         """Model-free uncertainty of every estimated parameter: the residuals of each voxel's own fit are resampled
         into ``B`` replicate signals, every replicate is fitted by the plain fit, and the B parameter rows of a voxel
         are reduced to statistics, all on the device (``engine.fit_bootstrap``; include/mfx_boot.h states the rule).
@@ -848,10 +848,22 @@ class MFModelFit():
         ``inflate`` scales the residuals by sqrt(M / (M - number of active compartments)).  ``q``: the quantiles kept.
         ``voxels``: positions in the ROI (default: all of it); the random stream is keyed by the ROI position, so a
         subset gives the replicates the whole ROI gives.  ``keep``: also return the replicate parameter rows.  Every
-        voxel class of the plain fit is served (CSF, EAR); a fit made with ``weights=`` or ``robust=`` is not.
+        voxel class of the plain fit is served (CSF, EAR).  A fit made with ``weights=`` or ``robust=`` is served only
+        with ``fixed_weights=True``: the bootstrap then holds the fit's final measurement weights (``weights_roi``) fixed
+        - every replicate is fitted by the weighted fit on those weights and the fit's own parameters are the ones
+        resampled around (``engine.fit_weighted_bootstrap``; include/mfx_wboot.h states the rule).  No replicate re-runs
+        the rejection, so after a robust fit the result is CONDITIONAL ON THE ROWS THAT WERE REJECTED: it says how
+        stable the estimate is given that choice of outliers, not how stable the choice is.  Rows of weight 0 are left
+        as measured, 'residual' draws among the rows of positive weight in units of sqrt(weight), and ``inflate`` counts
+        the rows of positive weight.  ``fixed_weights=True`` on a fit without weights is a ValueError.
         Returns a ``BootstrapResult``."""
-        if self.weights_roi is not None or self.robust_info is not None:
+        if not isinstance(fixed_weights, (bool, np.bool_)):
+            raise ValueError("fixed_weights should be True or False, got %r" % (fixed_weights,))
+        weighted = self.weights_roi is not None or self.robust_info is not None
+        if weighted and not fixed_weights:
             raise NotImplementedError("bootstrap of a weighted or robust fit is not served")
+        if fixed_weights and self.weights_roi is None:
+            raise ValueError("fixed_weights=True needs a fit made with weights= or robust=: this fit has no measurement weights")
         B, _, qa = engine._boot_rule(B, kind, q, seed)
         if self._model is None or self._pgse_scheme is None or self._numfasc_roi is None:
             raise RuntimeError("this fit object was not made by MFModel.fit: it knows neither its model nor its protocol "
@@ -872,6 +884,16 @@ class MFModelFit():
         plan = m.ms_interpolator.plan_for(sch)
         names = list(self._props)
         props = np.stack([self._props[n] for n in names]) if names else None
+        if fixed_weights:
+            W = np.asarray(self.weights_roi, dtype=np.float64)
+            W = W if W.ndim == 1 else np.ascontiguousarray(W[vox])   # the shared [M] vector as it is, else the voxels' rows
+            res = engine.fit_weighted_bootstrap(plan, self._data_rows(data_arr, self._roi_flat[vox]), W, self._numfasc_roi[vox],
+                                                self._csf_roi[vox], self._peaks_roi[vox] if self._nf > 0 else None, self._nf,
+                                                self._csf_on, sig_csf, B=B, kind=kind, seed=seed, inflate=inflate, q=qa,
+                                                props=props, groups=gr, params=np.ascontiguousarray(self.params_in_mask[vox]),
+                                                vox=vox, keep=keep)
+            return BootstrapResult(res, names, qa, vox, self._roi_flat, self._grid, self._nf, self._csf_on, False, B, seed,
+                                   weights=W)
         res = engine.fit_bootstrap(plan, self._data_rows(data_arr, self._roi_flat[vox]), self._numfasc_roi[vox],
                                    self._csf_roi[vox], self._ear_roi[vox], self._peaks_roi[vox] if self._nf > 0 else None,
                                    self._nf, self._csf_on, self._ear_on, sig_csf, sig_ear, num_ear, B=B, kind=kind, seed=seed,
@@ -973,9 +995,12 @@ class BootstrapResult(object):
     ``agreement`` (``mask.shape + (maxfasc,)``): the share of replicates that chose the original fit's atom with a
     positive weight; ``status`` (``mask.shape``, -1 outside): 0 fine, 1 no degree of freedom, 2 original row not
     usable; ``B``, ``seed``, ``q``, ``voxels`` (the ROI positions bootstrapped); ``stats`` [n x C x (5 + Q)] with
-    ``columns``, the table the maps are cut from; ``replicates`` [n x B x num_params] with ``keep=True``, else None."""
+    ``columns``, the table the maps are cut from; ``replicates`` [n x B x num_params] with ``keep=True``, else None.
+    ``weights``: the measurement weights [n x M] or [M] a ``fixed_weights=True`` bootstrap held fixed (status then also
+    3: a weight negative or not finite, 4: no positive weight), else None."""
 
-    def __init__(self, res, prop_names, q, voxels, roi_flat, grid, nf, csf_on, ear_on, B, seed):
+    def __init__(self, res, prop_names, q, voxels, roi_flat, grid, nf, csf_on, ear_on, B, seed, weights=None):
+        self.weights = weights
         self.stats, self.columns, self.replicates = res['stats'], res['columns'], res['replicates']
         self.B, self.seed, self.q, self.voxels = int(B), seed, np.asarray(q, dtype=np.float64), voxels
         self._names, self._flat, self._grid, self._nf = list(prop_names), roi_flat[voxels], tuple(grid), nf
