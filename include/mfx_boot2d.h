@@ -19,7 +19,7 @@
  * mfx_fit2d.h); its replicate rows are NaN, its bootstrap status is 2 and its statistics are NaN.  No fit kernel sees a
  * NaN signal: the replicate signals of a voxel in a non-zero status are zero rows while they are fitted.
  * B <= MFX_BOOT_MAX_B and Q <= MFX_BOOT_MAX_Q in the bootstrap entry points, else MFX_ERR_UNSUPPORTED before any launch.
- * Not served: measurement weights, robust fits, EAR columns.
+ * Measurement weights and robust fits are served by mfx_wboot2d.h (the weights held fixed).  Not served: EAR columns.
  */
 #ifndef MFX_BOOT2D_H
 #define MFX_BOOT2D_H

@@ -49,7 +49,8 @@
  * A voxel in a non-zero status is fitted as a zero row and its replicate rows are NaN afterwards: no fit kernel sees a
  * NaN of this header's making.  B <= MFX_BOOT_MAX_B, Q <= MFX_BOOT_MAX_Q and maxfasc <= 3, else MFX_ERR_UNSUPPORTED
  * before any launch; so for protocols of more than 8192 measurements.
- * Not served: re-running a robust rejection per replicate, EAR columns, 2-D protocols with weights.
+ * 2-D protocols with weights are served by mfx_wboot2d.h.  Not served: re-running a robust rejection per replicate, EAR
+ * columns.
  */
 #ifndef MFX_WBOOT_H
 #define MFX_WBOOT_H

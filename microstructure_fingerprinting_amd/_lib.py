@@ -83,6 +83,10 @@ BOOT2D_EXPORTS = ["mfx_boot2d_abi_version", "mfx_boot2d_rep_tile", "mfx_boot2d_d
 WBOOT_EXPORTS = ["mfx_wboot_abi_version", "mfx_wboot_rep_tile", "mfx_wboot_debug_set_force_plain", "mfx_wboot_resample_dev",
                  "mfx_wboot_fit_rows_dev", "mfx_wboot_fit_dev", "mfx_wboot_fit"]
 
+# every symbol include/mfx_wboot2d.h declares (bootstrap of 2-D protocols conditional on measurement weights; versioned on its own)
+WBOOT2D_EXPORTS = ["mfx_wboot2d_abi_version", "mfx_wboot2d_rep_tile", "mfx_wboot2d_max_atoms", "mfx_wboot2d_debug_set_force_plain",
+                   "mfx_wboot2d_fit_rows_dev", "mfx_wboot2d_fit_dev", "mfx_wboot2d_fit"]
+
 # every symbol include/mfx_solve.h declares (batched explicit-dictionary solver: many signals, one dictionary; versioned on its own)
 SOLVE_EXPORTS = ["mfx_solve_abi_version", "mfx_solve_create", "mfx_solve_destroy", "mfx_solve_num_columns",
                  "mfx_solve_bytes_per_signal", "mfx_solve_batch_dev", "mfx_solve_batch", "mfx_solve_debug_set_force_generic"]
@@ -283,6 +287,17 @@ def lib():
                                     C.c_int, C.c_uint64, C.c_uint64, vp, C.c_int, vp, C.c_int, C.c_int64, vp, vp, vp, vp, vp]
     L.mfx_wboot_fit.argtypes = [vp, dp, dp, C.c_int64, ip, bp, dp, C.c_int, C.c_int, dp, dp, ip, lp, C.c_int64, C.c_int, C.c_int,
                                 C.c_int, C.c_uint64, C.c_uint64, dp, C.c_int, dp, C.c_int, C.c_int64, dp, ip, ip, dp]
+    L.mfx_wboot2d_abi_version.restype = C.c_int
+    L.mfx_wboot2d_rep_tile.restype = C.c_int
+    L.mfx_wboot2d_max_atoms.argtypes = [vp]
+    L.mfx_wboot2d_max_atoms.restype = C.c_int
+    L.mfx_wboot2d_debug_set_force_plain.argtypes = [C.c_int]
+    L.mfx_wboot2d_debug_set_force_plain.restype = None
+    L.mfx_wboot2d_fit_rows_dev.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int, C.c_int64, C.c_int, vp, vp, vp, vp]
+    L.mfx_wboot2d_fit_dev.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int64, C.c_int, C.c_int,
+                                      C.c_int, C.c_uint64, C.c_uint64, vp, C.c_int, vp, C.c_int, C.c_int64, vp, vp, vp, vp, vp, vp]
+    L.mfx_wboot2d_fit.argtypes = [vp, dp, dp, C.c_int64, ip, bp, dp, C.c_int, C.c_int, dp, dp, ip, lp, C.c_int64, C.c_int, C.c_int,
+                                  C.c_int, C.c_uint64, C.c_uint64, dp, C.c_int, dp, C.c_int, C.c_int64, dp, ip, ip, ip, dp]
     L.mfx_solve_abi_version.restype = C.c_int
     L.mfx_solve_create.argtypes = [dp, C.c_int64, C.c_int, lp, C.c_int, C.c_int, C.POINTER(vp)]
     L.mfx_solve_destroy.argtypes = [vp]

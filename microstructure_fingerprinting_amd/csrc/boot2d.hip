@@ -108,7 +108,7 @@ int b2_rows(const mfx_rot2d* h, const double* d_Ys, const double* d_peaks, const
     if (K == 2) HIPCHK(sG.alloc(sizeof(double) * (size_t)Vc * NP * NP));
     const size_t lds2 = b2_k2_lds_bytes(NP, M);
     if (K == 2 && lds2 > 64 * 1024)
-      HIPCHK(hipFuncSetAttribute((const void*)boot2d_k2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+      HIPCHK(hipFuncSetAttribute((const void*)boot2d_k2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
     for (int64_t v0 = 0; v0 < V; v0 += Vc) {
       const int64_t nv = std::min(Vc, V - v0);
       B2Args a{};
@@ -120,21 +120,21 @@ int b2_rows(const mfx_rot2d* h, const double* d_Ys, const double* d_peaks, const
       a.params = d_params + (size_t)v0 * B * np; a.num_params = np; a.maxfasc = K;
       const dim3 gs((unsigned)((K * NP + B2_ST_WG - 1) / B2_ST_WG), (unsigned)((B + B2_R - 1) / B2_R), (unsigned)nv);
       if (K == 1) {
-        hipLaunchKernelGGL(boot2d_stats_kernel<1>, gs, dim3(B2_ST_WG), 0, st, a);
+        hipLaunchKernelGGL((boot2d_stats_kernel<1, false>), gs, dim3(B2_ST_WG), 0, st, a);
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(boot2d_ysq_kernel<1>, dim3(b2_grid(nv * B)), dim3(256), 0, st, a, nv * B);
+        hipLaunchKernelGGL((boot2d_ysq_kernel<1, false>), dim3(b2_grid(nv * B)), dim3(256), 0, st, a, nv * B);
         HIPCHK(hipGetLastError());
         const size_t lds = (2 * F2_K1_WG + 8 + (size_t)M) * sizeof(double);
-        hipLaunchKernelGGL(boot2d_k1_kernel, dim3((unsigned)(nv * B)), dim3(F2_K1_WG), lds, st, a);
+        hipLaunchKernelGGL(boot2d_k1_kernel<false>, dim3((unsigned)(nv * B)), dim3(F2_K1_WG), lds, st, a);
         HIPCHK(hipGetLastError());
       } else {
-        hipLaunchKernelGGL(boot2d_stats_kernel<2>, gs, dim3(B2_ST_WG), 0, st, a);
+        hipLaunchKernelGGL((boot2d_stats_kernel<2, false>), gs, dim3(B2_ST_WG), 0, st, a);
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(boot2d_ysq_kernel<2>, dim3(b2_grid(nv * B)), dim3(256), 0, st, a, nv * B);
+        hipLaunchKernelGGL((boot2d_ysq_kernel<2, false>), dim3(b2_grid(nv * B)), dim3(256), 0, st, a, nv * B);
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(boot2d_gram_kernel, dim3((unsigned)nv), dim3(F2_WG), b2_gram_lds_bytes(), st, a, sG.as<double>());
+        hipLaunchKernelGGL(boot2d_gram_kernel<false>, dim3((unsigned)nv), dim3(F2_WG), b2_gram_lds_bytes(), st, a, sG.as<double>());
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(boot2d_k2_kernel, dim3((unsigned)(nv * B)), dim3(F2_WG), lds2, st, a);
+        hipLaunchKernelGGL(boot2d_k2_kernel<false>, dim3((unsigned)(nv * B)), dim3(F2_WG), lds2, st, a);
         HIPCHK(hipGetLastError());
       }
     }

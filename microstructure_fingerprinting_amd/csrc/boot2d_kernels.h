@@ -2,8 +2,16 @@
 // set of directions.  What the plain kernels of fit2d_kernels.h form per row - both rotated dictionaries, their column
 // norms, the cross-Gram D_0^T D_1 - belongs to the directions and is formed once per voxel here; only D^T y* and |y*|^2
 // belong to a replicate.  Every sum a result depends on is formed by the arithmetic of the plain kernels, in their order,
-// so a replicate's row is the row mfx_fit2d_batch_dev returns for that signal, bit for bit.  No translation unit of its own
-// (boot2d.hip).
+// so a replicate's row is the row mfx_fit2d_batch_dev returns for that signal, bit for bit.  No translation unit of its own:
+// boot2d.hip instantiates WGT = false, wboot2d.hip (include/mfx_wboot2d.h) WGT = true.
+//
+// WGT: the replicate fit on a voxel's measurement weights, the arithmetic of the WGT kernels of fit2d_kernels.h.  Once per
+// voxel w2d_prep_kernel gives s = sqrt(W), sum W and the weights' status; boot2d_wsig_kernel forms y'* = fl(s_m y*_m) for every
+// replicate row.  The kernels then read y'* where the unweighted ones read y*, every generated entry is fl(s_m d) (one
+// multiply by the wave-uniform s_m in the statistics kernel and the exact stage; s of a chunk staged in LDS by chunk parity
+// and one multiply in store_chunk of the Gram kernel, the chunk loop of mfx_fit2d_k2_kernel<true>), and the packing is the
+// weighted one: MSE = min_obj / sum W, f2_r2w on the unscaled y* and W.  A voxel with unusable weights is skipped like one
+// with a failing direction.  The WGT = false instantiations are the kernels as they were.
 //
 // boot2d_stats_kernel<K>  column statistics: one thread per atom (and side), serial over the rows in row order, one rounded
 //                     multiply and one rounded add per step - phase 1 of mfx_fit2d_k2_kernel, the atom loop of
@@ -49,6 +57,40 @@ struct B2Args {
   double* params;        // [V x B x num_params]
   int num_params, maxfasc;
 };
+// WGT: the same and what w2d_prep_kernel and boot2d_wsig_kernel prepared of the weights
+struct WB2Args {
+  int M, N, NP, B;
+  const double* base;
+  const F2Rec* rec;      // [V K x M], per voxel
+  const double* Y;       // [V x B x M] replicate signals, unscaled (the weighted R2 reads them)
+  const int* vstat;      // [V x 5], per voxel
+  double* a2;            // [V][K][NP]  |fl(s_m d)|^2
+  double* ay;            // [V][B][K][NP]  fl(s_m d) . y'*
+  double* ysq;           // [V][B]  |y'*|^2
+  const double* G;       // [V][NP][NP] (K = 2)
+  double* params;        // [V x B x num_params]
+  int num_params, maxfasc;
+  const double* Ys;      // [V x B x M] y'* = fl(s_m y*_m)  (boot2d_wsig_kernel)
+  const double* W;       // [V x M] or [M]
+  int64_t wstride;       // M or 0
+  const double* S;       // [V x M] sqrt(W)                 (w2d_prep_kernel)
+  const double* sumw;    // [V] sum_m W                     (w2d_prep_kernel)
+  const int* wstat;      // [V] 0 usable, 1 a negative or non-finite weight, 2 no positive weight
+};
+template <bool WGT> using B2ArgsT = std::conditional_t<WGT, WB2Args, B2Args>;
+
+// a voxel no kernel works on: a failing direction, or (WGT) unusable weights
+template <class Args>
+__device__ __forceinline__ bool b2_skip(const Args& a, size_t vox) {
+  if constexpr (std::is_same_v<Args, WB2Args>) return a.vstat[5 * vox] != 0 || a.wstat[vox] != 0;
+  else return a.vstat[5 * vox] != 0;
+}
+// the signals of the fit: y* or (WGT) y'*
+template <class Args>
+__device__ __forceinline__ const double* b2_fit_signals(const Args& a) {
+  if constexpr (std::is_same_v<Args, WB2Args>) return a.Ys;
+  else return a.Y;
+}
 
 // NaN rows for the replicates of a voxel with a failing direction (what fit2d_status_kernel writes per row of the plain fit)
 __global__ void boot2d_nan_rows_kernel(const int* __restrict__ vstat, int64_t V, int64_t per_vox, double* __restrict__ params) {
@@ -57,16 +99,28 @@ __global__ void boot2d_nan_rows_kernel(const int* __restrict__ vstat, int64_t V,
   if (vstat[5 * (i / per_vox)] != 0) params[i] = __builtin_nan("");
 }
 
-template <int K>
-__global__ __launch_bounds__(B2_ST_WG) void boot2d_stats_kernel(B2Args a) {
+// y'* = fl(s_m y*_m) for every replicate row of the chunk (WGT), one rounded multiply each; zero rows for a skipped voxel
+__global__ void boot2d_wsig_kernel(const double* __restrict__ Y, const double* __restrict__ S, const int* __restrict__ vstat,
+                                   const int* __restrict__ wstat, int64_t V, int B, int M, double* __restrict__ Ys) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= V * B * M) return;
+  const int64_t row = i / M, v = row / B;
+  const int m = (int)(i - row * M);
+  Ys[i] = (vstat[5 * v] != 0 || wstat[v] != 0) ? 0.0 : S[v * M + m] * Y[i];
+}
+
+template <int K, bool WGT>
+__global__ __launch_bounds__(B2_ST_WG) void boot2d_stats_kernel(B2ArgsT<WGT> a) {
   const int M = a.M, N = a.N, NP = a.NP, B = a.B;
   const size_t vox = blockIdx.z;
-  if (a.vstat[5 * vox] != 0) return;
+  if (b2_skip(a, vox)) return;
+  const double* __restrict__ sv = nullptr;   // s (WGT), wave-uniform addresses
+  if constexpr (WGT) sv = a.S + vox * M;
   const int b0 = blockIdx.y * B2_R;
   const int nb = min(B2_R, B - b0);
   const double* __restrict__ ys[B2_R];   // rows beyond the tile read the tile's last signal and are not stored
 #pragma unroll
-  for (int r = 0; r < B2_R; ++r) ys[r] = a.Y + (vox * B + (size_t)(b0 + min(r, nb - 1))) * M;
+  for (int r = 0; r < B2_R; ++r) ys[r] = b2_fit_signals(a) + (vox * B + (size_t)(b0 + min(r, nb - 1))) * M;
   const int col = blockIdx.x * B2_ST_WG + threadIdx.x;
   if (col < K * NP) {
     const int k = col >= NP, n = col - k * NP;
@@ -78,7 +132,7 @@ __global__ __launch_bounds__(B2_ST_WG) void boot2d_stats_kernel(B2Args a) {
 #pragma unroll 2
       for (int m = 0; m < M; ++m) {
         const F2Rec rc = rec[m];
-        const double d = f2_value(a.base, rc, n);
+        const double d = WGT ? sv[m] * f2_value(a.base, rc, n) : f2_value(a.base, rc, n);   // WGT: fl(s_m d)
         s2 += d * d;
 #pragma unroll
         for (int r = 0; r < B2_R; ++r) sy[r] += ys[r][m] * d;
@@ -92,12 +146,12 @@ __global__ __launch_bounds__(B2_ST_WG) void boot2d_stats_kernel(B2Args a) {
 }
 
 // |y*|^2 per replicate row, one thread each: the serial sum for K = 2, np.sum's pairwise order for K = 1, as the plain kernels
-template <int K>
-__global__ void boot2d_ysq_kernel(B2Args a, int64_t rows) {
+template <int K, bool WGT>
+__global__ void boot2d_ysq_kernel(B2ArgsT<WGT> a, int64_t rows) {
   const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (row >= rows || a.vstat[5 * (row / a.B)] != 0) return;
+  if (row >= rows || b2_skip(a, (size_t)(row / a.B))) return;
   const int M = a.M;
-  const double* __restrict__ y = a.Y + row * M;
+  const double* __restrict__ y = b2_fit_signals(a) + row * M;   // WGT: |y'*|^2
   double s;
   if (K == 1) {
     s = mfx_np_sumsq(y, M);   // _1 uses np.sum(y**2)
@@ -108,18 +162,19 @@ __global__ void boot2d_ysq_kernel(B2Args a, int64_t rows) {
   a.ysq[row] = s;
 }
 
-// K = 1: the tail of mfx_fit2d_k1_kernel<false>; grid = V B rows
-__global__ __launch_bounds__(F2_K1_WG) void boot2d_k1_kernel(B2Args a) {
+// K = 1: the tail of mfx_fit2d_k1_kernel<WGT>; grid = V B rows
+template <bool WGT>
+__global__ __launch_bounds__(F2_K1_WG) void boot2d_k1_kernel(B2ArgsT<WGT> a) {
   extern __shared__ double smem[];
   const int tid = threadIdx.x;
   const int M = a.M, N = a.N, NP = a.NP;
   const size_t row = blockIdx.x, vox = row / a.B;
-  if (a.vstat[5 * vox] != 0) return;
+  if (b2_skip(a, vox)) return;
   double* s_res = smem;                         // [WG]
   long* s_key = (long*)(s_res + F2_K1_WG);      // [WG]
   double* s_misc = (double*)(s_key + F2_K1_WG); // [8]
   double* s_yrec = s_misc + 8;                  // [M]
-  const double* __restrict__ yv = a.Y + row * M;
+  const double* __restrict__ yv = a.Y + row * M;   // unscaled (WGT: only the weighted R2 reads it)
   const double* __restrict__ va2 = a.a2 + vox * NP;
   const double* __restrict__ vay = a.ay + row * NP;
   const F2Rec* __restrict__ rec = a.rec + vox * M;
@@ -151,23 +206,30 @@ __global__ __launch_bounds__(F2_K1_WG) void boot2d_k1_kernel(B2Args a) {
   if (tid < 64) {
     const int lane = tid;
     for (int m = lane; m < M; m += 64) s_yrec[m] = w * f2_value(a.base, rec[m], ia);
-    const double r2 = f2_r2(yv, s_yrec, M, lane);
+    double r2;
+    if constexpr (WGT) r2 = f2_r2w(yv, a.W + vox * a.wstride, s_yrec, M, lane);
+    else r2 = f2_r2(yv, s_yrec, M, lane);
     if (lane == 0) {   // params packing, mf.py:420-450
       double* out = a.params + row * a.num_params;
       out[0] = w;
       out[1] = (fabs(w) > 0) ? w / w : w;
       out[1 + a.maxfasc] = (double)ia;
-      out[a.num_params - 2] = res / M;
+      if constexpr (WGT) out[a.num_params - 2] = res / a.sumw[vox];   // MSE = min_obj / sum W
+      else out[a.num_params - 2] = res / M;
       out[a.num_params - 1] = r2;
     }
   }
 }
 
-size_t b2_gram_lds_bytes() { return (size_t)2 * F2_NT * F2_TS * sizeof(double) + F2_REC * sizeof(F2Rec); }
+size_t b2_gram_lds_bytes(bool wgt = false) {   // wgt: plus the staged s of two chunks
+  return ((size_t)2 * F2_NT * F2_TS + (wgt ? 2 * F2_MC : 0)) * sizeof(double) + F2_REC * sizeof(F2Rec);
+}
 
-// K = 2, per voxel: the cross-Gram of the padded dictionaries.  The chunk loop is that of mfx_fit2d_k2_kernel<false>
-// (fit2d_kernels.h, "phase 2"): keep the two texts in step.
-__global__ __launch_bounds__(F2_WG, 2) void boot2d_gram_kernel(B2Args a, double* __restrict__ G) {
+// K = 2, per voxel: the cross-Gram of the padded dictionaries.  The chunk loop is that of mfx_fit2d_k2_kernel<WGT>
+// (fit2d_kernels.h, "phase 2"): keep the two texts in step.  WGT: s of a chunk's rows staged beside the records, one
+// multiply in store_chunk.
+template <bool WGT>
+__global__ __launch_bounds__(F2_WG, 2) void boot2d_gram_kernel(B2ArgsT<WGT> a, double* __restrict__ G) {
   extern __shared__ double smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -176,9 +238,12 @@ __global__ __launch_bounds__(F2_WG, 2) void boot2d_gram_kernel(B2Args a, double*
   const int M = a.M, N = a.N, NP = a.NP;
   const int ntiles = NP >> 4;
   const size_t vox = blockIdx.x;
-  if (a.vstat[5 * vox] != 0) return;
+  if (b2_skip(a, vox)) return;
   double* sT = smem;                                      // [2][F2_NT][F2_TS]: tiles 0..7 the D_0 block, 8..15 the D_1 block
-  F2Rec* s_rec = (F2Rec*)(sT + 2 * F2_NT * F2_TS);        // [F2_REC] staged records of two chunks
+  double* s_sc = sT + 2 * F2_NT * F2_TS;                  // [2][F2_MC] staged s of two chunks (WGT)
+  F2Rec* s_rec = (F2Rec*)(s_sc + (WGT ? 2 * F2_MC : 0));  // [F2_REC] staged records of two chunks
+  const double* __restrict__ sv = nullptr;                // s (WGT)
+  if constexpr (WGT) sv = a.S + vox * M;
   const size_t rec0 = 2 * vox * M;
   double* __restrict__ Gv = G + vox * (size_t)NP * NP;
 
@@ -195,6 +260,9 @@ __global__ __launch_bounds__(F2_WG, 2) void boot2d_gram_kernel(B2Args a, double*
       F2Rec rc = a.rec[rec0 + (size_t)side * M + (in ? m : 0)];
       if (!in) { rc.s = 0.0; rc.dx = 0.0; rc.o = R2_OP_ZERO; rc.a = 0; rc.b = 0; }
       s_rec[q] = rc;
+    } else if (WGT && tid < 3 * F2_MC) {   // s of the chunk's rows (0 beyond the protocol), by chunk parity
+      const int r = tid - 2 * F2_MC, m = ch * F2_MC + r;
+      s_sc[(ch & 1) * F2_MC + r] = m < M ? sv[m] : 0.0;
     }
   };
 
@@ -218,7 +286,8 @@ __global__ __launch_bounds__(F2_WG, 2) void boot2d_gram_kernel(B2Args a, double*
         double* dst = gdst0 + (size_t)buf * (F2_NT * F2_TS);
 #pragma unroll
         for (int r = 0; r < F2_MC; ++r) {
-          const double v = r2_value(s_rec[q0 + r].o, s_rec[q0 + r].s, va[r], s_rec[q0 + r].dx, vb[r]);
+          double v = r2_value(s_rec[q0 + r].o, s_rec[q0 + r].s, va[r], s_rec[q0 + r].dx, vb[r]);
+          if constexpr (WGT) v = s_sc[(ch & 1) * F2_MC + r] * v;   // fl(s_m d)
           dst[r * 16] = gn < N ? v : 0.0;   // atoms beyond the dictionary: zero columns
         }
       };
@@ -281,8 +350,9 @@ size_t b2_k2_lds_bytes(int NP, int M) {
   return ((size_t)4 * NP + 32 + 48 + (size_t)M) * sizeof(double) + F2_MAXC * sizeof(Cand) + 4 * sizeof(int);
 }
 
-// K = 2, per (voxel, replicate): mfx_fit2d_k2_kernel<false> behind its chunk loop, on the stored statistics and Gram
-__global__ __launch_bounds__(F2_WG) void boot2d_k2_kernel(B2Args a) {
+// K = 2, per (voxel, replicate): mfx_fit2d_k2_kernel<WGT> behind its chunk loop, on the stored statistics and Gram
+template <bool WGT>
+__global__ __launch_bounds__(F2_WG) void boot2d_k2_kernel(B2ArgsT<WGT> a) {
   extern __shared__ double smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -291,7 +361,7 @@ __global__ __launch_bounds__(F2_WG) void boot2d_k2_kernel(B2Args a) {
   const int M = a.M, N = a.N, NP = a.NP;
   const int ntiles = NP >> 4;
   const size_t row = blockIdx.x, vox = row / a.B;
-  if (a.vstat[5 * vox] != 0) return;
+  if (b2_skip(a, vox)) return;
 
   double2* s_st = (double2*)smem;                // [2][NP] column statistics {|d|^2, d.y*} of D_0, then of D_1
   double* s_red = (double*)(s_st + 2 * NP);      // [32] scratch
@@ -299,10 +369,17 @@ __global__ __launch_bounds__(F2_WG) void boot2d_k2_kernel(B2Args a) {
   Cand* s_cand = (Cand*)(s_wk + 48 + M);         // [F2_MAXC]
   int* s_cnt = (int*)(s_cand + F2_MAXC);         // [4]
 
-  const double* __restrict__ ys = a.Y + row * M;
+  const double* __restrict__ yv = a.Y + row * M;              // unscaled (WGT: only the weighted R2 reads it)
+  const double* __restrict__ ys = b2_fit_signals(a) + row * M;   // the signal of the fit (WGT: y'*)
+  const double* __restrict__ sv = nullptr;                    // s (WGT)
+  if constexpr (WGT) sv = a.S + vox * M;
   const double* __restrict__ Gv = a.G + vox * (size_t)NP * NP;
   const size_t rec0 = 2 * vox * M;               // records of direction k: + k M
-  auto elem = [&](int k, int m, int n) -> double { return f2_value(a.base, a.rec[rec0 + (size_t)k * M + m], n); };
+  auto elem_raw = [&](int k, int m, int n) -> double { return f2_value(a.base, a.rec[rec0 + (size_t)k * M + m], n); };
+  auto elem = [&](int k, int m, int n) -> double {   // WGT: fl(s_m d)
+    if constexpr (WGT) return sv[m] * elem_raw(k, m, n);
+    else return elem_raw(k, m, n);
+  };
 
   // ---- the stored statistics; the best single-atom score of either dictionary is the scan's first bound
   if (tid == 0) { s_cnt[0] = 0; s_red[31] = a.ysq[row]; }
@@ -522,8 +599,10 @@ __global__ __launch_bounds__(F2_WG) void boot2d_k2_kernel(B2Args a) {
     const double nu0 = (fabs(M0) > 0) ? w0 / M0 : w0;
     const double nu1 = (fabs(M0) > 0) ? w1 / M0 : w1;
     double* s_yrec = s_win + 8;   // [M]: s_wk holds 48 + M doubles
-    for (int m = lane; m < M; m += 64) s_yrec[m] = elem(0, m, bi) * w0 + elem(1, m, bjx) * w1;
-    const double r2 = f2_r2(ys, s_yrec, M, lane);
+    for (int m = lane; m < M; m += 64) s_yrec[m] = elem_raw(0, m, bi) * w0 + elem_raw(1, m, bjx) * w1;   // unscaled columns
+    double r2;
+    if constexpr (WGT) r2 = f2_r2w(yv, a.W + vox * a.wstride, s_yrec, M, lane);
+    else r2 = f2_r2(yv, s_yrec, M, lane);
     double* out = a.params + row * a.num_params;
     if (lane == 0) {
       out[0] = M0;
@@ -531,7 +610,8 @@ __global__ __launch_bounds__(F2_WG) void boot2d_k2_kernel(B2Args a) {
       out[2] = nu1;
       out[1 + a.maxfasc] = (double)bi;
       out[2 + a.maxfasc] = (double)bjx;
-      out[a.num_params - 2] = best / M;
+      if constexpr (WGT) out[a.num_params - 2] = best / a.sumw[vox];   // MSE = min_obj / sum W
+      else out[a.num_params - 2] = best / M;
       out[a.num_params - 1] = r2;
     }
   }

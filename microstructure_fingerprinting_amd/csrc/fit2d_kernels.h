@@ -3,7 +3,7 @@
 //
 // WGT: the reference chain on rows scaled by s = sqrt(W) (include/mfx_w2d.h).  Every dictionary entry is fl(s_m * d) with d
 // the unweighted entry, y' = s y, MSE = min_obj / sum W and the weighted R2 on the unscaled columns; s, y' and sum W come
-// from w2d_prep_kernel (w2d.hip) through W2Args.  For W = 1 the weighted kernels see the unweighted columns (s = 1) and
+// from w2d_prep_kernel (below) through W2Args.  For W = 1 the weighted kernels see the unweighted columns (s = 1) and
 // return the unweighted rows bit for bit.  What WGT adds to a kernel is listed at its head; everything else - the chunk
 // loop, the scan, the 4 M eps interval, the unranked hand-over, the family expansion, the overflow pass - is one text.
 //
@@ -152,6 +152,44 @@ __device__ __forceinline__ double f2_r2w(const double* __restrict__ yv, const do
     r2 = r * r;
   }
   return r2;
+}
+
+// One wave per voxel: the weights are tested over the whole voxel first (the result is uniform), then s, y' and sum W are
+// written.  A voxel with a failing direction is left alone (weight status 0: the direction is reported); a voxel with
+// unusable weights gets zeros in s and y' (nobody reads them), its code, and with params its NaN row.  ok (may be null):
+// 1 where the fit runs.  Y and Ys null: no y' (the replicate fit of boot2d_kernels.h forms y'* per replicate row).
+__global__ __launch_bounds__(64) void w2d_prep_kernel(const double* __restrict__ Y, const double* __restrict__ W, int64_t wstride, int M,
+                                                      const int* __restrict__ vstat, double* __restrict__ S, double* __restrict__ Ys,
+                                                      double* __restrict__ sumw, int* __restrict__ wstat, int* __restrict__ ok,
+                                                      double* __restrict__ params, int np) {
+  const size_t v = blockIdx.x;
+  const int lane = threadIdx.x;
+  if (vstat[5 * v] != 0) {
+    if (lane == 0) { wstat[v] = 0; sumw[v] = 0.0; if (ok) ok[v] = 0; }
+    return;
+  }
+  const double* __restrict__ wv = W + v * wstride;
+  const double* __restrict__ yv = Y + v * M;
+  int bad = 0, pos = 0;
+  double sw = 0.0;
+  for (int m = lane; m < M; m += 64) {
+    const double w = wv[m];
+    bad |= !(w >= 0.0) || !(w <= 1.79769313486231570815e308);
+    pos |= w > 0.0;
+    sw += w;
+  }
+  bad = __any(bad);
+  pos = __any(pos);
+  sw = wave_sum(sw);
+  const int code = bad ? 1 : (pos ? 0 : 2);
+  for (int m = lane; m < M; m += 64) {
+    const double s = code == 0 ? sqrt(wv[m]) : 0.0;
+    S[v * M + m] = s;
+    if (Ys) Ys[v * M + m] = s * yv[m];
+  }
+  if (params && code != 0)
+    for (int q = lane; q < np; q += 64) params[v * np + q] = __builtin_nan("");
+  if (lane == 0) { wstat[v] = code; sumw[v] = sw; if (ok) ok[v] = code == 0; }
 }
 
 // wgt: plus the staged s of two chunks

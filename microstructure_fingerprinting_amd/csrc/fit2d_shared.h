@@ -105,7 +105,7 @@ __global__ void fit2d_status_kernel(const int* __restrict__ pstat, int K, int64_
 }
 
 // The arguments of the weighted (WGT) kernels of fit2d_kernels.h and soft2d_kernels.h: those of the unweighted ones and what
-// w2d_prep_kernel (w2d.hip) prepared of the weights.
+// w2d_prep_kernel (fit2d_kernels.h) prepared of the weights.
 struct W2Args {
   int M, N;
   const double* base;

@@ -2,7 +2,7 @@
 // weights (soft2d.hip instantiates <MODE, false>) and with them (w2d.hip, <MODE, true>).  No translation unit of its own.
 //
 // WGT: F_W is the F below on rows scaled by s = sqrt(W) (include/mfx_w2d.h): every entry fl(s_m * d), y' = s y, both from
-// w2d_prep_kernel (w2d.hip) through W2Args.  What WGT adds: the weights' status, tested after T (posterior 3 / 4); s_m of a
+// w2d_prep_kernel (fit2d_kernels.h) through W2Args.  What WGT adds: the weights' status, tested after T (posterior 3 / 4); s_m of a
 // chunk's rows staged in LDS beside the rows' records and store_chunk's multiply by it, as in mfx_fit2d_k2_kernel; the
 // serial sums of phase 1 over fl(s_m d) and y'.  The chunk loop and the pair walk are one text.
 //

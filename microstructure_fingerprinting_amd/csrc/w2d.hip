@@ -9,10 +9,10 @@
 //
 // The fitting kernels are the WGT = true instantiations of fit2d_kernels.h (mfx_fit2d_k2_kernel, mfx_fit2d_k1_kernel,
 // fit2d_mat_kernel) and soft2d_kernels.h (mfx_soft2d_k2_kernel<MODE>, mfx_soft2d_k1_kernel<MODE>); what the weights add to
-// each is listed there.  Only this file instantiates them.  Its own:
-// w2d_prep_kernel        once per call, one wave per voxel: the weights' status (uniform over the voxel), s [V x M],
-//                        y' = s y [V x M] and sum W into the stream's scratch arena; NaN row of a flagged voxel (fit).  s
-//                        and y' live in memory, not LDS: the kernels' LDS footprint stays independent of M.
+// each is listed there.  w2d_prep_kernel (fit2d_kernels.h; the replicate fit of wboot2d.hip runs it too), once per call,
+// one wave per voxel: the weights' status (uniform over the voxel), s [V x M], y' = s y [V x M] and sum W into the stream's
+// scratch arena; NaN row of a flagged voxel (fit).  s and y' live in memory, not LDS: the kernels' LDS footprint stays
+// independent of M.  This file's own:
 // w2d_repack_kernel      behind the explicit solver of mfx_api.hip, which ran per voxel on the materialised (s A, y'): puts
 //                        the weighted MSE and R2 into the row.
 // The explicit fallback's chunk loop is mfx_solve_dense_chunks (mfx_host.h); the host side of a mixed batch is class_batch.h
@@ -28,44 +28,6 @@
 namespace {
 
 thread_local int g_force_explicit = 0;
-
-// One wave per voxel: the weights are tested over the whole voxel first (the result is uniform), then s, y' and sum W are
-// written.  A voxel with a failing direction is left alone (weight status 0: the direction is reported); a voxel with
-// unusable weights gets zeros in s and y' (nobody reads them), its code, and with params its NaN row.  ok (may be null):
-// 1 where the fit runs.
-__global__ __launch_bounds__(64) void w2d_prep_kernel(const double* __restrict__ Y, const double* __restrict__ W, int64_t wstride, int M,
-                                                      const int* __restrict__ vstat, double* __restrict__ S, double* __restrict__ Ys,
-                                                      double* __restrict__ sumw, int* __restrict__ wstat, int* __restrict__ ok,
-                                                      double* __restrict__ params, int np) {
-  const size_t v = blockIdx.x;
-  const int lane = threadIdx.x;
-  if (vstat[5 * v] != 0) {
-    if (lane == 0) { wstat[v] = 0; sumw[v] = 0.0; if (ok) ok[v] = 0; }
-    return;
-  }
-  const double* __restrict__ wv = W + v * wstride;
-  const double* __restrict__ yv = Y + v * M;
-  int bad = 0, pos = 0;
-  double sw = 0.0;
-  for (int m = lane; m < M; m += 64) {
-    const double w = wv[m];
-    bad |= !(w >= 0.0) || !(w <= 1.79769313486231570815e308);
-    pos |= w > 0.0;
-    sw += w;
-  }
-  bad = __any(bad);
-  pos = __any(pos);
-  sw = wave_sum(sw);
-  const int code = bad ? 1 : (pos ? 0 : 2);
-  for (int m = lane; m < M; m += 64) {
-    const double s = code == 0 ? sqrt(wv[m]) : 0.0;
-    S[v * M + m] = s;
-    Ys[v * M + m] = s * yv[m];
-  }
-  if (params && code != 0)
-    for (int q = lane; q < np; q += 64) params[v * np + q] = __builtin_nan("");
-  if (lane == 0) { wstat[v] = code; sumw[v] = sw; if (ok) ok[v] = code == 0; }
-}
 
 // The explicit solver packed the row for (s A, y'): MSE = min_obj / M and the unweighted R2 of the scaled signals.  One
 // wave per voxel puts the weighted figures in: MSE (M / sum W), and the weighted R2 of y and y_rec = D w + w_csf x_csf on

@@ -1924,6 +1924,137 @@ def fit2d_bootstrap(tables, Y, K, csf, peaks, maxfasc, csf_on, sig_csf=None, B=2
     return {'stats': stats, 'agree': agree, 'status': status, 'dir_status': dstat, 'replicates': reps, 'columns': cols}
 
 
+def fit2d_weighted_replicates_dev(tables, d_Ystar, d_W, d_peaks, maxfasc):
+    """The weighted replicate fit of a 2-D protocol on the device (mfx_wboot2d_fit_rows_dev, include/mfx_wboot2d.h) for a
+    mf_utils.RotateAtom2DTables and ONE voxel class (every voxel ``maxfasc`` fascicles, no CSF column): B signals per
+    voxel on the voxel's weights and directions.  torch CUDA float64 tensors d_Ystar [V, B, M], d_W [V, M] or [M],
+    d_peaks [V, 3 maxfasc] -> (params [V, B, num_params(maxfasc, False, False)], status [V, 5] int32 per voxel, wstatus
+    [V] int32 as ``fit2d_weighted_dev`` gives it for the voxel's weights).  Every row equals, bit for bit, the row
+    ``fit2d_weighted_dev`` returns for that signal with those weights and directions; for one and two fascicles sqrt(W),
+    the directions' records, the scaled dictionaries' column norms and their cross-Gram are formed once per voxel, not
+    once per row.  Enqueues on torch's current stream and returns without waiting."""
+    import torch
+    maxfasc = _boot2d_maxfasc(maxfasc)
+    _f64_cuda(d_Ystar, d_W, d_peaks if maxfasc > 0 else None)
+    if d_Ystar.dim() != 3 or d_Ystar.shape[1] < 1 or d_Ystar.shape[2] != tables.M:
+        raise ValueError("replicate signals should have shape (voxels, B >= 1, %d), got %s" % (tables.M, tuple(d_Ystar.shape)))
+    V, B, M = d_Ystar.shape
+    if maxfasc > 0 and (d_peaks is None or tuple(d_peaks.shape) != (V, 3 * maxfasc)):
+        raise ValueError("peaks should have shape (%d, %d)" % (V, 3 * maxfasc))
+    w_stride = _w_stride(M, V, d_W.shape)
+    dev = d_Ystar.device
+    out = torch.empty((V, B, num_params(maxfasc, False, False)), dtype=torch.float64, device=dev)
+    status = torch.empty((V, 5), dtype=torch.int32, device=dev)
+    wstatus = torch.empty((V,), dtype=torch.int32, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        L.check(L.lib().mfx_wboot2d_fit_rows_dev(tables.handle(), d_Ystar.data_ptr(), d_W.data_ptr(), w_stride,
+                                                 _tptr(d_peaks) if maxfasc > 0 else None, maxfasc, V, B, out.data_ptr(),
+                                                 status.data_ptr(), wstatus.data_ptr(), st))
+    return out, status, wstatus
+
+
+def fit2d_weighted_bootstrap_dev(tables, d_Y, d_W, d_peaks, maxfasc, csf_on=False, d_sig_csf=None, B=200, kind='wild', seed=0,
+                                 inflate=True, offset=0, q=(0.025, 0.975), d_props=None, d_groups=None, d_params=None,
+                                 d_pred=None, d_vox=None, max_bytes=BOOT_DEFAULT_BYTES, keep=False):
+    """Device-resident bootstrap of voxels of a 2-D protocol conditional on measurement weights (mfx_wboot2d_fit_dev) for
+    ONE voxel class (every voxel: K == maxfasc, csf == csf_on), arguments as ``fit2d_bootstrap_dev`` takes them plus the
+    weights d_W [V, M] or [M].  The weights are held fixed: the own weighted fit (``d_params``, fitted here if None) is
+    predicted, its residuals are resampled by the rule of ``wboot_resample_dev``, the replicates are fitted with the same
+    weights (``fit2d_weighted_replicates_dev``) and reduced.  Returns the dict of ``fit2d_bootstrap_dev`` (the MSE column is
+    the weighted MSE; status 2 for a failing direction, else as ``wboot_resample_dev``).  Enqueues on torch's current
+    stream and returns without waiting."""
+    import torch
+    B, code, qa = _boot_rule(B, kind, q, seed, offset)
+    maxfasc = _boot2d_maxfasc(maxfasc)
+    _f64_cuda(d_Y, d_W, d_peaks if maxfasc > 0 else None, d_sig_csf if csf_on else None, d_props, d_params, d_pred)
+    if d_Y.dim() != 2 or d_Y.shape[1] != tables.M:
+        raise ValueError("data should have shape (voxels, %d), got %s" % (tables.M, tuple(d_Y.shape)))
+    V, M = d_Y.shape
+    w_stride = _w_stride(M, V, d_W.shape)
+    npar = num_params(maxfasc, csf_on, False)
+    if maxfasc > 0 and (d_peaks is None or tuple(d_peaks.shape) != (V, 3 * maxfasc)):
+        raise ValueError("peaks should have shape (%d, %d)" % (V, 3 * maxfasc))
+    if csf_on and (d_sig_csf is None or d_sig_csf.numel() != M):
+        raise ValueError("csf_on needs sig_csf with %d entries" % M)
+    if d_params is not None and tuple(d_params.shape) != (V, npar):
+        raise ValueError("params should have shape (%d, %d), got %s" % (V, npar, tuple(d_params.shape)))
+    if d_pred is not None and (d_params is None or tuple(d_pred.shape) != (V, M)):
+        raise ValueError("a prediction needs the parameters it was made from and the data's shape (%d, %d)" % (V, M))
+    nprop = _boot2d_props_shape(tables, d_props.shape) if d_props is not None else 0
+    d_groups = _wboot_dev_opts(M, V, code, d_groups, d_vox)
+    dev = d_Y.device
+    cols = boot_columns(maxfasc, csf_on, False, nprop)
+    d_q = torch.from_numpy(qa).to(dev) if qa.size else None
+    stats = torch.empty((V, len(cols), BOOT_NSTAT + qa.size), dtype=torch.float64, device=dev)
+    agree = torch.zeros((V, maxfasc), dtype=torch.int32, device=dev)
+    status = torch.zeros((V,), dtype=torch.int32, device=dev)
+    dstat = torch.zeros((V, 5), dtype=torch.int32, device=dev)
+    reps = torch.empty((V, B, npar), dtype=torch.float64, device=dev) if keep else None
+    st = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        L.check(L.lib().mfx_wboot2d_fit_dev(tables.handle(), d_Y.data_ptr(), d_W.data_ptr(), w_stride,
+                                            _tptr(d_peaks) if maxfasc > 0 else None, maxfasc, int(bool(csf_on)),
+                                            _tptr(d_sig_csf) if csf_on else None, _tptr(d_params), _tptr(d_pred),
+                                            _tptr(d_groups) if code == 1 else None, _tptr(d_vox), V, B, code, int(bool(inflate)),
+                                            int(seed) & _U64, int(offset) & _U64, _tptr(d_props), nprop, _tptr(d_q), int(qa.size),
+                                            int(max_bytes), stats.data_ptr(), agree.data_ptr() if maxfasc > 0 else None,
+                                            status.data_ptr(), dstat.data_ptr(), _tptr(reps), st))
+    return {'stats': stats, 'agree': agree, 'status': status, 'dir_status': dstat, 'replicates': reps, 'columns': cols}
+
+
+def fit2d_weighted_bootstrap(tables, Y, W, K, csf, peaks, maxfasc, csf_on, sig_csf=None, B=200, kind='wild', seed=0, inflate=True,
+                             offset=0, q=(0.025, 0.975), props=None, groups=None, params=None, vox=None,
+                             max_bytes=BOOT_DEFAULT_BYTES, keep=False):
+    """Bootstrap of a mixed set of voxels of a 2-D protocol conditional on measurement weights, on NumPy arrays
+    (mfx_wboot2d_fit): arguments as ``fit2d_weighted`` takes them and the options of ``fit2d_bootstrap``; every voxel class
+    of ``fit2d_weighted`` is served (K in 0..maxfasc, CSF).  The weights W [V, M] or [M] - those of a weighted fit, or the
+    final weights of a robust fit - are held fixed in every replicate: nothing is rejected anew, so the result is
+    conditional on them.  ``params`` [V, num_params(maxfasc, csf_on, False)]: the voxels' own weighted fit (fitted here if
+    None).  Returns the dict of ``fit2d_bootstrap``; status 2 for a failing direction (its record in 'dir_status'), else
+    0 fine, 1 no degree of freedom among the rows of positive weight, 2 original row not usable, 3 a weight negative or
+    not finite, 4 no positive weight."""
+    B, code, qa = _boot_rule(B, kind, q, seed, offset)
+    maxfasc = _boot2d_maxfasc(maxfasc)
+    Y = L.f64c(Y)
+    W = L.f64c(W)
+    pk = L.f64c(peaks).reshape(Y.shape[0], -1) if (maxfasc > 0 and Y.ndim == 2) else np.zeros((Y.shape[0], 0))
+    V = _fit2d_shapes(tables, Y.shape, pk.shape, maxfasc)
+    M = tables.M
+    w_stride = _w_stride(M, V, W.shape)
+    csf_on = bool(csf_on)
+    K, cs, sc = _mixed_args(M, V, maxfasc, K, csf, csf_on, sig_csf, need_sig=True)
+    npar = num_params(maxfasc, csf_on, False)
+    p0 = None
+    if params is not None:
+        p0 = L.f64c(params)
+        if p0.shape != (V, npar):
+            raise ValueError("params should have shape (%d, %d), got %s" % (V, npar, p0.shape))
+    vx = None
+    if vox is not None:
+        vx = np.ascontiguousarray(np.asarray(vox).reshape(-1), dtype=np.int64)
+        if vx.shape != (V,):
+            raise ValueError("vox should have one entry per voxel")
+    pr, nprop = None, 0
+    if props is not None:
+        pr = np.atleast_2d(L.f64c(props))
+        nprop = _boot2d_props_shape(tables, pr.shape)
+    gr = _boot_groups_arg(code, groups, M, None)
+    cols = boot_columns(maxfasc, csf_on, False, nprop)
+    stats = np.zeros((V, len(cols), BOOT_NSTAT + qa.size))
+    agree = np.zeros((V, maxfasc), dtype=np.int32)
+    status = np.zeros(V, dtype=np.int32)
+    dstat = np.zeros((V, 5), dtype=np.int32)
+    reps = np.zeros((V, B, npar)) if keep else None
+    L.check(L.lib().mfx_wboot2d_fit(tables.handle(), L.dptr(Y), L.dptr(W), w_stride, L.iptr(K), L.opt(cs, L.bptr),
+                                    L.dptr(pk) if maxfasc > 0 else None, maxfasc, int(csf_on), L.opt(sc) if csf_on else None,
+                                    L.opt(p0), L.opt(gr, L.iptr), L.opt(vx, L.lptr), V, B, code, int(bool(inflate)),
+                                    int(seed) & _U64, int(offset) & _U64, L.opt(pr), nprop, L.dptr(qa) if qa.size else None,
+                                    int(qa.size), int(max_bytes), L.dptr(stats), L.iptr(agree) if maxfasc > 0 else None,
+                                    L.iptr(status), L.iptr(dstat), L.opt(reps)))
+    return {'stats': stats, 'agree': agree, 'status': status, 'dir_status': dstat, 'replicates': reps, 'columns': cols}
+
+
 def solve_batch_dev(solver, d_Y, out=None, recons=True, max_bytes=0):
     """The batched explicit-dictionary solver on the device (mfx_solve_batch_dev, include/mfx_solve.h) for a
     mf_utils.ExhaustiveSolver: torch CUDA float64 signals d_Y [V, M] (or one [M] vector) -> (w [V, Kp] float64, sub [V, Kp]

@@ -624,7 +624,8 @@ class RotateAtom2DTables:
         return _fit2d(self, data, peaks, numfasc, csf_mask, sig_csf, on_error, weights, robust)
 
     def bootstrap(self, data, peaks, numfasc, fit=None, csf_mask=None, sig_csf=None, on_error='raise', *, B=200, kind='wild',
-                  seed=0, inflate=True, q=(0.025, 0.975), props=None, voxels=None, keep=False, groups=None):
+                  seed=0, inflate=True, q=(0.025, 0.975), props=None, voxels=None, keep=False, groups=None, weights=None,
+                  fixed_weights=False):
         """Model-free uncertainty of every estimated parameter (``engine.fit2d_bootstrap``, include/mfx_boot2d.h; the rule is
         that of include/mfx_boot.h): the residuals of each voxel's own fit - ``fit``, a :class:`Fit2DResult` of these
         voxels, or a fit made here - are resampled into ``B`` replicate signals, every replicate is fitted as ``fit`` fits
@@ -640,10 +641,19 @@ class RotateAtom2DTables:
         ``voxels``: positions in this batch (default: all); the random stream is keyed by the batch position, so a subset
         gives the replicates the whole batch gives.  ``keep``: also return the replicate parameter rows.  A voxel with a
         failing direction: ``on_error='raise'`` raises the reference's exception for the lowest of them, ``'nan'`` keeps
-        its record in ``dir_status``, status 2 and NaN statistics.  A ``fit`` made with ``weights=`` or ``robust=`` raises
-        NotImplementedError.  Returns a :class:`Bootstrap2DResult`."""
+        its record in ``dir_status``, status 2 and NaN statistics.  A ``fit`` made with ``weights=`` or ``robust=`` is
+        served only with ``fixed_weights=True`` (without it: NotImplementedError): the bootstrap then holds the fit's final
+        measurement weights (``fit.weights``; without a ``fit``, ``weights=`` as for ``fit``, and the own weighted fit is
+        made here) fixed - every replicate is fitted by the weighted fit on those weights and the fit's own parameters are
+        the ones resampled around (``engine.fit2d_weighted_bootstrap``; include/mfx_wboot2d.h, the rule is that of
+        include/mfx_wboot.h).  No replicate re-runs the rejection, so after a robust fit the result is CONDITIONAL ON THE
+        ROWS THAT WERE REJECTED: it says how stable the estimate is given that choice of outliers, not how stable the
+        choice is.  Rows of weight 0 are left as measured, 'residual' draws among the rows of positive weight in units of
+        sqrt(weight), and ``inflate`` counts the rows of positive weight.  ``fit`` and ``weights=`` both given and
+        different, ``fixed_weights=True`` without either, and ``weights=`` without ``fixed_weights=True`` are ValueErrors.
+        Returns a :class:`Bootstrap2DResult`."""
         return _boot2d(self, data, peaks, numfasc, fit, csf_mask, sig_csf, on_error, B, kind, seed, inflate, q, props, voxels,
-                       keep, groups)
+                       keep, groups, weights=weights, fixed_weights=fixed_weights)
 
     def _predict_args(self, fit_or_params, peaks, sig_csf):
         """Argument checks of predict / residuals / simulate (before any device call): (params, peaks, maxfasc, csf_on, sig_csf)."""
@@ -876,9 +886,13 @@ class Bootstrap2DResult:
     usable (a non-finite measurement, a failing direction); ``dir_status`` [n, 5]: the failing directions' records of
     :class:`Fit2DResult`; ``stats`` [n, C, 5 + Q] with ``columns``, the table the members are cut from; ``replicates``
     [n, B, num_params] with ``keep=True``, else None; ``B``, ``seed``, ``q``, ``voxels`` (the batch positions the rows
-    stand for)."""
+    stand for).  ``weights``: the measurement weights [n, M] or [M] a ``fixed_weights=True`` bootstrap held fixed, else
+    None; ``status`` then also has 3 (a weight negative or not finite) and 4 (no positive weight), 1 counts the rows of
+    positive weight, and 'MSE' is the weighted MSE.  No replicate re-ran a rejection: after a robust fit the statistics are
+    conditional on the rows that were rejected."""
 
-    def __init__(self, res, prop_names, q, voxels, maxfasc, csf_on, B, seed):
+    def __init__(self, res, prop_names, q, voxels, maxfasc, csf_on, B, seed, weights=None):
+        self.weights = weights
         self.stats, self.columns, self.replicates = res['stats'], res['columns'], res['replicates']
         self.status, self.dir_status = res['status'], res['dir_status']
         self.B, self.seed, self.q, self.voxels = int(B), seed, np.asarray(q, dtype=np.float64), voxels
@@ -928,8 +942,12 @@ class Bootstrap2DResult:
 
 
 def _boot2d(T, data, peaks, numfasc, fit, csf_mask, sig_csf, on_error, B, kind, seed, inflate, q, props, voxels, keep, groups,
-            max_bytes=None):
+            max_bytes=None, weights=None, fixed_weights=False):
     """RotateAtom2DTables.bootstrap: every argument is checked before any device call."""
+    if not isinstance(fixed_weights, (bool, np.bool_)):
+        raise ValueError("fixed_weights should be True or False, got %r" % (fixed_weights,))
+    if weights is not None and not fixed_weights:
+        raise ValueError("weights= is served only with fixed_weights=True: the bootstrap holds them fixed in every replicate")
     B, code, qa = engine._boot_rule(B, kind, q, seed)
     data, peaks, numfasc, maxfasc = _soft2d_args(T, data, peaks, numfasc, on_error)
     if maxfasc > 3:
@@ -951,12 +969,23 @@ def _boot2d(T, data, peaks, numfasc, fit, csf_mask, sig_csf, on_error, B, kind, 
     if fit is not None:
         if not isinstance(fit, Fit2DResult):
             raise ValueError("fit should be the Fit2DResult of these voxels")
-        if fit.weights is not None or fit.robust_info is not None:
+        if (fit.weights is not None or fit.robust_info is not None) and not fixed_weights:
             raise NotImplementedError("bootstrap of a weighted or robust fit is not served")
         if fit.params.shape[0] != V or fit.maxfasc != maxfasc or fit.csf_on != csf_on:
             raise ValueError("fit should hold the same %d voxels in the layout of these arguments (maxfasc = %d, csf %s)"
                              % (V, maxfasc, csf_on))
         p0 = fit.params
+    W = None
+    if fixed_weights:
+        W = _w2d_weights(T, weights, V) if weights is not None else None
+        fw = fit.weights if fit is not None else None
+        if W is None:
+            W = None if fw is None else np.ascontiguousarray(fw, dtype=np.float64)   # (checked when the fit was made)
+        elif fit is not None and (fw is None or not np.array_equal(np.broadcast_to(fw, (V, T.M)), np.broadcast_to(W, (V, T.M)))):
+            raise ValueError("weights differ from those of fit (%d voxels): give one of them" % V)
+        if W is None:
+            raise ValueError("fixed_weights=True needs a fit made with weights= or robust=: %s"
+                             % ("this fit has no measurement weights" if fit is not None else "no fit and no weights= were given"))
     props = _soft2d_props(T, props)
     names = list(props)
     pr = np.stack([props[n] for n in names]) if names else None
@@ -967,6 +996,14 @@ def _boot2d(T, data, peaks, numfasc, fit, csf_mask, sig_csf, on_error, B, kind, 
     if vox.size and (vox.min() < 0 or vox.max() >= V):
         raise ValueError("voxels should be positions in the batch (0..%d)" % (V - 1))
     extra = {} if max_bytes is None else {'max_bytes': max_bytes}
+    if W is not None:
+        Wv = W if W.ndim == 1 else np.ascontiguousarray(W[vox])   # the shared [M] vector as it is, else the voxels' rows
+        res = engine.fit2d_weighted_bootstrap(T, data[vox], Wv, numfasc[vox], csf[vox] if csf_on else None, peaks[vox], maxfasc,
+                                              csf_on, sig_csf, B=B, kind=kind, seed=seed, inflate=inflate, q=qa, props=pr, groups=gr,
+                                              params=np.ascontiguousarray(p0[vox]) if p0 is not None else None, vox=vox, keep=keep,
+                                              **extra)
+        _soft2d_raise(T, res['dir_status'], on_error)
+        return Bootstrap2DResult(res, names, qa, vox, maxfasc, csf_on, B, seed, weights=Wv)
     res = engine.fit2d_bootstrap(T, data[vox], numfasc[vox], csf[vox] if csf_on else None, peaks[vox], maxfasc, csf_on, sig_csf,
                                  B=B, kind=kind, seed=seed, inflate=inflate, q=qa, props=pr, groups=gr,
                                  params=np.ascontiguousarray(p0[vox]) if p0 is not None else None, vox=vox, keep=keep, **extra)
