@@ -55,7 +55,8 @@ typedef struct mfx_plan mfx_plan;     /* device-resident per-protocol row plan  
 const char* mfx_last_error(void);
 int mfx_device_count(void);
 /* library/ABI version, bumped on any signature change or new entry point (3: mfx_fit_batch_volume, mfx_volume_rows, counters 8-10 of
- * mfx_debug_last_counter, mfx_debug_set_k3_cap, mfx_debug_set_force_generic, mfx_debug_set_k3_screen) */
+ * mfx_debug_last_counter, mfx_debug_set_k3_cap, mfx_debug_set_force_generic, mfx_debug_set_k3_screen; mfx_debug_seam, a host-side query, joined
+ * without a bump) */
 int mfx_abi_version(void);
 
 /* ---- tables: replaces the interpolator objects returned by
@@ -243,6 +244,18 @@ void mfx_debug_set_k2s_cap(int cap);
 /* Diagnostic: 2 forces the screening kernel's two-image schedule (a workgroup barrier per half-step) that otherwise
  * serves only the shapes whose LDS footprint leaves no room for a third chunk image; any other value: automatic. */
 void mfx_debug_set_k2s_images(int nb);
+/* Diagnostic: the items one piece holds at the most where the host code cuts a batch into pieces (a launch, an upload, a
+ * scratch block), by the very expression the host code uses -- tests size their batches from it, so that they go on
+ * crossing a seam when its threshold moves.  Host arithmetic only: no device call, usable without a GPU.  which:
+ *   1  mfx_rotate_dev: directions per launch              2  [N, N, 1] pipeline: voxels per screening + list-mode launch
+ *   3  two-fascicle + CSF/EAR kernel: voxels per launch   4  explicit fallback of a class launcher: 2^30 / per_vox, an
+ *                                                            upper bound (the budget is min(free / 4, 2^30) bytes)
+ *   5  mfx_wfit_batch: voxels per upload (M)              6  mfx_rfit_batch: voxels per upload (M)
+ *   7  mfx_solve_profile_dev / _post_dev: signals per launch
+ *   8  mfx_boot2d_rows_dev, shared-fit kernels: voxels per launch           10  the same of mfx_wboot2d_rows_dev
+ *   9  mfx_rfit2d_batch: voxels per upload (M) of a bin of per_vox = K fascicles
+ * M and per_vox are read only where named above; -1: unknown `which` or an argument out of range. */
+int64_t mfx_debug_seam(int which, int M, int64_t per_vox);
 
 #ifdef __cplusplus
 }

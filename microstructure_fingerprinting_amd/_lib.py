@@ -22,6 +22,7 @@ EXPORTS = [
     "mfx_plan_create_multishell", "mfx_plan_create_explicit", "mfx_plan_destroy", "mfx_plan_status",
     "mfx_rotate", "mfx_rotate_dev", "mfx_rotate_cols", "mfx_rotate_cols_dev", "mfx_fit_batch", "mfx_fit_batch_rows", "mfx_fit_batch_volume", "mfx_volume_rows", "mfx_thread_release", "mfx_fit_batch_dev",
     "mfx_solve_exhaustive", "mfx_monte_carlo_average", "mfx_monte_carlo_average_dev", "mfx_cleanup_2fascicles", "mfx_cleanup_2fascicles_dev", "mfx_last_kernel_ms", "mfx_set_profiling", "mfx_debug_set_stamps", "mfx_debug_last_fallback_count", "mfx_debug_last_guard_count", "mfx_debug_last_counter", "mfx_debug_set_k2_screen", "mfx_debug_set_k2_wide", "mfx_debug_set_k2x_screen", "mfx_debug_set_k2_maxc", "mfx_debug_set_k2x_maxc", "mfx_debug_set_k2s_cap", "mfx_debug_set_k2s_images", "mfx_debug_set_k3_cap", "mfx_debug_set_force_generic", "mfx_debug_set_k3_screen",
+    "mfx_debug_seam",
 ]
 
 # every symbol include/mfx_mcf.h declares (MCF signal synthesis; versioned on its own)
@@ -172,6 +173,8 @@ def lib():
     L.mfx_debug_set_k3_screen.restype = None
     L.mfx_debug_set_k2s_images.argtypes = [C.c_int]
     L.mfx_debug_set_k2s_images.restype = None
+    L.mfx_debug_seam.argtypes = [C.c_int, C.c_int, C.c_int64]
+    L.mfx_debug_seam.restype = C.c_int64
     L.mfx_mcf_abi_version.restype = C.c_int
     for fn in ("mfx_mcf_pgse", "mfx_mcf_dde"):
         getattr(L, fn).argtypes = [dp, dp, C.c_int, dp, C.c_int64, dp, dp, C.c_int64, dp, C.c_double, dp]

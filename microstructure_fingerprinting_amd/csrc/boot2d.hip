@@ -100,7 +100,7 @@ int b2_rows(const mfx_rot2d* h, const double* d_Ys, const double* d_peaks, const
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(boot2d_nan_rows_kernel, dim3(b2_grid(V * B * np)), dim3(256), 0, st, d_vstat, V, (int64_t)B * np, d_params);
     HIPCHK(hipGetLastError());
-    const int64_t Vc = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(V, 65535), budget / per_vox));
+    const int64_t Vc = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(V, MFX_B2_VOX_PER_LAUNCH), budget / per_vox));
     StreamMem sa2(st), say(st), sysq(st), sG(st);
     HIPCHK(sa2.alloc(sizeof(double) * (size_t)Vc * K * NP));
     HIPCHK(say.alloc(sizeof(double) * (size_t)Vc * B * K * NP));

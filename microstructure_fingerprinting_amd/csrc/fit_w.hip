@@ -237,7 +237,7 @@ extern "C" int mfx_wfit_batch(const void* pv, const double* Y, const double* W, 
   DevBuf<double> dxc, dWs;
   if (sig_csf) HIPCHK(dxc.upload(sig_csf, M));
   if (w_stride == 0) HIPCHK(dWs.upload(W, M));   // the shared vector is uploaded once
-  const size_t chunk = std::max<size_t>(1, ((size_t)256 << 20) / (sizeof(double) * 2 * (size_t)M));   // voxels per upload
+  const size_t chunk = mfx_wfit_upload_chunk(M);   // voxels per upload
   return mfx_class_walk(bins, chunk, [&](int k, int c, const int64_t* ix, size_t nv) -> int {
     DevBuf<double> dY, dW, dpk, dpr;
     DevBuf<int32_t> dst;

@@ -243,6 +243,22 @@ extern "C" void mfx_debug_set_k3_cap(int cap) { mfx_thread().k3_cap = cap > 0 ? 
 extern "C" void mfx_debug_set_force_generic(int enabled) { mfx_thread().force_generic = enabled ? 1 : 0; }
 extern "C" void mfx_debug_set_k3_screen(int enabled) { mfx_thread().k3_screen = enabled ? 1 : 0; }
 extern "C" void mfx_debug_set_k2s_images(int nb) { mfx_thread().k2s_nb = (nb == 2) ? 2 : 0; }
+// items per piece of a host seam, by the expressions the host code itself uses (mfx_host.h); host arithmetic only
+extern "C" int64_t mfx_debug_seam(int which, int M, int64_t per_vox) {
+  switch (which) {
+    case MFX_SEAM_ROTATE: return MFX_ROT_DIRS_PER_LAUNCH;
+    case MFX_SEAM_K2SX_BIG: return MFX_K2SX_VOX_PER_LAUNCH;
+    case MFX_SEAM_K2X_CHUNK: return MFX_K2X_VOX_PER_LAUNCH;
+    case MFX_SEAM_DENSE: return per_vox > 0 ? (int64_t)(MFX_DENSE_MAX_BYTES / (size_t)per_vox) : -1;
+    case MFX_SEAM_WFIT_UPLOAD: return M > 0 ? (int64_t)mfx_wfit_upload_chunk(M) : -1;
+    case MFX_SEAM_RFIT_UPLOAD: return M > 0 ? (int64_t)mfx_rfit_upload_chunk(M) : -1;
+    case MFX_SEAM_SOLVE_SOFT: return MFX_SS_SIGNALS_PER_LAUNCH;
+    case MFX_SEAM_BOOT2D: return MFX_B2_VOX_PER_LAUNCH;
+    case MFX_SEAM_RFIT2D_UPLOAD: return (M > 0 && per_vox >= 0 && per_vox <= 3) ? (int64_t)std::max<size_t>(1, mfx_rfit2d_upload_chunk(M, (int)per_vox)) : -1;
+    case MFX_SEAM_WBOOT2D: return MFX_WB2_VOX_PER_LAUNCH;
+  }
+  return -1;
+}
 extern "C" void mfx_debug_set_k2s_cap(int cap) {
   int c = 4;
   while (2 * c <= cap) c *= 2;   // a power of two
@@ -1489,8 +1505,8 @@ extern "C" int mfx_rotate_dev(const mfx_plan* p, const double* d_dirs, int64_t B
   if (B == 0) return MFX_OK;
   if (int rc = mfx_require_device(p->t->device)) return rc;
   const int M = p->d.M;
-  for (int64_t b0 = 0; b0 < B; b0 += 32768) {  // gridDim.y limit
-    const int nb = (int)std::min<int64_t>(32768, B - b0);
+  for (int64_t b0 = 0; b0 < B; b0 += MFX_ROT_DIRS_PER_LAUNCH) {  // gridDim.y limit
+    const int nb = (int)std::min<int64_t>(MFX_ROT_DIRS_PER_LAUNCH, B - b0);
     dim3 grid((M + MFX_ROT_ROWS - 1) / MFX_ROT_ROWS, nb);
     hipLaunchKernelGGL(mfx_rotate_kernel, grid, dim3(MFX_ROT_WG), 0, (hipStream_t)stream, p->t->d, p->d,
                        d_dirs + 3 * b0, normalise_dirs, d_out + (size_t)b0 * M * p->t->d.N, (long)M * p->t->d.N, (long)p->t->d.N);

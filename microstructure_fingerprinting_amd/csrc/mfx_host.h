@@ -10,6 +10,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -89,6 +90,38 @@ int mfx_require_device(int device);
     hipError_t e_ = (x);                                                                            \
     if (e_ != hipSuccess) return mfx_fail(MFX_ERR_HIP, "%s failed: %s", #x, hipGetErrorString(e_)); \
   } while (0)
+
+// ---- host seams: where an entry point cuts a batch into pieces, the items a piece holds at the most.  The host code
+// uses these very expressions and mfx_debug_seam (mfx_api.hip; `which` = the MFX_SEAM_* below) returns them, so that a
+// test can size its batch from the library's own figure and cross the seam whatever the figure becomes.
+enum {
+  MFX_SEAM_ROTATE = 1,        // mfx_rotate_dev: directions per launch (gridDim.y)
+  MFX_SEAM_K2SX_BIG = 2,      // launch_k2sx_pipeline: voxels per screening + list-mode launch
+  MFX_SEAM_K2X_CHUNK = 3,     // launch_k2x_t and the pipeline's hand-back pass: voxels per plain launch (slab)
+  MFX_SEAM_DENSE = 4,         // mfx_solve_dense_chunks: upper bound, voxels in the largest budget at per_vox bytes each
+  MFX_SEAM_WFIT_UPLOAD = 5,   // mfx_wfit_batch: voxels per upload
+  MFX_SEAM_RFIT_UPLOAD = 6,   // mfx_rfit_batch: voxels per upload
+  MFX_SEAM_SOLVE_SOFT = 7,    // ss_chunk: signals per launch (gridDim.y)
+  MFX_SEAM_BOOT2D = 8,        // b2_rows, shared-fit kernels: voxels per launch (gridDim.z)
+  MFX_SEAM_RFIT2D_UPLOAD = 9, // mfx_rfit2d_batch: voxels per upload of a K-fascicle bin (per_vox carries K)
+  MFX_SEAM_WBOOT2D = 10,      // wb2_rows, shared-fit kernels: voxels per launch (gridDim.z)
+};
+constexpr int MFX_ROT_DIRS_PER_LAUNCH = 32768;
+constexpr int MFX_K2SX_VOX_PER_LAUNCH = 32768;
+constexpr int MFX_K2X_VOX_PER_LAUNCH = 2048;
+constexpr size_t MFX_DENSE_MAX_BYTES = (size_t)1 << 30;
+constexpr size_t MFX_UPLOAD_BYTES = (size_t)256 << 20;   // the host entry points' byte budget per upload chunk
+constexpr int64_t MFX_SS_SIGNALS_PER_LAUNCH = 65535;
+constexpr int64_t MFX_B2_VOX_PER_LAUNCH = 65535;
+constexpr int64_t MFX_WB2_VOX_PER_LAUNCH = 65535;
+inline size_t mfx_wfit_upload_chunk(int M) { return std::max<size_t>(1, MFX_UPLOAD_BYTES / (sizeof(double) * 2 * (size_t)M)); }   // Y, W
+inline size_t mfx_rfit_upload_chunk(int M) { return std::max<size_t>(1, MFX_UPLOAD_BYTES / (sizeof(double) * 4 * (size_t)M)); }   // Y, W0, W, prediction
+// Y, W0, W, the prediction and the weighted fit's s and y' (8 M bytes each), the plan's records (28 K M) and the kernels'
+// records (F2Rec, 32 K M; robust2d.hip asserts the size)
+constexpr size_t MFX_F2REC_BYTES = 32;
+inline size_t mfx_rfit2d_upload_chunk(int M, int k) {
+  return MFX_UPLOAD_BYTES / ((size_t)M * (sizeof(double) * 6 + (size_t)k * (28 + MFX_F2REC_BYTES)));
+}
 
 // device allocation released on every exit path
 struct DevMem {
@@ -192,7 +225,7 @@ int mfx_solve_dense_chunks(int M, int K, int N, int has_csf, size_t per_vox, int
   size_t free_b = 0, total_b = 0, scratch_b = 0;
   HIPCHK(hipMemGetInfo(&free_b, &total_b));
   if (int rc = mfx_solve_dense_scratch_bytes(M, K, N, has_csf, &scratch_b)) return rc;
-  const size_t budget = std::min<size_t>(free_b / 4, (size_t)1 << 30);
+  const size_t budget = std::min<size_t>(free_b / 4, MFX_DENSE_MAX_BYTES);
   const int64_t nvc = std::max<int64_t>(1, std::min<int64_t>(V, (int64_t)(budget / per_vox)));
   StreamMem dA(st), dS(st);
   HIPCHK(dA.alloc(per_vox * nvc));

@@ -380,7 +380,7 @@ extern "C" int mfx_rfit_batch(const void* pv, const double* Y, const double* W0,
   if (sig_csf) HIPCHK(dxc.upload(sig_csf, M));
   if (W0 && w0_stride == 0) HIPCHK(dW0s.upload(W0, M));   // the shared vector is uploaded once
   HIPCHK(dnc.alloc_n((size_t)std::max(n_iter, 1)));
-  const size_t chunk = std::max<size_t>(1, ((size_t)256 << 20) / (sizeof(double) * 4 * (size_t)M));   // voxels per upload: Y, W0, W, prediction
+  const size_t chunk = mfx_rfit_upload_chunk(M);   // voxels per upload: Y, W0, W, prediction
   return mfx_class_walk(bins, chunk, [&](int k, int cf, const int64_t* ix, size_t nv) -> int {
     DevBuf<double> dY, dW0, dW, dpK, dpF, dpr, dsc;
     DevBuf<int32_t> dstt, dst;

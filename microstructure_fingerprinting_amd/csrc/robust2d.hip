@@ -169,9 +169,8 @@ extern "C" int mfx_rfit2d_batch(void* hv, const double* Y, const double* W0, int
   HIPCHK(dnc.alloc_n((size_t)std::max(n_iter, 1)));
   // voxels per upload from a byte budget: Y, W0, W, the prediction and the weighted fit's s and y' (8 M bytes each), the
   // plan's records (28 K M) and the kernels' records (32 K M)
-  const auto chunk_of = [M](int k) {
-    return ((size_t)256 << 20) / ((size_t)M * (sizeof(double) * 6 + (size_t)k * (28 + sizeof(F2Rec))));
-  };
+  static_assert(sizeof(F2Rec) == MFX_F2REC_BYTES, "mfx_rfit2d_upload_chunk counts 32 bytes per record");
+  const auto chunk_of = [M](int k) { return mfx_rfit2d_upload_chunk(M, k); };
   return mfx_class_walk(bins, chunk_of, [&](int k, int cf, const int64_t* ix, size_t nv) -> int {
     DevBuf<double> dY, dW0, dW, dpK, dpr, dsc;
     DevBuf<int32_t> dstt, dvs, dws;

@@ -481,7 +481,7 @@ int ss_head(const char* fn, const mfx_solve* h, int64_t V, bool ptrs, bool secon
 }
 int64_t ss_chunk(const mfx_solve* h, int what, int64_t V, int64_t max_bytes) {
   if (max_bytes <= 0) max_bytes = SB_DEFAULT_BYTES;
-  return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(V, 65535), max_bytes / ss_bytes_per_signal(h, what)));
+  return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(V, MFX_SS_SIGNALS_PER_LAUNCH), max_bytes / ss_bytes_per_signal(h, what)));
 }
 
 }  // namespace

@@ -44,7 +44,7 @@ static int launch_k2x_t(FitK2XArgs a, int nvox, hipStream_t st) {
   auto kern = mfx_fit_k2x_kernel<KSTEPS, BRACKET, NW, NBUF>;
   HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   // per-workgroup scratch slab: launch in chunks so the slab stays modest
-  const int chunk = 2048;
+  const int chunk = MFX_K2X_VOX_PER_LAUNCH;
   const size_t slab = (size_t)2 * a.T.ldn * (MFX_XS + 2 * (ntup + 1));   // doubles per workgroup: inner products + filter base values
   StreamMem ws(st), cnt(st);
   HIPCHK(ws.alloc(sizeof(double) * slab * std::min(chunk, nvox)));
@@ -83,7 +83,7 @@ static int launch_k2sx_pipeline(FitK2XArgs a, int nvox, hipStream_t st) {
   HIPCHK(hipFuncSetAttribute((const void*)kern_full, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   // the screening and list-mode launches take up to 32 768 voxels at a time (4 KB of list per voxel; the list-mode
   // kernel uses no slab), the plain kernel its usual 2 048 (256 KB of slab per workgroup)
-  const int chunk = 2048, big = 32768, cap = MFX_XLCAP;
+  const int chunk = MFX_K2X_VOX_PER_LAUNCH, big = MFX_K2SX_VOX_PER_LAUNCH, cap = MFX_XLCAP;
   const int nc = std::min(chunk, nvox), nb = std::min(big, nvox);
   const size_t slab = (size_t)2 * a.T.ldn * (MFX_XS + 2 * (ntup + 1));
   StreamMem ws(st), cnt(st), fbm(st), xlc(st), xln(st), xlm(st), aud(st);

@@ -116,7 +116,7 @@ int wb2_rows(const mfx_rot2d* h, const double* d_Ys, const double* d_W, int64_t 
     hipLaunchKernelGGL(fit2d_status_kernel, dim3(wb2_grid(V)), dim3(256), 0, st, dirs->pstat.as<int>(), K, V, d_vstat, (int*)nullptr,
                        (double*)nullptr, np);
     HIPCHK(hipGetLastError());
-    const int64_t Vc = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(V, 65535), budget / per_vox));
+    const int64_t Vc = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(V, MFX_WB2_VOX_PER_LAUNCH), budget / per_vox));
     StreamMem sS(st), ssw(st), sYs(st), sa2(st), say(st), sysq(st), sG(st);
     HIPCHK(sS.alloc(sizeof(double) * (size_t)Vc * M));
     HIPCHK(ssw.alloc(sizeof(double) * (size_t)Vc));

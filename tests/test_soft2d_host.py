@@ -50,7 +50,7 @@ def test_header_binding_and_library_are_in_step():
                                  ("mfx_wsoft.h", _lib.WSOFT_EXPORTS, (lib.mfx_wsoft_abi_version, 1))):
         assert _declared(header) == sorted(lst), header
         assert version[0]() == version[1], header
-    assert len(_lib.EXPORTS) == 41 and len(_lib.FIT2D_EXPORTS) == 5 and len(_lib.POST_EXPORTS) == 5 and len(_lib.PROFILE_EXPORTS) == 8
+    assert len(_lib.EXPORTS) == 42 and len(_lib.FIT2D_EXPORTS) == 5 and len(_lib.POST_EXPORTS) == 5 and len(_lib.PROFILE_EXPORTS) == 8
 
 
 def test_header_states_the_definitions():
