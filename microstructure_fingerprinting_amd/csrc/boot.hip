@@ -1,7 +1,8 @@
 // boot.hip -- the bootstrap (include/mfx_boot.h): replicate signals from the residuals of a voxel's own fit, the plain
 // fit on the replicates (mfx_fit_batch_dev, unchanged), and the B parameter rows of every voxel reduced to statistics.
 // The fit and the prediction are the entry points of mfx.h and mfx_predict.h; what is new here is three kernels and a
-// small table.  The host side of a mixed batch is class_batch.h.
+// small table.  The host side of a mixed batch is boot_shared.h's boot_run_mixed (binning and walking: class_batch.h; the
+// column maps, the gather and the scatter: boot_batch.h), shared with wboot.hip, boot2d.hip and wboot2d.hip.
 //
 // boot_group_table_kernel     kind 1, once per call: for every row m the place of its group's row list in `rows`
 //                        (start[m]: the number of rows of smaller groups), the group's size (cnt[m]) and the list
@@ -24,9 +25,8 @@
 //                        interpolation.  No sort, no atomics, one fixed result.
 // LDS of the reduction: 8 B + 24 Q bytes per wave, at most 64 KB per workgroup: 4 waves up to B = 2000 or so, 1 wave at
 // B = 4096 (32 KiB + the quantiles' 768 bytes).
-#include "mfx_host.h"
+#include "boot_shared.h"
 #include "sos_shared.h"
-#include "../../include/mfx_boot.h"
 #include "../../include/mfx_predict.h"
 
 #include <algorithm>
@@ -41,11 +41,6 @@ constexpr int BOOT_MAXF = 3;                      // mfx_fit_batch_dev's limit o
 constexpr int BOOT_MAX_ACT = BOOT_MAXF + 2;       // active weights of a row at the most
 constexpr size_t BOOT_LDS_MAX = 64 * 1024;
 constexpr double BOOT_DBL_MAX = 1.79769313486231570815e308;
-constexpr int64_t BOOT_DEFAULT_BYTES = (int64_t)256 << 20;
-
-inline int boot_np(int F, int c, int e) { return 1 + 2 * F + c + 2 * e + 2; }
-inline int boot_c0(int F, int c, int e) { return 2 + F + c + e; }
-inline int boot_ncol(int F, int c, int e, int nprop) { return boot_c0(F, c, e) + F * nprop; }
 
 __global__ __launch_bounds__(256) void boot_group_table_kernel(const int* __restrict__ groups, int M, int* __restrict__ start,
                                                               int* __restrict__ cnt, int* __restrict__ rows) {
@@ -405,53 +400,18 @@ int boot_launch_reduce(const double* d_X, const uint8_t* d_valid, int64_t V, int
 }
 
 // One class on device buffers (what mfx_boot_fit_dev does after its checks; mfx_boot_fit runs it per class chunk).
-struct BootClass {
-  const mfx_plan* p;
-  const double *Y, *peaks;
-  int F, csf_on, ear_on;
-  const double *sig_csf, *sig_ear;
-  int E;
-  const double *params0, *pred0;
-  const int32_t* groups;
-  const int64_t* vox;
-  int64_t V;
-  int B, kind, inflate;
-  uint64_t seed, offset;
-  const double* props;
-  int nprop;
-  const double* q;
-  int Q;
-  int64_t max_bytes;
-  double* stats;
-  int32_t *agree, *status;
-  double* keep;
-  hipStream_t st;
-};
-
-int boot_class_dev(const BootClass& r) {
+int boot_class_dev(const mfx_plan* p, const BootClass& r) {
   TablesDev T;
   PlanDev P;
   int device = 0;
-  mfx_plan_view(r.p, &T, &P, &device);
-  const int M = P.M, N = T.N, F = r.F;
-  const int np = boot_np(F, r.csf_on, r.ear_on), C = boot_ncol(F, r.csf_on, r.ear_on, r.nprop), B = r.B;
-  const int64_t budget = r.max_bytes > 0 ? r.max_bytes : BOOT_DEFAULT_BYTES;
-  const int64_t per_vox = (int64_t)B * M * (int64_t)sizeof(double);
-  int64_t Vc = std::max<int64_t>(1, std::min<int64_t>(r.V, budget / per_vox));
-  Vc = std::min<int64_t>(Vc, 0x7fffffff / B);   // the replicate rows of a chunk are one launch of the fit
+  mfx_plan_view(p, &T, &P, &device);
+  const int M = P.M, N = T.N, F = r.F, B = r.B;
   hipStream_t st = r.st;
-  StreamMem ys(st), pk(st), prm(st), X(st), vd(st), par0(st), pred(st), pst(st), tab(st);
-  HIPCHK(ys.alloc(sizeof(double) * (size_t)Vc * B * M));
+  BootChunkMem mem(r, M);
+  StreamMem pk(st), tab(st);
+  if (int rc = mem.alloc((int64_t)B * M * (int64_t)sizeof(double))) return rc;
+  const int64_t Vc = mem.Vc;
   if (F > 0) HIPCHK(pk.alloc(sizeof(double) * (size_t)Vc * B * 3 * F));
-  if (!r.keep) HIPCHK(prm.alloc(sizeof(double) * (size_t)Vc * B * np));
-  HIPCHK(X.alloc(sizeof(double) * (size_t)Vc * B * C));
-  HIPCHK(vd.alloc((size_t)Vc * B * C));
-  if (!r.params0) HIPCHK(par0.alloc(sizeof(double) * (size_t)Vc * np));
-  if (!r.pred0) {
-    HIPCHK(pred.alloc(sizeof(double) * (size_t)Vc * M));
-    HIPCHK(pst.alloc(2 * sizeof(int)));
-    HIPCHK(hipMemsetAsync(pst.p, 0, 2 * sizeof(int), st));   // a row the fit could not serve is flagged there and predicted as NaN: status 2
-  }
   if (r.kind == MFX_BOOT_RESIDUAL) {
     HIPCHK(tab.alloc(sizeof(int) * 3 * (size_t)M));
     if (int rc = boot_launch_table(r.groups, M, tab.as<int>(), st)) return rc;
@@ -464,27 +424,23 @@ int boot_class_dev(const BootClass& r) {
     const int64_t nv = std::min(Vc, r.V - v0);
     const double* y = r.Y + (size_t)v0 * M;
     const double* pks = F > 0 ? r.peaks + (size_t)v0 * 3 * F : nullptr;
-    const double* p0 = r.params0 ? r.params0 + (size_t)v0 * np : par0.as<double>();
+    const double* p0 = mem.p0(v0);
     if (!r.params0) {
-      HIPCHK(hipMemsetAsync(par0.p, 0, sizeof(double) * (size_t)nv * np, st));
-      if (int rc = mfx_fit_batch_dev(r.p, y, pks, F, r.csf_on, r.ear_on, r.sig_csf, r.sig_ear, r.E, nv, par0.as<double>(), st)) return rc;
+      HIPCHK(hipMemsetAsync(mem.par0.p, 0, sizeof(double) * (size_t)nv * mem.np, st));
+      if (int rc = mfx_fit_batch_dev(p, y, pks, F, r.csf_on, r.ear_on, r.sig_csf, r.sig_ear, r.E, nv, mem.par0.as<double>(), st)) return rc;
     }
-    const double* pr = r.pred0 ? r.pred0 + (size_t)v0 * M : pred.as<double>();
     if (!r.pred0)
-      if (int rc = mfx_predict_dev(r.p, p0, pks, F, r.csf_on, r.ear_on, r.sig_csf, r.sig_ear, r.E, nv, nullptr, nullptr, 0, 0, 0, 0,
-                                   pred.as<double>(), nullptr, pst.as<int32_t>(), st)) return rc;
-    double* rows = r.keep ? r.keep + (size_t)v0 * B * np : prm.as<double>();
+      if (int rc = mfx_predict_dev(p, p0, pks, F, r.csf_on, r.ear_on, r.sig_csf, r.sig_ear, r.E, nv, nullptr, nullptr, 0, 0, 0, 0,
+                                   mem.pred.as<double>(), nullptr, mem.pst.as<int32_t>(), st)) return rc;
+    double* rows = mem.rows(v0);
     // (zero rows for a voxel in a non-zero status: the fit never sees a NaN made here; the gather turns its rows into NaN)
-    if (int rc = boot_launch_resample(M, y, pr, p0, F, r.csf_on, r.ear_on, pks, tab.as<int>(), r.vox ? r.vox + v0 : nullptr, nv, B, r.kind,
-                                      r.inflate, r.seed, r.vox ? r.offset : r.offset + (uint64_t)v0 * (uint64_t)M, 0.0,
-                                      ys.as<double>(), pk.as<double>(), r.status + v0, st)) return rc;
-    HIPCHK(hipMemsetAsync(rows, 0, sizeof(double) * (size_t)nv * B * np, st));   // classes without a column keep zero rows (mf.py:387-388)
-    if (int rc = mfx_fit_batch_dev(r.p, ys.as<double>(), F > 0 ? pk.as<double>() : nullptr, F, r.csf_on, r.ear_on, r.sig_csf, r.sig_ear,
+    if (int rc = boot_launch_resample(M, y, mem.pr(v0), p0, F, r.csf_on, r.ear_on, pks, tab.as<int>(), r.vox ? r.vox + v0 : nullptr, nv, B,
+                                      r.kind, r.inflate, r.seed, r.vox ? r.offset : r.offset + (uint64_t)v0 * (uint64_t)M, 0.0,
+                                      mem.ys.as<double>(), pk.as<double>(), r.status + v0, st)) return rc;
+    HIPCHK(hipMemsetAsync(rows, 0, sizeof(double) * (size_t)nv * B * mem.np, st));   // classes without a column keep zero rows (mf.py:387-388)
+    if (int rc = mfx_fit_batch_dev(p, mem.ys.as<double>(), F > 0 ? pk.as<double>() : nullptr, F, r.csf_on, r.ear_on, r.sig_csf, r.sig_ear,
                                    r.E, nv * B, rows, st)) return rc;
-    if (int rc = boot_launch_gather(rows, p0, F, r.csf_on, r.ear_on, r.props, r.nprop, N, r.status + v0, nv, B, X.as<double>(),
-                                    vd.as<uint8_t>(), r.agree ? r.agree + (size_t)v0 * F : nullptr, st)) return rc;
-    if (int rc = boot_launch_reduce(X.as<double>(), vd.as<uint8_t>(), nv, B, C, r.q, r.Q,
-                                    r.stats + (size_t)v0 * C * (MFX_BOOT_NSTAT + r.Q), st)) return rc;
+    if (int rc = mem.gather_reduce(v0, nv, N)) return rc;
     if (marked) mfx_scratch_rewind(st, mark);
   }
   return MFX_OK;
@@ -572,9 +528,12 @@ extern "C" int mfx_boot_fit_dev(const mfx_plan* p, const double* d_Y, const doub
   int device = 0;
   mfx_plan_view(p, &T, &P, &device);
   if (int rc = mfx_require_device(device)) return rc;
-  const BootClass r{p, d_Y, d_peaks, maxfasc, csf_on, ear_on, d_sig_csf, d_sig_ear, E, d_params0, d_pred0, d_groups, d_vox, V, B, kind,
-                    inflate != 0, seed, offset, d_props, nprop, d_q, Q, max_bytes, d_stats, d_agree, d_status, d_keep, (hipStream_t)stream};
-  return boot_class_dev(r);
+  BootClass r{};
+  r.Y = d_Y; r.peaks = d_peaks; r.F = maxfasc; r.csf_on = csf_on; r.ear_on = ear_on; r.sig_csf = d_sig_csf; r.sig_ear = d_sig_ear; r.E = E;
+  r.params0 = d_params0; r.pred0 = d_pred0; r.groups = d_groups; r.vox = d_vox; r.V = V; r.B = B; r.kind = kind; r.inflate = inflate != 0;
+  r.seed = seed; r.offset = offset; r.props = d_props; r.nprop = nprop; r.q = d_q; r.Q = Q; r.max_bytes = max_bytes;
+  r.stats = d_stats; r.agree = d_agree; r.status = d_status; r.keep = d_keep; r.st = (hipStream_t)stream;
+  return boot_class_dev(p, r);
 }
 
 extern "C" int mfx_boot_fit(const mfx_plan* p, const double* Y, const int32_t* K, const uint8_t* csf, const uint8_t* ear,
@@ -594,114 +553,18 @@ extern "C" int mfx_boot_fit(const mfx_plan* p, const double* Y, const int32_t* K
   PlanDev P;
   int device = 0;
   mfx_plan_view(p, &T, &P, &device);
-  const int M = P.M, N = T.N, F = maxfasc;
-  const int npF = boot_np(F, csf_on, ear_on), CF = boot_ncol(F, csf_on, ear_on, nprop), NS = MFX_BOOT_NSTAT + Q;
-  // the classes (K, CSF flag) of the voxels without and with the EAR columns, each binned before any device call
+  const int F = maxfasc;
+  // K, then the EAR flag, then the CSF flag of every voxel; the first offending voxel is the one reported
   for (int64_t v = 0; v < V; ++v) {
     if (K[v] < 0 || K[v] > F) return mfx_fail(MFX_ERR_ARG, "%s: K[%lld] = %d outside 0..%d", fn, (long long)v, K[v], F);
     if (ear && ear[v] && !ear_on) return mfx_fail(MFX_ERR_ARG, "%s: voxels flagged EAR need ear_on and sig_ear", fn);
     if (csf && csf[v] && !csf_on) return mfx_fail(MFX_ERR_ARG, "%s: voxels flagged CSF need csf_on and sig_csf", fn);
   }
-  std::vector<int64_t> sub[2];
-  for (int64_t v = 0; v < V; ++v) sub[(ear && ear[v]) ? 1 : 0].push_back(v);
-  MfxClassBins bins[2];
-  for (int e = 0; e < 2; ++e) {
-    std::vector<int32_t> Ks(sub[e].size());
-    std::vector<uint8_t> cs(sub[e].size());
-    for (size_t i = 0; i < sub[e].size(); ++i) { Ks[i] = K[sub[e][i]]; cs[i] = csf ? csf[sub[e][i]] : 0; }
-    if (int rc = mfx_class_bins(fn, Ks.data(), cs.data(), F, csf_on && sig_csf, (int64_t)sub[e].size(), &bins[e])) return rc;
-    for (auto& b : bins[e]) for (auto& i : b) i = sub[e][(size_t)i];   // positions in the sub-list -> batch positions
-  }
-  if (V == 0) return MFX_OK;
-  if (int rc = mfx_require_device(device)) return rc;
-  DevBuf<double> dxc, dxe, dprops, dq;
-  DevBuf<int32_t> dgr;
-  if (csf_on) HIPCHK(dxc.upload(sig_csf, M));
-  if (ear_on) HIPCHK(dxe.upload(sig_ear, (size_t)M * E));
-  if (nprop > 0) HIPCHK(dprops.upload(props, (size_t)nprop * N));
-  if (Q > 0) HIPCHK(dq.upload(q, Q));
-  if (kind == MFX_BOOT_RESIDUAL) HIPCHK(dgr.upload(groups, M));
-  const double qnan = __builtin_nan("");
-  const int64_t budget = max_bytes > 0 ? max_bytes : BOOT_DEFAULT_BYTES;
-  // voxels per upload: what four device chunks of replicate signals hold, 65536 at the most
-  const size_t chunk = (size_t)std::max<int64_t>(1, std::min<int64_t>(65536, 4 * std::max<int64_t>(1, budget / ((int64_t)B * M * 8))));
-  for (int e = 0; e < 2; ++e) {
-    const int rc = mfx_class_walk(bins[e], chunk, [&](int k, int cf, const int64_t* ix, size_t nv) -> int {
-      const int npc = boot_np(k, cf, e), Cc = boot_ncol(k, cf, e, nprop);
-      // class layout <-> batch layout: parameter columns and statistic columns
-      std::vector<int> pmap(npc), cmap(Cc);
-      pmap[0] = 0;
-      for (int f = 0; f < k; ++f) { pmap[1 + f] = 1 + f; pmap[1 + k + f] = 1 + F + f; }
-      if (cf) pmap[1 + 2 * k] = 1 + 2 * F;
-      if (e) { pmap[1 + 2 * k + cf] = 1 + 2 * F + csf_on; pmap[2 + 2 * k + cf] = 2 + 2 * F + csf_on; }
-      pmap[npc - 2] = npF - 2; pmap[npc - 1] = npF - 1;
-      cmap[0] = 0;
-      for (int f = 0; f < k; ++f) cmap[1 + f] = 1 + f;
-      if (cf) cmap[1 + k] = 1 + F;
-      if (e) cmap[1 + k + cf] = 1 + F + csf_on;
-      cmap[1 + k + cf + e] = 1 + F + csf_on + ear_on;
-      for (int f = 0; f < k; ++f)
-        for (int t = 0; t < nprop; ++t) cmap[boot_c0(k, cf, e) + f * nprop + t] = boot_c0(F, csf_on, ear_on) + f * nprop + t;
-      DevBuf<double> dY, dpk, dp0, dst, dkeep;
-      DevBuf<int32_t> dag, dstat;
-      DevBuf<int64_t> dvox;
-      HIPCHK(dY.upload_rows(Y, ix, nv, M, M));
-      HIPCHK(mfx_upload_peaks(dpk, peaks, ix, nv, F, k));
-      if (params0) {
-        std::vector<double> rows(nv * npc);
-        for (size_t i = 0; i < nv; ++i)
-          for (int j = 0; j < npc; ++j) rows[i * npc + j] = params0[(size_t)ix[i] * npF + pmap[j]];
-        HIPCHK(dp0.upload(rows.data(), rows.size()));
-      }
-      {
-        std::vector<int64_t> vi(nv);
-        for (size_t i = 0; i < nv; ++i) vi[i] = vox ? vox[ix[i]] : ix[i];
-        HIPCHK(dvox.upload(vi.data(), nv));
-      }
-      HIPCHK(dst.alloc_n(nv * Cc * NS));
-      HIPCHK(dag.alloc_n(nv * (size_t)std::max(k, 1)));
-      HIPCHK(dstat.alloc_n(nv));
-      if (keep) HIPCHK(dkeep.alloc_n(nv * B * npc));
-      const BootClass r{p, dY.get(), k > 0 ? dpk.get() : nullptr, k, cf, e, cf ? dxc.get() : nullptr, e ? dxe.get() : nullptr, e ? E : 0,
-                        params0 ? dp0.get() : nullptr, nullptr, dgr.get(), dvox.get(), (int64_t)nv, B, kind, inflate != 0, seed, offset,
-                        dprops.get(), nprop, dq.get(), Q, budget, dst.get(), dag.get(), dstat.get(), keep ? dkeep.get() : nullptr, nullptr};
-      if (int rc2 = boot_class_dev(r)) return rc2;
-      HIPCHK(hipStreamSynchronize(nullptr));
-      std::vector<double> hs(dst.n), hk;
-      std::vector<int32_t> ha(dag.n), hst(nv);
-      HIPCHK(dst.download(hs.data()));
-      HIPCHK(dag.download(ha.data()));
-      HIPCHK(dstat.download(hst.data()));
-      if (keep) { hk.resize(dkeep.n); HIPCHK(dkeep.download(hk.data())); }
-      for (size_t i = 0; i < nv; ++i) {
-        const size_t v = (size_t)ix[i];
-        const bool ok = hst[i] == 0;
-        status[v] = hst[i];
-        // columns the class does not have: a weight that is 0 in every replicate, a property that is never valid
-        double* sv = stats + v * CF * NS;
-        for (int c = 0; c < CF; ++c) {
-          double* s = sv + (size_t)c * NS;
-          const bool weight = c < boot_c0(F, csf_on, ear_on);
-          if (weight && ok) {
-            s[0] = (double)B; s[1] = 0.0; s[2] = B > 1 ? 0.0 : qnan; s[3] = 0.0; s[4] = 0.0;
-            for (int t = 0; t < Q; ++t) s[MFX_BOOT_NSTAT + t] = 0.0;
-          } else {
-            s[0] = 0.0;
-            for (int t = 1; t < NS; ++t) s[t] = qnan;
-          }
-        }
-        for (int c = 0; c < Cc; ++c) std::memcpy(sv + (size_t)cmap[c] * NS, hs.data() + (i * Cc + c) * NS, sizeof(double) * NS);
-        for (int f = 0; f < F; ++f) agree[v * F + f] = f < k ? ha[i * k + f] : 0;
-        if (keep)
-          for (int b = 0; b < B; ++b) {
-            double* dst_row = keep + (v * B + b) * npF;
-            for (int j = 0; j < npF; ++j) dst_row[j] = ok ? 0.0 : qnan;
-            for (int j = 0; j < npc; ++j) dst_row[pmap[j]] = hk[(i * B + b) * npc + j];
-          }
-      }
-      return MFX_OK;
-    });
-    if (rc) return rc;
-  }
-  return MFX_OK;
+  BootBatch b{};
+  b.fn = fn; b.device = device; b.M = P.M; b.N = T.N; b.Y = Y; b.K = K; b.csf = csf; b.ear = ear; b.peaks = peaks;
+  b.F = F; b.csf_on = csf_on; b.ear_on = ear_on; b.sig_csf = sig_csf; b.sig_ear = sig_ear; b.E = E;
+  b.params0 = params0; b.groups = groups; b.vox = vox; b.V = V; b.B = B; b.kind = kind; b.inflate = inflate != 0;
+  b.seed = seed; b.offset = offset; b.props = props; b.nprop = nprop; b.q = q; b.Q = Q; b.max_bytes = max_bytes;
+  b.stats = stats; b.agree = agree; b.status = status; b.keep = keep;
+  return boot_run_mixed(b, [&](const BootClass& r) { return boot_class_dev(p, r); });
 }

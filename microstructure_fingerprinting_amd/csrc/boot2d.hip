@@ -10,8 +10,10 @@
 // mfx_boot2d_debug_set_force_plain(1), takes the plain path: the directions are copied to the replicate rows of a voxel
 // chunk and fit2d.hip's class launcher runs on them untouched (records of B rows per voxel: chunks keep records and plan
 // within the budget; the explicit solver behind it sizes its dictionaries' block itself, mfx_solve_dense_chunks).
-// The host side of a mixed batch is class_batch.h, as in boot.hip.
+// The host side of a mixed batch, the per-class arguments and the front and tail of the class loop are boot_shared.h's,
+// as in boot.hip.
 #include "boot2d_kernels.h"
+#include "boot_shared.h"
 #include "../../include/mfx_boot2d.h"
 #include "../../include/mfx_fit2d.h"
 
@@ -23,20 +25,8 @@ namespace {
 
 thread_local int g_force_plain = 0;
 
-constexpr int64_t B2_DEFAULT_BYTES = (int64_t)256 << 20;
 constexpr int B2_MAXF = 3;
 
-inline int b2_np(int F, int c) { return 1 + 2 * F + c + 2; }
-inline int b2_c0(int F, int c) { return 2 + F + c; }
-inline int b2_ncol(int F, int c, int nprop) { return b2_c0(F, c) + F * nprop; }
-
-// peaks [V x w] -> [V B x w]
-__global__ void boot2d_expand_kernel(const double* __restrict__ src, int64_t V, int B, int w, double* __restrict__ dst) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= V * B * w) return;
-  const int64_t row = i / w;
-  dst[i] = src[(row / B) * w + (i - row * w)];
-}
 // the voxel's record = the record of its first replicate row
 __global__ void boot2d_first_row_kernel(const int* __restrict__ rows, int64_t V, int B, int* __restrict__ vstat) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -78,7 +68,7 @@ int64_t b2_rows_bytes(const mfx_rot2d* h, int K, bool has_csf, int B) {
 int b2_rows(const mfx_rot2d* h, const double* d_Ys, const double* d_peaks, const F2Dirs* dirs, int K, const double* d_xc, int64_t V,
             int B, double* d_params, int32_t* d_vstat, int64_t budget, hipStream_t st) {
   const int M = h->d.M, N = h->d.N, NP = (N + 15) & ~15, has_csf = d_xc != nullptr;
-  const int np = b2_np(K, has_csf);
+  const int np = boot_np(K, has_csf, 0);
   if (int rc = f2_limits("mfx_boot2d", h, K, V)) return rc;
   if (V > 0x7fffffff / B) return mfx_fail(MFX_ERR_UNSUPPORTED, "mfx_boot2d: more than 2^31 replicate rows in one call");
   HIPCHK(hipMemsetAsync(d_params, 0, sizeof(double) * (size_t)V * B * np, st));
@@ -86,7 +76,7 @@ int b2_rows(const mfx_rot2d* h, const double* d_Ys, const double* d_peaks, const
     HIPCHK(hipMemsetAsync(d_vstat, 0, sizeof(int32_t) * 5 * (size_t)V, st));
     return MFX_OK;
   }
-  if (budget <= 0) budget = B2_DEFAULT_BYTES;
+  if (budget <= 0) budget = BOOT_DEFAULT_BYTES;
   const int64_t per_vox = std::max<int64_t>(1, b2_rows_bytes(h, K, has_csf, B));
 
   if (b2_shared_serves(h, K, has_csf)) {
@@ -153,7 +143,7 @@ int b2_rows(const mfx_rot2d* h, const double* d_Ys, const double* d_peaks, const
     {
       F2Dirs rows(st);
       if (K > 0) {
-        hipLaunchKernelGGL(boot2d_expand_kernel, dim3(b2_grid(nv * B * 3 * K)), dim3(256), 0, st, d_peaks + (size_t)v0 * 3 * K, nv, B, 3 * K,
+        hipLaunchKernelGGL(boot_expand_kernel, dim3(b2_grid(nv * B * 3 * K)), dim3(256), 0, st, d_peaks + (size_t)v0 * 3 * K, nv, B, 3 * K,
                            pk.as<double>());
         HIPCHK(hipGetLastError());
       }
@@ -187,50 +177,15 @@ int b2_check(const char* fn, const mfx_rot2d* h, int F, int csf_on, const void* 
 }
 
 // One class on device buffers (what mfx_boot2d_fit_dev does after its checks; mfx_boot2d_fit runs it per class chunk)
-struct B2Class {
-  const mfx_rot2d* h;
-  const double *Y, *peaks;
-  int F, csf_on;
-  const double* sig_csf;
-  const double *params0, *pred0;
-  const int32_t* groups;
-  const int64_t* vox;
-  int64_t V;
-  int B, kind, inflate;
-  uint64_t seed, offset;
-  const double* props;
-  int nprop;
-  const double* q;
-  int Q;
-  int64_t max_bytes;
-  double* stats;
-  int32_t *agree, *status, *dir_status;
-  double* keep;
-  hipStream_t st;
-};
-
-int b2_class_dev(const B2Class& r) {
-  const mfx_rot2d* h = r.h;
+int b2_class_dev(const mfx_rot2d* h, const BootClass& r) {
   const int M = h->d.M, N = h->d.N, F = r.F, B = r.B;
-  const int np = b2_np(F, r.csf_on), C = b2_ncol(F, r.csf_on, r.nprop);
   const double* xc = r.csf_on ? r.sig_csf : nullptr;
-  const int64_t budget = r.max_bytes > 0 ? r.max_bytes : B2_DEFAULT_BYTES;
-  const int64_t per_vox = (int64_t)B * M * (int64_t)sizeof(double) + b2_rows_bytes(h, F, r.csf_on != 0, B);
-  int64_t Vc = std::max<int64_t>(1, std::min<int64_t>(r.V, budget / per_vox));
-  Vc = std::min<int64_t>(Vc, 0x7fffffff / B);
   hipStream_t st = r.st;
-  StreamMem ys(st), prm(st), X(st), vd(st), par0(st), pred(st), pst(st), dst(st);
-  HIPCHK(ys.alloc(sizeof(double) * (size_t)Vc * B * M));
-  if (!r.keep) HIPCHK(prm.alloc(sizeof(double) * (size_t)Vc * B * np));
-  HIPCHK(X.alloc(sizeof(double) * (size_t)Vc * B * C));
-  HIPCHK(vd.alloc((size_t)Vc * B * C));
-  if (!r.params0) HIPCHK(par0.alloc(sizeof(double) * (size_t)Vc * np));
-  if (!r.pred0) {
-    HIPCHK(pred.alloc(sizeof(double) * (size_t)Vc * M));
-    HIPCHK(pst.alloc(2 * sizeof(int)));
-    HIPCHK(dst.alloc(sizeof(int) * 5 * (size_t)Vc));
-    HIPCHK(hipMemsetAsync(pst.p, 0, 2 * sizeof(int), st));   // a NaN parameter row is flagged there and predicted as NaN: status 2
-  }
+  BootChunkMem mem(r, M);
+  StreamMem dst(st);
+  if (int rc = mem.alloc((int64_t)B * M * (int64_t)sizeof(double) + b2_rows_bytes(h, F, r.csf_on != 0, B))) return rc;
+  const int64_t Vc = mem.Vc;
+  if (!r.pred0) HIPCHK(dst.alloc(sizeof(int) * 5 * (size_t)Vc));   // the prediction's own record of the directions
   ScratchMark mark;
   const bool marked = mfx_scratch_mark(st, &mark);
   for (int64_t v0 = 0; v0 < r.V; v0 += Vc) {
@@ -242,33 +197,29 @@ int b2_class_dev(const B2Class& r) {
       // the directions of the chunk, prepared once: the own fit, the prediction and the replicate fit read them
       F2Dirs dirs(st);
       if (int rc = dirs.enqueue(h, pks, nv * F, st)) return rc;
-      const double* p0 = r.params0 ? r.params0 + (size_t)v0 * np : par0.as<double>();
+      const double* p0 = mem.p0(v0);
       if (!r.params0)
-        if (int rc = mfx_fit2d_class_prepared(h, y, dirs.rec.p, dirs.pstat.as<int>(), F, xc, F, r.csf_on, nv, par0.as<double>(), vstat, st))
+        if (int rc = mfx_fit2d_class_prepared(h, y, dirs.rec.p, dirs.pstat.as<int>(), F, xc, F, r.csf_on, nv, mem.par0.as<double>(), vstat, st))
           return rc;
-      const double* pr = r.pred0 ? r.pred0 + (size_t)v0 * M : pred.as<double>();
       if (!r.pred0)
         if (int rc = mfx_predict2d_launch(h, dirs.rec.p, dirs.pstat.as<int>(), F, p0, F, r.csf_on, xc, nv, nullptr, nullptr, 0, 0, 0, 0,
-                                          pred.as<double>(), nullptr, pst.as<int32_t>(), dst.as<int32_t>(), st)) return rc;
-      double* rows = r.keep ? r.keep + (size_t)v0 * B * np : prm.as<double>();
-      if (int rc = mfx_boot_resample_dev(M, y, pr, p0, F, r.csf_on, 0, nullptr, r.groups, r.vox ? r.vox + v0 : nullptr, nv, B, r.kind,
-                                         r.inflate, r.seed, r.vox ? r.offset : r.offset + (uint64_t)v0 * (uint64_t)M, ys.as<double>(),
-                                         nullptr, r.status + v0, st)) return rc;
+                                          mem.pred.as<double>(), nullptr, mem.pst.as<int32_t>(), dst.as<int32_t>(), st)) return rc;
+      double* ys = mem.ys.as<double>();
+      if (int rc = mfx_boot_resample_dev(M, y, mem.pr(v0), p0, F, r.csf_on, 0, nullptr, r.groups, r.vox ? r.vox + v0 : nullptr, nv, B, r.kind,
+                                         r.inflate, r.seed, r.vox ? r.offset : r.offset + (uint64_t)v0 * (uint64_t)M, ys, nullptr,
+                                         r.status + v0, st)) return rc;
       // the voxels' records (the replicate fit writes them again, the same); then no NaN signal reaches a fit kernel
       if (F == 0 && !r.csf_on) {
         HIPCHK(hipMemsetAsync(vstat, 0, sizeof(int32_t) * 5 * (size_t)nv, st));
       } else {
         hipLaunchKernelGGL(fit2d_status_kernel, dim3(b2_grid(nv)), dim3(256), 0, st, dirs.pstat.as<int>(), F, nv, vstat, (int*)nullptr,
-                           (double*)nullptr, np);
+                           (double*)nullptr, mem.np);
         HIPCHK(hipGetLastError());
       }
-      hipLaunchKernelGGL(boot2d_mask_kernel, dim3((unsigned)nv), dim3(256), 0, st, r.status + v0, vstat, nv, (int64_t)B * M, ys.as<double>());
+      hipLaunchKernelGGL(boot2d_mask_kernel, dim3((unsigned)nv), dim3(256), 0, st, r.status + v0, vstat, nv, (int64_t)B * M, ys);
       HIPCHK(hipGetLastError());
-      if (int rc = b2_rows(h, ys.as<double>(), pks, &dirs, F, xc, nv, B, rows, vstat, budget, st)) return rc;
-      if (int rc = mfx_boot_gather_dev(rows, p0, F, r.csf_on, 0, r.props, r.nprop, N, r.status + v0, nv, B, X.as<double>(), vd.as<uint8_t>(),
-                                       r.agree ? r.agree + (size_t)v0 * F : nullptr, st)) return rc;
-      if (int rc = mfx_boot_reduce_dev(X.as<double>(), vd.as<uint8_t>(), nv, B, C, r.q, r.Q,
-                                       r.stats + (size_t)v0 * C * (MFX_BOOT_NSTAT + r.Q), st)) return rc;
+      if (int rc = b2_rows(h, ys, pks, &dirs, F, xc, nv, B, mem.rows(v0), vstat, mem.budget(), st)) return rc;
+      if (int rc = mem.gather_reduce(v0, nv, N)) return rc;
     }
     if (marked) mfx_scratch_rewind(st, mark);
   }
@@ -294,7 +245,7 @@ extern "C" int mfx_boot2d_fit_rows_dev(void* hv, const double* d_Ystar, const do
   if (maxfasc > B2_MAXF) return mfx_fail(MFX_ERR_UNSUPPORTED, "%s: at most 3 fascicles (got %d)", fn, maxfasc);
   if (V == 0) return MFX_OK;
   if (int rc = mfx_require_device(h->device)) return rc;
-  return b2_rows(h, d_Ystar, d_peaks, nullptr, maxfasc, nullptr, V, B, d_params, d_status, B2_DEFAULT_BYTES, (hipStream_t)stream);
+  return b2_rows(h, d_Ystar, d_peaks, nullptr, maxfasc, nullptr, V, B, d_params, d_status, BOOT_DEFAULT_BYTES, (hipStream_t)stream);
 }
 
 extern "C" int mfx_boot2d_fit_dev(void* hv, const double* d_Y, const double* d_peaks, int maxfasc, int csf_on, const double* d_sig_csf,
@@ -313,9 +264,12 @@ extern "C" int mfx_boot2d_fit_dev(void* hv, const double* d_Y, const double* d_p
   if (V == 0) return MFX_OK;
   if (int rc = f2_limits(fn, h, maxfasc, V)) return rc;
   if (int rc = mfx_require_device(h->device)) return rc;
-  const B2Class r{h, d_Y, d_peaks, maxfasc, csf_on, d_sig_csf, d_params0, d_pred0, d_groups, d_vox, V, B, kind, inflate != 0, seed, offset,
-                  d_props, nprop, d_q, Q, max_bytes, d_stats, d_agree, d_status, d_dir_status, d_keep, (hipStream_t)stream};
-  return b2_class_dev(r);
+  BootClass r{};
+  r.Y = d_Y; r.peaks = d_peaks; r.F = maxfasc; r.csf_on = csf_on; r.sig_csf = d_sig_csf; r.params0 = d_params0; r.pred0 = d_pred0;
+  r.groups = d_groups; r.vox = d_vox; r.V = V; r.B = B; r.kind = kind; r.inflate = inflate != 0; r.seed = seed; r.offset = offset;
+  r.props = d_props; r.nprop = nprop; r.q = d_q; r.Q = Q; r.max_bytes = max_bytes;
+  r.stats = d_stats; r.agree = d_agree; r.status = d_status; r.dir_status = d_dir_status; r.keep = d_keep; r.st = (hipStream_t)stream;
+  return b2_class_dev(h, r);
 }
 
 extern "C" int mfx_boot2d_fit(void* hv, const double* Y, const int32_t* K, const uint8_t* csf, const double* peaks, int maxfasc,
@@ -332,95 +286,10 @@ extern "C" int mfx_boot2d_fit(void* hv, const double* Y, const int32_t* K, const
     return mfx_fail(MFX_ERR_ARG, "%s: bad argument", fn);
   for (int i = 0; i < Q; ++i)
     if (!(q[i] >= 0.0 && q[i] <= 1.0)) return mfx_fail(MFX_ERR_ARG, "%s: q[%d] = %g outside [0, 1]", fn, i, q[i]);
-  const int M = h->d.M, N = h->d.N, F = maxfasc;
-  const int npF = b2_np(F, csf_on), CF = b2_ncol(F, csf_on, nprop), NS = MFX_BOOT_NSTAT + Q;
-  MfxClassBins bins;   // by class (K, CSF flag), before any device call
-  if (int rc = mfx_class_bins(fn, K, csf, F, csf_on && sig_csf, V, &bins)) return rc;
-  if (V == 0) return MFX_OK;
-  if (int rc = mfx_require_device(h->device)) return rc;
-  DevBuf<double> dxc, dprops, dq;
-  DevBuf<int32_t> dgr;
-  if (csf_on) HIPCHK(dxc.upload(sig_csf, M));
-  if (nprop > 0) HIPCHK(dprops.upload(props, (size_t)nprop * N));
-  if (Q > 0) HIPCHK(dq.upload(q, Q));
-  if (kind == MFX_BOOT_RESIDUAL) HIPCHK(dgr.upload(groups, M));
-  const double qnan = __builtin_nan("");
-  const int64_t budget = max_bytes > 0 ? max_bytes : B2_DEFAULT_BYTES;
-  // voxels per upload: what four device chunks of replicate signals hold, 65536 at the most
-  const size_t chunk = (size_t)std::max<int64_t>(1, std::min<int64_t>(65536, 4 * std::max<int64_t>(1, budget / ((int64_t)B * M * 8))));
-  return mfx_class_walk(bins, chunk, [&](int k, int cf, const int64_t* ix, size_t nv) -> int {
-    const int npc = b2_np(k, cf), Cc = b2_ncol(k, cf, nprop);
-    // class layout <-> batch layout: parameter columns and statistic columns
-    std::vector<int> pmap(npc), cmap(Cc);
-    pmap[0] = 0;
-    for (int f = 0; f < k; ++f) { pmap[1 + f] = 1 + f; pmap[1 + k + f] = 1 + F + f; }
-    if (cf) pmap[1 + 2 * k] = 1 + 2 * F;
-    pmap[npc - 2] = npF - 2; pmap[npc - 1] = npF - 1;
-    cmap[0] = 0;
-    for (int f = 0; f < k; ++f) cmap[1 + f] = 1 + f;
-    if (cf) cmap[1 + k] = 1 + F;
-    cmap[1 + k + cf] = 1 + F + csf_on;
-    for (int f = 0; f < k; ++f)
-      for (int t = 0; t < nprop; ++t) cmap[b2_c0(k, cf) + f * nprop + t] = b2_c0(F, csf_on) + f * nprop + t;
-    DevBuf<double> dY, dpk, dp0, dst, dkeep;
-    DevBuf<int32_t> dag, dstat, ddir;
-    DevBuf<int64_t> dvox;
-    HIPCHK(dY.upload_rows(Y, ix, nv, M, M));
-    HIPCHK(mfx_upload_peaks(dpk, peaks, ix, nv, F, k));
-    if (params0) {
-      std::vector<double> rows(nv * npc);
-      for (size_t i = 0; i < nv; ++i)
-        for (int j = 0; j < npc; ++j) rows[i * npc + j] = params0[(size_t)ix[i] * npF + pmap[j]];
-      HIPCHK(dp0.upload(rows.data(), rows.size()));
-    }
-    {
-      std::vector<int64_t> vi(nv);
-      for (size_t i = 0; i < nv; ++i) vi[i] = vox ? vox[ix[i]] : ix[i];
-      HIPCHK(dvox.upload(vi.data(), nv));
-    }
-    HIPCHK(dst.alloc_n(nv * Cc * NS));
-    HIPCHK(dag.alloc_n(nv * (size_t)std::max(k, 1)));
-    HIPCHK(dstat.alloc_n(nv));
-    HIPCHK(ddir.alloc_n(nv * 5));
-    if (keep) HIPCHK(dkeep.alloc_n(nv * B * npc));
-    const B2Class r{h, dY.get(), k > 0 ? dpk.get() : nullptr, k, cf, cf ? dxc.get() : nullptr, params0 ? dp0.get() : nullptr, nullptr,
-                    dgr.get(), dvox.get(), (int64_t)nv, B, kind, inflate != 0, seed, offset, dprops.get(), nprop, dq.get(), Q, budget,
-                    dst.get(), dag.get(), dstat.get(), ddir.get(), keep ? dkeep.get() : nullptr, nullptr};
-    if (int rc2 = b2_class_dev(r)) return rc2;
-    HIPCHK(hipStreamSynchronize(nullptr));
-    std::vector<double> hs(dst.n), hk;
-    std::vector<int32_t> ha(dag.n), hst(nv);
-    HIPCHK(dst.download(hs.data()));
-    HIPCHK(dag.download(ha.data()));
-    HIPCHK(dstat.download(hst.data()));
-    HIPCHK(ddir.download_rows(dir_status, ix, nv, 5));
-    if (keep) { hk.resize(dkeep.n); HIPCHK(dkeep.download(hk.data())); }
-    for (size_t i = 0; i < nv; ++i) {
-      const size_t v = (size_t)ix[i];
-      const bool ok = hst[i] == 0;
-      status[v] = hst[i];
-      // columns the class does not have: a weight that is 0 in every replicate, a property that is never valid
-      double* sv = stats + v * CF * NS;
-      for (int c = 0; c < CF; ++c) {
-        double* s = sv + (size_t)c * NS;
-        const bool weight = c < b2_c0(F, csf_on);
-        if (weight && ok) {
-          s[0] = (double)B; s[1] = 0.0; s[2] = B > 1 ? 0.0 : qnan; s[3] = 0.0; s[4] = 0.0;
-          for (int t = 0; t < Q; ++t) s[MFX_BOOT_NSTAT + t] = 0.0;
-        } else {
-          s[0] = 0.0;
-          for (int t = 1; t < NS; ++t) s[t] = qnan;
-        }
-      }
-      for (int c = 0; c < Cc; ++c) std::memcpy(sv + (size_t)cmap[c] * NS, hs.data() + (i * Cc + c) * NS, sizeof(double) * NS);
-      for (int f = 0; f < F; ++f) agree[v * F + f] = f < k ? ha[i * k + f] : 0;
-      if (keep)
-        for (int b = 0; b < B; ++b) {
-          double* dst_row = keep + (v * B + b) * npF;
-          for (int j = 0; j < npF; ++j) dst_row[j] = ok ? 0.0 : qnan;
-          for (int j = 0; j < npc; ++j) dst_row[pmap[j]] = hk[(i * B + b) * npc + j];
-        }
-    }
-    return MFX_OK;
-  });
+  BootBatch b{};
+  b.fn = fn; b.device = h->device; b.M = h->d.M; b.N = h->d.N; b.Y = Y; b.K = K; b.csf = csf; b.peaks = peaks;
+  b.F = maxfasc; b.csf_on = csf_on; b.sig_csf = sig_csf; b.params0 = params0; b.groups = groups; b.vox = vox; b.V = V;
+  b.B = B; b.kind = kind; b.inflate = inflate != 0; b.seed = seed; b.offset = offset; b.props = props; b.nprop = nprop;
+  b.q = q; b.Q = Q; b.max_bytes = max_bytes; b.stats = stats; b.agree = agree; b.status = status; b.dir_status = dir_status; b.keep = keep;
+  return boot_run_mixed(b, [&](const BootClass& r) { return b2_class_dev(h, r); });
 }

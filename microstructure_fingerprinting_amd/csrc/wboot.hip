@@ -1,7 +1,7 @@
 // wboot.hip -- the bootstrap conditional on a fit's measurement weights (include/mfx_wboot.h): the own weighted fit
 // (fit_w.hip's class launcher), its prediction (mfx_predict_dev), the resampling rule of mfx_wboot.h, the REPLICATE
 // WEIGHTED FIT, and the value table and statistics of boot.hip through their public entry points.  The host side of a
-// mixed batch is class_batch.h, as in boot.hip and boot2d.hip.
+// mixed batch, the per-class arguments and the front and tail of the class loop are boot_shared.h's, as in boot.hip.
 //
 // wboot_table_kernel     kind 1, once per weight row (one workgroup per voxel, or one for a shared vector): boot.hip's
 //                        group table over the rows with W > 0 only - for every such row m the place of its group's list
@@ -15,6 +15,7 @@
 // class, and everything under mfx_wboot_debug_set_force_plain(1): weight rows and directions copied to the replicate
 // rows of a voxel chunk (a shared vector stays shared), fit_w.hip's class launcher on them untouched.
 #include "wfit_kernels.h"
+#include "boot_shared.h"
 #include "sos_shared.h"
 #include "../../include/mfx_wboot.h"
 #include "../../include/mfx_predict.h"
@@ -32,11 +33,7 @@ constexpr int WB_R = 1;                  // replicates per workgroup of the shar
 constexpr int WB_MAX_ROWS = 8192;
 constexpr int WB_MAXF = 3;
 constexpr double WB_DBL_MAX = 1.79769313486231570815e308;
-constexpr int64_t WB_DEFAULT_BYTES = (int64_t)256 << 20;
 
-inline int wb_np(int F, int c) { return 1 + 2 * F + c + 2; }
-inline int wb_c0(int F, int c) { return 2 + F + c; }
-inline int wb_ncol(int F, int c, int nprop) { return wb_c0(F, c) + F * nprop; }
 unsigned wb_grid(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 // per weight row: start, cnt, rows [M] ints each (3 M ints a row), over the rows with W > 0
@@ -162,13 +159,6 @@ __global__ __launch_bounds__(256) void mfx_wboot_resample_kernel(WBootRsArgs a) 
   }
 }
 
-// rows [V x w] -> [V B x w]
-__global__ void wboot_expand_kernel(const double* __restrict__ src, int64_t V, int B, int w, double* __restrict__ dst) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= V * B * w) return;
-  const int64_t row = i / w;
-  dst[i] = src[(row / B) * w + (i - row * w)];
-}
 // the voxel's status = that of its first replicate row
 __global__ void wboot_first_row_kernel(const int* __restrict__ rows, int64_t V, int B, int* __restrict__ vstat) {
   const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -226,7 +216,7 @@ int wb_launch_resample(int M, const double* d_Y, const double* d_P, const double
   a.Y = d_Y; a.P = d_P; a.W = d_W; a.wstride = wstride; a.params = d_params; a.peaks = d_peaks; a.tab = d_tab; a.vox = d_vox;
   a.Ys = d_Ystar; a.pk_out = (d_peaks && F > 0) ? d_peaks_out : nullptr; a.status = d_status;
   a.V = V; a.seed = seed; a.offset = offset; a.fill = fill;
-  a.M = M; a.B = B; a.np = wb_np(F, csf_on); a.F = F; a.csf_on = csf_on; a.inflate = inflate;
+  a.M = M; a.B = B; a.np = boot_np(F, csf_on, 0); a.F = F; a.csf_on = csf_on; a.inflate = inflate;
   const unsigned grid = (unsigned)((V * B + 3) / 4);
   if (kind == MFX_BOOT_WILD) hipLaunchKernelGGL(mfx_wboot_resample_kernel<MFX_BOOT_WILD>, dim3(grid), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(mfx_wboot_resample_kernel<MFX_BOOT_RESIDUAL>, dim3(grid), dim3(256), 0, st, a);
@@ -259,9 +249,9 @@ int wb_rows(const mfx_plan* p, const double* d_Ys, const double* d_W, int64_t ws
   mfx_plan_view(p, &a.T, &a.P, &device);
   const int M = a.P.M, has_csf = d_xc != nullptr;
   const bool br = a.P.any_bracket != 0;
-  const int np = wb_np(K, has_csf);
+  const int np = boot_np(K, has_csf, 0);
   if (V > 0x7fffffff / B) return mfx_fail(MFX_ERR_UNSUPPORTED, "mfx_wboot: more than 2^31 replicate rows in one call");
-  if (budget <= 0) budget = WB_DEFAULT_BYTES;
+  if (budget <= 0) budget = BOOT_DEFAULT_BYTES;
   const int64_t per_vox = std::max<int64_t>(1, wb_rows_bytes(a, K, has_csf, wstride, B));
 
   if (wb_shared_serves(a, K, has_csf)) {
@@ -312,12 +302,12 @@ int wb_rows(const mfx_plan* p, const double* d_Ys, const double* d_W, int64_t ws
   for (int64_t v0 = 0; v0 < V; v0 += Vc) {
     const int64_t nv = std::min(Vc, V - v0);
     if (K > 0) {
-      hipLaunchKernelGGL(wboot_expand_kernel, dim3(wb_grid(nv * B * 3 * K)), dim3(256), 0, st, d_peaks + (size_t)v0 * 3 * K, nv, B, 3 * K,
+      hipLaunchKernelGGL(boot_expand_kernel, dim3(wb_grid(nv * B * 3 * K)), dim3(256), 0, st, d_peaks + (size_t)v0 * 3 * K, nv, B, 3 * K,
                          pk.as<double>());
       HIPCHK(hipGetLastError());
     }
     if (wstride) {
-      hipLaunchKernelGGL(wboot_expand_kernel, dim3(wb_grid(nv * B * M)), dim3(256), 0, st, d_W + (size_t)v0 * M, nv, B, M, wr.as<double>());
+      hipLaunchKernelGGL(boot_expand_kernel, dim3(wb_grid(nv * B * M)), dim3(256), 0, st, d_W + (size_t)v0 * M, nv, B, M, wr.as<double>());
       HIPCHK(hipGetLastError());
     }
     if (int rc = mfx_wfit_class_dev(p, d_Ys + (size_t)v0 * B * M, wstride ? wr.as<double>() : d_W, wstride, pk.as<double>(), K, d_xc, K,
@@ -330,54 +320,18 @@ int wb_rows(const mfx_plan* p, const double* d_Ys, const double* d_W, int64_t ws
 }
 
 // One class on device buffers (what mfx_wboot_fit_dev does after its checks; mfx_wboot_fit runs it per class chunk)
-struct WBClass {
-  const mfx_plan* p;
-  const double *Y, *W;
-  int64_t wstride;
-  const double* peaks;
-  int F, csf_on;
-  const double* sig_csf;
-  const double *params0, *pred0;
-  const int32_t* groups;
-  const int64_t* vox;
-  int64_t V;
-  int B, kind, inflate;
-  uint64_t seed, offset;
-  const double* props;
-  int nprop;
-  const double* q;
-  int Q;
-  int64_t max_bytes;
-  double* stats;
-  int32_t *agree, *status;
-  double* keep;
-  hipStream_t st;
-};
-
-int wb_class_dev(const WBClass& r) {
+int wb_class_dev(const mfx_plan* p, const BootClass& r) {
   WArgs wa{};
   int device = 0;
-  mfx_plan_view(r.p, &wa.T, &wa.P, &device);
+  mfx_plan_view(p, &wa.T, &wa.P, &device);
   const int M = wa.P.M, N = wa.T.N, F = r.F, B = r.B;
-  const int np = wb_np(F, r.csf_on), C = wb_ncol(F, r.csf_on, r.nprop);
   const double* xc = r.csf_on ? r.sig_csf : nullptr;
-  const int64_t budget = r.max_bytes > 0 ? r.max_bytes : WB_DEFAULT_BYTES;
-  const int64_t per_vox = (int64_t)B * M * (int64_t)sizeof(double) + wb_rows_bytes(wa, F, r.csf_on != 0, r.wstride, B);
-  int64_t Vc = std::max<int64_t>(1, std::min<int64_t>(r.V, budget / per_vox));
-  Vc = std::min<int64_t>(Vc, 0x7fffffff / B);
   hipStream_t st = r.st;
-  StreamMem ys(st), prm(st), X(st), vd(st), par0(st), pred(st), pst(st), wst(st), tab(st);
-  HIPCHK(ys.alloc(sizeof(double) * (size_t)Vc * B * M));
-  if (!r.keep) HIPCHK(prm.alloc(sizeof(double) * (size_t)Vc * B * np));
-  HIPCHK(X.alloc(sizeof(double) * (size_t)Vc * B * C));
-  HIPCHK(vd.alloc((size_t)Vc * B * C));
-  if (!r.params0) HIPCHK(par0.alloc(sizeof(double) * (size_t)Vc * np));
+  BootChunkMem mem(r, M);
+  StreamMem wst(st), tab(st);
+  if (int rc = mem.alloc((int64_t)B * M * (int64_t)sizeof(double) + wb_rows_bytes(wa, F, r.csf_on != 0, r.wstride, B))) return rc;
+  const int64_t Vc = mem.Vc;
   HIPCHK(wst.alloc(sizeof(int) * (size_t)Vc));   // mfx_wfit.h's status of the weights (the bootstrap's own says more)
-  if (!r.pred0) {
-    HIPCHK(pred.alloc(sizeof(double) * (size_t)Vc * M));
-    HIPCHK(pst.alloc(2 * sizeof(int)));
-    HIPCHK(hipMemsetAsync(pst.p, 0, 2 * sizeof(int), st));   // a NaN parameter row is flagged there and predicted as NaN
-  }
   if (r.kind == MFX_BOOT_RESIDUAL) HIPCHK(tab.alloc(wb_tab_bytes(r.kind, M, r.wstride, Vc)));
   ScratchMark mark;
   const bool marked = mfx_scratch_mark(st, &mark);
@@ -386,23 +340,20 @@ int wb_class_dev(const WBClass& r) {
     const double* y = r.Y + (size_t)v0 * M;
     const double* w = r.W + (size_t)v0 * r.wstride;
     const double* pks = F > 0 ? r.peaks + (size_t)v0 * 3 * F : nullptr;
-    const double* p0 = r.params0 ? r.params0 + (size_t)v0 * np : par0.as<double>();
+    const double* p0 = mem.p0(v0);
     if (!r.params0)
-      if (int rc = mfx_wfit_class_dev(r.p, y, w, r.wstride, pks, F, xc, F, r.csf_on, nv, par0.as<double>(), wst.as<int32_t>(), st)) return rc;
-    const double* pr = r.pred0 ? r.pred0 + (size_t)v0 * M : pred.as<double>();
+      if (int rc = mfx_wfit_class_dev(p, y, w, r.wstride, pks, F, xc, F, r.csf_on, nv, mem.par0.as<double>(), wst.as<int32_t>(), st)) return rc;
     if (!r.pred0)
-      if (int rc = mfx_predict_dev(r.p, p0, pks, F, r.csf_on, 0, xc, nullptr, 0, nv, nullptr, nullptr, 0, 0, 0, 0, pred.as<double>(), nullptr,
-                                   pst.as<int32_t>(), st)) return rc;
-    double* rows = r.keep ? r.keep + (size_t)v0 * B * np : prm.as<double>();
+      if (int rc = mfx_predict_dev(p, p0, pks, F, r.csf_on, 0, xc, nullptr, 0, nv, nullptr, nullptr, 0, 0, 0, 0, mem.pred.as<double>(),
+                                   nullptr, mem.pst.as<int32_t>(), st)) return rc;
     // (zero rows for a voxel in a non-zero status: the fit never sees a NaN made here; the gather turns its rows into NaN)
-    if (int rc = wb_launch_resample(M, y, pr, w, r.wstride, p0, F, r.csf_on, nullptr, r.groups, tab.as<int>(), r.vox ? r.vox + v0 : nullptr,
-                                    nv, B, r.kind, r.inflate, r.seed, r.vox ? r.offset : r.offset + (uint64_t)v0 * (uint64_t)M, 0.0,
-                                    ys.as<double>(), nullptr, r.status + v0, st)) return rc;
-    if (int rc = wb_rows(r.p, ys.as<double>(), w, r.wstride, pks, F, xc, nv, B, rows, wst.as<int32_t>(), budget, st)) return rc;
-    if (int rc = mfx_boot_gather_dev(rows, p0, F, r.csf_on, 0, r.props, r.nprop, N, r.status + v0, nv, B, X.as<double>(), vd.as<uint8_t>(),
-                                     r.agree ? r.agree + (size_t)v0 * F : nullptr, st)) return rc;
-    if (int rc = mfx_boot_reduce_dev(X.as<double>(), vd.as<uint8_t>(), nv, B, C, r.q, r.Q,
-                                     r.stats + (size_t)v0 * C * (MFX_BOOT_NSTAT + r.Q), st)) return rc;
+    if (int rc = wb_launch_resample(M, y, mem.pr(v0), w, r.wstride, p0, F, r.csf_on, nullptr, r.groups, tab.as<int>(),
+                                    r.vox ? r.vox + v0 : nullptr, nv, B, r.kind, r.inflate, r.seed,
+                                    r.vox ? r.offset : r.offset + (uint64_t)v0 * (uint64_t)M, 0.0, mem.ys.as<double>(), nullptr,
+                                    r.status + v0, st)) return rc;
+    if (int rc = wb_rows(p, mem.ys.as<double>(), w, r.wstride, pks, F, xc, nv, B, mem.rows(v0), wst.as<int32_t>(), mem.budget(), st))
+      return rc;
+    if (int rc = mem.gather_reduce(v0, nv, N)) return rc;
     if (marked) mfx_scratch_rewind(st, mark);
   }
   return MFX_OK;
@@ -453,7 +404,7 @@ extern "C" int mfx_wboot_fit_rows_dev(const void* pv, const double* d_Ystar, con
     return mfx_fail(MFX_ERR_ARG, "%s: w_stride should be M = %d or 0 (got %lld)", fn, P.M, (long long)w_stride);
   if (V == 0) return MFX_OK;
   if (int rc = mfx_require_device(device)) return rc;
-  return wb_rows(p, d_Ystar, d_W, w_stride, d_peaks, maxfasc, nullptr, V, B, d_params, d_status, WB_DEFAULT_BYTES, (hipStream_t)stream);
+  return wb_rows(p, d_Ystar, d_W, w_stride, d_peaks, maxfasc, nullptr, V, B, d_params, d_status, BOOT_DEFAULT_BYTES, (hipStream_t)stream);
 }
 
 extern "C" int mfx_wboot_fit_dev(const void* pv, const double* d_Y, const double* d_W, int64_t w_stride, const double* d_peaks, int maxfasc,
@@ -475,9 +426,12 @@ extern "C" int mfx_wboot_fit_dev(const void* pv, const double* d_Y, const double
   int device = 0;
   mfx_plan_view(p, &T, &P, &device);
   if (int rc = mfx_require_device(device)) return rc;
-  const WBClass r{p, d_Y, d_W, w_stride, d_peaks, maxfasc, csf_on, d_sig_csf, d_params0, d_pred0, d_groups, d_vox, V, B, kind, inflate != 0,
-                  seed, offset, d_props, nprop, d_q, Q, max_bytes, d_stats, d_agree, d_status, d_keep, (hipStream_t)stream};
-  return wb_class_dev(r);
+  BootClass r{};
+  r.Y = d_Y; r.W = d_W; r.wstride = w_stride; r.peaks = d_peaks; r.F = maxfasc; r.csf_on = csf_on; r.sig_csf = d_sig_csf;
+  r.params0 = d_params0; r.pred0 = d_pred0; r.groups = d_groups; r.vox = d_vox; r.V = V; r.B = B; r.kind = kind; r.inflate = inflate != 0;
+  r.seed = seed; r.offset = offset; r.props = d_props; r.nprop = nprop; r.q = d_q; r.Q = Q; r.max_bytes = max_bytes;
+  r.stats = d_stats; r.agree = d_agree; r.status = d_status; r.keep = d_keep; r.st = (hipStream_t)stream;
+  return wb_class_dev(p, r);
 }
 
 extern "C" int mfx_wboot_fit(const void* pv, const double* Y, const double* W, int64_t w_stride, const int32_t* K, const uint8_t* csf,
@@ -498,95 +452,10 @@ extern "C" int mfx_wboot_fit(const void* pv, const double* Y, const double* W, i
   PlanDev P;
   int device = 0;
   mfx_plan_view(p, &T, &P, &device);
-  const int M = P.M, N = T.N, F = maxfasc;
-  const int npF = wb_np(F, csf_on), CF = wb_ncol(F, csf_on, nprop), NS = MFX_BOOT_NSTAT + Q;
-  MfxClassBins bins;   // by class (K, CSF flag), before any device call
-  if (int rc = mfx_class_bins(fn, K, csf, F, csf_on && sig_csf, V, &bins)) return rc;
-  if (V == 0) return MFX_OK;
-  if (int rc = mfx_require_device(device)) return rc;
-  DevBuf<double> dxc, dprops, dq, dWs;
-  DevBuf<int32_t> dgr;
-  if (csf_on) HIPCHK(dxc.upload(sig_csf, M));
-  if (nprop > 0) HIPCHK(dprops.upload(props, (size_t)nprop * N));
-  if (Q > 0) HIPCHK(dq.upload(q, Q));
-  if (kind == MFX_BOOT_RESIDUAL) HIPCHK(dgr.upload(groups, M));
-  if (w_stride == 0) HIPCHK(dWs.upload(W, M));   // the shared vector is uploaded once
-  const double qnan = __builtin_nan("");
-  const int64_t budget = max_bytes > 0 ? max_bytes : WB_DEFAULT_BYTES;
-  // voxels per upload: what four device chunks of replicate signals hold, 65536 at the most
-  const size_t chunk = (size_t)std::max<int64_t>(1, std::min<int64_t>(65536, 4 * std::max<int64_t>(1, budget / ((int64_t)B * M * 8))));
-  return mfx_class_walk(bins, chunk, [&](int k, int cf, const int64_t* ix, size_t nv) -> int {
-    const int npc = wb_np(k, cf), Cc = wb_ncol(k, cf, nprop);
-    // class layout <-> batch layout: parameter columns and statistic columns
-    std::vector<int> pmap(npc), cmap(Cc);
-    pmap[0] = 0;
-    for (int f = 0; f < k; ++f) { pmap[1 + f] = 1 + f; pmap[1 + k + f] = 1 + F + f; }
-    if (cf) pmap[1 + 2 * k] = 1 + 2 * F;
-    pmap[npc - 2] = npF - 2; pmap[npc - 1] = npF - 1;
-    cmap[0] = 0;
-    for (int f = 0; f < k; ++f) cmap[1 + f] = 1 + f;
-    if (cf) cmap[1 + k] = 1 + F;
-    cmap[1 + k + cf] = 1 + F + csf_on;
-    for (int f = 0; f < k; ++f)
-      for (int t = 0; t < nprop; ++t) cmap[wb_c0(k, cf) + f * nprop + t] = wb_c0(F, csf_on) + f * nprop + t;
-    DevBuf<double> dY, dW, dpk, dp0, dst, dkeep;
-    DevBuf<int32_t> dag, dstat;
-    DevBuf<int64_t> dvox;
-    HIPCHK(dY.upload_rows(Y, ix, nv, M, M));
-    if (w_stride) HIPCHK(dW.upload_rows(W, ix, nv, M, M));
-    HIPCHK(mfx_upload_peaks(dpk, peaks, ix, nv, F, k));
-    if (params0) {
-      std::vector<double> rows(nv * npc);
-      for (size_t i = 0; i < nv; ++i)
-        for (int j = 0; j < npc; ++j) rows[i * npc + j] = params0[(size_t)ix[i] * npF + pmap[j]];
-      HIPCHK(dp0.upload(rows.data(), rows.size()));
-    }
-    {
-      std::vector<int64_t> vi(nv);
-      for (size_t i = 0; i < nv; ++i) vi[i] = vox ? vox[ix[i]] : ix[i];
-      HIPCHK(dvox.upload(vi.data(), nv));
-    }
-    HIPCHK(dst.alloc_n(nv * Cc * NS));
-    HIPCHK(dag.alloc_n(nv * (size_t)std::max(k, 1)));
-    HIPCHK(dstat.alloc_n(nv));
-    if (keep) HIPCHK(dkeep.alloc_n(nv * B * npc));
-    const WBClass r{p, dY.get(), w_stride ? dW.get() : dWs.get(), w_stride, k > 0 ? dpk.get() : nullptr, k, cf, cf ? dxc.get() : nullptr,
-                    params0 ? dp0.get() : nullptr, nullptr, dgr.get(), dvox.get(), (int64_t)nv, B, kind, inflate != 0, seed, offset,
-                    dprops.get(), nprop, dq.get(), Q, budget, dst.get(), dag.get(), dstat.get(), keep ? dkeep.get() : nullptr, nullptr};
-    if (int rc2 = wb_class_dev(r)) return rc2;
-    HIPCHK(hipStreamSynchronize(nullptr));
-    std::vector<double> hs(dst.n), hk;
-    std::vector<int32_t> ha(dag.n), hst(nv);
-    HIPCHK(dst.download(hs.data()));
-    HIPCHK(dag.download(ha.data()));
-    HIPCHK(dstat.download(hst.data()));
-    if (keep) { hk.resize(dkeep.n); HIPCHK(dkeep.download(hk.data())); }
-    for (size_t i = 0; i < nv; ++i) {
-      const size_t v = (size_t)ix[i];
-      const bool ok = hst[i] == 0;
-      status[v] = hst[i];
-      // columns the class does not have: a weight that is 0 in every replicate, a property that is never valid
-      double* sv = stats + v * CF * NS;
-      for (int c = 0; c < CF; ++c) {
-        double* s = sv + (size_t)c * NS;
-        const bool weight = c < wb_c0(F, csf_on);
-        if (weight && ok) {
-          s[0] = (double)B; s[1] = 0.0; s[2] = B > 1 ? 0.0 : qnan; s[3] = 0.0; s[4] = 0.0;
-          for (int t = 0; t < Q; ++t) s[MFX_BOOT_NSTAT + t] = 0.0;
-        } else {
-          s[0] = 0.0;
-          for (int t = 1; t < NS; ++t) s[t] = qnan;
-        }
-      }
-      for (int c = 0; c < Cc; ++c) std::memcpy(sv + (size_t)cmap[c] * NS, hs.data() + (i * Cc + c) * NS, sizeof(double) * NS);
-      for (int f = 0; f < F; ++f) agree[v * F + f] = f < k ? ha[i * k + f] : 0;
-      if (keep)
-        for (int b = 0; b < B; ++b) {
-          double* dst_row = keep + (v * B + b) * npF;
-          for (int j = 0; j < npF; ++j) dst_row[j] = ok ? 0.0 : qnan;
-          for (int j = 0; j < npc; ++j) dst_row[pmap[j]] = hk[(i * B + b) * npc + j];
-        }
-    }
-    return MFX_OK;
-  });
+  BootBatch b{};
+  b.fn = fn; b.device = device; b.M = P.M; b.N = T.N; b.Y = Y; b.W = W; b.w_stride = w_stride; b.K = K; b.csf = csf; b.peaks = peaks;
+  b.F = maxfasc; b.csf_on = csf_on; b.sig_csf = sig_csf; b.params0 = params0; b.groups = groups; b.vox = vox; b.V = V;
+  b.B = B; b.kind = kind; b.inflate = inflate != 0; b.seed = seed; b.offset = offset; b.props = props; b.nprop = nprop;
+  b.q = q; b.Q = Q; b.max_bytes = max_bytes; b.stats = stats; b.agree = agree; b.status = status; b.keep = keep;
+  return boot_run_mixed(b, [&](const BootClass& r) { return wb_class_dev(p, r); });
 }

@@ -12,8 +12,10 @@
 // 8 (M + 1 + B M + NP^2 + K NP (B + 1) + B) + 4 bytes; the voxels go in chunks within the byte budget.  Every other class,
 // and everything under mfx_wboot2d_debug_set_force_plain(1), takes the plain path: weight rows and directions are copied
 // to the replicate rows of a voxel chunk (a shared [M] vector stays shared) and w2d.hip's class launcher runs on them
-// untouched.  The host side of a mixed batch is class_batch.h, as in boot2d.hip and wboot.hip.
+// untouched.  The host side of a mixed batch, the per-class arguments and the front and tail of the class loop are
+// boot_shared.h's, as in boot.hip.
 #include "boot2d_kernels.h"
+#include "boot_shared.h"
 #include "../../include/mfx_wboot2d.h"
 #include "../../include/mfx_wboot.h"
 #include "../../include/mfx_w2d.h"
@@ -26,21 +28,10 @@ namespace {
 
 thread_local int g_force_plain = 0;
 
-constexpr int64_t WB2_DEFAULT_BYTES = (int64_t)256 << 20;
 constexpr int WB2_MAXF = 3;
 
-inline int wb2_np(int F, int c) { return 1 + 2 * F + c + 2; }
-inline int wb2_c0(int F, int c) { return 2 + F + c; }
-inline int wb2_ncol(int F, int c, int nprop) { return wb2_c0(F, c) + F * nprop; }
 unsigned wb2_grid(int64_t n) { return (unsigned)((n + 255) / 256); }
 
-// rows [V x w] -> [V B x w]
-__global__ void wboot2d_expand_kernel(const double* __restrict__ src, int64_t V, int B, int w, double* __restrict__ dst) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= V * B * w) return;
-  const int64_t row = i / w;
-  dst[i] = src[(row / B) * w + (i - row * w)];
-}
 // the voxel's records = those of its first replicate row: the directions' [5] and the weights' [1]
 __global__ void wboot2d_first_row_kernel(const int* __restrict__ rows, const int* __restrict__ wrows, int64_t V, int B,
                                          int* __restrict__ vstat, int* __restrict__ wstat) {
@@ -100,10 +91,10 @@ int wb2_rows(const mfx_rot2d* h, const double* d_Ys, const double* d_W, int64_t 
              int K, const double* d_xc, int64_t V, int B, double* d_params, int32_t* d_vstat, int32_t* d_wstat, int64_t budget,
              hipStream_t st) {
   const int M = h->d.M, N = h->d.N, NP = (N + 15) & ~15, has_csf = d_xc != nullptr;
-  const int np = wb2_np(K, has_csf);
+  const int np = boot_np(K, has_csf, 0);
   if (int rc = f2_limits("mfx_wboot2d", h, K, V)) return rc;
   if (V > 0x7fffffff / B) return mfx_fail(MFX_ERR_UNSUPPORTED, "mfx_wboot2d: more than 2^31 replicate rows in one call");
-  if (budget <= 0) budget = WB2_DEFAULT_BYTES;
+  if (budget <= 0) budget = BOOT_DEFAULT_BYTES;
   const int64_t per_vox = std::max<int64_t>(1, wb2_rows_bytes(h, K, has_csf, wstride, B));
 
   if (wb2_shared_serves(h, K, has_csf)) {
@@ -189,12 +180,12 @@ int wb2_rows(const mfx_rot2d* h, const double* d_Ys, const double* d_W, int64_t 
     {
       F2Dirs rows(st);
       if (K > 0) {
-        hipLaunchKernelGGL(wboot2d_expand_kernel, dim3(wb2_grid(nv * B * 3 * K)), dim3(256), 0, st, d_peaks + (size_t)v0 * 3 * K, nv, B,
+        hipLaunchKernelGGL(boot_expand_kernel, dim3(wb2_grid(nv * B * 3 * K)), dim3(256), 0, st, d_peaks + (size_t)v0 * 3 * K, nv, B,
                            3 * K, pk.as<double>());
         HIPCHK(hipGetLastError());
       }
       if (wstride) {
-        hipLaunchKernelGGL(wboot2d_expand_kernel, dim3(wb2_grid(nv * B * M)), dim3(256), 0, st, d_W + (size_t)v0 * M, nv, B, M,
+        hipLaunchKernelGGL(boot_expand_kernel, dim3(wb2_grid(nv * B * M)), dim3(256), 0, st, d_W + (size_t)v0 * M, nv, B, M,
                            wr.as<double>());
         HIPCHK(hipGetLastError());
       }
@@ -237,53 +228,16 @@ int wb2_check(const char* fn, const mfx_rot2d* h, int64_t w_stride, int F, int c
 }
 
 // One class on device buffers (what mfx_wboot2d_fit_dev does after its checks; mfx_wboot2d_fit runs it per class chunk)
-struct WB2Class {
-  const mfx_rot2d* h;
-  const double *Y, *W;
-  int64_t wstride;
-  const double* peaks;
-  int F, csf_on;
-  const double* sig_csf;
-  const double *params0, *pred0;
-  const int32_t* groups;
-  const int64_t* vox;
-  int64_t V;
-  int B, kind, inflate;
-  uint64_t seed, offset;
-  const double* props;
-  int nprop;
-  const double* q;
-  int Q;
-  int64_t max_bytes;
-  double* stats;
-  int32_t *agree, *status, *dir_status;
-  double* keep;
-  hipStream_t st;
-};
-
-int wb2_class_dev(const WB2Class& r) {
-  const mfx_rot2d* h = r.h;
+int wb2_class_dev(const mfx_rot2d* h, const BootClass& r) {
   const int M = h->d.M, N = h->d.N, F = r.F, B = r.B;
-  const int np = wb2_np(F, r.csf_on), C = wb2_ncol(F, r.csf_on, r.nprop);
   const double* xc = r.csf_on ? r.sig_csf : nullptr;
-  const int64_t budget = r.max_bytes > 0 ? r.max_bytes : WB2_DEFAULT_BYTES;
-  const int64_t per_vox = (int64_t)B * M * (int64_t)sizeof(double) + wb2_rows_bytes(h, F, r.csf_on != 0, r.wstride, B);
-  int64_t Vc = std::max<int64_t>(1, std::min<int64_t>(r.V, budget / per_vox));
-  Vc = std::min<int64_t>(Vc, 0x7fffffff / B);
   hipStream_t st = r.st;
-  StreamMem ys(st), prm(st), X(st), vd(st), par0(st), pred(st), pst(st), dst(st), wst(st);
-  HIPCHK(ys.alloc(sizeof(double) * (size_t)Vc * B * M));
-  if (!r.keep) HIPCHK(prm.alloc(sizeof(double) * (size_t)Vc * B * np));
-  HIPCHK(X.alloc(sizeof(double) * (size_t)Vc * B * C));
-  HIPCHK(vd.alloc((size_t)Vc * B * C));
-  if (!r.params0) HIPCHK(par0.alloc(sizeof(double) * (size_t)Vc * np));
+  BootChunkMem mem(r, M);
+  StreamMem dst(st), wst(st);
+  if (int rc = mem.alloc((int64_t)B * M * (int64_t)sizeof(double) + wb2_rows_bytes(h, F, r.csf_on != 0, r.wstride, B))) return rc;
+  const int64_t Vc = mem.Vc;
   HIPCHK(wst.alloc(sizeof(int) * (size_t)Vc));   // mfx_w2d.h's status of the weights (the bootstrap's own says more)
-  if (!r.pred0) {
-    HIPCHK(pred.alloc(sizeof(double) * (size_t)Vc * M));
-    HIPCHK(pst.alloc(2 * sizeof(int)));
-    HIPCHK(dst.alloc(sizeof(int) * 5 * (size_t)Vc));
-    HIPCHK(hipMemsetAsync(pst.p, 0, 2 * sizeof(int), st));   // a NaN parameter row is flagged there and predicted as NaN: status 2
-  }
+  if (!r.pred0) HIPCHK(dst.alloc(sizeof(int) * 5 * (size_t)Vc));   // the prediction's own record of the directions
   ScratchMark mark;
   const bool marked = mfx_scratch_mark(st, &mark);
   for (int64_t v0 = 0; v0 < r.V; v0 += Vc) {
@@ -296,36 +250,31 @@ int wb2_class_dev(const WB2Class& r) {
       // the directions of the chunk, prepared once: the own fit, the prediction and the replicate fit read them
       F2Dirs dirs(st);
       if (int rc = dirs.enqueue(h, pks, nv * F, st)) return rc;
-      const double* p0 = r.params0 ? r.params0 + (size_t)v0 * np : par0.as<double>();
+      const double* p0 = mem.p0(v0);
       if (!r.params0)
         if (int rc = mfx_wfit2d_class_prepared(h, y, w, r.wstride, dirs.rec.p, dirs.pstat.as<int>(), F, xc, F, r.csf_on, nv,
-                                               par0.as<double>(), vstat, wst.as<int32_t>(), st)) return rc;
-      const double* pr = r.pred0 ? r.pred0 + (size_t)v0 * M : pred.as<double>();
+                                               mem.par0.as<double>(), vstat, wst.as<int32_t>(), st)) return rc;
       if (!r.pred0)
         if (int rc = mfx_predict2d_launch(h, dirs.rec.p, dirs.pstat.as<int>(), F, p0, F, r.csf_on, xc, nv, nullptr, nullptr, 0, 0, 0, 0,
-                                          pred.as<double>(), nullptr, pst.as<int32_t>(), dst.as<int32_t>(), st)) return rc;
-      double* rows = r.keep ? r.keep + (size_t)v0 * B * np : prm.as<double>();
-      if (int rc = mfx_wboot_resample_dev(M, y, pr, w, r.wstride, p0, F, r.csf_on, nullptr, r.groups, r.vox ? r.vox + v0 : nullptr, nv, B,
-                                          r.kind, r.inflate, r.seed, r.vox ? r.offset : r.offset + (uint64_t)v0 * (uint64_t)M,
-                                          ys.as<double>(), nullptr, r.status + v0, st)) return rc;
+                                          mem.pred.as<double>(), nullptr, mem.pst.as<int32_t>(), dst.as<int32_t>(), st)) return rc;
+      double* ys = mem.ys.as<double>();
+      if (int rc = mfx_wboot_resample_dev(M, y, mem.pr(v0), w, r.wstride, p0, F, r.csf_on, nullptr, r.groups, r.vox ? r.vox + v0 : nullptr,
+                                          nv, B, r.kind, r.inflate, r.seed, r.vox ? r.offset : r.offset + (uint64_t)v0 * (uint64_t)M, ys,
+                                          nullptr, r.status + v0, st)) return rc;
       // the voxels' records (the replicate fit writes them again, the same); a failing direction comes first in the
       // status, and no NaN signal reaches a fit kernel
       if (F == 0) {
         HIPCHK(hipMemsetAsync(vstat, 0, sizeof(int32_t) * 5 * (size_t)nv, st));
       } else {
         hipLaunchKernelGGL(fit2d_status_kernel, dim3(wb2_grid(nv)), dim3(256), 0, st, dirs.pstat.as<int>(), F, nv, vstat, (int*)nullptr,
-                           (double*)nullptr, np);
+                           (double*)nullptr, mem.np);
         HIPCHK(hipGetLastError());
       }
-      hipLaunchKernelGGL(wboot2d_mask_kernel, dim3((unsigned)nv), dim3(256), 0, st, r.status + v0, vstat, nv, (int64_t)B * M,
-                         ys.as<double>());
+      hipLaunchKernelGGL(wboot2d_mask_kernel, dim3((unsigned)nv), dim3(256), 0, st, r.status + v0, vstat, nv, (int64_t)B * M, ys);
       HIPCHK(hipGetLastError());
-      if (int rc = wb2_rows(h, ys.as<double>(), w, r.wstride, pks, &dirs, F, xc, nv, B, rows, vstat, wst.as<int32_t>(), budget, st))
+      if (int rc = wb2_rows(h, ys, w, r.wstride, pks, &dirs, F, xc, nv, B, mem.rows(v0), vstat, wst.as<int32_t>(), mem.budget(), st))
         return rc;
-      if (int rc = mfx_boot_gather_dev(rows, p0, F, r.csf_on, 0, r.props, r.nprop, N, r.status + v0, nv, B, X.as<double>(),
-                                       vd.as<uint8_t>(), r.agree ? r.agree + (size_t)v0 * F : nullptr, st)) return rc;
-      if (int rc = mfx_boot_reduce_dev(X.as<double>(), vd.as<uint8_t>(), nv, B, C, r.q, r.Q,
-                                       r.stats + (size_t)v0 * C * (MFX_BOOT_NSTAT + r.Q), st)) return rc;
+      if (int rc = mem.gather_reduce(v0, nv, N)) return rc;
     }
     if (marked) mfx_scratch_rewind(st, mark);
   }
@@ -355,7 +304,7 @@ extern "C" int mfx_wboot2d_fit_rows_dev(void* hv, const double* d_Ystar, const d
   if (int rc = wb2_stride_check(fn, h, w_stride)) return rc;
   if (V == 0) return MFX_OK;
   if (int rc = mfx_require_device(h->device)) return rc;
-  return wb2_rows(h, d_Ystar, d_W, w_stride, d_peaks, nullptr, maxfasc, nullptr, V, B, d_params, d_status, d_wstatus, WB2_DEFAULT_BYTES,
+  return wb2_rows(h, d_Ystar, d_W, w_stride, d_peaks, nullptr, maxfasc, nullptr, V, B, d_params, d_status, d_wstatus, BOOT_DEFAULT_BYTES,
                   (hipStream_t)stream);
 }
 
@@ -376,10 +325,12 @@ extern "C" int mfx_wboot2d_fit_dev(void* hv, const double* d_Y, const double* d_
   if (V == 0) return MFX_OK;
   if (int rc = f2_limits(fn, h, maxfasc, V)) return rc;
   if (int rc = mfx_require_device(h->device)) return rc;
-  const WB2Class r{h, d_Y, d_W, w_stride, d_peaks, maxfasc, csf_on, d_sig_csf, d_params0, d_pred0, d_groups, d_vox, V, B, kind,
-                   inflate != 0, seed, offset, d_props, nprop, d_q, Q, max_bytes, d_stats, d_agree, d_status, d_dir_status, d_keep,
-                   (hipStream_t)stream};
-  return wb2_class_dev(r);
+  BootClass r{};
+  r.Y = d_Y; r.W = d_W; r.wstride = w_stride; r.peaks = d_peaks; r.F = maxfasc; r.csf_on = csf_on; r.sig_csf = d_sig_csf;
+  r.params0 = d_params0; r.pred0 = d_pred0; r.groups = d_groups; r.vox = d_vox; r.V = V; r.B = B; r.kind = kind; r.inflate = inflate != 0;
+  r.seed = seed; r.offset = offset; r.props = d_props; r.nprop = nprop; r.q = d_q; r.Q = Q; r.max_bytes = max_bytes;
+  r.stats = d_stats; r.agree = d_agree; r.status = d_status; r.dir_status = d_dir_status; r.keep = d_keep; r.st = (hipStream_t)stream;
+  return wb2_class_dev(h, r);
 }
 
 extern "C" int mfx_wboot2d_fit(void* hv, const double* Y, const double* W, int64_t w_stride, const int32_t* K, const uint8_t* csf,
@@ -396,98 +347,10 @@ extern "C" int mfx_wboot2d_fit(void* hv, const double* Y, const double* W, int64
     return mfx_fail(MFX_ERR_ARG, "%s: bad argument", fn);
   for (int i = 0; i < Q; ++i)
     if (!(q[i] >= 0.0 && q[i] <= 1.0)) return mfx_fail(MFX_ERR_ARG, "%s: q[%d] = %g outside [0, 1]", fn, i, q[i]);
-  const int M = h->d.M, N = h->d.N, F = maxfasc;
-  const int npF = wb2_np(F, csf_on), CF = wb2_ncol(F, csf_on, nprop), NS = MFX_BOOT_NSTAT + Q;
-  MfxClassBins bins;   // by class (K, CSF flag), before any device call
-  if (int rc = mfx_class_bins(fn, K, csf, F, csf_on && sig_csf, V, &bins)) return rc;
-  if (V == 0) return MFX_OK;
-  if (int rc = mfx_require_device(h->device)) return rc;
-  DevBuf<double> dxc, dprops, dq, dWs;
-  DevBuf<int32_t> dgr;
-  if (csf_on) HIPCHK(dxc.upload(sig_csf, M));
-  if (nprop > 0) HIPCHK(dprops.upload(props, (size_t)nprop * N));
-  if (Q > 0) HIPCHK(dq.upload(q, Q));
-  if (kind == MFX_BOOT_RESIDUAL) HIPCHK(dgr.upload(groups, M));
-  if (w_stride == 0) HIPCHK(dWs.upload(W, M));   // the shared vector is uploaded once and read with stride 0
-  const double qnan = __builtin_nan("");
-  const int64_t budget = max_bytes > 0 ? max_bytes : WB2_DEFAULT_BYTES;
-  // voxels per upload: what four device chunks of replicate signals hold, 65536 at the most
-  const size_t chunk = (size_t)std::max<int64_t>(1, std::min<int64_t>(65536, 4 * std::max<int64_t>(1, budget / ((int64_t)B * M * 8))));
-  return mfx_class_walk(bins, chunk, [&](int k, int cf, const int64_t* ix, size_t nv) -> int {
-    const int npc = wb2_np(k, cf), Cc = wb2_ncol(k, cf, nprop);
-    // class layout <-> batch layout: parameter columns and statistic columns
-    std::vector<int> pmap(npc), cmap(Cc);
-    pmap[0] = 0;
-    for (int f = 0; f < k; ++f) { pmap[1 + f] = 1 + f; pmap[1 + k + f] = 1 + F + f; }
-    if (cf) pmap[1 + 2 * k] = 1 + 2 * F;
-    pmap[npc - 2] = npF - 2; pmap[npc - 1] = npF - 1;
-    cmap[0] = 0;
-    for (int f = 0; f < k; ++f) cmap[1 + f] = 1 + f;
-    if (cf) cmap[1 + k] = 1 + F;
-    cmap[1 + k + cf] = 1 + F + csf_on;
-    for (int f = 0; f < k; ++f)
-      for (int t = 0; t < nprop; ++t) cmap[wb2_c0(k, cf) + f * nprop + t] = wb2_c0(F, csf_on) + f * nprop + t;
-    DevBuf<double> dY, dW, dpk, dp0, dst, dkeep;
-    DevBuf<int32_t> dag, dstat, ddir;
-    DevBuf<int64_t> dvox;
-    HIPCHK(dY.upload_rows(Y, ix, nv, M, M));
-    if (w_stride) HIPCHK(dW.upload_rows(W, ix, nv, M, M));
-    HIPCHK(mfx_upload_peaks(dpk, peaks, ix, nv, F, k));
-    if (params0) {
-      std::vector<double> rows(nv * npc);
-      for (size_t i = 0; i < nv; ++i)
-        for (int j = 0; j < npc; ++j) rows[i * npc + j] = params0[(size_t)ix[i] * npF + pmap[j]];
-      HIPCHK(dp0.upload(rows.data(), rows.size()));
-    }
-    {
-      std::vector<int64_t> vi(nv);
-      for (size_t i = 0; i < nv; ++i) vi[i] = vox ? vox[ix[i]] : ix[i];
-      HIPCHK(dvox.upload(vi.data(), nv));
-    }
-    HIPCHK(dst.alloc_n(nv * Cc * NS));
-    HIPCHK(dag.alloc_n(nv * (size_t)std::max(k, 1)));
-    HIPCHK(dstat.alloc_n(nv));
-    HIPCHK(ddir.alloc_n(nv * 5));
-    if (keep) HIPCHK(dkeep.alloc_n(nv * B * npc));
-    const WB2Class r{h, dY.get(), w_stride ? dW.get() : dWs.get(), w_stride, k > 0 ? dpk.get() : nullptr, k, cf, cf ? dxc.get() : nullptr,
-                     params0 ? dp0.get() : nullptr, nullptr, dgr.get(), dvox.get(), (int64_t)nv, B, kind, inflate != 0, seed, offset,
-                     dprops.get(), nprop, dq.get(), Q, budget, dst.get(), dag.get(), dstat.get(), ddir.get(),
-                     keep ? dkeep.get() : nullptr, nullptr};
-    if (int rc2 = wb2_class_dev(r)) return rc2;
-    HIPCHK(hipStreamSynchronize(nullptr));
-    std::vector<double> hs(dst.n), hk;
-    std::vector<int32_t> ha(dag.n), hst(nv);
-    HIPCHK(dst.download(hs.data()));
-    HIPCHK(dag.download(ha.data()));
-    HIPCHK(dstat.download(hst.data()));
-    HIPCHK(ddir.download_rows(dir_status, ix, nv, 5));
-    if (keep) { hk.resize(dkeep.n); HIPCHK(dkeep.download(hk.data())); }
-    for (size_t i = 0; i < nv; ++i) {
-      const size_t v = (size_t)ix[i];
-      const bool ok = hst[i] == 0;
-      status[v] = hst[i];
-      // columns the class does not have: a weight that is 0 in every replicate, a property that is never valid
-      double* sv = stats + v * CF * NS;
-      for (int c = 0; c < CF; ++c) {
-        double* s = sv + (size_t)c * NS;
-        const bool weight = c < wb2_c0(F, csf_on);
-        if (weight && ok) {
-          s[0] = (double)B; s[1] = 0.0; s[2] = B > 1 ? 0.0 : qnan; s[3] = 0.0; s[4] = 0.0;
-          for (int t = 0; t < Q; ++t) s[MFX_BOOT_NSTAT + t] = 0.0;
-        } else {
-          s[0] = 0.0;
-          for (int t = 1; t < NS; ++t) s[t] = qnan;
-        }
-      }
-      for (int c = 0; c < Cc; ++c) std::memcpy(sv + (size_t)cmap[c] * NS, hs.data() + (i * Cc + c) * NS, sizeof(double) * NS);
-      for (int f = 0; f < F; ++f) agree[v * F + f] = f < k ? ha[i * k + f] : 0;
-      if (keep)
-        for (int b = 0; b < B; ++b) {
-          double* dst_row = keep + (v * B + b) * npF;
-          for (int j = 0; j < npF; ++j) dst_row[j] = ok ? 0.0 : qnan;
-          for (int j = 0; j < npc; ++j) dst_row[pmap[j]] = hk[(i * B + b) * npc + j];
-        }
-    }
-    return MFX_OK;
-  });
+  BootBatch b{};
+  b.fn = fn; b.device = h->device; b.M = h->d.M; b.N = h->d.N; b.Y = Y; b.W = W; b.w_stride = w_stride; b.K = K; b.csf = csf; b.peaks = peaks;
+  b.F = maxfasc; b.csf_on = csf_on; b.sig_csf = sig_csf; b.params0 = params0; b.groups = groups; b.vox = vox; b.V = V;
+  b.B = B; b.kind = kind; b.inflate = inflate != 0; b.seed = seed; b.offset = offset; b.props = props; b.nprop = nprop;
+  b.q = q; b.Q = Q; b.max_bytes = max_bytes; b.stats = stats; b.agree = agree; b.status = status; b.dir_status = dir_status; b.keep = keep;
+  return boot_run_mixed(b, [&](const BootClass& r) { return wb2_class_dev(h, r); });
 }

@@ -117,7 +117,7 @@ def host_bytes(name):
 
 # ---- byte budgets that must NOT be what cuts where a clamp is under test (restated from the sources; the GPU tests ask the
 # library where it answers: mfx_solve_soft_bytes_per_signal)
-DEFAULT_BYTES = 256 << 20      # SB_DEFAULT_BYTES, B2_DEFAULT_BYTES, WB2_DEFAULT_BYTES
+DEFAULT_BYTES = 256 << 20      # SB_DEFAULT_BYTES, BOOT_DEFAULT_BYTES
 
 
 def boot2d_shared_bytes(K, N, M, B, weighted):
